@@ -32,6 +32,15 @@ N > 1: layers are sharded in contiguous blocks over the ranks.  `v
 
 Extra objects on the JSON line: "roofline" (dominant kernel, HIP-event timed live), "cpu_baseline" (oracle on the host cores,
 N = 1 only), "parity" (token ids / logits vs that oracle run).
+
+A plain run does only what the headline needs: set up, W warm-up steps, the K timed steps, the result line (with "eval_per_token_loop" and
+"roofline_token", which cost nothing beyond the timed steps).  Every other measurement or check - "resident_loop", "sampled_decode",
+"kernels", "roofline", "cpu_baseline", "parity", "pods_batched", "prefill_13b", "prompt_8_tokens", "int8_decode" and, for N > 1,
+"pods_batched_4n", "single_stream", "pipeline_breakdown" and the golden-ids parity - runs only with `--full` (`--no-cpu-baseline` /
+`--no-prefill` then leave out their parts of it), each over min(K, 32) steps after min(W, 32) warm-up steps, so that the cost of a
+--full run does not grow with --steps.  `--dump-outputs DIR` writes what the timed path handed its caller in its last step
+(N = 1: DIR/logits.npy float32 [vocab] and DIR/tokens.npy float64 [K], the ids the K timed steps produced; N > 1: DIR/tokens.npy float64
+[streams, K]): inputs are fixed (seed, prompt), so two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -47,6 +56,7 @@ os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # dmabuf IPC: what RC
 
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec (6.3 TB/s measured copy ceiling)
 SEED = 1234
+SIDE_STEPS = 32   # most decode / warm-up steps of any --full side measurement, whatever --steps is
 
 
 def bytes_per_token(hp_d, L, F, V, T):
@@ -113,6 +123,15 @@ def spawn_ranks(n):
 _OUT = None   # the real stdout once main() has pointed fd 1 at stderr
 
 
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array (float32 / float64; a few hundred KB at most)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -121,11 +140,14 @@ def main():
     ap.add_argument("--shape", default="7B")
     ap.add_argument("--layers", type=int, default=0, help="override layer count (debug only; invalidates the metric)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-steps", type=int, default=0, help="decode steps of the CPU baseline / parity legs (default: all --steps, BASELINE.md §3)")
+    ap.add_argument("--cpu-steps", type=int, default=0, help="decode steps of the CPU baseline / parity legs (default and most: min(--steps, 32), BASELINE.md §3)")
     ap.add_argument("--pods", type=int, default=0, help="independent greedy streams in flight for N > 1 (default N, one row per weight pass; 1 = the single-stream latency curve)")
     ap.add_argument("--rows-per-pass", type=int, default=1, help="N > 1: streams a tick evaluates in ONE pass over a rank's weights (default 1 = comparable with N = 1; 0 = as many as fit)")
     ap.add_argument("--no-prefill", action="store_true", help="skip the config-3 side measurement (13B, one 1024-token Eval)")
     ap.add_argument("--int8", action="store_true", help="BASELINE config 4: block-int8 weight matrices (36 B per 32 weights); not the headline metric")
+    ap.add_argument("--full", action="store_true", help="also run every side measurement and check (CPU baseline, parity, kernel roofline, pods, prefill, int8, ...); "
+                                                        "off: only what the headline line needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -179,6 +201,10 @@ def main():
         kw["layers"] = args.layers
     K, W = args.steps, args.warmup
     ctx_size = max(128, len(PROMPT) + K + W + 1 + 8)   # (+ 8: the head steps of the per-token host loop measurement)
+    # --full's side measurements and checks run at most SIDE_STEPS steps each: their cost - the CPU legs' above all, a 7B step takes the host
+    # hundreds of ms - must not grow with the step count the headline is timed over (chosen from ms_per_step, it can be thousands)
+    KS, WS = min(K, SIDE_STEPS), min(W, SIDE_STEPS)
+    side_ctx = max(128, len(PROMPT) + KS + WS + 1 + 8)
     hp = make_hparams(**kw, ctx=ctx_size)
     d, L, V = hp.embdSize, hp.layersCount, hp.vocabSize
     PROMPT = [t % V for t in PROMPT]  # the fixed ids are 7B-vocabulary ids; debug shapes have smaller tables
@@ -223,76 +249,79 @@ def main():
                                          "note": "the SAME K timed steps by the wall clock between the barrier + synchronize pairs: llama.Eval per token - the host mirror moves the graph it keeps for one-token Evals to the new position (1 us; "
                                                  "building it anew as the reference's llama.Eval does cost 53 + 13 us, rounds 1-5) - the library's match (12 us), the wait, the logits row and the host argmax; "
                                                  "`value` is the HIP-event time of the lh_graph_compute calls inside it (it starts at the call's entry: validate and match are in it)"}
-        # ---- rounds 1-5's `value`: the device-resident loop (argmax on the GPU feeds the next step, hipGraph replay of eight steps, no host round trip)
-        cr = model.NewContext(ctx_size, 1)
-        cr.Eval(PROMPT, 0)
-        if W > 0:
-            decode_greedy_resident(cr, first, P0, W)
-        torch.cuda.synchronize()
-        t_r = time.perf_counter()
-        toks_res, _ = decode_greedy_resident(cr, first, P0, K, want_logits=True)
-        torch.cuda.synchronize()
-        dt_res = time.perf_counter() - t_r
-        cr.free()
-        result["resident_loop"] = {"tokens_per_s": round(K / dt_res, 2), "ms_per_token": round(dt_res / K * 1e3, 4), "ids_equal_contract_route": [int(t) for t in toks_res] == [int(t) for t in toks],
-                                   "note": "lh_llama_decode_greedy: the whole loop on the device (an extension of the boundary, not the contract call); `value` of rounds 1-5"}
-        # ---- the reference's real generation loop: SampleTopPTopK (topK 40, topP 0.95, repeat penalty 1.10 — main.go:87-90) after every
-        # Eval, sampler resident on the device (no logits D2H).  Decode rate = (t[K+1 samples] - t[1 sample]) / K, same prefill in both.
-        SMP = dict(topK=min(40, V), topP=0.95, temp=0.8, repeatPenalty=1.10, seed=SEED)
-        c4 = model.NewContext(ctx_size, 1)
-        c4.SampleDecode(PROMPT, min(W, 2) + 1, **SMP)
-        torch.cuda.synchronize()
-        t_s = time.perf_counter()
-        c4.SampleDecode(PROMPT, 1, **SMP)
-        t_s1 = time.perf_counter()
-        sampled = c4.SampleDecode(PROMPT, K + 1, **SMP)
-        t_s2 = time.perf_counter()
-        c4.free()
-        smp_dt = max(1e-9, (t_s2 - t_s1) - (t_s1 - t_s))
-        result["sampled_decode"] = {"tokens_per_s": round(K / smp_dt, 2), "ms_per_token": round(smp_dt / K * 1e3, 4), "params": SMP,
-                                    "note": "llama.SampleTopPTopK on the device after every Eval (server.go:201-204); counter-based uniforms (not `value`)"}
-        # ---- dominant kernel, HIP-event timed with eager launches of the same kernels (all weights distinct: HBM-cold)
-        prof = profile_decode(ctx, first, P0, repeats=2)
-        result["kernels"] = {k["name"]: {"avg_us": round(k["avg_us"], 2), "launches": k["launches"], "GBps": round(k["gbps"], 1)} for k in prof if not k["name"].endswith("/b2b")}
-        b2b = {k["name"][:-4]: k for k in prof if k["name"].endswith("/b2b")}
-        prof = [k for k in prof if not k["name"].endswith("/b2b")]
-        dom = max(prof, key=lambda k: k["avg_us"] * k["launches"])
-        per_pair_us = dom["avg_us"]
-        if dom["name"] in b2b:  # the dominant kernel's launches of a step back to back between ONE event pair (no per-kernel event cost)
-            dom = dict(b2b[dom["name"]], name=dom["name"])
-        traffic, traffic_src, traffic_ok = None, None, None
-        try:  # HBM bytes per launch from the committed PMC pass (counters cannot be collected from inside this process); only believed while the
-            # kernel sources are the ones the pass profiled (tools/source_hash.py: sha256 over csrc/ + include/llamahip.h, stamped by tools/pmc_summary.py)
-            sys.path.insert(0, os.path.join(ROOT, "tools"))
-            from source_hash import kernel_source_hash
-            pmc = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
-            if not args.int8 and args.shape == "7B":
-                traffic_ok = pmc.get("kernel_source_sha256") == kernel_source_hash()
-                if traffic_ok:
-                    traffic, traffic_src = pmc["bytes_per_launch"].get(dom["name"]), pmc["source"]
-                else:
-                    traffic_src = ("dropped: profiles/pmc_traffic.json was measured on other kernel sources (kernel_source_sha256 differs) - rerun the pmc:f32 step of "
-                                   "tools/gpu/r6_final.sh")
-        except Exception:
-            pass
-        # what this box's HBM delivers to a kernel that only reads (lh_hbm_read_probe: the weight stream's access pattern, no arithmetic),
-        # measured live: the nominal 8 TB/s is not reachable by any access pattern; SURVEY 8d asks for both yardsticks
-        meas = None
-        try:
-            from llama_go_amd.mlapi import hbm_read_probe
-            meas = hbm_read_probe(prod)
-        except Exception:
-            pass
-        result["roofline"] = {
-            "bound": "hbm", "kernel": dom["name"], "achieved": round(dom["gbps"], 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-            "frac": round(dom["gbps"] / HBM_PEAK_GBPS, 4), "measured_read_stream_GBps": round(meas, 1) if meas else None,
-            "frac_of_measured_stream": round(dom["gbps"] / meas, 4) if meas else None, "traffic": traffic, "traffic_source": traffic_src, "traffic_build_matches": traffic_ok,
-            "bytes_per_launch": dom["bytes_per_launch"], "avg_us": round(dom["avg_us"], 2), "avg_us_with_event_pair_per_launch": round(per_pair_us, 2),
-            "note": "algorithmic bytes = rows*cols*4 of the weights one launch streams (SURVEY 8d); avg_us = HIP events around the kernel's 32 launches "
-                    "of a step, back to back, all weights distinct (agrees with the rocprofv3 kernel trace in profiles/); traffic (PMC) in profiles/",
-        }
+        if args.dump_outputs:   # what llamago_GreedyContinue's caller holds after the last timed step: its logits row and the ids of the K steps
+            dump_outputs(args.dump_outputs, {"logits": np.asarray(last_logits, np.float32), "tokens": np.asarray(toks, np.float64)})
+        if args.full:
+            # ---- rounds 1-5's `value`: the device-resident loop (argmax on the GPU feeds the next step, hipGraph replay of eight steps, no host round trip)
+            cr = model.NewContext(side_ctx, 1)
+            cr.Eval(PROMPT, 0)
+            if WS > 0:
+                decode_greedy_resident(cr, first, P0, WS)
+            torch.cuda.synchronize()
+            t_r = time.perf_counter()
+            toks_res, _ = decode_greedy_resident(cr, first, P0, KS, want_logits=True)
+            torch.cuda.synchronize()
+            dt_res = time.perf_counter() - t_r
+            cr.free()
+            result["resident_loop"] = {"tokens_per_s": round(KS / dt_res, 2), "ms_per_token": round(dt_res / KS * 1e3, 4), "ids_equal_contract_route": [int(t) for t in toks_res] == [int(t) for t in toks[:KS]],
+                                       "note": "lh_llama_decode_greedy: the whole loop on the device (an extension of the boundary, not the contract call); `value` of rounds 1-5"}
+            # ---- the reference's real generation loop: SampleTopPTopK (topK 40, topP 0.95, repeat penalty 1.10 — main.go:87-90) after every
+            # Eval, sampler resident on the device (no logits D2H).  Decode rate = (t[KS+1 samples] - t[1 sample]) / KS, same prefill in both.
+            SMP = dict(topK=min(40, V), topP=0.95, temp=0.8, repeatPenalty=1.10, seed=SEED)
+            c4 = model.NewContext(side_ctx, 1)
+            c4.SampleDecode(PROMPT, min(W, 2) + 1, **SMP)
+            torch.cuda.synchronize()
+            t_s = time.perf_counter()
+            c4.SampleDecode(PROMPT, 1, **SMP)
+            t_s1 = time.perf_counter()
+            sampled = c4.SampleDecode(PROMPT, KS + 1, **SMP)
+            t_s2 = time.perf_counter()
+            c4.free()
+            smp_dt = max(1e-9, (t_s2 - t_s1) - (t_s1 - t_s))
+            result["sampled_decode"] = {"tokens_per_s": round(KS / smp_dt, 2), "ms_per_token": round(smp_dt / KS * 1e3, 4), "params": SMP,
+                                        "note": "llama.SampleTopPTopK on the device after every Eval (server.go:201-204); counter-based uniforms (not `value`)"}
+            # ---- dominant kernel, HIP-event timed with eager launches of the same kernels (all weights distinct: HBM-cold)
+            prof = profile_decode(ctx, first, P0, repeats=2)
+            result["kernels"] = {k["name"]: {"avg_us": round(k["avg_us"], 2), "launches": k["launches"], "GBps": round(k["gbps"], 1)} for k in prof if not k["name"].endswith("/b2b")}
+            b2b = {k["name"][:-4]: k for k in prof if k["name"].endswith("/b2b")}
+            prof = [k for k in prof if not k["name"].endswith("/b2b")]
+            dom = max(prof, key=lambda k: k["avg_us"] * k["launches"])
+            per_pair_us = dom["avg_us"]
+            if dom["name"] in b2b:  # the dominant kernel's launches of a step back to back between ONE event pair (no per-kernel event cost)
+                dom = dict(b2b[dom["name"]], name=dom["name"])
+            traffic, traffic_src, traffic_ok = None, None, None
+            try:  # HBM bytes per launch from the committed PMC pass (counters cannot be collected from inside this process); only believed while the
+                # kernel sources are the ones the pass profiled (tools/source_hash.py: sha256 over csrc/ + include/llamahip.h, stamped by tools/pmc_summary.py)
+                sys.path.insert(0, os.path.join(ROOT, "tools"))
+                from source_hash import kernel_source_hash
+                pmc = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
+                if not args.int8 and args.shape == "7B":
+                    traffic_ok = pmc.get("kernel_source_sha256") == kernel_source_hash()
+                    if traffic_ok:
+                        traffic, traffic_src = pmc["bytes_per_launch"].get(dom["name"]), pmc["source"]
+                    else:
+                        traffic_src = ("dropped: profiles/pmc_traffic.json was measured on other kernel sources (kernel_source_sha256 differs) - rerun the pmc:f32 step of "
+                                       "tools/gpu/r6_final.sh")
+            except Exception:
+                pass
+            # what this box's HBM delivers to a kernel that only reads (lh_hbm_read_probe: the weight stream's access pattern, no arithmetic),
+            # measured live: the nominal 8 TB/s is not reachable by any access pattern; SURVEY 8d asks for both yardsticks
+            meas = None
+            try:
+                from llama_go_amd.mlapi import hbm_read_probe
+                meas = hbm_read_probe(prod)
+            except Exception:
+                pass
+            result["roofline"] = {
+                "bound": "hbm", "kernel": dom["name"], "achieved": round(dom["gbps"], 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                "frac": round(dom["gbps"] / HBM_PEAK_GBPS, 4), "measured_read_stream_GBps": round(meas, 1) if meas else None,
+                "frac_of_measured_stream": round(dom["gbps"] / meas, 4) if meas else None, "traffic": traffic, "traffic_source": traffic_src, "traffic_build_matches": traffic_ok,
+                "bytes_per_launch": dom["bytes_per_launch"], "avg_us": round(dom["avg_us"], 2), "avg_us_with_event_pair_per_launch": round(per_pair_us, 2),
+                "note": "algorithmic bytes = rows*cols*4 of the weights one launch streams (SURVEY 8d); avg_us = HIP events around the kernel's 32 launches "
+                        "of a step, back to back, all weights distinct (agrees with the rocprofv3 kernel trace in profiles/); traffic (PMC) in profiles/",
+            }
         # ---- CPU baseline + parity on the same inputs (oracle = test infrastructure; only used here as the checker / baseline)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             orc = MLLib(os.path.join(ROOT, "oracle", "liboracle.so"))
             ncpu = ncpu_early
             t_gen = time.perf_counter()
@@ -300,12 +329,12 @@ def main():
             if args.int8:
                 om.QuantizeQ8()
             t_gen = time.perf_counter() - t_gen
-            nsteps = max(1, min(args.cpu_steps or K, K))
+            nsteps = max(1, min(args.cpu_steps or KS, KS))
             # (B) "--avx-equivalent": the reference's own vdot (oracle/_ref), rows chunked over the host cores as ml.go:2010-2013 does;
             # three samples of the same nsteps (fresh context each), the MEDIAN is reported
             avx_samples = []
             for rep_ in range(3):
-                oc = om.NewContext(ctx_size, ncpu, True)
+                oc = om.NewContext(side_ctx, ncpu, True)
                 lg = oc.Eval(PROMPT, 0)
                 tok = int(np.argmax(lg))
                 avx_logits = [lg]
@@ -318,18 +347,18 @@ def main():
                 oc.free()
             avx_dt = sorted(avx_samples)[1]
             # (A) "pure-Go-equivalent" scalar order = the PARITY reference: all cores only redistribute rows (same values)
-            oc = om.NewContext(ctx_size, ncpu, False)
+            oc = om.NewContext(side_ctx, ncpu, False)
             otoks, ologits = oc.GreedyDecode(PROMPT, nsteps + 1)
             oc.free()
             # (C) float64-accumulation truth leg: the yardstick for (A), (B) and the GPU's tree order
-            oc = om.NewContext(ctx_size, ncpu, 2)
+            oc = om.NewContext(side_ctx, ncpu, 2)
             ftoks, flogits = oc.GreedyDecode(PROMPT, nsteps + 1)
             oc.free()
-            oc = om.NewContext(ctx_size, ncpu, False)
+            oc = om.NewContext(side_ctx, ncpu, False)
             osampled = oc.SampleDecode(PROMPT, min(nsteps, 4) + 1, **SMP)
             oc.free()
             # one scalar step on ONE thread for the 1-thread figure of BASELINE.md row A
-            oc1 = om.NewContext(ctx_size, 1, False)
+            oc1 = om.NewContext(side_ctx, 1, False)
             t2 = time.perf_counter()
             oc1.Eval([7], 0)
             scalar1_dt = time.perf_counter() - t2
@@ -346,7 +375,7 @@ def main():
                 "weights_gen_s": round(t_gen, 1), "host_logical_cpus": os.cpu_count(),
             }
             # parity: GPU ids/logits (llama.Eval per token through ml_GraphCompute) vs the scalar-order checker on ALL compared steps
-            c2 = model.NewContext(ctx_size, 1)
+            c2 = model.NewContext(side_ctx, 1)
             c2.Eval(PROMPT, 0)
             gt, glog = [first], []
             for s in range(nsteps):
@@ -371,29 +400,29 @@ def main():
             }
         # ---- the reference's --pods on ONE GPU (server.go:88-101: MaxPods concurrent Do() over one Model): P streams whose decode
         # steps share one pass over the weights (lh_batch through the pipeline scheduler, world = 1) - aggregate tokens/s, not `value`
-        if not args.no_prefill:
+        if args.full and not args.no_prefill:
             try:
                 from llama_go_amd.mlapi import Pipeline
                 pb = {}
-                wb_tick, kv_row = bytes_per_token(d, L, F, V, P0 + W + (K + 1) / 2.0)
+                wb_tick, kv_row = bytes_per_token(d, L, F, V, P0 + max(WS, 1) + (KS + 1) / 2.0)
                 macs_row = L * (4 * d * d + 3 * d * F) + V * d   # weight MACs of one stream's token
                 for P in (4, 8, 16, 32, 64):
-                    plb = Pipeline(model, ctx_size, P, 0, 1)
-                    plb.run([PROMPT] * P, max(W, 1))
+                    plb = Pipeline(model, side_ctx, P, 0, 1)
+                    plb.run([PROMPT] * P, max(WS, 1))
                     torch.cuda.synchronize()
                     t_b = time.perf_counter()
-                    plb.run(None, K)
+                    plb.run(None, KS)
                     torch.cuda.synchronize()
                     d_b = time.perf_counter() - t_b
                     ids_b = [plb.tokens(i) for i in range(P)]
                     plb.free()
                     solo = [first] + toks   # the single stream's ids from the same prompt (timed region above)
                     n_c = min(len(solo), len(ids_b[0]))
-                    tick = d_b / K
+                    tick = d_b / KS
                     # a tick reads the weights once + every row's KV; its matmuls are P rows deep: both rooflines, the binding one named
                     f_hbm = (wb_tick + P * kv_row) / tick / (HBM_PEAK_GBPS * 1e9)
                     f_mfma = 2.0 * P * macs_row / tick / 157.3e12
-                    pb[str(P)] = {"tokens_per_s": round(P * K / d_b, 1), "ms_per_tick": round(tick * 1e3, 4),
+                    pb[str(P)] = {"tokens_per_s": round(P * KS / d_b, 1), "ms_per_tick": round(tick * 1e3, 4),
                                   "frac_of_hbm_roofline": round(f_hbm, 4), "frac_of_fp32_mfma_peak": round(f_mfma, 4), "bound": "hbm" if f_hbm >= f_mfma else "mfma",
                                   "ids_match_single_stream": all(t[:n_c] == solo[:n_c] for t in ids_b)}
                     if P >= 49 and not args.int8:   # 49..64 rows: k_stream_b9 - eight exact bf16 products per weight (round 6), priced against ITS pipe as well
@@ -411,7 +440,7 @@ def main():
         model.free()
         # ---- BASELINE config 3 beside the headline (not `value`): LLaMA-13B fp32, ONE Eval of 1024 tokens at past = 0 -> TFLOP/s on
         # the executed weight-matmul flops against the 157.3 TFLOP/s fp32 MFMA peak (tools/bench_prefill.py is the standalone form)
-        if not args.no_prefill and args.shape == "7B" and not args.layers:
+        if args.full and not args.no_prefill and args.shape == "7B" and not args.layers:
             try:
                 hp13 = make_hparams(**SHAPES["13B"], ctx=1024)
                 m13 = prod.NewSyntheticModel(hp13, SEED)
@@ -453,10 +482,10 @@ def main():
                 result["prefill_13b"] = {"error": str(e)}
         # ---- side objects the driver should see on the default line (not `value`): time to first token for the 8-token prompt, and
         # BASELINE config 4 (block-int8 weights) through the same resident decode loop
-        if args.shape == "7B" and not args.layers and not args.int8 and not args.no_prefill:
+        if args.full and args.shape == "7B" and not args.layers and not args.int8 and not args.no_prefill:
             try:
                 mt = prod.NewSyntheticModel(hp, SEED)
-                ct = mt.NewContext(ctx_size, 1)
+                ct = mt.NewContext(side_ctx, 1)
                 ct.Eval(PROMPT, 0)
                 tt = []
                 for _ in range(3):
@@ -492,18 +521,18 @@ def main():
                 result["prompt_8_tokens"]["ms_by_prompt_length"] = by_len
                 ct.free()
                 mt.QuantizeQ8()
-                cq = mt.NewContext(ctx_size, 1)
+                cq = mt.NewContext(side_ctx, 1)
                 fq = int(np.argmax(cq.Eval(PROMPT, 0)))
-                decode_greedy_resident(cq, fq, P0, W or 1)
+                decode_greedy_resident(cq, fq, P0, WS or 1)
                 torch.cuda.synchronize()
                 t_q = time.perf_counter()
-                tq, _ = decode_greedy_resident(cq, fq, P0, K)
+                tq, _ = decode_greedy_resident(cq, fq, P0, KS)
                 torch.cuda.synchronize()
                 dq = time.perf_counter() - t_q
                 mat = 4 * (L * (4 * d * d + 3 * d * F) + V * d)
                 qbytes = (wbytes_f32 - mat) + mat * 36 // 128
-                result["int8_decode"] = {"tokens_per_s": round(K / dq, 2), "ms_per_token": round(dq / K * 1e3, 4), "bytes_per_token": int(qbytes),
-                                         "frac_of_hbm_roofline": round(K / dq * qbytes / (HBM_PEAK_GBPS * 1e9), 4), "tokens": tq[: min(K, 16)],
+                result["int8_decode"] = {"tokens_per_s": round(KS / dq, 2), "ms_per_token": round(dq / KS * 1e3, 4), "bytes_per_token": int(qbytes),
+                                         "frac_of_hbm_roofline": round(KS / dq * qbytes / (HBM_PEAK_GBPS * 1e9), 4), "tokens": tq[: min(KS, 16)],
                                          "note": "BASELINE config 4: block-int8 weight matrices (36 B per 32 weights, format ours), same resident loop"}
                 # what a chain of dependent launches can reach: every launch costs t = 3.2 us + bytes / 7.0 TB/s (fit over the five fp32 decode launches of a
                 # layer; the five per layer are one all-to-all dependency chain), and the int8 streams are 3.55x shorter than the fp32 ones
@@ -532,16 +561,16 @@ def main():
                     from llama_go_amd.mlapi import Pipeline
                     pq8 = {}
                     for P in (4, 8, 16, 32):
-                        plq = Pipeline(mt, ctx_size, P, 0, 1)
-                        plq.run([PROMPT] * P, max(W, 1))
+                        plq = Pipeline(mt, side_ctx, P, 0, 1)
+                        plq.run([PROMPT] * P, max(WS, 1))
                         torch.cuda.synchronize()
                         t_b = time.perf_counter()
-                        plq.run(None, K)
+                        plq.run(None, KS)
                         torch.cuda.synchronize()
                         d_b = time.perf_counter() - t_b
                         idq = [plq.tokens(i) for i in range(P)]
                         plq.free()
-                        pq8[str(P)] = {"tokens_per_s": round(P * K / d_b, 1), "ms_per_tick": round(d_b / K * 1e3, 4), "all_streams_equal": all(t == idq[0] for t in idq)}
+                        pq8[str(P)] = {"tokens_per_s": round(P * KS / d_b, 1), "ms_per_tick": round(d_b / KS * 1e3, 4), "all_streams_equal": all(t == idq[0] for t in idq)}
                     result["int8_decode"]["pods_batched"] = pq8
                     cq.Eval(PROMPT, 0)
                     tq8 = []
@@ -556,22 +585,22 @@ def main():
                 # the ids of ALL timed steps + the last logits against the dequantise-then-fp32 checker on the full model (scalar Go order)
                 lgq = None
                 if not args.no_cpu_baseline:
-                    cq2 = mt.NewContext(ctx_size, 1)
+                    cq2 = mt.NewContext(side_ctx, 1)
                     glq = [cq2.Eval(PROMPT, 0)]
-                    for s_ in range(K):
+                    for s_ in range(KS):
                         glq.append(cq2.Eval([int(np.argmax(glq[-1]))], P0 + s_))
                     cq2.free()
                     gq_ids = [int(np.argmax(l_)) for l_ in glq]
                     orc_q = MLLib(os.path.join(ROOT, "oracle", "liboracle.so"))
                     omq = orc_q.NewSyntheticModel(hp, SEED)
                     omq.QuantizeQ8()
-                    ocq = omq.NewContext(ctx_size, ncpu_early, False)
-                    oq_ids, oq_lg = ocq.GreedyDecode(PROMPT, K + 1)
+                    ocq = omq.NewContext(side_ctx, ncpu_early, False)
+                    oq_ids, oq_lg = ocq.GreedyDecode(PROMPT, KS + 1)
                     ocq.free()
                     omq.free()
                     errq = float((np.abs(np.stack(glq).astype(np.float64) - oq_lg).max(axis=-1) / np.abs(oq_lg).max(axis=-1)).max())
-                    result["int8_decode"]["parity"] = {"ids_match": gq_ids == list(oq_ids) and gq_ids[1:] == tq[:K], "max_rel_logit_err": errq, "tolerance": 1e-4,
-                                                       "steps_compared": K + 1, "checker": "dequantise to fp32 (fl32(d*q)), then the fp32 Eval in scalar Go order"}
+                    result["int8_decode"]["parity"] = {"ids_match": gq_ids == list(oq_ids) and gq_ids[1:] == tq[:KS], "max_rel_logit_err": errq, "tolerance": 1e-4,
+                                                       "steps_compared": KS + 1, "checker": "dequantise to fp32 (fl32(d*q)), then the fp32 Eval in scalar Go order"}
                 cq.free()
                 mt.free()
             except Exception as e:  # a side measurement must never take the headline line down
@@ -607,13 +636,13 @@ def main():
 
         transport = {"kind": "host-staged over gloo (BENCH_SHARED_GPU)" if shared_gpu else "rccl"}
 
-        def new_pipeline(n_streams, max_rows=0):
+        def new_pipeline(n_streams, max_rows=0, ctx=ctx_size):
             if transport["kind"] == "rccl":
                 obj = [comm_unique_id(prod) if rank == 0 else None]   # ncclGetUniqueId on rank 0; any channel may carry the 128 bytes
                 dist.broadcast_object_list(obj, src=0)
                 pl, err = None, None
                 try:
-                    pl = Pipeline(model, ctx_size, n_streams, rank, R, comm_id=obj[0], max_rows=max_rows)   # ncclCommInitRank + per-stream stages, one HIP stream
+                    pl = Pipeline(model, ctx, n_streams, rank, R, comm_id=obj[0], max_rows=max_rows)   # ncclCommInitRank + per-stream stages, one HIP stream
                 except Exception as e:
                     err = f"rank {rank}: {e}"
                 errs = [None] * world
@@ -629,14 +658,14 @@ def main():
                 transport["kind"] = "host-staged over gloo (RCCL communicator failed: " + errs[0][:300] + ")"
                 if rank == 0:
                     print(f"[bench] RCCL pipeline failed ({errs[0]}); falling back to the host-staged transport", file=sys.stderr, flush=True)
-            return Pipeline(model, ctx_size, n_streams, rank, R, hooks=gloo_comm_hooks(dist), max_rows=max_rows)
+            return Pipeline(model, ctx, n_streams, rank, R, hooks=gloo_comm_hooks(dist), max_rows=max_rows)
 
-        def timed_phase(n_streams, max_rows=0):
-            pl = new_pipeline(n_streams, max_rows)
-            pl.run([PROMPT] * n_streams, W)   # prefill + W warm-up decode steps per stream (lh_pipeline_run); the pipeline drains at the end
+        def timed_phase(n_streams, max_rows=0, steps=K, warm=W, ctx=ctx_size):
+            pl = new_pipeline(n_streams, max_rows, ctx)
+            pl.run([PROMPT] * n_streams, warm)   # prefill + W warm-up decode steps per stream (lh_pipeline_run); the pipeline drains at the end
             sync_all()
             t0 = time.perf_counter()
-            pl.run(None, K)                   # K decode steps per stream, continuing each stream: includes pipeline fill + drain
+            pl.run(None, steps)               # K decode steps per stream, continuing each stream: includes pipeline fill + drain
             sync_all()
             tdt = torch.tensor([time.perf_counter() - t0], dtype=torch.float64)
             dist.all_reduce(tdt, op=dist.ReduceOp.MAX)
@@ -651,18 +680,21 @@ def main():
             fail(f"pipeline phase with {pods} streams", e)
         tokens_total = K * pods
         groups = pl.groups
-        prof = pl.profile_decode(1, P0, repeats=2)
-        b2b = {k["name"][:-4]: k for k in prof if k["name"].endswith("/b2b")}
-        prof = [k for k in prof if not k["name"].endswith("/b2b")]
-        dom = max(prof, key=lambda k: k["avg_us"] * k["launches"])
-        if dom["name"] in b2b:
-            dom = dict(b2b[dom["name"]], name=dom["name"])
-        result["roofline"] = {"bound": "hbm", "kernel": dom["name"], "achieved": round(dom["gbps"], 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                              "frac": round(dom["gbps"] / HBM_PEAK_GBPS, 4), "traffic": None, "bytes_per_launch": dom["bytes_per_launch"],
-                              "avg_us": round(dom["avg_us"], 2),
-                              "note": "the rank's batch-1 weight-stream kernel, HIP-event timed (the timed ticks carry several rows through the same stream: k_gemv_rows up to 4 rows per pass, the stream-GEMM kernels beyond)"}
         allt = all_ids[0]
         assert len(allt) == 1 + W + K, (len(allt), W, K)
+        if args.dump_outputs and rank == 0:   # the ids every stream's K timed steps produced (rank 0 receives them from the last stage)
+            dump_outputs(args.dump_outputs, {"tokens": np.asarray([ids[1 + W:] for ids in all_ids], np.float64)})
+        if args.full:
+            prof = pl.profile_decode(1, P0, repeats=2)
+            b2b = {k["name"][:-4]: k for k in prof if k["name"].endswith("/b2b")}
+            prof = [k for k in prof if not k["name"].endswith("/b2b")]
+            dom = max(prof, key=lambda k: k["avg_us"] * k["launches"])
+            if dom["name"] in b2b:
+                dom = dict(b2b[dom["name"]], name=dom["name"])
+            result["roofline"] = {"bound": "hbm", "kernel": dom["name"], "achieved": round(dom["gbps"], 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                                  "frac": round(dom["gbps"] / HBM_PEAK_GBPS, 4), "traffic": None, "bytes_per_launch": dom["bytes_per_launch"],
+                                  "avg_us": round(dom["avg_us"], 2),
+                                  "note": "the rank's batch-1 weight-stream kernel, HIP-event timed (the timed ticks carry several rows through the same stream: k_gemv_rows up to 4 rows per pass, the stream-GEMM kernels beyond)"}
         pl.free()
         # Side measurements from here on: a failure in one of them must not cost the headline line that is already measured.  A rank
         # that fails records the error; the ranks compare notes (gloo) behind every side phase and skip the remaining ones together, so nobody
@@ -674,12 +706,12 @@ def main():
 
         side_alive = True
         # ---- rounds 3-5's headline as a side object: 4 N streams, a tick = ONE 4-row pass over the rank's weights (lh_batch)
-        if pods == R and rows_per_pass_arg == 1:
+        if args.full and pods == R and rows_per_pass_arg == 1:
             err = None
             try:
-                pl4, dt4, ids4 = timed_phase(4 * R)
-                result["pods_batched_4n"] = {"tokens_per_s": round(4 * R * K / dt4, 2), "ms_per_step": round(dt4 / K * 1e3, 4), "streams": 4 * R, "groups": pl4.groups,
-                                             "rows_per_weight_pass": 4 * R // pl4.groups, "all_streams_equal_value_stream0": all(t == allt for t in ids4),
+                pl4, dt4, ids4 = timed_phase(4 * R, steps=KS, warm=WS, ctx=side_ctx)
+                result["pods_batched_4n"] = {"tokens_per_s": round(4 * R * KS / dt4, 2), "ms_per_step": round(dt4 / KS * 1e3, 4), "streams": 4 * R, "groups": pl4.groups,
+                                             "rows_per_weight_pass": 4 * R // pl4.groups, "all_streams_equal_value_stream0": all(t == allt[: len(t)] for t in ids4),
                                              "note": "more tokens per weight byte than `value`: compare with pods_batched['4'] of the N = 1 line, not with its single stream"}
                 pl4.free()
             except Exception as e:
@@ -689,13 +721,13 @@ def main():
                 result["pods_batched_4n"] = {"error": "; ".join(bad)}
                 side_alive = False
         # ---- second curve of SURVEY §8e in the same invocation: ONE greedy stream walking through the stages (latency, not throughput)
-        if pods != 1 and side_alive:
+        if args.full and pods != 1 and side_alive:
             err = None
             try:
-                pl1, dt1, ids1 = timed_phase(1)
+                pl1, dt1, ids1 = timed_phase(1, steps=KS, warm=WS, ctx=side_ctx)
                 pl1.free()
-                result["single_stream"] = {"tokens_per_s": round(K / dt1, 2), "ms_per_token": round(dt1 / K * 1e3, 4), "steps": K,
-                                           "ids_match_batched_stream0": ids1[0] == allt,
+                result["single_stream"] = {"tokens_per_s": round(KS / dt1, 2), "ms_per_token": round(dt1 / KS * 1e3, 4), "steps": KS,
+                                           "ids_match_batched_stream0": ids1[0] == allt[: len(ids1[0])],
                                            "note": "pods = 1: every token passes the stages one after the other (R weight-stream stages + R hops per token); not `value`"}
             except Exception as e:
                 err = f"rank {rank}: {e}"
@@ -705,10 +737,10 @@ def main():
                 side_alive = False
         # ---- where the time goes, per rank (not part of the timed runs above: three event records per tick): the rank's own stage, the
         # exchange behind it (RCCL: includes waiting for the predecessor, i.e. pipeline bubbles), and a pre-flight of the ring itself
-        if side_alive:
+        if args.full and side_alive:
             mine, err = None, None
             try:
-                pld = new_pipeline(pods, rows_per_pass_arg)
+                pld = new_pipeline(pods, rows_per_pass_arg, side_ctx)
                 pld.run([PROMPT] * pods, 2)
                 hop_us = pld.hop_probe(d * 4, 1000)          # one residual row (16 KB on 7B), every rank shifting at the same time
                 hop_us_tick = pld.hop_probe(d * 4 * max(1, pods // pld.groups), 200)   # the rows of one tick's exchange
@@ -731,20 +763,21 @@ def main():
                 result["pipeline_breakdown"] = {"by_rank": allst, "steps": min(K, 8), "streams": pods,
                                                 "note": "HIP events on each rank's compute stream around every tick's stage and exchange (lh_pipeline_profile); exchange includes waiting for the "
                                                         "predecessor's rows; hop_us = grouped send + receive round the ring (lh_pipeline_hop_probe)"}
-        else:
+        elif args.full:
             result["pipeline_breakdown"] = {"error": "skipped: the single-stream phase failed"}
-        # ---- parity: every stream saw the same prompt, so all of them must produce the ids of the single-GPU run (committed with the
-        # checker's verdict on them: tests/golden/7b_seed1234_ids.json, written by tools/make_golden_ids.py from a bench.py --gpus 1 run)
-        par = {"all_streams_equal": all(t == allt for t in all_ids), "ids_match_single_gpu": None}
-        gpath = os.path.join(ROOT, "tests", "golden", "7b_seed1234_ids.json")
-        if args.shape == "7B" and not args.layers and not args.int8 and os.path.exists(gpath):
-            gold = json.load(open(gpath))
-            n_cmp = min(len(allt), len(gold["ids"]))
-            par.update(ids_match_single_gpu=allt[:n_cmp] == gold["ids"][:n_cmp], ids_compared=n_cmp, golden="tests/golden/7b_seed1234_ids.json",
-                       golden_checked_against_oracle=gold.get("oracle_ids_match"))
-        else:
-            par["reason"] = "golden ids exist for the full fp32 7B model only"
-        result["parity"] = par
+        if args.full:
+            # ---- parity: every stream saw the same prompt, so all of them must produce the ids of the single-GPU run (committed with the
+            # checker's verdict on them: tests/golden/7b_seed1234_ids.json, written by tools/make_golden_ids.py from a bench.py --gpus 1 run)
+            par = {"all_streams_equal": all(t == allt for t in all_ids), "ids_match_single_gpu": None}
+            gpath = os.path.join(ROOT, "tests", "golden", "7b_seed1234_ids.json")
+            if args.shape == "7B" and not args.layers and not args.int8 and os.path.exists(gpath):
+                gold = json.load(open(gpath))
+                n_cmp = min(len(allt), len(gold["ids"]))
+                par.update(ids_match_single_gpu=allt[:n_cmp] == gold["ids"][:n_cmp], ids_compared=n_cmp, golden="tests/golden/7b_seed1234_ids.json",
+                           golden_checked_against_oracle=gold.get("oracle_ids_match"))
+            else:
+                par["reason"] = "golden ids exist for the full fp32 7B model only"
+            result["parity"] = par
         result["scaling_reference"] = {"ideal": f"{R} x value(N = 1)", "why": "N streams, one row per weight pass: each token reads every weight once on N GPUs as on one; "
                                        "value(N) / (N x value(1)) = efficiency of the layer shard (pipeline fill + drain of K + N - 1 ticks and the hops included)",
                                        "rows_per_weight_pass": max(1, pods // groups)}

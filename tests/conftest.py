@@ -28,6 +28,16 @@ def gpu_tests_passed():
     return lambda: _SESSION.get("gpu_passed", 0)
 
 
+@pytest.fixture(scope="session", autouse=True)
+def route_file(tmp_path_factory):
+    """Route log (include/llamahip.h lh_route_log; tests/test_gpu_zz_routes.py): mlapi.load_product switches it on at the FIRST load of the
+    product in a process, so the file is named before any test runs - in a whole-suite session not-gpu tests (test_abi, test_graph_twin)
+    load the product before the first gpu-marked test asks for it.  This process and the worker processes the pipeline tests spawn note the
+    kernel family of every launch; the workers append theirs to this file when they exit."""
+    os.environ.setdefault("LLAMAHIP_ROUTE_FILE", str(tmp_path_factory.mktemp("routes") / "routes.txt"))
+    return os.environ["LLAMAHIP_ROUTE_FILE"]
+
+
 @pytest.fixture(scope="session")
 def built():
     """Make sure every native library exists (build() is a no-op when they are up to date)."""
@@ -95,11 +105,8 @@ def oracle(built):
 
 
 @pytest.fixture(scope="session")
-def product(built, tmp_path_factory):
+def product(built, route_file):
     """The product: libllamago.so -> libllamahip.so -> MI355X.  No CPU fallback exists."""
-    # route log (include/llamahip.h lh_route_log; tests/test_gpu_zz_routes.py): this process and the worker processes the pipeline tests spawn
-    # note the kernel family of every launch; the workers append theirs to this file when they exit (mlapi.load_product)
-    os.environ.setdefault("LLAMAHIP_ROUTE_FILE", str(tmp_path_factory.mktemp("routes") / "routes.txt"))
     from llama_go_amd.mlapi import load_product
     lib = load_product()
     lib.lib.llamago_DeviceCount.restype = __import__("ctypes").c_int

@@ -33,7 +33,7 @@ def only_json(text):
 
 
 def test_two_rank_pipeline_reproduces_single_process_tokens(product):
-    args = ["--shape", "small", "--steps", "6", "--warmup", "1", "--no-cpu-baseline"]
+    args = ["--shape", "small", "--steps", "6", "--warmup", "1", "--full", "--no-cpu-baseline"]   # --full: the side objects asserted below
     env = dict(os.environ)
     env.pop("RANK", None), env.pop("WORLD_SIZE", None), env.pop("LOCAL_RANK", None)
     r1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + args, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
@@ -75,8 +75,9 @@ def _bench(args, env, nranks, launcher):
 
 def test_single_stream_and_self_spawned_ranks(product):
     """`bench.py --gpus 3 --pods 1` without a launcher: one greedy stream walking through three stages (SURVEY §8e single-stream
-    curve), ids equal to the 1-GPU run; and block-int8 weights through the same pipeline."""
-    args = ["--shape", "small", "--steps", "5", "--warmup", "1", "--no-cpu-baseline"]
+    curve), ids equal to the 1-GPU run; and block-int8 weights through the same pipeline.  (--full: the side phases of these lines launch
+    kernel families that tests/test_gpu_zz_routes.py counts.)"""
+    args = ["--shape", "small", "--steps", "5", "--warmup", "1", "--full", "--no-cpu-baseline"]
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
@@ -88,6 +89,26 @@ def test_single_stream_and_self_spawned_ranks(product):
     q1 = _bench(args + ["--int8"], env, 1, "self")
     q2 = _bench(args + ["--int8", "--pods", "2"], env2, 2, "self")
     assert q2["tokens_stream0"][:5] == q1["tokens_stream0"][:5]
+
+
+def test_plain_bench_line_and_dumped_outputs(product, tmp_path):
+    """A plain `bench.py --gpus 1` carries the headline and no side measurement, and `--dump-outputs DIR` writes what the timed path's caller
+    holds after its last step: the logits row (float32) and the ids the K timed steps produced - the ids the line itself reports."""
+    import numpy as np
+    from llama_go_amd.mlapi import SHAPES
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    out = tmp_path / "dump"
+    one = _bench(["--shape", "small", "--steps", "5", "--warmup", "1", "--dump-outputs", str(out)], env, 1, "self")
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(one)
+    assert one["steps"] == 5 and one["value"] > 0 and abs(one["ms_per_step"] - 1e3 / one["value"]) <= 1e-3 * one["ms_per_step"] + 1e-4
+    side = {"resident_loop", "sampled_decode", "kernels", "roofline", "cpu_baseline", "parity", "pods_batched", "prefill_13b", "prompt_8_tokens", "int8_decode"}
+    assert not side & set(one), sorted(side & set(one))
+    lg, tk = np.load(out / "logits.npy"), np.load(out / "tokens.npy")
+    assert lg.dtype == np.float32 and lg.shape == (SHAPES["small"]["vocab"],)
+    assert tk.dtype == np.float64 and [int(t) for t in tk] == one["tokens_stream0"] and len(tk) == 5
+    assert int(np.argmax(lg)) == int(tk[-1])
 
 
 @pytest.mark.parametrize("sample", [0, 1])
@@ -216,7 +237,7 @@ def test_real_rccl_two_ranks_when_the_box_has_two_gpus(product):
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "BENCH_SHARED_GPU"):
         env.pop(k, None)
-    two = _bench(["--steps", "8", "--warmup", "2", "--no-cpu-baseline"], env, 2, "torchrun")
+    two = _bench(["--steps", "8", "--warmup", "2", "--full", "--no-cpu-baseline"], env, 2, "torchrun")
     assert two["n_gpus"] == 2 and two["config"]["streams"] == 2
     assert "SHARED-GPU" not in two["config"]["parallelism"]
     assert two["parity"]["ids_match_single_gpu"] is True and two["parity"]["all_streams_equal"] is True, two["parity"]

@@ -2,10 +2,10 @@
 # round 5, evidence session: the bench line, kernel traces + counters of the final build, configs 3 / 4 / 5 side measurements
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/../..}" || exit 1
 bash tools/gpu_run.sh r5final \
-  bench \
-  "trace:f32:python bench.py --no-cpu-baseline --no-prefill" \
-  "pmc:f32:FETCH_SIZE:python bench.py --no-cpu-baseline --no-prefill" \
-  "trace:q8:python bench.py --int8 --no-cpu-baseline --no-prefill" \
+  bench:--full \
+  "trace:f32:python bench.py --full --no-cpu-baseline --no-prefill" \
+  "pmc:f32:FETCH_SIZE:python bench.py --full --no-cpu-baseline --no-prefill" \
+  "trace:q8:python bench.py --full --int8 --no-cpu-baseline --no-prefill" \
   "trace:pods16q8:python tools/bench_pods.py --int8 --pods 16 --steps 16" \
   "trace:p13:python tools/bench_prefill.py --shape 13B --n 1024 --layers 12" \
   "pmc:p13:SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE:python tools/bench_prefill.py --shape 13B --n 1024 --layers 6 --reps 1" \

@@ -57,5 +57,5 @@ if len(sys.argv) > 2:
     import os
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     from source_hash import kernel_source_hash
-    json.dump({"kernel_source_sha256": kernel_source_hash(), "source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE -- python bench.py --no-cpu-baseline --no-prefill, x2 gfx950 correction per MI355X_MICROARCH.md "
+    json.dump({"kernel_source_sha256": kernel_source_hash(), "source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE -- python bench.py --full --no-cpu-baseline --no-prefill, x2 gfx950 correction per MI355X_MICROARCH.md "
                          "(a separate profiling run of the same kernels, not a measurement of this bench run)", "bytes_per_launch": traffic}, open(sys.argv[2], "w"), indent=1)
