@@ -135,6 +135,14 @@ int lh_ctx_compute_stats(lh_ctx* ctx, lh_compute_stats* out);
 int lh_route_log(int on);
 int64_t lh_route_names(char* buf, uint64_t cap);
 
+/* Route trace (test instrumentation, per calling thread): while it is on, every matmul launch the thread enqueues appends the kernel's
+ * INSTANTIATION - template arguments and, where the launch has one, the split-K factor: "k_gemm_glds<2,2,2,1>/s3", "k_gemm_b9/s1",
+ * "k_gemv_cols<2,2,8>" - and the passes that belong to it ("k_split3_rows", "k_splitk_reduce"), in launch order, repeats included.
+ * Two different instantiations never give the same string.  lh_route_trace(1) clears the list and starts, lh_route_trace(0) stops
+ * (the list stays readable); lh_route_trace_read writes the list like lh_route_names.  Independent of the route log above. */
+int lh_route_trace(int on);
+int64_t lh_route_trace_read(char* buf, uint64_t cap);
+
 /* ---- convenience layer over the same fused plan executor (harnesses, bench, pipeline stages) ------
  * Describes the weights of llama.Model (llama.go:181-193) + one KV cache (llama.go:173-178) for the
  * layer range [layer0, layer1) held by this process. */

@@ -126,6 +126,36 @@ __global__ __launch_bounds__(256) void k_fill_synth(float* __restrict__ dst, uin
     }
 }
 
+// any value outside split_exact_values' range (common.h) in dev[0, n) -> *bad != 0
+__global__ __launch_bounds__(256) void k_split_range_check(const float* __restrict__ v, uint64_t n, unsigned int* bad) {
+    uint32_t acc = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
+        const uint32_t b = __builtin_bit_cast(uint32_t, v[i]);
+        acc |= (uint32_t)((b & 0x7fffffffu) != 0) & (uint32_t)(((b >> 23) & 0xffu) - 27u >= 228u);
+    }
+    if (acc) atomicOr(bad, 1u);
+}
+
+// marks the buffer unchecked when [off, off + n) of it holds a value outside the bf16 split's exact range: checked on the device after an
+// upload (a 13B model's 52 GB of fp32 weights in milliseconds; one thread on the host takes seconds).  Synchronises.
+static int check_split_range(lh_ctx* ctx, Buffer* b, uint64_t off, uint64_t n) {
+    if (b->unchecked.load(std::memory_order_relaxed) || n == 0) return LH_OK;
+    unsigned int* bad = nullptr;
+    unsigned int h = 0;
+    LH_HIP(ctx, hipMalloc((void**)&bad, sizeof(unsigned int)));
+    hipError_t e = hipMemsetAsync(bad, 0, sizeof(unsigned int), ctx->stream);
+    if (e == hipSuccess) {
+        LH_LAUNCH(k_split_range_check, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 4096)), dim3(256), 0, ctx->stream, b->dev + off, n, bad);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&h, bad, sizeof h, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    hipFree(bad);
+    if (e != hipSuccess) LH_FAIL(ctx, LH_EHIP, "check_split_range: %s", hipGetErrorString(e));
+    if (h) b->unchecked = true;
+    return LH_OK;
+}
+
 }  // namespace lh
 
 using namespace lh;
@@ -168,6 +198,18 @@ void route_note(const char* kernel_expr) {
     std::lock_guard<std::mutex> g(g_route_mu);
     for (const auto& s : g_route_names) if (s == n) return;
     g_route_names.push_back(n);
+}
+std::atomic<int> g_route_trace_threads{0};
+static thread_local bool t_trace_on = false;
+static thread_local std::vector<std::string> t_trace;
+bool route_trace_on() { return t_trace_on; }
+void route_trace(const char* fmt, ...) {
+    char b[128];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(b, sizeof b, fmt, ap);
+    va_end(ap);
+    t_trace.emplace_back(b);
 }
 }  // namespace lh
 
@@ -291,6 +333,10 @@ int lh_tensor_register(lh_ctx* ctx, uint64_t key, int dtype, const uint32_t ne[4
     if (host) LH_HIP(ctx, hipMemcpyAsync(b->dev, host, b->bytes, hipMemcpyHostToDevice, ctx->stream));
     else LH_HIP(ctx, hipMemsetAsync(b->dev, 0, b->bytes, ctx->stream));
     LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (host && dtype == 0) {
+        const int rc = check_split_range(ctx, b.get(), 0, n);
+        if (rc) { hipFree(b->dev); return rc; }
+    }
     std::lock_guard<std::mutex> lk(ds->mu);
     lh_buf id = ds->next_id++;
     if (key) ds->by_key[key] = id;
@@ -319,7 +365,7 @@ int lh_buf_upload(lh_ctx* ctx, lh_buf buf, uint64_t off, const float* host, uint
     LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     LH_HIP(ctx, hipMemcpyAsync(b->dev + off, host, n * 4, hipMemcpyHostToDevice, ctx->stream));
     LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LH_OK;
+    return check_split_range(ctx, b, off, n);
 }
 
 int lh_buf_read(lh_ctx* ctx, lh_buf buf, uint64_t off, float* dst, uint64_t n) {
@@ -343,6 +389,7 @@ int lh_buf_fill_synth(lh_ctx* ctx, lh_buf buf, uint64_t off, uint64_t n, uint64_
     const uint64_t key = mix64(seed ^ ((uint64_t)tensor_id * 0xD6E8FEB86659FD93ull));
     uint64_t blocks = (n + 255) / 256;
     if (blocks > 65536) blocks = 65536;
+    b->unchecked = true;   // (values the host never sees)
     LH_LAUNCH(k_fill_synth, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, b->dev + off, n, key, scale, offset);
     LH_HIP(ctx, hipGetLastError());
     return LH_OK;
@@ -412,6 +459,7 @@ int lh_buf_free(lh_ctx* ctx, lh_buf buf) {
 void* lh_buf_devptr(lh_ctx* ctx, lh_buf buf) {
     if (!ctx) return nullptr;
     Buffer* b = find_buffer(ctx->ds, buf);
+    if (b) b->unchecked = true;   // (the caller may write it by means the library does not see)
     return b ? (void*)b->dev : nullptr;
 }
 
@@ -425,6 +473,18 @@ int lh_route_log(int on) {
     if (on) { std::lock_guard<std::mutex> g(lh::g_route_mu); lh::g_route_names.clear(); }
     lh::g_route_log_on.store(on ? 1 : 0);
     return LH_OK;
+}
+int lh_route_trace(int on) {
+    if (on) lh::t_trace.clear();
+    if ((on != 0) != lh::t_trace_on) lh::g_route_trace_threads.fetch_add(on ? 1 : -1);
+    lh::t_trace_on = on != 0;
+    return LH_OK;
+}
+int64_t lh_route_trace_read(char* buf, uint64_t cap) {
+    std::string all;
+    for (const auto& s : lh::t_trace) { all += s; all += '\n'; }
+    if (buf && cap) { const size_t n = std::min<size_t>(all.size(), (size_t)cap - 1); memcpy(buf, all.data(), n); buf[n] = 0; }
+    return (int64_t)all.size() + 1;
 }
 int64_t lh_route_names(char* buf, uint64_t cap) {
     std::lock_guard<std::mutex> g(lh::g_route_mu);

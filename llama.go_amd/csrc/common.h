@@ -40,6 +40,16 @@ void route_note(const char* kernel_expr);
         if (lh::g_route_log_on.load(std::memory_order_relaxed)) lh::route_note(family); \
         hipLaunchKernelGGL(kern, __VA_ARGS__);                                      \
     } while (0)
+// Route trace (lh_route_trace; tests/test_gpu_matmul_routes.py): a per-thread, ordered list of the matmul INSTANTIATIONS launched - template
+// arguments and split count spelled out (k_gemm_glds<2,2,2,1>/s3), so that a test can name the one kernel a shape must take.  Every launch site
+// of a matmul kernel (and of the passes that belong to it: k_split3_rows, k_splitk_reduce) records one entry next to its LH_LAUNCH.
+extern std::atomic<int> g_route_trace_threads;   // threads with the trace on: the launch sites test this before the thread-local flag
+bool route_trace_on();
+void route_trace(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
+#define LH_TRACE(...)                                                                                          \
+    do {                                                                                                       \
+        if (lh::g_route_trace_threads.load(std::memory_order_relaxed) && lh::route_trace_on()) lh::route_trace(__VA_ARGS__); \
+    } while (0)
 
 #define LH_FAIL(ctx, code, ...)          \
     do {                                 \
@@ -61,7 +71,29 @@ struct Buffer {
     // every plan over the cache (the graph path's and the resident loop's) sees the same history, and a new cache starts without one;
     // created on first use (plan.hip: context swap of the generation loops, server.go:160-172).
     std::shared_ptr<std::vector<uint32_t>> kv_hist;
+    // set when the buffer may hold values the bf16-split kernels do not multiply exactly (split_exact_values below): an upload that had
+    // one, a device-side fill, a graph node that wrote into it, or its device address handed out (lh_buf_devptr).  Sticky.  The node
+    // path's long-prompt GEMM consults it (graph.hip, OP_MUL_MAT).  Limit: the fused LLaMA plan and the resident decode / batch loops write
+    // their KV caches without passing the node path and do not set it - no node-path MulMat takes a cache buffer as a plain 2-D operand, but one that did would be
+    // trusted.
+    std::atomic<bool> unchecked{false};
 };
+// true when every value is 0 or finite with |v| >= 2^-100: the range in which the exact bf16 split (split3, kernels_common.h) keeps all three
+// parts normal and every product of parts IEEE-exact.  Non-finite values (x - hi = inf - inf) and tiny ones (parts below 2^-126, at the mercy
+// of the matrix pipe's denormal handling) are outside it.
+inline bool split_exact_values(const float* v, uint64_t n) {
+    for (uint64_t i0 = 0; i0 < n; i0 += 4096) {   // blocks without an early exit inside: the compiler vectorises the loop
+        const uint64_t i1 = i0 + 4096 < n ? i0 + 4096 : n;
+        uint32_t bad = 0;
+        for (uint64_t i = i0; i < i1; ++i) {
+            uint32_t b;
+            memcpy(&b, v + i, 4);
+            bad |= (uint32_t)((b & 0x7fffffffu) != 0) & (uint32_t)(((b >> 23) & 0xffu) - 27u >= 228u);   // exponent field outside 27..254
+        }
+        if (bad) return false;
+    }
+    return true;
+}
 
 // Per-device shared state: buffer registry (Model is shared read-only across pods, server.go:45).
 struct DeviceState {

@@ -14,7 +14,7 @@
 namespace lh {
 
 int gemm_small_n(lh_ctx* ctx, const float* w, const float* x, float* y, const float* resid, uint32_t M, uint32_t K, uint32_t n,
-                 uint32_t ldx, uint32_t ldy, const char* name);  // plan.hip
+                 uint32_t ldx, uint32_t ldy, const char* name, bool split_ok = true);  // plan.hip
 
 enum { OP_NONE = 0, OP_ADD = 2, OP_MUL = 4, OP_REPEAT = 10, OP_SILU = 17, OP_RMS_NORM = 19, OP_MUL_MAT = 20, OP_SCALE = 21, OP_CPY = 22,
        OP_RESHAPE = 23, OP_VIEW = 24, OP_PERMUTE = 25, OP_TRANSPOSE = 26, OP_GET_ROWS = 27, OP_DIAG_MASK_INF = 28, OP_SOFT_MAX = 29, OP_ROPE = 30 };
@@ -401,8 +401,21 @@ static int run_node(lh_ctx* ctx, const lh_tensor* T, const std::vector<float*>& 
             if (a.dtype != 0) LH_FAIL(ctx, LH_EUNSUPPORTED, "MulMat: block-int8 weights are only supported inside the fused LLaMA plan");
             const bool plain2d = contiguous(a) && contiguous(b) && contiguous(t) && a.ne[2] == 1 && a.ne[3] == 1 && b.ne[2] == 1 && b.ne[3] == 1 &&
                                  a.ne[0] % 4 == 0 && a.ne[0] <= 24576 && a.ne[1] >= 256;
-            if (plain2d) return gemm_small_n(ctx, P[t.src0], P[t.src1], P[i], nullptr, a.ne[1], a.ne[0], b.ne[1], a.ne[0], a.ne[1], "mul_mat");
+            if (plain2d) {
+                // the long-prompt GEMM on the bf16 pipe (k_gemm_b9, N > 128 rows) multiplies exactly only values in split_exact_values' range
+                // (common.h): it takes operands the host has seen - host leafs scanned here, buffers whose uploads were scanned - and any
+                // other MulMat runs on the fp32 GEMM, which gives the reference's IEEE results for inf, NaN and tiny values.  Decided
+                // before anything is enqueued.
+                auto seen_exact = [&](int32_t j) {
+                    const lh_tensor& o = T[T[j].storage];
+                    if (o.buf) { const Buffer* bb = find_buffer_fast(ctx, o.buf); return bb && !bb->unchecked.load(std::memory_order_relaxed); }
+                    return o.op == OP_NONE && o.host && split_exact_values(o.host, nelem(o));
+                };
+                const bool split_ok = b.ne[1] > 128 && seen_exact(t.src0) && seen_exact(t.src1);
+                return gemm_small_n(ctx, P[t.src0], P[t.src1], P[i], nullptr, a.ne[1], a.ne[0], b.ne[1], a.ne[0], a.ne[1], "mul_mat", split_ok);
+            }
             const uint64_t outs = (uint64_t)a.ne[1] * a.ne[2] * a.ne[3] * b.ne[1];
+            LH_TRACE("g_mul_mat");
             LH_LAUNCH(g_mul_mat, dim3((unsigned)((outs + 3) / 4)), dim3(256), 0, st, V(t.src0), V(t.src1), V(i));
             break;
         }
@@ -516,11 +529,15 @@ int lh_graph_compute(lh_ctx* ctx, const lh_tensor* T, uint32_t n_leafs, uint32_t
     }
     std::vector<uint64_t> offs(total, 0);
     uint64_t arena = 0, stage = 0;
+    std::vector<char> written(total, 0);   // owners a node of this graph writes into
+    for (uint32_t i = 0; i < total; ++i)
+        if (T[i].op != OP_NONE) written[T[i].storage] = 1;
     for (uint32_t i = 0; i < total; ++i) {
         if ((uint32_t)T[i].storage != i) continue;
         if (T[i].buf) {
             Buffer* b = find_buffer(ctx->ds, T[i].buf);
             if (!b) LH_FAIL(ctx, LH_EINVAL, "tensor %u: unknown buffer %llu", i, (unsigned long long)T[i].buf);
+            if (written[i]) b->unchecked.store(true, std::memory_order_relaxed);
             if (b->nfloats < need[i]) LH_FAIL(ctx, LH_ESHAPE, "tensor %u: views reach %llu floats, buffer holds %llu", i, (unsigned long long)need[i], (unsigned long long)b->nfloats);
             continue;
         }

@@ -128,4 +128,19 @@ __device__ __forceinline__ void rope_rotate(float x0f, float x1f, double2 cs, fl
     *o1 = (float)__dadd_rn(__dmul_rn(x0, cs.y), __dmul_rn(x1, cs.x));
 }
 
+// x = hi + mid + lo exactly, each piece a bf16 (its 16 bits returned): the activation planes of the bf16-pipe matmuls (k_stream_q8b, k_stream_b9,
+// k_gemm_b9, k_gemm_q8b3).  Every producer of planes goes through here.  A non-finite x goes WHOLE into hi and mid = lo = 0 (x - hi would be
+// inf - inf = NaN, and a NaN whose payload sits in the low 16 bits would truncate to an infinite hi): +-inf stays +-inf, a NaN stays a NaN
+// (quiet, sign kept).  Finite x: hi = x with the low 16 bits cleared, mid / lo the same of the exact remainders - every piece has x's sign or is 0.
+__device__ __forceinline__ void split3(float x, uint32_t* hi, uint32_t* mid, uint32_t* lo) {
+    const uint32_t xb = __builtin_bit_cast(uint32_t, x);
+    const bool nonfinite = (xb & 0x7f800000u) == 0x7f800000u;
+    const uint32_t h = xb & 0xffff0000u;
+    const float r1 = nonfinite ? 0.f : __fsub_rn(x, __builtin_bit_cast(float, h));   // exact: the low 16 bits of x's significand
+    const uint32_t m = __builtin_bit_cast(uint32_t, r1) & 0xffff0000u;
+    const float r2 = __fsub_rn(r1, __builtin_bit_cast(float, m));                     // exact: <= 8 significant bits
+    *hi = (h >> 16) | ((nonfinite && (xb & 0x007fffffu)) ? 0x0040u : 0u);            // (NaN: the quiet bit keeps it one after truncation)
+    *mid = m >> 16; *lo = __builtin_bit_cast(uint32_t, r2) >> 16;
+}
+
 }  // namespace lh

@@ -3,7 +3,7 @@
 //
 // Why: v_mfma_f32_32x32x2_f32 runs at the fp32 VECTOR rate - 64 clocks per SIMD for 32 x 32 x 2 - and k_gemm_glds holds 0.80 of that peak
 // (profiles/r04_mfma_clock.txt).  v_mfma_f32_32x32x16_bf16 does 32 x 32 x 16 in 32 clocks: 16x the rate.  An fp32 number is exactly the sum
-// of three bf16 (8 + 8 + 8 significand bits: split3, kernels_stream.h), so
+// of three bf16 (8 + 8 + 8 significand bits: split3, kernels_common.h), so
 //     x * w = (xh + xm + xl) * (wh + wm + wl) = nine products of 8-bit significands, each EXACT in fp32,
 // i.e. nine bf16 MFMAs (288 clocks) do the work of eight fp32 MFMAs (512 clocks) with no narrow-precision input anywhere: what differs from
 // the fp32 instruction is only the order in which exact products meet in the fp32 accumulator (small terms first here), as any tiling changes
@@ -27,8 +27,17 @@
 // on the 13B matrices, 206 -> 191-197 ms for the 40-layer 1024-token prompt.  Scheduling is by hand (see the loop): the compiler's
 // sched_group_barrier solver gave up the interleave when one group could not be filled, and through the LDS-DMA builtin it drains the ring
 // (vmcnt(0)) before every operand read, so the DMA is inline asm.
-// Values: every product is exact for finite inputs whose three parts are normal bf16 numbers; parts below 2^-126 (inputs below ~2^-110)
-// are at the mercy of the matrix pipe's denormal handling, far below anything a model's activations or weights hold.
+// Products: EIGHT of the nine (xl * wl dropped, see the loop).
+// Values - the contract of every bf16-split matmul (this kernel, k_gemm_q8b3, k_stream_b9, k_stream_q8b):
+//   * finite inputs that are 0 or of magnitude >= 2^-100 (split_exact_values, common.h): every part is a normal bf16 and every product of
+//     parts exact; the result is within the fp32 GEMM's bound (tests/test_gpu_matmul_routes.py: C 2^-24 sum_k |x_k w_k|, C = 16);
+//   * smaller inputs: parts fall below 2^-126 and are at the mercy of the matrix pipe's denormal handling - up to sum over such k of
+//     |x_k w_k| more error;
+//   * non-finite inputs: split3 (kernels_common.h) puts a non-finite activation whole into its head (mid = lo = 0), so inf stays inf and NaN
+//     stays NaN, but hi * 0-part products of an infinity are NaN where the reference has +-inf, and an infinite WEIGHT splits into NaN parts
+//     (inf - inf) - the IEEE result is not promised.  The node path (graph.hip, OP_MUL_MAT) therefore sends a MulMat here only when the
+//     host has seen both operands inside the first range, and the fp32 GEMM otherwise; the fused LLaMA plan feeds model weights and
+//     RMSNorm rows.
 #pragma once
 #include "kernels_gemm.h"
 #include "kernels_stream.h"

@@ -344,11 +344,9 @@ struct AttnArgs {
     uint64_t out_plane;
 };
 __device__ __forceinline__ void attn_store_split3(const AttnArgs& a, size_t idx, float o) {
-    const uint32_t h = __builtin_bit_cast(uint32_t, o) & 0xffff0000u;
-    const float r1 = __fsub_rn(o, __builtin_bit_cast(float, h));
-    const uint32_t m = __builtin_bit_cast(uint32_t, r1) & 0xffff0000u;
-    const float r2 = __fsub_rn(r1, __builtin_bit_cast(float, m));
-    a.out_s3[idx] = (uint16_t)(h >> 16); a.out_s3[idx + a.out_plane] = (uint16_t)(m >> 16); a.out_s3[idx + 2 * a.out_plane] = (uint16_t)(__builtin_bit_cast(uint32_t, r2) >> 16);
+    uint32_t h, m, l;
+    split3(o, &h, &m, &l);
+    a.out_s3[idx] = (uint16_t)h; a.out_s3[idx + a.out_plane] = (uint16_t)m; a.out_s3[idx + 2 * a.out_plane] = (uint16_t)l;
 }
 
 constexpr int ATT_TH = 1024;

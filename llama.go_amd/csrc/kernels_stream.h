@@ -114,14 +114,6 @@ __device__ __forceinline__ void barrier_lds_only() {
     asm volatile("" ::: "memory");
 }
 
-// x = hi + mid + lo exactly, each piece a bf16 (its 16 bits returned): the activation format of k_stream_q8b (kernels_stream_q8b.h)
-__device__ __forceinline__ void split3(float x, uint32_t* hi, uint32_t* mid, uint32_t* lo) {
-    const uint32_t h = __builtin_bit_cast(uint32_t, x) & 0xffff0000u;
-    const float r1 = __fsub_rn(x, __builtin_bit_cast(float, h));          // exact: the low 16 bits of x's significand
-    const uint32_t m = __builtin_bit_cast(uint32_t, r1) & 0xffff0000u;
-    const float r2 = __fsub_rn(r1, __builtin_bit_cast(float, m));         // exact: <= 8 significant bits
-    *hi = h >> 16; *mid = m >> 16; *lo = __builtin_bit_cast(uint32_t, r2) >> 16;
-}
 // four consecutive features `row..row + 3` of token row `col` into the three output planes (StreamArgs::ys)
 __device__ __forceinline__ void stream_store_split3(const StreamArgs& a, uint32_t col, uint32_t row, f4 v) {
     uint32_t h[4], m[4], l[4];

@@ -1,4 +1,4 @@
-// csrc/kernels_stream_b9.h — fp32 weights, 17..64 token rows per weight pass, on the bf16 matrix pipe with EXACT products (round 6).
+// csrc/kernels_stream_b9.h — fp32 weights, 49..64 token rows per weight pass (B9S_MIN_ROWS..B9S_MAX_ROWS, plan.hip), on the bf16 matrix pipe with EXACT products (round 6).
 //     Y_g[c][m] (+ R_g[c][m]) = sum_k X[c][k] * W_g[m][k]        (ComputeForwardMulMatFP32, pkg/ml/ml.go:1976-2098)
 // The rows are a short prompt's tokens (server.Do feeds the prompt as ONE Eval, pkg/server/server.go:185-192) or the pods of a tick
 // (server.go:84-106).
@@ -6,7 +6,7 @@
 // Why: k_stream_dma (kernels_stream.h) multiplies on v_mfma_f32_16x16x4_f32, which issues at the fp32 VECTOR rate (32 clocks per SIMD for
 // 16 x 16 x 4); from 33 rows on its launches are bound by the matrix pipe, not by the weight stream (64 rows: w1|w3 of 7B 110-130 us against a
 // 53 us stream, matrix pipe 78 % busy), and the chip drops to 2.09 GHz beside the HBM stream.  An fp32 number is exactly the sum of three bf16
-// (8 + 8 + 8 significand bits: split3, kernels_stream.h), so
+// (8 + 8 + 8 significand bits: split3, kernels_common.h), so
 //     x * w = (xh + xm + xl) * (wh + wm + wl) = nine products of 8-bit significands, each EXACT in fp32,
 // i.e. nine v_mfma_f32_16x16x32_bf16 (9 x 16 clocks) contract what eight fp32 MFMAs (8 x 32 clocks) do, with no narrow-precision input
 // anywhere: what differs from the fp32 instruction is the order in which exact products meet in the fp32 accumulator (small terms first), as
@@ -33,7 +33,8 @@
 //   image per chunk: weights [MAXT * 16 rows][64 floats], dense (the DMA writes lane-linearly), 16-byte granule g of row r at position
 //     g ^ (r & 15) (a ds_read_b128 lane group - eight rows at slot s, eight at slot s ^ 1 - touches sixteen different positions); planes
 //     [3][NCT * 16 rows][64 bf16], 128-byte rows, granule g of row r at g ^ ((r >> 1) & 7) (two rows per bank line).
-// Values: every product is exact for finite inputs whose three parts are normal bf16 numbers (inputs above ~2^-110: kernels_gemm_b9.h).
+// Products: EIGHT of the nine (B9S_PRODUCTS, plan.hip; xl * wl, <= 2^-32 of its product, is dropped).
+// Values: the contract of kernels_gemm_b9.h - exact products for finite inputs of magnitude >= 2^-100 (or 0), nothing promised beyond.
 #pragma once
 #include "kernels_stream_q8b.h"
 

@@ -10,7 +10,7 @@
 // (16 clocks per SIMD for 16 x 16 x 32: 16x the rate) and stays EXACT:
 //   * a quant q (|q| <= 127) is exactly a bf16 (8 significand bits);
 //   * an fp32 activation is exactly the sum of three bf16: x = hi + mid + lo, each piece 8 consecutive bits of x's 24-bit significand
-//     (hi = x with the low 16 bits cleared, r = x - hi exact, mid = r with the low 16 bits cleared, lo = r - mid exact: split3 below);
+//     (hi = x with the low 16 bits cleared, r = x - hi exact, mid = r with the low 16 bits cleared, lo = r - mid exact: split3, kernels_common.h);
 //   * so every product q * piece is exact in fp32 (8 + 8 bits) and  sum_k q_k x_k  over one quant block (K = 32 = ONE MFMA per piece)
 //     = three MFMAs accumulating in fp32 - no narrow-precision input anywhere (SURVEY App. C forbids LOSSY narrow inputs);
 //   * the block scale multiplies the BLOCK SUM:  acc += d_block * (sum_k q_k x_k)  - one fma per output element and block.  Against the

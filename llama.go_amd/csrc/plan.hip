@@ -305,6 +305,7 @@ static int launch_cols(lh_ctx* ctx, const GemmColsArgs& a, const char* name) {
     if (rc) return rc;
     if (g_prepare_only) return 0;
     ProfScope ps(ctx->stream, name, (uint64_t)a.M * a.K * 4);
+    LH_TRACE("k_gemv_cols<%d,%d,%d,%d>", KI, U, TH, NC);
     LH_LAUNCH_AS("k_gemv_cols", kern, dim3(ctx->ds->num_cu), dim3(TH), FAT_LDS, ctx->stream, a);
     LH_HIP(ctx, hipGetLastError());
     return 0;
@@ -375,9 +376,11 @@ static int launch_gemm(lh_ctx* ctx, const GemmArgs& a0, const char* name, uint32
             a.part = ctx->splitk;
         }
         const uint64_t work = (uint64_t)tiles * batch * splits;
+        LH_TRACE("k_gemm_glds<%d,%d,%d,%d>/s%u", WN, WM, TN, TM, splits);
         LH_LAUNCH_AS("k_gemm_glds", kern, dim3((uint32_t)std::min<uint64_t>(work, (uint64_t)ncu)), dim3(256), lds, ctx->stream, a);
         if (splits > 1) {
             const uint64_t quads = (uint64_t)a.groups * a.N * (a.M / 4);
+            LH_TRACE("k_splitk_reduce");
             LH_LAUNCH(k_splitk_reduce, dim3((uint32_t)std::min<uint64_t>((quads + 255) / 256, 4096)), dim3(256), 0, ctx->stream, a);
         }
     } else {
@@ -386,6 +389,7 @@ static int launch_gemm(lh_ctx* ctx, const GemmArgs& a0, const char* name, uint32
         int rc = set_lds_once(ctx, kern, lds, flags[0]);
         if (rc) return rc;
         if (g_prepare_only) return 0;
+        LH_TRACE("k_gemm_mfma<%d,%d,%d,%d>", WN, WM, TN, TM);
         LH_LAUNCH_AS("k_gemm_mfma", kern, dim3(tiles, batch), dim3(256), lds, ctx->stream, a);
     }
     LH_HIP(ctx, hipGetLastError());
@@ -457,13 +461,16 @@ static int launch_gemm_q8b3(lh_ctx* ctx, GemmArgs a, const char* name, uint32_t 
     {
         TraceScope ts_(ctx->stream, "split3_rows");
         Split3Args sa = {a.x, xs, a.xs_plane, a.K, a.ldx, a.K};
+        LH_TRACE("k_split3_rows");
         LH_LAUNCH(k_split3_rows, dim3(a.N), dim3(256), 0, ctx->stream, sa);
     }
     const uint64_t items = (uint64_t)((a.N + 127) / 128) * ((a.M + 255) / 256) * a.groups * (splits > 1 ? splits : 1);
     ProfScope ps(ctx->stream, name, (uint64_t)a.M * a.K / 32 * 36 * a.groups);
+    LH_TRACE("k_gemm_q8b3<4>/s%u", splits > 1 ? splits : 1u);
     LH_LAUNCH_AS("k_gemm_q8b3", kern, dim3((uint32_t)std::min<uint64_t>(items, (uint64_t)ctx->ds->num_cu)), dim3(512), lds, ctx->stream, a);
     if (splits > 1) {
         const uint64_t quads = (uint64_t)a.groups * a.N * (a.M / 4);
+        LH_TRACE("k_splitk_reduce");
         LH_LAUNCH(k_splitk_reduce, dim3((uint32_t)std::min<uint64_t>((quads + 255) / 256, 4096)), dim3(256), 0, ctx->stream, a);
     }
     LH_HIP(ctx, hipGetLastError());
@@ -519,22 +526,26 @@ static int gemm_q8_group(lh_ctx* ctx, const float* x, uint32_t ldx, uint32_t gro
         const size_t lds = std::max<size_t>((size_t)2 * (128 + 160) * 32 * sizeof(float), 82 * 1024);
         if ((rc = set_lds_once(ctx, kern, lds, flags[1]))) return rc;
         if (g_prepare_only) return 0;
+        LH_TRACE("k_gemm_q8<4,1,1,5>/s%u", a.splits > 1 ? a.splits : 1u);
         LH_LAUNCH_AS("k_gemm_q8", kern, dim3(std::min<uint32_t>(items, ncu)), dim3(256), lds, ctx->stream, a);
     } else if (shape == 2) {
         auto kern = k_gemm_q8<2, 2, 1, 2>;
         const size_t lds = std::max<size_t>((size_t)2 * (64 + 128) * 32 * sizeof(float), 82 * 1024);
         if ((rc = set_lds_once(ctx, kern, lds, flags[2]))) return rc;
         if (g_prepare_only) return 0;
+        LH_TRACE("k_gemm_q8<2,2,1,2>/s%u", a.splits > 1 ? a.splits : 1u);
         LH_LAUNCH_AS("k_gemm_q8", kern, dim3(std::min<uint32_t>(items, ncu)), dim3(256), lds, ctx->stream, a);
     } else {
         auto kern = k_gemm_q8<2, 2, 2, 2>;
         const size_t lds = std::max<size_t>((size_t)2 * (128 + 128) * 32 * sizeof(float), 82 * 1024);
         if ((rc = set_lds_once(ctx, kern, lds, flags[0]))) return rc;
         if (g_prepare_only) return 0;
+        LH_TRACE("k_gemm_q8<2,2,2,2>/s%u", a.splits > 1 ? a.splits : 1u);
         LH_LAUNCH_AS("k_gemm_q8", kern, dim3(std::min<uint32_t>(items, ncu)), dim3(256), lds, ctx->stream, a);
     }
     if (a.splits > 1) {
         const uint64_t quads = (uint64_t)groups * n * (M / 4);
+        LH_TRACE("k_splitk_reduce");
         LH_LAUNCH(k_splitk_reduce, dim3((uint32_t)std::min<uint64_t>((quads + 255) / 256, 4096)), dim3(256), 0, ctx->stream, a);
     }
     LH_HIP(ctx, hipGetLastError());
@@ -664,6 +675,7 @@ static int launch_stream(lh_ctx* ctx, const StreamArgs& a, const char* name) {
     if (rc) return rc;
     if (g_prepare_only) return 0;
     ProfScope ps(ctx->stream, name, (uint64_t)a.groups * a.M * a.K * 4);
+    LH_TRACE("k_stream_mm2<%d,%d,%d>/s%u", MAXT, NCT, KC2, a.ksplit > 1 ? a.ksplit : 1u);
     LH_LAUNCH((k_stream_mm2<MAXT, NCT, KC2>), dim3(grid), dim3(2 * ST_TH), lds, ctx->stream, a);
     LH_HIP(ctx, hipGetLastError());
     return 0;
@@ -688,6 +700,7 @@ static int launch_stream_dma(lh_ctx* ctx, const StreamArgs& a, const char* name)
     if (g_prepare_only) return 0;
     const uint32_t grid = a.ksplit > 1 ? (uint32_t)ctx->ds->num_cu / a.ksplit * a.ksplit : (uint32_t)ctx->ds->num_cu;
     ProfScope ps(ctx->stream, name, (uint64_t)a.groups * a.M * a.K * 4);
+    LH_TRACE("k_stream_dma<%d,%d,%d,%d,%d,%d>/s%u", MAXT, NCT, KC, NIMG, (int)PIPE, CS, a.ksplit > 1 ? a.ksplit : 1u);
     LH_LAUNCH_AS("k_stream_dma", kern, dim3(grid), dim3(2 * ST_TH), lds, ctx->stream, a);
     LH_HIP(ctx, hipGetLastError());
     return 0;
@@ -845,6 +858,7 @@ static int launch_stream_q8b(lh_ctx* ctx, const StreamArgs& a, const char* name)
         if (g_prepare_only) return 0;
         const uint32_t grid = a.ksplit > 1 ? (uint32_t)ctx->ds->num_cu / a.ksplit * a.ksplit : (uint32_t)ctx->ds->num_cu;
         ProfScope ps(ctx->stream, name, (uint64_t)a.groups * a.M * a.K / 32 * 36);
+        LH_TRACE("k_stream_q8b<%d,%d,%d,%d,%d>/s%u", MAXT, NCT, KC, NIMG, XR, a.ksplit > 1 ? a.ksplit : 1u);
         LH_LAUNCH_AS("k_stream_q8b", kern, dim3(grid), dim3(Q8B_TH), lds, ctx->stream, a);
         LH_HIP(ctx, hipGetLastError());
         return 0;
@@ -899,6 +913,7 @@ static int launch_stream_b9(lh_ctx* ctx, const StreamArgs& a, const char* name) 
         if (g_prepare_only) return 0;
         const uint32_t grid = a.ksplit > 1 ? (uint32_t)ctx->ds->num_cu / a.ksplit * a.ksplit : (uint32_t)ctx->ds->num_cu;
         ProfScope ps(ctx->stream, name, (uint64_t)a.groups * a.M * a.K * 4);
+        LH_TRACE("k_stream_b9<%d,%d,%d,%d>/s%u", MAXT, NCT, NIMG, B9S_PRODUCTS, a.ksplit > 1 ? a.ksplit : 1u);
         LH_LAUNCH_AS("k_stream_b9", kern, dim3(grid), dim3(B9S_TH), lds, ctx->stream, a);
         LH_HIP(ctx, hipGetLastError());
         return 0;
@@ -1010,13 +1025,16 @@ static int launch_gemm_b9(lh_ctx* ctx, GemmArgs a, const char* name, uint32_t sp
     {
         TraceScope ts_(ctx->stream, "split3_rows");
         Split3Args sa = {a.x, ctx->xs3, a.xs_plane, a.K, a.ldx, a.K};
+        LH_TRACE("k_split3_rows");
         LH_LAUNCH(k_split3_rows, dim3(a.N), dim3(256), 0, ctx->stream, sa);
     }
     const uint64_t items = (uint64_t)((a.N + 127) / 128) * ((a.M + 255) / 256) * a.groups * (splits > 1 ? splits : 1);
     ProfScope ps(ctx->stream, name, (uint64_t)a.M * a.K * 4 * a.groups);
+    LH_TRACE("k_gemm_b9<1,8,4,1,2>/s%u", splits > 1 ? splits : 1u);
     LH_LAUNCH_AS("k_gemm_b9", kern, dim3((uint32_t)std::min<uint64_t>(items, (uint64_t)ctx->ds->num_cu)), dim3(512), lds, ctx->stream, a);
     if (splits > 1) {
         const uint64_t quads = (uint64_t)a.groups * a.N * (a.M / 4);
+        LH_TRACE("k_splitk_reduce");
         LH_LAUNCH(k_splitk_reduce, dim3((uint32_t)std::min<uint64_t>((quads + 255) / 256, 4096)), dim3(256), 0, ctx->stream, a);
     }
     LH_HIP(ctx, hipGetLastError());
@@ -1027,7 +1045,7 @@ static int launch_gemm_b9(lh_ctx* ctx, GemmArgs a, const char* name, uint32_t sp
 // the epilogue of the LDS-DMA tile GEMM; returns ST_NA when the launch cannot take it (short prompt, split-K, register-staged kernel) and
 // the caller runs the plain GEMM + the separate pass.
 int gemm_mfma_group(lh_ctx* ctx, const float* x, uint32_t ldx, uint32_t groups, const float* const* w, float* const* y, const float* const* r, uint32_t M,
-                    uint32_t K, uint32_t n, uint32_t ldy, const char* name, const GemmArgs* fused = nullptr) {
+                    uint32_t K, uint32_t n, uint32_t ldy, const char* name, const GemmArgs* fused = nullptr, bool split_ok = true) {
     if (n <= stream_max_rows() && !fused) {
         const int rs = gemm_stream_group(ctx, x, ldx, groups, w, y, r, M, K, n, ldy, name);
         if (rs != ST_NA) return rs;
@@ -1054,7 +1072,7 @@ int gemm_mfma_group(lh_ctx* ctx, const float* x, uint32_t ldx, uint32_t groups, 
     // up to 64 rows: 64 x 128 tiles (half the matrix work of a 128-row tile whose upper half would be padding)
     if (n <= 64) return launch_gemm<2, 2, 1, 2>(ctx, a, name);
     const double c128 = cost(128, 1.0), c160 = cost(160, 1.03), c64 = cost(64, 1.10);
-    if (gemm_b9_ok(a)) {
+    if (split_ok && gemm_b9_ok(a)) {
         const uint64_t tiles9 = (uint64_t)tn * ((a.M + 255) / 256) * a.groups;
         const uint32_t nkf = a.K / GBK;
         const double unit = may_split ? 2.0 * 128 * GBK / (157.3e6 / 256.0) : 1.0;      // cost() is in microseconds when split-K is on the table
@@ -1075,8 +1093,8 @@ int gemm_mfma_group(lh_ctx* ctx, const float* x, uint32_t ldx, uint32_t groups, 
 }
 
 static int gemm_mfma(lh_ctx* ctx, const float* w, const float* x, float* y, const float* resid, uint32_t M, uint32_t K, uint32_t n, uint32_t ldx,
-                     uint32_t ldy, const char* name) {
-    return gemm_mfma_group(ctx, x, ldx, 1, &w, &y, resid ? &resid : nullptr, M, K, n, ldy, name);
+                     uint32_t ldy, const char* name, bool split_ok) {
+    return gemm_mfma_group(ctx, x, ldx, 1, &w, &y, resid ? &resid : nullptr, M, K, n, ldy, name, nullptr, split_ok);
 }
 
 // Y[n][M] = X[n][K] . W[M][K]^T (+ resid).  N >= 32: fp32 MFMA GEMM (compute-bound side); smaller N: the weight-streaming
@@ -1084,12 +1102,13 @@ static int gemm_mfma(lh_ctx* ctx, const float* w, const float* x, float* y, cons
 static constexpr uint32_t MFMA_MIN_ROWS = 9;
 // block-int8: below this many tokens single-token steps on the int8 stream (2.1 ms each on 7B) beat the dequantising GEMM
 static constexpr uint32_t Q8_GEMM_MIN_ROWS = 9;
+// split_ok = false: the operands may hold values outside split_exact_values' range (common.h) - no launch on the bf16-split GEMM
 int gemm_small_n(lh_ctx* ctx, const float* w, const float* x, float* y, const float* resid, uint32_t M, uint32_t K, uint32_t n,
-                 uint32_t ldx, uint32_t ldy, const char* name) {
+                 uint32_t ldx, uint32_t ldy, const char* name, bool split_ok = true) {
     if (K % 4) LH_FAIL(ctx, LH_ESHAPE, "gemm %s: K=%u must be a multiple of 4", name, K);
     // from 9 rows on the MFMA GEMM (64-row tiles, split-K) beats two or more passes of the 8-column weight stream (7B, one Eval:
     // 8 rows 10.0 ms and 16 rows 18.4 ms on the stream; 17 rows 11.1 ms on the MFMA path)
-    if (n >= MFMA_MIN_ROWS && K % GBK == 0 && ldx % 4 == 0) return gemm_mfma(ctx, w, x, y, resid, M, K, n, ldx, ldy, name);
+    if (n >= MFMA_MIN_ROWS && K % GBK == 0 && ldx % 4 == 0) return gemm_mfma(ctx, w, x, y, resid, M, K, n, ldx, ldy, name, split_ok);
     if (n >= 2) {   // 2..8 rows on the general path: the streaming MFMA kernel
         const int rs = gemm_stream_group(ctx, x, ldx, 1, &w, &y, resid ? &resid : nullptr, M, K, n, ldy, name);
         if (rs != ST_NA) return rs;
@@ -1926,7 +1945,7 @@ int plan_eval(Plan* p, const uint32_t* tokens_host, const float* x_in_dev, float
         return rs;
     }
     static const int b9s_min = getenv("LLAMAHIP_B9S_MIN") ? atoi(getenv("LLAMAHIP_B9S_MIN")) : (int)B9S_MIN_ROWS;   // (A/B switch of round 6's measurements: 65 = off)
-    if (m.wtype == 0 && (int)n >= b9s_min && n <= B9S_MAX_ROWS) {   // fp32, 33..64 rows: the same schedule over planes on k_stream_b9 (nine exact bf16 products)
+    if (m.wtype == 0 && (int)n >= b9s_min && n <= B9S_MAX_ROWS) {   // fp32, 49..64 rows: the same schedule over planes on k_stream_b9 (eight of the nine exact bf16 products)
         const int rs = eval_q8b_layers(p, x, x_out_dev, n, past, last_row_only, bc);
         if (rs != ST_NA) return rs;   // (ST_NA comes back before anything is enqueued: the fp32-MFMA route below takes the Eval)
     }

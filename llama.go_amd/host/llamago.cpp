@@ -873,7 +873,8 @@ int llama_Eval(llama_context* lctx, llama_model* model, const uint32_t* tokens, 
     static const bool timing = getenv("LLAMAGO_TIMING") != nullptr;  // stderr: host-side phases of one Eval in microseconds
     const auto tp0 = std::chrono::steady_clock::now();
     auto us_since = [](std::chrono::steady_clock::time_point a) { return (long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - a).count(); };
-    static const bool no_fusion = getenv("LLAMAGO_NO_FUSION") && getenv("LLAMAGO_NO_FUSION")[0] == '1';
+    const char* nf_env = getenv("LLAMAGO_NO_FUSION");   // read on every call, as the N > 1 branch does (a test switches it inside one process)
+    const bool no_fusion = nf_env && nf_env[0] == '1';
     if (N == 1 && !no_fusion && g_keep_decode_graph.load(std::memory_order_relaxed)) {   // the decode loop (server.go:153-217): the kept graph of a one-token Eval, moved to this position
         const bool with_emb = !lctx->embedding.empty();
         eval_cache* c = lctx->decode_graph;

@@ -638,6 +638,25 @@ def _kernel_times(arr, n):
     return res
 
 
+def route_trace(fn):
+    """Run fn() with the calling thread's route trace on (include/llamahip.h lh_route_trace) and return (fn's result, the matmul instantiations
+    it launched, in order).  Test instrumentation."""
+    from . import LIBLLAMAHIP
+    hip = C.CDLL(LIBLLAMAHIP, mode=C.RTLD_GLOBAL)
+    hip.lh_route_trace.restype = C.c_int
+    hip.lh_route_trace.argtypes = [C.c_int]
+    hip.lh_route_trace_read.restype = C.c_int64
+    hip.lh_route_trace_read.argtypes = [C.c_char_p, C.c_uint64]
+    hip.lh_route_trace(1)
+    try:
+        res = fn()
+    finally:
+        hip.lh_route_trace(0)
+    buf = C.create_string_buffer(int(hip.lh_route_trace_read(None, 0)) + 16)
+    hip.lh_route_trace_read(buf, len(buf))
+    return res, buf.value.decode().split()
+
+
 _product = None
 
 

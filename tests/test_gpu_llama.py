@@ -369,6 +369,7 @@ def test_generic_path_matches_fused_and_oracle(product, oracle):
     os.environ["LLAMAGO_NO_FUSION"] = "1"
     try:
         g2 = c.Eval([42], 5)
+        assert product.lib.llamago_LastGraphFused(product.lib.llama_MLContext(c.h)) == 0   # the one-token step took the generic route too
     finally:
         del os.environ["LLAMAGO_NO_FUSION"]
     f2 = c2.Eval([42], 5)
