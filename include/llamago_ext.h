@@ -66,6 +66,17 @@ int llamago_ProfileDecode(llama_context* c, uint32_t token, uint32_t past, uint3
 /* One pipeline stage of Eval on the context's own KV cache (lh_llama_stage). */
 int llamago_Stage(llama_context* c, const uint32_t* tokens, const void* tokens_dev, const void* x_in_dev, void* x_out_dev, uint32_t n, uint32_t past,
                   void* logits_dev, void* argmax_dev);
+/* lh_score_rows on the model context's device: rows of host logits [n_rows][n_logits] scored against targets[row] (op-level parity). */
+int llamago_ScoreRows(const float* logits, uint32_t n_rows, uint32_t n_logits, const uint32_t* targets, lh_row_score* out);
+/* lh_llama_score on the context's own KV cache: llama.Eval of tokens[0..n) at pastCount with the lm_head for all n rows (llama.go:384), every row
+ * reduced on the device (softmax arithmetic llama.go:581-609); out[i] belongs to the logits behind tokens[i].  targets_or_null == NULL: row i against
+ * tokens[i+1], the last row against its own greedy id.  Leaves the cache as llama_Eval with the same arguments does. */
+int llamago_Score(llama_context* c, llama_model* m, const uint32_t* tokens, uint32_t n, uint32_t pastCount, const uint32_t* targets_or_null, lh_row_score* out);
+/* Perplexity of a token sequence.  Convention: the sequence is cut into consecutive windows of ctxSize tokens (the last one shorter; a window of
+ * one token is dropped); each window starts at position 0 and is evaluated in Evals of at most `chunk` rows (chunk = 0: 512) with advancing
+ * pastCount; row i of a window is scored against token i+1 of the window, the window's last row is not scored.  nll_sum = -sum logprob in f64,
+ * n_scored = the number of terms; perplexity = exp(nll_sum / n_scored).  The context's cache holds the last window afterwards. */
+int llamago_Perplexity(llama_context* c, llama_model* m, const uint32_t* tokens, uint32_t n_tokens, uint32_t chunk, double* nll_sum, uint64_t* n_scored);
 
 /* ModelParams.Embedding (llama.go:52, 88): from now on every llama_Eval also leaves row N-1 of `embeddings` (the final norm * weight rows,
  * llama.go:381, 414-419) in lctx.Embedding; llama_Embedding (llamago.h) returns it ([embd] floats; NULL when not enabled).  On the GPU the fused plan

@@ -207,6 +207,31 @@ int lh_sample_top_p_top_k(lh_ctx* ctx, const float* logits, uint32_t n_logits, c
 int lh_llama_decode_sample(lh_llama* m, const uint32_t* prompt, uint32_t n_prompt, uint32_t n_predict, uint32_t ring_size,
                            const lh_sample_params* sp, uint32_t* out_tokens);
 
+/* ---- scoring token sequences on the device ---------------------------------------------------------------------------
+ * The reference evaluates the lm_head for all N rows of an Eval (llama.go:384) and reads only the last (llama.go:394-401); its
+ * softmax takes exp in f64 (llama.go:581-609, ml.go:2491).  Per row x[0..V) with target id t:
+ *   m = max_j x_j;  s = sum_j exp_f64((double)x_j - (double)m) in f64;  lse = m + ln(s);  logprob = (double)x_t - lse.
+ * Entries equal to -inf add 0.  A row that holds a NaN, or whose maximum is +inf or -inf, gives logprob = lse = NaN; with a NaN in
+ * the row the other fields are unspecified except argmax < V. */
+typedef struct lh_row_score {
+    double   logprob;        /* ln p(targets[i] | row i) */
+    double   lse;            /* ln sum_j exp(x_j) of the row */
+    float    target_logit;   /* x[targets[i]] */
+    float    max_logit;      /* x[argmax] */
+    uint32_t argmax;         /* lowest index on ties: the greedy id of the generation loops */
+    uint32_t target_rank;    /* number of j with x_j > x_t, plus number of j < t with x_j == x_t (0 = the target is the greedy id) */
+} lh_row_score;
+/* One call on host logits [n_rows][n_logits] (op-level parity, the twin of lh_sample_top_p_top_k): uploads, scores every row against
+ * targets_host[row] on the device, returns after the stream drained.  targets_host[i] >= n_logits: LH_EINVAL, nothing is enqueued. */
+int lh_score_rows(lh_ctx* ctx, const float* logits_host, uint32_t n_rows, uint32_t n_logits, const uint32_t* targets_host, lh_row_score* out_host);
+/* llama.Eval of tokens[0..n) at position past with the lm_head for ALL n rows (llama.go:384), every row scored on the device:
+ * out_host[i] for the logits that follow tokens[i].  The [n][vocab] logits never leave the device; n * 32 bytes come back.
+ * targets == NULL: the next token, targets[i] = tokens[i+1]; the last row has none and is scored against its own greedy id
+ * (target_rank = 0).  The KV cache and the context's token history are left as lh_llama_eval with the same arguments leaves them.
+ * Whole-model plans, weight_dtype 0 and 7; a stage that lacks the lm_head (or the embeddings) returns LH_EUNSUPPORTED.  past + n
+ * beyond the window, a token or a target outside the vocabulary: LH_EINVAL before anything is enqueued. */
+int lh_llama_score(lh_llama* m, const uint32_t* tokens, uint32_t n, uint32_t past, const uint32_t* targets, lh_row_score* out_host);
+
 /* ---- pods in ONE weight pass (batched decode) ---------------------------------------------------------------------
  * The reference's only parallelism is request-level: Engine() starts up to MaxPods concurrent Do() goroutines
  * (pkg/server/server.go:84-106), each with its own llama.Context over the shared Model (server.go:151).  On the CPU they share

@@ -79,6 +79,8 @@ struct Plan {
     uint32_t* ring_dev = nullptr;             // lastNTokens ring
     uint32_t ring_cap = 0;
     uint32_t smp_topk = 0;                    // topK the sampler launches (and the captured graph) were chosen for
+    char* score_dev = nullptr;                // lh_llama_score: [score_cap] lh_row_score, then [score_cap] target ids
+    uint32_t score_cap = 0;
     uint32_t slot_counter = 0;   // round-robin over the pinned StepParams slots of eager (non-graph) steps
     bool use_graph = true;
     // Context swap of the generation loops (pkg/server/server.go:160-172): the token evaluated at every position of this plan's KV cache, as far as
@@ -122,6 +124,9 @@ void destroy_plans(lh_ctx* ctx);
 int sample_check(lh_ctx* ctx, const lh_sample_params* sp, uint32_t V);
 int sample_launch(lh_ctx* ctx, const float* logits, uint32_t V, SampleState* st, uint32_t* ring, StepParams* sp, uint32_t* out_tokens, uint32_t* token_out,
                   uint32_t* dbg_ids, float* dbg_probs, uint32_t* dbg_keep, int advance, uint32_t topk_hint);
+
+// score.hip
+int score_launch(lh_ctx* ctx, const float* logits, uint32_t n, uint32_t V, const uint32_t* targets, lh_row_score* out);
 
 }  // namespace lh
 

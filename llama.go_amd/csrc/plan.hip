@@ -1316,6 +1316,7 @@ void plan_destroy(Plan* p) {
     if (p->argmax_dev) hipFree(p->argmax_dev);
     if (p->attn_part) hipFree(p->attn_part);
     if (p->s3) hipFree(p->s3);
+    if (p->score_dev) hipFree(p->score_dev);
     delete p;
 }
 

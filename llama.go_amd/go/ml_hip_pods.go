@@ -134,6 +134,29 @@ func (st *StageHIP) Release() {
 	st.h = nil
 }
 
+// RowScoreHIP has the layout of lh_row_score (include/llamahip.h, 32 bytes): what one logits row says about its target id.
+type RowScoreHIP struct {
+	LogProb, LSE          float64 // ln p(target | row), ln sum exp of the row (f64 exp as in llama.go:581-609)
+	TargetLogit, MaxLogit float32
+	Argmax, TargetRank    uint32 // greedy id (lowest index on ties); 0 = the target is the greedy id
+}
+
+// Score is llama.Eval (llama.go:211-426) of tokens at pastCount on a whole-model stage with the lm_head for ALL rows (llama.go:384), every
+// row reduced on the device: the [N][vocab] logits stay in HBM, 32 bytes per row come back.  targets == nil scores row i against
+// tokens[i+1] and the last row against its own greedy id.  The KV cache is left as Eval leaves it.  C++ twin: llamago_Score.
+func (st *StageHIP) Score(tokens []uint32, pastCount uint32, targets []uint32) []RowScoreHIP {
+	out := make([]RowScoreHIP, len(tokens))
+	var tg *C.uint32_t
+	if targets != nil {
+		tg = (*C.uint32_t)(unsafe.Pointer(&targets[0]))
+	}
+	if rc := C.lh_llama_score(st.h, (*C.uint32_t)(unsafe.Pointer(&tokens[0])), C.uint32_t(len(tokens)), C.uint32_t(pastCount), tg,
+		(*C.lh_row_score)(unsafe.Pointer(&out[0]))); rc != 0 {
+		hipHalt(st.ctx.hip.ctx)
+	}
+	return out
+}
+
 // ---- the pods of ONE GPU in one weight pass (include/llamahip.h: lh_batch_*) --------------------------------------------
 // server.Engine starts up to MaxPods concurrent Do() goroutines over one Model (server.go:84-106, 151).  With UseHIP the engine
 // instead keeps ONE BatchHIP per GPU: every pod is a row; Prompt() evaluates the pods' prompts, each Tick() advances every pod by

@@ -1187,6 +1187,47 @@ int llamago_Stage(llama_context* c, const uint32_t* tokens, const void* tokens_d
         return halt_rc(lh_last_error(c->mlctx->hip));
     return 0;
 }
+// ---- scoring (lh_score_rows / lh_llama_score): per-row log-probs, greedy ids and perplexity without the [N][vocab] logits on the host ----
+int llamago_ScoreRows(const float* logits, uint32_t n_rows, uint32_t n_logits, const uint32_t* targets, lh_row_score* out) {
+    lh_ctx* h = model_ctx();
+    if (!h) return 1;
+    if (lh_score_rows(h, logits, n_rows, n_logits, targets, out)) return halt_rc(lh_last_error(h));
+    return 0;
+}
+int llamago_Score(llama_context* c, llama_model* m, const uint32_t* tokens, uint32_t n, uint32_t pastCount, const uint32_t* targets_or_null, lh_row_score* out) {
+    if (!c || c->model != m) return halt_rc("llamago_Score: context does not belong to this model");
+    if (!tokens || !out) return halt_rc("llamago_Score: null argument");
+    lh_llama* r = resident(c);
+    if (!r) return 1;
+    if (lh_llama_score(r, tokens, n, pastCount, targets_or_null, out)) return halt_rc(lh_last_error(c->mlctx->hip));
+    return 0;
+}
+int llamago_Perplexity(llama_context* c, llama_model* m, const uint32_t* tokens, uint32_t n_tokens, uint32_t chunk, double* nll_sum, uint64_t* n_scored) {
+    if (!c || c->model != m) return halt_rc("llamago_Perplexity: context does not belong to this model");
+    if (!tokens || !nll_sum || !n_scored) return halt_rc("llamago_Perplexity: null argument");
+    lh_llama* r = resident(c);
+    if (!r) return 1;
+    if (chunk == 0) chunk = 512;
+    const uint32_t win = c->ctxSize;
+    std::vector<lh_row_score> rows(std::min(chunk, win));
+    std::vector<uint32_t> tgt(rows.size());
+    double sum = 0.0;
+    uint64_t terms = 0;
+    for (uint32_t w0 = 0; w0 < n_tokens; w0 += win) {
+        const uint32_t len = std::min(win, n_tokens - w0);
+        if (len < 2) break;   // a window of one token has nothing to predict
+        const uint32_t* wt = tokens + w0;
+        for (uint32_t off = 0; off < len; off += chunk) {
+            const uint32_t n = std::min(chunk, len - off);
+            for (uint32_t i = 0; i < n; i++) tgt[i] = wt[std::min(off + i + 1, len - 1)];   // (the window's last row is evaluated, not scored: any valid id)
+            if (lh_llama_score(r, wt + off, n, off, tgt.data(), rows.data())) return halt_rc(lh_last_error(c->mlctx->hip));
+            for (uint32_t i = 0; i < n && off + i + 1 < len; i++) { sum -= rows[i].logprob; terms++; }
+        }
+    }
+    *nll_sum = sum;
+    *n_scored = terms;
+    return 0;
+}
 // ---- the pods of one GPU in ONE weight pass (lh_batch): contexts of the same model, one KV cache each --------------------------
 // All contexts must have been created on the same ml.Context stream: llama_NewContext makes one lh_ctx per context, so a batch is built
 // over contexts that SHARE one - llamago_NewBatchContexts creates them.

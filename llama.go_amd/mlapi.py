@@ -356,6 +356,35 @@ class Context:
             raise MLError(f"llama_SampleDecode: {self.ml.last_error()}")
         return list(out)
 
+    def Score(self, tokens, pastCount, targets=None):
+        """llamago_Score: llama.Eval of `tokens` at pastCount with the lm_head for every row (llama.go:384), each row reduced on the device.
+        Returns a structured array (ROW_SCORE_DTYPE) with one record per token; targets=None scores row i against tokens[i+1] and the
+        last row against its own greedy id."""
+        L = self.ml.lib
+        L.llamago_Score.restype = C.c_int
+        L.llamago_Score.argtypes = [VP, VP, c_u32p, c_u32, c_u32, c_u32p, C.POINTER(RowScore)]
+        n = len(tokens)
+        toks = (c_u32 * max(n, 1))(*[int(t) for t in tokens])
+        tg = None
+        if targets is not None:
+            assert len(targets) == n, (len(targets), n)
+            tg = (c_u32 * max(n, 1))(*[int(t) for t in targets])
+        out = (RowScore * max(n, 1))()
+        if L.llamago_Score(self.h, self.model.h, toks, n, int(pastCount), tg, out):
+            raise MLError(f"llamago_Score: {self.ml.last_error()}")
+        return np.frombuffer(out, dtype=ROW_SCORE_DTYPE, count=n).copy()
+
+    def Perplexity(self, tokens, chunk=0):
+        """llamago_Perplexity (convention: include/llamago_ext.h) -> (nll_sum, n_scored); perplexity = exp(nll_sum / n_scored)."""
+        L = self.ml.lib
+        L.llamago_Perplexity.restype = C.c_int
+        L.llamago_Perplexity.argtypes = [VP, VP, c_u32p, c_u32, c_u32, C.POINTER(C.c_double), C.POINTER(c_u64)]
+        toks = (c_u32 * max(len(tokens), 1))(*[int(t) for t in tokens])
+        nll, cnt = C.c_double(0), c_u64(0)
+        if L.llamago_Perplexity(self.h, self.model.h, toks, len(tokens), int(chunk), C.byref(nll), C.byref(cnt)):
+            raise MLError(f"llamago_Perplexity: {self.ml.last_error()}")
+        return float(nll.value), int(cnt.value)
+
     def free(self):
         if self.h:
             self.ml.lib.llama_ReleaseContext(self.h)
@@ -378,6 +407,31 @@ def usable_threads():
 class KernelTime(C.Structure):
     """lh_kernel_time (include/llamahip.h)."""
     _fields_ = [("name", C.c_char * 48), ("launches", c_u32), ("total_ms", C.c_float), ("bytes_per_launch", c_u64)]
+
+
+class RowScore(C.Structure):
+    """lh_row_score (include/llamahip.h)."""
+    _fields_ = [("logprob", C.c_double), ("lse", C.c_double), ("target_logit", C.c_float), ("max_logit", C.c_float), ("argmax", c_u32),
+                ("target_rank", c_u32)]
+
+
+ROW_SCORE_DTYPE = np.dtype([("logprob", "<f8"), ("lse", "<f8"), ("target_logit", "<f4"), ("max_logit", "<f4"), ("argmax", "<u4"), ("target_rank", "<u4")])
+
+
+def score_rows(ml, logits, targets):
+    """llamago_ScoreRows: every row of host logits [n_rows][V] scored against targets[row] on the device (lh_score_rows)."""
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    if lg.ndim == 1:
+        lg = lg[None, :]
+    n, V = lg.shape
+    assert len(targets) == n, (len(targets), n)
+    ml.lib.llamago_ScoreRows.restype = C.c_int
+    ml.lib.llamago_ScoreRows.argtypes = [c_f32p, c_u32, c_u32, c_u32p, C.POINTER(RowScore)]
+    tg = (c_u32 * max(n, 1))(*[int(t) for t in targets])
+    out = (RowScore * max(n, 1))()
+    if ml.lib.llamago_ScoreRows(lg.ctypes.data_as(c_f32p), n, V, tg, out):
+        raise MLError(f"llamago_ScoreRows: {ml.last_error()}")
+    return np.frombuffer(out, dtype=ROW_SCORE_DTYPE, count=n).copy()
 
 
 def _bind_extensions(ml):

@@ -95,6 +95,12 @@ if ("pipeline_groups" in flt or not flt) and "--search" not in sys.argv:
         rng = np.random.default_rng(21)
         report(f"pipeline_groups int8={int8}", streams(hp, 17, tb.make_prompts(rng, hp.vocabSize, [5, 1, 8, 2, 12, 3]), 6, 40, int8))
 
+if ("score" in flt or not flt) and "--search" not in sys.argv:
+    import test_gpu_score as ts  # noqa: E402
+    for name in ts.CONFIGS:      # every row of the scored sequences (tests/test_gpu_score.py asserts the greedy id of each); another sequence: SEQ_SEED there
+        rows = ts.checker_rows(orc, name)
+        report(f"score {name} sequence seed={ts.SEQ_SEED[name]} rows={len(rows)}", margin(rows))
+
 # --search: model seeds for the batched-decode configurations whose default seed leaves a near-tie (usage: ... --search <config index> <n seeds>)
 if "--search" in sys.argv:
     i = sys.argv.index("--search")
