@@ -48,6 +48,10 @@ int llamago_TimeComputes(llama_context* c, int on);  /* lh_ctx_time_computes on 
 int llamago_ComputeStats(llama_context* c, uint64_t* calls, double* wall_us, double* device_us);   /* lh_ctx_compute_stats */
 int llamago_LastGraphFused(ml_context* ctx);         /* 1 if the last ml_GraphCompute ran as the fused LLaMA plan */
 int llamago_GraphComputeNoFusion(ml_context* ctx, ml_graph* g);   /* ml_GraphCompute node by node with the generic kernels (op-level parity) */
+/* Test instrumentation: overwrites one fp32 tensor of the model ("layers.0.attention.wq.weight", "norm.weight", ...: llama_ModelTensor's names) in HBM with
+ * `n` host floats, row-major as llama_ModelTensor / ml_TensorRead show it (lh_buf_upload).  Fails (non-zero, ml_LastError) on an unknown name, n different from
+ * the tensor's element count, a block-int8 tensor, or a model with live contexts / batches / pipelines (their plans may hold derived copies). */
+int llamago_SetModelTensor(llama_model* m, const char* name, const float* data, uint64_t n);
 
 /* ---- [product] harness helper of the kept decode graph (no GPU needed) -------------------------------------------------- */
 /* The array llama_Eval hands to lh_graph_compute for N tokens (ids 1..N) at pastQuery, as numbers: per tensor 16 int64 = op, dtype, flags, ne[4],

@@ -139,7 +139,11 @@ int64_t lh_route_names(char* buf, uint64_t cap);
  * INSTANTIATION - template arguments and, where the launch has one, the split-K factor: "k_gemm_glds<2,2,2,1>/s3", "k_gemm_b9/s1",
  * "k_gemv_cols<2,2,8>" - and the passes that belong to it ("k_split3_rows", "k_splitk_reduce"), in launch order, repeats included.
  * Two different instantiations never give the same string.  lh_route_trace(1) clears the list and starts, lh_route_trace(0) stops
- * (the list stays readable); lh_route_trace_read writes the list like lh_route_names.  Independent of the route log above. */
+ * (the list stays readable); lh_route_trace_read writes the list like lh_route_names.  Independent of the route log above.
+ * The fused plan's attention launch sites record theirs too (tests/test_gpu_attention_bound.py): "k_attention/hd128/n1" ("k_attention/rows/..." when
+ * every query row has its own cache and position), "k_attention_split/c9/n1" + "k_attention_combine/c9/n1" (c = key chunks), "k_attn_flash/uncut/p1" or
+ * "k_attn_flash/cut/p3" + "k_attn_flash_combine/p3" (p = the most parts a block is cut into), and "attention_gemm/hd64/n70" in front of its four
+ * launches (the QK GEMM's entry, "k_softmax_causal", "k_transpose_v", the PV GEMM's entry).  A launch replayed from a captured graph records nothing. */
 int lh_route_trace(int on);
 int64_t lh_route_trace_read(char* buf, uint64_t cap);
 

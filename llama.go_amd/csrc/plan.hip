@@ -578,6 +578,7 @@ static int attention_gemm(Plan* p, const float* q, const float* kc, const float*
         p->vt_cap = need_v;
     }
     int rc;
+    LH_TRACE("attention_gemm/hd%u/n%u", hd, n);   // (its four launches follow: the QK GEMM, k_softmax_causal, k_transpose_v, the PV GEMM)
     {   // S[h][j][t] = sum_c Q[j][h*hd + c] * K[t][h*hd + c]
         GemmArgs a = {};
         a.x = q; a.w[0] = kc; a.y[0] = p->scores; a.groups = 1; a.N = n; a.M = T; a.K = hd; a.ldx = d; a.ldw = d; a.ldy = Tp;
@@ -585,7 +586,9 @@ static int attention_gemm(Plan* p, const float* q, const float* kc, const float*
         a.causal = 1; a.past = past;
         if ((rc = launch_gemm<2, 2, 2, 2>(ctx, a, "attn_qk_gemm", H))) return rc;
     }
+    LH_TRACE("k_softmax_causal");
     LH_LAUNCH(k_softmax_causal, dim3(n, H), dim3(256), 0, ctx->stream, p->scores, n, Tp, past, scale);
+    LH_TRACE("k_transpose_v");
     LH_LAUNCH(k_transpose_v, dim3(Tp / 32, hd / 32, H), dim3(256), 0, ctx->stream, vc, p->vt, T, Tp, d, hd);
     LH_HIP(ctx, hipGetLastError());
     {   // O[j][h*hd + c] = sum_t P[h][j][t] * VT[h][c][t]
@@ -631,10 +634,12 @@ static int attention_flash(Plan* p, const float* q, const float* kc, const float
     const uint32_t items = (a.nwork ? a.nwork : a.nqb) * m.H, grid = std::min<uint32_t>(items, slots);
     {
         ProfScope ps(ctx->stream, "attn_flash", (uint64_t)2 * (past + n) * m.d * 4);
+        LH_TRACE("k_attn_flash/%s/p%u", cut ? "cut" : "uncut", cut ? w.pmax : 1u);
         LH_LAUNCH(k_attn_flash, dim3(grid), dim3(FA_TH), FA_LDS_BYTES, ctx->stream, a);
     }
     if (cut) {
         ProfScope ps(ctx->stream, "attn_flash_combine", (uint64_t)m.H * (a.nqb - w.qb_cut) * w.pmax * FA_BQ * FA_PSTRIDE * 4);
+        LH_TRACE("k_attn_flash_combine/p%u", w.pmax);
         LH_LAUNCH(k_attn_flash_combine, dim3(m.H, a.nqb - w.qb_cut), dim3(256), 0, ctx->stream, a);
     }
     LH_HIP(ctx, hipGetLastError());
@@ -1205,6 +1210,7 @@ static int launch_attention(lh_ctx* ctx, const AttnArgs& a, uint32_t max_T) {
     if (g_prepare_only) return 0;
     if (g_only) return 0;
     ProfScope ps(ctx->stream, "attention", (uint64_t)2 * max_T * a.d * 4);
+    LH_TRACE("k_attention%s/hd%u/n%u", a.rows ? "/rows" : "", a.hd, a.n);
     LH_LAUNCH(k_attention, dim3(a.d / a.hd, a.n), dim3(ATT_TH), lds, ctx->stream, a);
     LH_HIP(ctx, hipGetLastError());
     return 0;
@@ -1220,10 +1226,12 @@ static int launch_attention_split(Plan* p, const AttnArgs& a, float* part) {
     if (g_prepare_only || g_only) return 0;
     {
         ProfScope ps(ctx->stream, "attention_split", (uint64_t)2 * m.ctx * a.d * 4 * nrows);
+        LH_TRACE("k_attention_split%s/c%u/n%u", a.rows ? "/rows" : "", nch, nrows);
         LH_LAUNCH(k_attention_split, dim3(m.H, nch, nrows), dim3(ATT_TH), 0, ctx->stream, a, part);
     }
     {
         ProfScope ps(ctx->stream, "attention_combine", (uint64_t)m.H * nch * (a.hd + 2) * 4 * nrows);
+        LH_TRACE("k_attention_combine/c%u/n%u", nch, nrows);
         LH_LAUNCH(k_attention_combine, dim3(m.H, nrows), dim3(128), 0, ctx->stream, a, (const float*)part, nch);
     }
     LH_HIP(ctx, hipGetLastError());

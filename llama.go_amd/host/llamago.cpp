@@ -1453,6 +1453,21 @@ int llamago_QuantizeModelQ8(llama_model* m) {
     if (!rc) m->wtype = ML_TYPE_Q8_0;
     return rc;
 }
+// Test instrumentation (tests/test_gpu_attention_bound.py: the probe layer): one fp32 tensor of the model replaced by host values.
+int llamago_SetModelTensor(llama_model* m, const char* name, const float* data, uint64_t n) {
+    if (!m || !name || !data) return halt_rc("llamago_SetModelTensor: null argument");
+    { std::lock_guard<std::mutex> lk(m->mu);
+      if (m->users > 0) return halt_rc("llamago_SetModelTensor: contexts of this model are alive (their plans address the weights); set tensors before creating contexts"); }
+    ml_tensor* t = llama_ModelTensor(m, name);
+    char msg[256];
+    if (!t) { snprintf(msg, sizeof msg, "llamago_SetModelTensor: the model has no tensor \"%s\"", name); return halt_rc(msg); }
+    if (t->type != ML_TYPE_F32) { snprintf(msg, sizeof msg, "llamago_SetModelTensor: \"%s\" is quantised (set tensors before llamago_QuantizeModelQ8)", name); return halt_rc(msg); }
+    if (n != nelements(t)) { snprintf(msg, sizeof msg, "llamago_SetModelTensor: \"%s\" has %llu elements, %llu given", name, (unsigned long long)nelements(t), (unsigned long long)n); return halt_rc(msg); }
+    lh_ctx* h = model_ctx();
+    if (!h) return 1;
+    if (lh_buf_upload(h, t->buf, 0, data, n) || lh_ctx_sync(h)) return halt_rc(lh_last_error(h));
+    return 0;
+}
 int llamago_TimeComputes(llama_context* c, int on) { return c && c->mlctx && c->mlctx->hip ? lh_ctx_time_computes(c->mlctx->hip, on) : 1; }
 int llamago_ComputeStats(llama_context* c, uint64_t* calls, double* wall_us, double* device_us) {
     lh_compute_stats st = {};

@@ -265,6 +265,16 @@ class Model:
             raise MLError(f"llamago_QuantizeModelQ8: {self.ml.last_error()}")
         return self
 
+    def SetTensor(self, name, values):
+        """llamago_SetModelTensor (product only, test instrumentation): one fp32 tensor of the model overwritten in HBM; values in the layout read()
+        shows (rows = ne1, columns = ne0).  Raises on an unknown name, a size mismatch, a quantised tensor or a model with live contexts."""
+        f = self.ml.lib.llamago_SetModelTensor
+        f.restype, f.argtypes = C.c_int, [VP, C.c_char_p, c_f32p, c_u64]
+        a = np.ascontiguousarray(values, dtype=np.float32).ravel()
+        if f(self.h, name.encode(), a.ctypes.data_as(c_f32p), a.size):
+            raise MLError(f"llamago_SetModelTensor: {self.ml.last_error()}")
+        return self
+
     def NewContext(self, ctxSize=128, maxThreads=1, useAVX=False, useNEON=False):
         h = self.ml._chk(self.ml.lib.llama_NewContext(self.h, ctxSize, maxThreads, int(useAVX), int(useNEON)), "llama_NewContext")
         return Context(self, h)
