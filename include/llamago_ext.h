@@ -105,6 +105,13 @@ int llamago_BatchGreedyDecode(llama_batch* b, const uint32_t* const* prompts, co
 void llamago_BatchSetKeepCount(llama_batch* b, uint32_t keep);   /* ModelParams.KeepCount of every pod (see llamago_SetKeepCount) */
 int llamago_BatchPrompt(llama_batch* b, const uint32_t* const* prompts, const uint32_t* n_prompt, uint32_t* ids_out);
 int llamago_BatchTick(llama_batch* b, uint32_t* ids_out);
+int llamago_BatchSet(llama_batch* b, const uint32_t* tokens_or_null, const uint32_t* past);   /* lh_batch_set: token and position of every pod's next tick */
+/* lh_batch_feed: llama.Eval for any subset of the pods, packed into shared weight passes - prompts of new jobs, next turns, chunks of long prompts
+ * and decode rows ride one pass over the weights.  Pod i evaluates tokens[i][0..n_tokens[i]) at position past[i] of its own cache; n_tokens[i] == 0:
+ * not fed.  A fed pod's next tick evaluates the greedy id of its last fed row (ids_out[i]); the other pods go on as if nothing had happened.
+ * Optional outputs: ids_out [pods], logits_last [pods][vocab] (fed pods' entries only), logits_rows [sum n_tokens][vocab] (pods in index order). */
+int llamago_BatchFeed(llama_batch* b, const uint32_t* const* tokens, const uint32_t* n_tokens, const uint32_t* past, uint32_t* ids_out, float* logits_last,
+                      float* logits_rows);
 /* lh_batch_set_sampler on the batch: the following ticks pick every pod's id with SampleTopPTopK (llama.go:455-707) instead of the argmax, every
  * pod seeded like a solo run; ringSize slots of lastNTokens per pod, empty.  May be called mid-stream (behind llamago_BatchPrompt and ticks). */
 int llamago_BatchSetSampler(llama_batch* b, uint32_t topK, float topP, float temp, float repeatPenalty, uint64_t seed, uint32_t ringSize);

@@ -282,6 +282,37 @@ int lh_batch_set_sampler(lh_batch* b, const lh_sample_params* sp, uint32_t ring_
  * row's prompt ran through lh_batch_prompt (or its Evals through its lh_llama with host ids); otherwise, and for a stage of a layer shard,
  * such a tick fails with LH_EINVAL before anything is enqueued. */
 int lh_batch_decode(lh_batch* b, const uint32_t* first_tokens, const uint32_t* past, uint32_t n_steps, uint32_t* out_tokens, float* logits_last_host);
+/* llama.Eval for any subset of the pods, packed into shared weight passes of <= 64 rows (whole-model batches, greedy).
+ * Pod i evaluates tokens[i][0..n_tokens[i]) at positions past[i].. of ITS cache.
+ * n_tokens[i] == 0: pod i is not fed (tokens[i], past[i] ignored).
+ * A fed pod afterwards stands at past[i] + n_tokens[i]; its next tick evaluates the greedy id of its last fed row (in lh_batch_ids_dev, in
+ * lh_batch_tokens_dev and in entry 0 of the row's output list - the conventions lh_batch_prompt leaves); its tokens are in the pod's window
+ * history, so a later context swap knows them; a pending id it had before the feed is dropped (feed it to have it evaluated).
+ * A pod that is not fed keeps its position, the token its next tick evaluates, its KV cache and what a context swap knows of it.  The output
+ * lists of ALL rows restart (as with lh_batch_set).  The first feed of a fresh batch (no lh_batch_set / lh_batch_prompt yet) must feed every row.
+ * c consecutive rows of one pod in a pass are a causal prompt chunk: the wq|wk|wv launch appends every row's K / V before the attention launch
+ * reads them.  Which rows share which pass is lh_feed_schedule's fixed partition (below), so results never depend on timing.
+ * Refused before anything is enqueued, the batch left exactly as it was: past[i] + n_tokens[i] > ctx, a token id >= vocab, all n_tokens[i] == 0,
+ * tokens[i] == NULL with n_tokens[i] > 0 (LH_EINVAL); a batch with a sampler set, a batch of layer-shard stages (LH_EUNSUPPORTED).
+ * Out of scope: sampler rings across a feed; layer shards and the pipeline; a context swap INSIDE a feed (a feed never leaves the window: the
+ * swap happens in the ticks behind it); lh_batch_prompt keeps its own route (one Eval per pod).
+ * Switches (read per call): LLAMAHIP_FEED_SOLO_MIN (rows from which a pod's feed is an Eval of its own, default 129), LLAMAHIP_FEED_QB (query rows
+ * per attention block: 2, 4 or 8), LLAMAHIP_FEED_ROW_ATTN=1 (debug / A-B: the per-row attention kernels on the pass's row table). */
+int lh_batch_feed(lh_batch* b, const uint32_t* const* tokens, const uint32_t* n_tokens, const uint32_t* past,
+                  uint32_t* ids_host,          /* optional [rows]: greedy id of each FED pod's last row; other entries not written */
+                  float* logits_last_host,     /* optional [rows][vocab]: logits of each fed pod's last row; other rows not written */
+                  float* logits_rows_host);    /* optional [sum n_tokens][vocab]: every fed row, pods in index order */
+/* The pass schedule of a feed: the pure function (no GPU) lh_batch_feed executes.  A pod with n_tokens >= solo_min is a solo pass (an Eval on
+ * its own plan); the other fed rows, in pod order with ascending positions, are cut into batched passes of <= 64 rows (a pod's rows in a pass
+ * are one segment; a segment may continue in the next pass); a pass of one row, and the segments of a pass whose row count n has bit n - 1 of
+ * sizes_ok clear, are solo passes.  Blocks: <= qb consecutive rows of ONE segment of a batched pass (the query blocks of its attention).
+ * Fills up to the given capacities, writes the full counts {passes, segments, blocks} to counts[3] and returns the pass count (-1: bad arguments). */
+enum { LH_FEED_BATCHED = 0, LH_FEED_SOLO = 1 };
+typedef struct lh_feed_pass { uint32_t kind, seg0, nseg, blk0, nblk, rows; } lh_feed_pass;   /* segments [seg0, seg0 + nseg), blocks [blk0, blk0 + nblk) */
+typedef struct lh_feed_seg { uint32_t pod, row0, n, pos0; } lh_feed_seg;                      /* rows [row0, row0 + n) of its pass: pod's positions pos0.. */
+typedef struct lh_feed_block { uint32_t row0, n; } lh_feed_block;                            /* rows [row0, row0 + n) of its pass */
+int lh_feed_schedule(const uint32_t* n_tokens, const uint32_t* past, uint32_t rows, uint32_t solo_min, uint32_t qb, uint64_t sizes_ok,
+                     lh_feed_pass* passes, uint32_t pass_cap, lh_feed_seg* segs, uint32_t seg_cap, lh_feed_block* blocks, uint32_t block_cap, uint32_t* counts);
 
 /* ---- multi-GPU: layer shard over RCCL point-to-point ------------------------------------------------
  * The reference's only parallel dimension is request-level "pods" (pkg/server/server.go:84-106: Engine() starts up to

@@ -878,6 +878,13 @@ __global__ void k_batch_from_sp(BatchRow* rows, uint32_t* tok, uint32_t* ids, co
     if (i < n) { tok[i] = sp[i].token; ids[i] = sp[i].token; rows[i].pos += 1; rows[i].step += 1; }
 }
 
+// lh_batch_feed: entry 0 of every row's output list = the token the row's next tick evaluates (a fed row: the greedy id of its last fed row, written to
+// tok[] just before; a row that was not fed: the token it had pending) - what lh_batch_prompt leaves, so the host reads a row's pending token there
+__global__ void k_batch_feed_heads(uint32_t* __restrict__ out, uint32_t out_cap, const uint32_t* __restrict__ tok, uint32_t n) {
+    const uint32_t i = threadIdx.x;
+    if (i < n) out[(size_t)i * out_cap] = tok[i];
+}
+
 // silu(a) * b elementwise (prefill FFN gate).
 __global__ __launch_bounds__(256) void k_silu_mul(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ y, uint64_t n) {
     uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;

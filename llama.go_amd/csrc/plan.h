@@ -7,6 +7,7 @@
 namespace lh {
 
 struct SampleState;
+struct AttnBlock;
 
 struct LayerW {
     const float *attn_norm = nullptr, *wq = nullptr, *wk = nullptr, *wv = nullptr, *wo = nullptr, *ffn_norm = nullptr, *w1 = nullptr, *w2 = nullptr, *w3 = nullptr;
@@ -103,6 +104,12 @@ struct BatchCtx {
     const BatchRow* rows;      // device: row -> (its stream's KV cache, its position)
     const uint32_t* tok_dev;   // device: the rows' token ids (first stage)
     float* attn_part;          // split-T attention partials [rows][H][chunks][hd + 2] (plans with ctx > 256), else nullptr
+    // lh_batch_feed: rows of one pod that follow each other in the table are a causal chunk of ITS cache; the attention then works on query
+    // blocks (<= qb consecutive rows of one pod each, kernels_attn_seg.h) instead of row by row.  blocks == nullptr: the per-row kernels.
+    const AttnBlock* blocks = nullptr;   // device: [n_blocks] of this pass
+    uint32_t n_blocks = 0, qb = 0;
+    uint32_t n_blocks1 = 0;              // the first n_blocks1 blocks hold ONE row each (decode rows, one-token tails): they take the QB = 1 instantiation
+    uint32_t max_T = 0;                  // keys the pass's longest row sees (its highest position + 1): LDS of the single pass, chunk grid of the split
 };
 
 int plan_create(lh_ctx* ctx, const ModelDesc& md, Plan** out);

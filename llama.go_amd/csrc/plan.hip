@@ -13,6 +13,8 @@
 #include "kernels_stream_b9.h"
 #include "kernels_gemm_b9.h"
 #include "kernels_rows.h"
+#include "kernels_attn_seg.h"
+#include "feed_schedule.h"
 #include <math.h>
 #include <string.h>
 #include <algorithm>
@@ -1238,6 +1240,70 @@ static int launch_attention_split(Plan* p, const AttnArgs& a, float* part) {
     return 0;
 }
 
+// lh_batch_feed: blocks of query rows that share a cache (kernels_attn_seg.h).  QB = rows per block the schedule was cut for (2, 4, 8); the blocks of ONE
+// row at the head of the table (decode rows) take the QB = 1 instantiation: with the registers of QB queries the kernels fit one workgroup per CU, with one
+// query two, like the per-row kernels - 32 decode rows behind 1000 keys ran 322 us per layer on the QB = 8 build against 174 us row by row
+// (profiles/feed_ragged.txt).
+template <int QB>
+static int launch_attention_seg_blocks(Plan* p, const AttnArgs& a, const BatchCtx* bc, const AttnBlock* blocks, uint32_t n_blocks) {
+    lh_ctx* ctx = p->ctx;
+    const ModelDesc& m = p->md;
+    if (!n_blocks) return 0;
+    if (bc->attn_part) {
+        const uint32_t nch = (m.ctx + ATT_TC - 1) / ATT_TC, nch_pass = (bc->max_T + ATT_TC - 1) / ATT_TC;
+        ProfScope ps(ctx->stream, "attention_split_seg", (uint64_t)2 * bc->max_T * a.d * 4 * n_blocks);
+        LH_TRACE("k_attention_split_seg/c%u/qb%u/n%u", nch_pass, (uint32_t)QB, a.n);
+        LH_LAUNCH_AS("k_attention_split_seg", k_attention_split_seg<QB>, dim3(m.H, nch_pass, n_blocks), dim3(ATT_TH), 0, ctx->stream, a, blocks, bc->attn_part, nch);
+        return 0;
+    }
+    const uint32_t Tp = (bc->max_T + 63) & ~63u;
+    const size_t lds = ((size_t)2 * QB * Tp + (size_t)QB * ATT_TH) * 4;
+    ProfScope ps(ctx->stream, "attention_seg", (uint64_t)2 * bc->max_T * a.d * 4 * n_blocks);
+    LH_TRACE("k_attention_seg/hd%u/qb%u/n%u", a.hd, (uint32_t)QB, a.n);
+    LH_LAUNCH_AS("k_attention_seg", k_attention_seg<QB>, dim3(a.d / a.hd, n_blocks), dim3(ATT_TH), lds, ctx->stream, a, blocks, Tp);
+    return 0;
+}
+template <int QB>
+static int launch_attention_seg_qb(Plan* p, const AttnArgs& a, const BatchCtx* bc) {
+    lh_ctx* ctx = p->ctx;
+    const ModelDesc& m = p->md;
+    if (g_prepare_only || g_only) return 0;
+    if (bc->attn_part && a.hd != 128) LH_FAIL(ctx, LH_EUNSUPPORTED, "split attention: head dim %u", a.hd);
+    int rc;
+    if ((rc = launch_attention_seg_blocks<1>(p, a, bc, bc->blocks, bc->n_blocks1))) return rc;
+    if ((rc = launch_attention_seg_blocks<QB>(p, a, bc, bc->blocks + bc->n_blocks1, bc->n_blocks - bc->n_blocks1))) return rc;
+    if (bc->attn_part) {
+        const uint32_t nch = (m.ctx + ATT_TC - 1) / ATT_TC;
+        ProfScope ps(ctx->stream, "attention_combine", (uint64_t)m.H * nch * (a.hd + 2) * 4 * a.n);
+        LH_TRACE("k_attention_combine/c%u/n%u", nch, a.n);
+        LH_LAUNCH(k_attention_combine, dim3(m.H, a.n), dim3(128), 0, ctx->stream, a, (const float*)bc->attn_part, nch);
+    }
+    LH_HIP(ctx, hipGetLastError());
+    return 0;
+}
+static constexpr size_t ATT_SEG_LDS_MAX = 48 * 1024;   // the single-pass segment kernel stays inside the LDS a launch gets without an attribute
+static bool attention_seg_fits(uint32_t qb, uint32_t max_T) { return ((size_t)2 * qb * ((max_T + 63) & ~63u) + (size_t)qb * ATT_TH) * 4 <= ATT_SEG_LDS_MAX; }
+
+// the attention of a batched Eval's rows: query blocks (a feed), else row by row (ticks; LLAMAHIP_FEED_ROW_ATTN)
+static int launch_attention_rows(Plan* p, const AttnArgs& a, const BatchCtx* bc) {
+    lh_ctx* ctx = p->ctx;
+    if (bc->blocks) {
+        if (a.hd > ATT_TH || ATT_TH % a.hd || a.hd % 4) LH_FAIL(ctx, LH_EUNSUPPORTED, "attention: head dim %u unsupported (needs to divide %d)", a.hd, ATT_TH);
+        // (a single pass whose score rows outgrow the LDS budget - wide blocks on a head size without the split kernel - keeps the per-row kernel)
+        if (bc->attn_part || attention_seg_fits(bc->qb, bc->max_T)) {
+            switch (bc->qb) {
+                case 2: return launch_attention_seg_qb<2>(p, a, bc);
+                case 4: return launch_attention_seg_qb<4>(p, a, bc);
+                case 8: return launch_attention_seg_qb<8>(p, a, bc);
+                default: LH_FAIL(ctx, LH_EINVAL, "segment attention: blocks of %u rows (2, 4 or 8)", bc->qb);
+            }
+        }
+    }
+    if (bc->blocks) LH_TRACE("feed_attention_fallback/rows/qb%u/T%u", bc->qb, bc->max_T);   // (so that an A/B on such a shape shows what it compared)
+    if (bc->attn_part) return launch_attention_split(p, a, bc->attn_part);
+    return launch_attention(ctx, a, p->md.ctx);
+}
+
 // ---------------------------------------------------------------------------------------------------
 static void drop_graphs(Plan* p, uint32_t mask) {
     for (int i = 0; i < Plan::G_COUNT; ++i) {
@@ -1678,8 +1744,7 @@ static int eval_q8b_layers(Plan* p, const float* x, float* x_out_dev, uint32_t n
         if (rows) {   // rows of different streams: one query each, against its own cache up to its own position
             AttnArgs a = {};
             a.q = p->q; a.out = p->attn; a.d = d; a.hd = m.hd; a.n = n; a.scale = scale; a.rows = rows; a.kv_off = slot; a.out_s3 = as; a.out_plane = pd;
-            if (bc->attn_part) { if ((rc = launch_attention_split(p, a, bc->attn_part))) return rc; }
-            else if ((rc = launch_attention(ctx, a, m.ctx))) return rc;
+            if ((rc = launch_attention_rows(p, a, bc))) return rc;
         } else if (n >= 32 && m.hd == FA_HD) {   // a prompt: single pass, online softmax; its rows are split by a pass of their own
             if ((rc = attention_flash(p, p->q, m.kc + slot, m.vc + slot, p->attn, n, past, scale))) return rc;
             Split3Args sa = {p->attn, as, pd, d, d, d};
@@ -1810,8 +1875,7 @@ int plan_eval(Plan* p, const uint32_t* tokens_host, const float* x_in_dev, float
                 a.q = p->q; a.out = p->attn; a.d = d; a.hd = m.hd; a.n = n; a.scale = scale;
                 if (rows) {
                     a.rows = rows; a.kv_off = slot;
-                    if (bc->attn_part) { if ((rc = launch_attention_split(p, a, bc->attn_part))) return rc; }
-                    else if ((rc = launch_attention(ctx, a, m.ctx))) return rc;
+                    if ((rc = launch_attention_rows(p, a, bc))) return rc;
                 } else {
                     a.k_cache = m.kc + slot; a.v_cache = m.vc + slot; a.sp = nullptr; a.past_host = past;
                     if ((rc = launch_attention(ctx, a, past + n))) return rc;
@@ -2020,8 +2084,7 @@ int plan_eval(Plan* p, const uint32_t* tokens_host, const float* x_in_dev, float
         if (rows) {   // rows of different streams: one query each, against its own cache up to its own position
             AttnArgs a = {};
             a.q = p->q; a.out = p->attn; a.d = d; a.hd = m.hd; a.n = n; a.scale = scale; a.rows = rows; a.kv_off = slot;
-            if (bc->attn_part) { if ((rc = launch_attention_split(p, a, bc->attn_part))) return rc; }
-            else if ((rc = launch_attention(ctx, a, m.ctx))) return rc;
+            if ((rc = launch_attention_rows(p, a, bc))) return rc;
         } else if (mfma && n >= 32 && m.hd == FA_HD) {   // single pass, online softmax
             if ((rc = attention_flash(p, p->q, m.kc + slot, m.vc + slot, p->attn, n, past, scale))) return rc;
         } else if (mfma && n >= 32 && m.hd % 32 == 0) {  // other head sizes: batched MFMA GEMMs over heads with a score tensor
@@ -2170,6 +2233,10 @@ struct Batch {
     uint32_t step0 = 0, ticks = 0, drained = 0;   // ticks since the last batch_set / of them recorded in the pods' token histories
     bool collecting = false;                      // lh_batch_decode: keep every id a row produces across the resets of the device lists
     std::vector<std::vector<uint32_t>> gen;
+    // lh_batch_feed: the passes' row tables, token ids and query blocks (one device buffer, grown on demand) and split-T partials for a 64-row pass
+    char* feed_dev = nullptr;
+    size_t feed_cap = 0;
+    float* feed_part = nullptr;
     float* logits() const { return batched || B == 1 ? pods[0]->logits : logits_own; }
 };
 
@@ -2258,7 +2325,7 @@ static void batch_free(Batch* b) {
     hipSetDevice(b->ctx->device);
     hipStreamSynchronize(b->ctx->stream);
     batch_drop_graph(b);
-    void* bufs[] = {b->rows_dev, b->tok_dev, b->ids_dev, b->out_dev, b->sp_dev, b->logits_own, b->attn_part, b->ss_dev, b->ring_dev};
+    void* bufs[] = {b->rows_dev, b->tok_dev, b->ids_dev, b->out_dev, b->sp_dev, b->logits_own, b->attn_part, b->ss_dev, b->ring_dev, b->feed_dev, b->feed_part};
     for (void* q : bufs) if (q) hipFree(q);
     delete b;
 }
@@ -2334,6 +2401,160 @@ static int batch_swap(Batch* b) {
     }
     const std::vector<uint32_t> toks = b->pending;   // (batch_set overwrites b->tok0 from it)
     return batch_set(b, toks.data(), newpos.data(), 0);
+}
+
+// ---- lh_batch_feed: llama.Eval for any subset of the pods, packed into shared weight passes --------------------------------------------
+// The schedule (feed_schedule.h) is a fixed partition of the fed rows; this function executes exactly what it returns.  A batched pass is one
+// plan_eval on pod 0's plan over a row table of its own: the rows of one segment name the same cache at consecutive positions, the wq|wk|wv
+// launch appends every row's K / V before the attention launch reads them, so the segment is a causal chunk.  Host bookkeeping as batch_swap:
+// batch_drain, the per-row work, one batch_set (step0 = 1: entry 0 of every output list holds the row's pending token, as lh_batch_prompt leaves it).
+static constexpr uint32_t FEED_SOLO_MIN = 129;   // the first length that leaves the single stream pass (fp32: 128 rows).  NOT yet set by measurement:
+                                                 // DESIGN 3h; sweep with tools/bench_feed.py --sweep, override with LLAMAHIP_FEED_SOLO_MIN
+static constexpr uint32_t FEED_QB = 4;           // query rows per attention block (LLAMAHIP_FEED_QB: 2, 4, 8).  Measured, a 64-token chunk behind 1984 keys, 8 layers:
+                                                 // 3.9-4.2 ms at 4 (two workgroups per CU), 4.5-4.7 at 8 (one), 4.6-4.7 at 2; per-row kernels 6.6-6.8 (profiles/feed_ragged.txt)
+static uint32_t env_u32(const char* name, uint32_t dflt) {
+    const char* e = getenv(name);
+    return (e && *e) ? (uint32_t)strtoul(e, nullptr, 10) : dflt;
+}
+
+static int batch_feed(Batch* b, const uint32_t* const* tokens, const uint32_t* n_tokens, const uint32_t* past, uint32_t* ids_host, float* logits_last_host,
+                      float* logits_rows_host) {
+    lh_ctx* ctx = b->ctx;
+    Plan* p0 = b->pods[0];
+    const ModelDesc& m = p0->md;
+    const uint32_t B = b->B;
+    // ---- everything is checked before anything is enqueued or any host state moves
+    if (!m.first_stage() || !m.last_stage()) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_batch_feed needs whole-model pods (a layer shard's prompts are driven by the pipeline)");
+    if (b->sampling) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_batch_feed: the batch has a sampler set (sampler rings across a feed are out of scope; lh_batch_set_sampler(NULL) first)");
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < B; ++i) {
+        const uint32_t n = n_tokens[i];
+        if (!n) {
+            if (!b->pos_known) LH_FAIL(ctx, LH_EINVAL, "lh_batch_feed: the first feed of a fresh batch must feed every row (row %u has no position yet)", i);
+            continue;
+        }
+        if (!tokens || !tokens[i]) LH_FAIL(ctx, LH_EINVAL, "lh_batch_feed: row %u has %u tokens to feed and no token array", i, n);
+        if (!past || (uint64_t)past[i] + n > m.ctx) LH_FAIL(ctx, LH_EINVAL, "lh_batch_feed: row %u: past %u + n %u exceeds the context window of %u", i, past ? past[i] : 0u, n, m.ctx);
+        for (uint32_t j = 0; j < n; ++j)
+            if (tokens[i][j] >= m.V) LH_FAIL(ctx, LH_EINVAL, "lh_batch_feed: row %u: token id %u at index %u outside the vocabulary of %u", i, tokens[i][j], j, m.V);
+        total += n;
+    }
+    if (!total) LH_FAIL(ctx, LH_EINVAL, "lh_batch_feed: no row is fed");
+    const uint32_t solo_min = env_u32("LLAMAHIP_FEED_SOLO_MIN", FEED_SOLO_MIN), qb = env_u32("LLAMAHIP_FEED_QB", FEED_QB);
+    if (qb != 2 && qb != 4 && qb != 8) LH_FAIL(ctx, LH_EINVAL, "lh_batch_feed: LLAMAHIP_FEED_QB = %u (2, 4 or 8)", qb);
+    const char* ra = getenv("LLAMAHIP_FEED_ROW_ATTN");
+    const bool row_attn = ra && ra[0] == '1';
+    uint64_t sizes_ok = 0;   // the row counts that may share one weight pass on this plan
+    if (b->batched)
+        for (uint32_t n = 2; n <= FEED_PASS_ROWS; ++n) if (plan_batch_rows_ok(p0, n)) sizes_ok |= 1ull << (n - 1);
+    FeedSchedule fs;
+    feed_schedule(n_tokens, past, B, solo_min, qb, sizes_ok, &fs);
+    // ---- the passes' tables: [BatchRow x rows | token id x rows | AttnBlock x blocks] per batched pass, one upload through the pinned staging buffer
+    std::vector<size_t> pass_off(fs.passes.size(), 0);
+    size_t bytes = 0;
+    for (size_t k = 0; k < fs.passes.size(); ++k) {
+        const lh_feed_pass& ps = fs.passes[k];
+        if (ps.kind != LH_FEED_BATCHED) continue;
+        pass_off[k] = bytes;
+        bytes += (sizeof(BatchRow) * ps.rows + 4 * (size_t)ps.rows + sizeof(AttnBlock) * ps.nblk + 15) & ~(size_t)15;
+    }
+    int rc;
+    if (bytes) {
+        if ((rc = plan_ensure_rows(p0, FEED_PASS_ROWS))) return rc;   // (the captured tick re-captures on scratch_gen)
+        if ((rc = ensure_staging(ctx, bytes))) return rc;
+        if (bytes > b->feed_cap) {
+            LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            if (b->feed_dev) LH_HIP(ctx, hipFree(b->feed_dev));
+            b->feed_dev = nullptr; b->feed_cap = 0;
+            LH_HIP(ctx, hipMalloc((void**)&b->feed_dev, bytes));
+            b->feed_cap = bytes;
+        }
+        if (p0->attn_part && !b->feed_part)
+            LH_HIP(ctx, hipMalloc((void**)&b->feed_part, 4 * (size_t)FEED_PASS_ROWS * m.H * ((m.ctx + ATT_TC - 1) / ATT_TC) * (m.hd + 2)));
+    }
+    // what the ticks so far did goes into the pods' histories (and waits for the stream: the staging buffer is free)
+    if (b->pos_known) { if ((rc = batch_drain(b))) return rc; }
+    else LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (bytes) {
+        for (size_t k = 0; k < fs.passes.size(); ++k) {
+            const lh_feed_pass& ps = fs.passes[k];
+            if (ps.kind != LH_FEED_BATCHED) continue;
+            BatchRow* hr = (BatchRow*)(ctx->staging + pass_off[k]);
+            uint32_t* ht = (uint32_t*)(hr + ps.rows);
+            AttnBlock* hb = (AttnBlock*)(ht + ps.rows);
+            for (uint32_t s = ps.seg0; s < ps.seg0 + ps.nseg; ++s) {
+                const lh_feed_seg& sg = fs.segs[s];
+                const Plan* pp = b->pods[sg.pod];
+                for (uint32_t j = 0; j < sg.n; ++j) {
+                    hr[sg.row0 + j] = BatchRow{pp->md.kc, pp->md.vc, sg.pos0 + j, 0u};
+                    ht[sg.row0 + j] = tokens[sg.pod][sg.pos0 - past[sg.pod] + j];
+                }
+            }
+            uint32_t w = 0;   // the blocks of one row first (they take the QB = 1 instantiation), then the others, each group in schedule order
+            for (int one = 1; one >= 0; --one)
+                for (uint32_t q = 0; q < ps.nblk; ++q)
+                    if ((fs.blocks[ps.blk0 + q].n == 1) == (one == 1)) hb[w++] = AttnBlock{fs.blocks[ps.blk0 + q].row0, fs.blocks[ps.blk0 + q].n};
+        }
+        LH_HIP(ctx, hipMemcpyAsync(b->feed_dev, ctx->staging, bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    std::vector<uint64_t> row_off(B, 0);   // logits_rows_host: every fed row, pods in index order
+    for (uint32_t i = 1; i < B; ++i) row_off[i] = row_off[i - 1] + n_tokens[i - 1];
+    // rows [r0, r0 + n) of `lg` are tokens tok0.. of pod's feed: the copies the caller asked for, and the pod's next id behind its last row
+    auto rows_done = [&](uint32_t pod, uint32_t tok0, uint32_t n, const float* lg) -> int {
+        if (logits_rows_host)
+            LH_HIP(ctx, hipMemcpyAsync(logits_rows_host + (row_off[pod] + tok0) * m.V, lg, (size_t)n * m.V * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (tok0 + n != n_tokens[pod]) return 0;   // (the pod's feed continues in the next pass)
+        const float* last_row = lg + (size_t)(n - 1) * m.V;
+        LH_LAUNCH(k_argmax_advance, dim3(1), dim3(1024), 0, ctx->stream, last_row, m.V, (StepParams*)nullptr, b->out_dev + (size_t)pod * b->out_cap, b->ids_dev + pod, 0);
+        LH_HIP(ctx, hipMemcpyAsync(b->tok_dev + pod, b->ids_dev + pod, 4, hipMemcpyDeviceToDevice, ctx->stream));
+        if (logits_last_host) LH_HIP(ctx, hipMemcpyAsync(logits_last_host + (size_t)pod * m.V, last_row, (size_t)m.V * 4, hipMemcpyDeviceToHost, ctx->stream));
+        return 0;
+    };
+    for (size_t k = 0; k < fs.passes.size(); ++k) {
+        const lh_feed_pass& ps = fs.passes[k];
+        if (ps.kind == LH_FEED_SOLO) {   // an Eval on the pod's own plan (it records its tokens itself)
+            const lh_feed_seg& sg = fs.segs[ps.seg0];
+            Plan* pp = b->pods[sg.pod];
+            const uint32_t tok0 = sg.pos0 - past[sg.pod];
+            LH_TRACE("feed_pass/solo/n%u", sg.n);
+            if ((rc = plan_eval(pp, tokens[sg.pod] + tok0, nullptr, nullptr, sg.n, sg.pos0, logits_rows_host == nullptr))) return rc;
+            // (last_row_only leaves the last row in its usual place, row n - 1; the rows in front of it are then not the caller's)
+            if (logits_rows_host) { if ((rc = rows_done(sg.pod, tok0, sg.n, pp->logits))) return rc; }
+            else if ((rc = rows_done(sg.pod, tok0 + sg.n - 1, 1, pp->logits + (size_t)(sg.n - 1) * m.V))) return rc;
+            continue;
+        }
+        char* base = b->feed_dev + pass_off[k];
+        BatchCtx bc = {};
+        bc.rows = (const BatchRow*)base;
+        bc.tok_dev = (const uint32_t*)(base + sizeof(BatchRow) * ps.rows);
+        bc.attn_part = p0->attn_part ? b->feed_part : nullptr;
+        for (uint32_t s = ps.seg0; s < ps.seg0 + ps.nseg; ++s) {
+            const lh_feed_seg& sg = fs.segs[s];
+            bc.max_T = std::max(bc.max_T, sg.pos0 + sg.n);
+            for (uint32_t j = 0; j < sg.n; ++j) b->pods[sg.pod]->record(sg.pos0 + j, tokens[sg.pod][sg.pos0 - past[sg.pod] + j]);
+        }
+        if (!row_attn) {
+            bc.blocks = (const AttnBlock*)(base + (sizeof(BatchRow) + 4) * (size_t)ps.rows); bc.n_blocks = ps.nblk; bc.qb = qb;
+            for (uint32_t q = 0; q < ps.nblk; ++q) bc.n_blocks1 += fs.blocks[ps.blk0 + q].n == 1;
+        }
+        LH_TRACE("feed_pass/batched/n%u", ps.rows);
+        if ((rc = plan_eval(p0, nullptr, nullptr, nullptr, ps.rows, 0, false, &bc))) return rc;
+        for (uint32_t s = ps.seg0; s < ps.seg0 + ps.nseg; ++s) {   // before the next pass overwrites p0->logits
+            const lh_feed_seg& sg = fs.segs[s];
+            if ((rc = rows_done(sg.pod, sg.pos0 - past[sg.pod], sg.n, p0->logits + (size_t)sg.row0 * m.V))) return rc;
+        }
+    }
+    LH_LAUNCH(k_batch_feed_heads, dim3(1), dim3(64), 0, ctx->stream, b->out_dev, b->out_cap, (const uint32_t*)b->tok_dev, B);
+    LH_HIP(ctx, hipGetLastError());
+    std::vector<uint32_t> newpos(B);
+    for (uint32_t i = 0; i < B; ++i) newpos[i] = n_tokens[i] ? past[i] + n_tokens[i] : b->pos[i];
+    if ((rc = batch_set(b, nullptr, newpos.data(), 1))) return rc;
+    std::vector<uint32_t> ids(B);
+    if (ids_host) LH_HIP(ctx, hipMemcpyAsync(ids.data(), b->ids_dev, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
+    LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (ids_host)
+        for (uint32_t i = 0; i < B; ++i) if (n_tokens[i]) ids_host[i] = ids[i];
+    return 0;
 }
 
 }  // namespace lh
@@ -2773,6 +2994,25 @@ int lh_batch_decode(lh_batch* h, const uint32_t* first_tokens, const uint32_t* p
     if (logits_last_host) LH_HIP(ctx, hipMemcpyAsync(logits_last_host, b->logits(), (size_t)b->B * m.V * 4, hipMemcpyDeviceToHost, ctx->stream));
     LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return LH_OK;
+}
+
+int lh_batch_feed(lh_batch* h, const uint32_t* const* tokens, const uint32_t* n_tokens, const uint32_t* past, uint32_t* ids_host, float* logits_last_host,
+                  float* logits_rows_host) {
+    if (!h || !n_tokens) return LH_EINVAL;
+    LH_HIP(h->b->ctx, hipSetDevice(h->b->ctx->device));
+    return batch_feed(h->b, tokens, n_tokens, past, ids_host, logits_last_host, logits_rows_host);
+}
+
+int lh_feed_schedule(const uint32_t* n_tokens, const uint32_t* past, uint32_t rows, uint32_t solo_min, uint32_t qb, uint64_t sizes_ok, lh_feed_pass* passes,
+                     uint32_t pass_cap, lh_feed_seg* segs, uint32_t seg_cap, lh_feed_block* blocks, uint32_t block_cap, uint32_t* counts) {
+    if (!n_tokens || !past || !rows || rows > 64 || !qb || !solo_min) return -1;
+    FeedSchedule fs;
+    feed_schedule(n_tokens, past, rows, solo_min, qb, sizes_ok, &fs);
+    for (size_t i = 0; passes && i < fs.passes.size() && i < pass_cap; ++i) passes[i] = fs.passes[i];
+    for (size_t i = 0; segs && i < fs.segs.size() && i < seg_cap; ++i) segs[i] = fs.segs[i];
+    for (size_t i = 0; blocks && i < fs.blocks.size() && i < block_cap; ++i) blocks[i] = fs.blocks[i];
+    if (counts) { counts[0] = (uint32_t)fs.passes.size(); counts[1] = (uint32_t)fs.segs.size(); counts[2] = (uint32_t)fs.blocks.size(); }
+    return (int)fs.passes.size();
 }
 
 int lh_llama_profile_decode(lh_llama* m, uint32_t token, uint32_t past, uint32_t repeats, lh_kernel_time* out, uint32_t cap) {

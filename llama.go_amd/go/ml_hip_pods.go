@@ -229,6 +229,20 @@ func (bt *BatchHIP) Tick() []uint32 {
 	return bt.ids()
 }
 
+// Feed: llama.Eval for any subset of the pods, packed into shared weight passes (lh_batch_feed): pod i evaluates tokens[i] at position
+// past[i] of its own cache; a pod with no tokens is not fed and goes on as if nothing had happened.  This is how a new job's prompt (past 0),
+// a next turn or a chunk of a long prompt enters a running batch without the other pods leaving the one-pass route.  Returns the ids of the
+// batch: for a fed pod the greedy id of its last fed row, which its next Tick evaluates.  Greedy batches only (no SetSampler).
+func (bt *BatchHIP) Feed(tokens [][]uint32, past []uint32) []uint32 {
+	pp, nn, free := cPrompts(tokens)
+	defer free()
+	out := make([]uint32, len(bt.stages))
+	if rc := C.lh_batch_feed(bt.b, pp, nn, (*C.uint32_t)(unsafe.Pointer(&past[0])), (*C.uint32_t)(unsafe.Pointer(&out[0])), nil, nil); rc != 0 {
+		hipHalt(bt.ctx.hip.ctx)
+	}
+	return out
+}
+
 func (bt *BatchHIP) ids() []uint32 {
 	out := make([]uint32, len(bt.stages))
 	if rc := C.lh_batch_read_ids(bt.b, (*C.uint32_t)(unsafe.Pointer(&out[0]))); rc != 0 {

@@ -1322,6 +1322,22 @@ int llamago_BatchTick(llama_batch* p, uint32_t* ids_out) {
     if (lh_batch_read_ids(p->b, ids_out)) return halt_rc(lh_last_error(hip));
     return 0;
 }
+// lh_batch_set: the token (tokens may be NULL: the ids stay what the device holds) and position of every pod's next tick, from the host
+int llamago_BatchSet(llama_batch* p, const uint32_t* tokens, const uint32_t* past) {
+    if (!p || !past) return halt_rc("llamago_BatchSet: bad arguments");
+    if (lh_batch_set(p->b, tokens, past)) return halt_rc(lh_last_error(p->mlctx->hip));
+    return 0;
+}
+// llama.Eval for any subset of the pods in shared weight passes (lh_batch_feed): pod i evaluates tokens[i][0..n_tokens[i]) at past[i] of its own
+// cache; n_tokens[i] == 0 leaves pod i alone.  ids_out [pods] / logits_last [pods][vocab] are written for the fed pods only; logits_rows
+// [sum n_tokens][vocab] holds every fed row, pods in index order.  All three are optional.
+int llamago_BatchFeed(llama_batch* p, const uint32_t* const* tokens, const uint32_t* n_tokens, const uint32_t* past, uint32_t* ids_out, float* logits_last,
+                      float* logits_rows) {
+    if (!p || !n_tokens) return halt_rc("llamago_BatchFeed: bad arguments");
+    lh_ctx* hip = p->mlctx->hip;
+    if (lh_batch_feed(p->b, tokens, n_tokens, past, ids_out, logits_last, logits_rows)) return halt_rc(lh_last_error(hip));
+    return 0;
+}
 
 // ---- pods as pipeline streams over a layer-sharded model (server.go:84-106, 151) ----------------------
 // One ml.Context (= one HIP stream) per rank carries every pod's stage and the RCCL p2p; each pod owns its KV cache like a

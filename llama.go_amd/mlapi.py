@@ -486,6 +486,10 @@ def _bind_extensions(ml):
     L.llamago_BatchPrompt.argtypes = [VP, C.POINTER(c_u32p), c_u32p, c_u32p]
     L.llamago_BatchTick.restype = C.c_int
     L.llamago_BatchTick.argtypes = [VP, c_u32p]
+    L.llamago_BatchSet.restype = C.c_int
+    L.llamago_BatchSet.argtypes = [VP, c_u32p, c_u32p]
+    L.llamago_BatchFeed.restype = C.c_int
+    L.llamago_BatchFeed.argtypes = [VP, C.POINTER(c_u32p), c_u32p, c_u32p, c_u32p, c_f32p, c_f32p]
     L.llamago_FreePipeline.restype = None
     L.llamago_FreePipeline.argtypes = [VP]
     L.llamago_PipelineRun.restype = C.c_int
@@ -643,6 +647,37 @@ class Batch:
         if self.ml.lib.llamago_BatchPrompt(self.h, pp, nn, out):
             raise MLError(f"llamago_BatchPrompt: {self.ml.last_error()}")
         return list(out)
+
+    def Set(self, tokens, past):
+        """lh_batch_set: the token and the position of every pod's next tick, from the host (tokens None: the ids the device holds stay)."""
+        tk = (c_u32 * self.pods)(*[int(t) for t in tokens]) if tokens is not None else None
+        ps = (c_u32 * self.pods)(*[int(x) for x in past])
+        if self.ml.lib.llamago_BatchSet(self.h, tk, ps):
+            raise MLError(f"llamago_BatchSet: {self.ml.last_error()}")
+
+    def Feed(self, tokens_per_pod, past, want_logits=False, want_rows=False):
+        """lh_batch_feed: llama.Eval of tokens_per_pod[i] at position past[i] of pod i's cache for every pod with a non-empty list, packed into
+        shared weight passes; pods with an empty list are not fed.  Returns the list of ids (the greedy id of each fed pod's last row, None for
+        pods that were not fed), then - if asked for - the [pods][vocab] logits of the fed pods' last rows (other rows NaN) and the
+        [sum n][vocab] logits of every fed row, pods in index order."""
+        assert len(tokens_per_pod) == self.pods and len(past) == self.pods
+        arrs = [(c_u32 * max(len(p), 1))(*[int(t) for t in p]) for p in tokens_per_pod]
+        pp = (c_u32p * self.pods)(*[C.cast(a, c_u32p) if len(p) else None for a, p in zip(arrs, tokens_per_pod)])
+        nn = (c_u32 * self.pods)(*[len(p) for p in tokens_per_pod])
+        ps = (c_u32 * self.pods)(*[int(x) for x in past])
+        out = (c_u32 * self.pods)()
+        V = self.model.hp.vocabSize
+        last = np.full((self.pods, V), np.nan, dtype=np.float32) if want_logits else None
+        rows = np.empty((sum(len(p) for p in tokens_per_pod), V), dtype=np.float32) if want_rows else None
+        if self.ml.lib.llamago_BatchFeed(self.h, pp, nn, ps, out, last.ctypes.data_as(c_f32p) if want_logits else None,
+                                         rows.ctypes.data_as(c_f32p) if want_rows and rows.size else None):
+            raise MLError(f"llamago_BatchFeed: {self.ml.last_error()}")
+        res = ([int(out[i]) if len(p) else None for i, p in enumerate(tokens_per_pod)],)
+        if want_logits:
+            res += (last,)
+        if want_rows:
+            res += (rows,)
+        return res if len(res) > 1 else res[0]
 
     def SetSampler(self, topK=40, topP=0.95, temp=0.8, repeatPenalty=1.10, seed=0, ringSize=64):
         """lh_batch_set_sampler: the following ticks sample (SampleTopPTopK on the device) instead of taking the argmax; allowed mid-stream."""

@@ -101,6 +101,20 @@ if ("score" in flt or not flt) and "--search" not in sys.argv:
         rows = ts.checker_rows(orc, name)
         report(f"score {name} sequence seed={ts.SEQ_SEED[name]} rows={len(rows)}", margin(rows))
 
+if "feed" in flt and "--search" not in sys.argv:
+    # tests/test_gpu_batch_feed.py::test_feed_equals_every_stream_alone (usage: ... feed [--seeds 4321,5000,...]: the first seed of the list that clears the margin)
+    import test_gpu_batch_feed as tf  # noqa: E402
+    seeds = [int(x) for x in sys.argv[sys.argv.index("--seeds") + 1].split(",")] if "--seeds" in sys.argv else [tf.FEED_SEED]
+    for int8 in (False, True):
+        for total in sorted(tf.FEED_LENGTHS):
+            kw, prompts, seed = tf.feed_config(total, int8)
+            hp = make_hparams(**kw, ctx=tf.FEED_CTX)
+            for sd in ([seed] if (total, int8) in tf.FEED_SEEDS else seeds):
+                mg = streams(hp, sd, prompts, tf.FEED_PREDICT, tf.FEED_CTX, int8)
+                report(f"feed_equals total={total} int8={int8} seed={sd}", mg)
+                if mg > 2.5e-4:
+                    break
+
 # --search: model seeds for the batched-decode configurations whose default seed leaves a near-tie (usage: ... --search <config index> <n seeds>)
 if "--search" in sys.argv:
     i = sys.argv.index("--search")
