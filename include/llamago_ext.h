@@ -81,6 +81,14 @@ int llamago_Score(llama_context* c, llama_model* m, const uint32_t* tokens, uint
  * pastCount; row i of a window is scored against token i+1 of the window, the window's last row is not scored.  nll_sum = -sum logprob in f64,
  * n_scored = the number of terms; perplexity = exp(nll_sum / n_scored).  The context's cache holds the last window afterwards. */
 int llamago_Perplexity(llama_context* c, llama_model* m, const uint32_t* tokens, uint32_t n_tokens, uint32_t chunk, double* nll_sum, uint64_t* n_scored);
+/* Lookup-draft speculative decoding (lh_draft_lookup, lh_llama_verify, lh_llama_decode_lookup; the rule is stated in llamahip.h).
+ * llamago_DraftLookup: the drafter alone on host arrays, on the model context's device.  llamago_Verify: one verify pass of tokens[0..n) (pending
+ * token + a draft from anywhere) on the context's own KV cache.  llamago_DecodeLookup: llamago_DecodeGreedyResident through verify passes - the
+ * same ids, the same last logits, the same state left behind. */
+int llamago_DraftLookup(const uint32_t* window, uint32_t n_window, const lh_lookup_params* lp, uint32_t limit, uint32_t* draft_out, uint32_t* n_draft);
+int llamago_Verify(llama_context* c, const uint32_t* tokens, uint32_t n, uint32_t past, uint32_t* ids_out, uint32_t* n_accepted, float* logits);
+int llamago_DecodeLookup(llama_context* c, uint32_t first_token, uint32_t past, uint32_t n_steps, const lh_lookup_params* lp, uint32_t* out_tokens,
+                         float* logits_last, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap);
 
 /* ModelParams.Embedding (llama.go:52, 88): from now on every llama_Eval also leaves row N-1 of `embeddings` (the final norm * weight rows,
  * llama.go:381, 414-419) in lctx.Embedding; llama_Embedding (llamago.h) returns it ([embd] floats; NULL when not enabled).  On the GPU the fused plan

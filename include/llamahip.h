@@ -236,6 +236,50 @@ int lh_score_rows(lh_ctx* ctx, const float* logits_host, uint32_t n_rows, uint32
  * beyond the window, a token or a target outside the vocabulary: LH_EINVAL before anything is enqueued. */
 int lh_llama_score(lh_llama* m, const uint32_t* tokens, uint32_t n, uint32_t past, const uint32_t* targets, lh_row_score* out_host);
 
+/* ---- lossless lookup-draft speculative decoding (greedy) -------------------------------------------------------------
+ * Every one-token step streams all weights; a pass of 2..8 rows (block-int8: 2..4) rides the same stream with every row bit-identical to
+ * its solo step.  So: draft K tokens, evaluate [pending, d1..dK] as ONE pass of the context's own cache (a causal chunk), keep the longest
+ * prefix the model itself produced.  The accepted ids and their logits are the bytes lh_llama_decode_greedy produces.  Greedy only,
+ * whole-model plans, weight_dtype 0 and 7.
+ *
+ * The draft rule (tests/speculative_ref.py restates it).  H[0..n) = the tokens at positions 0..n-1 of the window, H[n-1] the pending token;
+ * an entry the context does not know (0xFFFFFFFF) never matches anything.  For G from ngram_max down to ngram_min: skip G when n < G or
+ * when the suffix S = H[n-G..n) holds an unknown entry.  Window first: the largest j <= n-G-1 with H[j..j+G) == S gives the draft
+ * H[j+G .. min(j+G+K, n)).  Else the corpus: the largest j with j+G < n_corpus and C[j..j+G) == S gives C[j+G .. min(j+G+K, n_corpus)).
+ * The first G with a match wins; no match = an empty draft.  The draft ends in front of the first unknown entry of its continuation and
+ * is cut to k = min(len, limit); in the loop limit = min(ctx - n, remaining - 1), remaining = n_steps - ids produced so far, so a pass
+ * never leaves the window and never produces more ids than asked. */
+typedef struct lh_lookup_params {
+    uint32_t draft_max;            /* K: 1..7 (block-int8: 1..3) */
+    uint32_t ngram_max, ngram_min; /* 1 <= ngram_min <= ngram_max <= 8 */
+    const uint32_t* corpus;        /* optional host tokens searched behind the window; NULL / 0 = none */
+    uint32_t n_corpus;             /* <= 65536 */
+} lh_lookup_params;
+typedef struct lh_spec_stats { uint32_t passes, rows, drafted, accepted, empty; } lh_spec_stats;
+/* The drafter on its own (op-level twin, host in / host out, like lh_score_rows): the rule above on window[0..n_window) with the given
+ * limit; draft_out has room for draft_max ids, *n_draft = k.  No vocabulary here: only 0xFFFFFFFF is unknown. */
+int lh_draft_lookup(lh_ctx* ctx, const uint32_t* window, uint32_t n_window, const lh_lookup_params* lp, uint32_t limit,
+                    uint32_t* draft_out, uint32_t* n_draft);
+/* One verify pass, the hook for any other drafter: tokens[0] = the pending token, tokens[1..n) a draft from anywhere, 1 <= n <= 8
+ * (block-int8: 4).  ONE pass of n rows of the context's own cache at positions past..past+n-1, the lm_head for every row, per-row argmax
+ * (lowest index on ties) and the accepted count a = the leading i < n-1 with argmax(row i) == tokens[i+1], all on the device.
+ * ids_out[0..a] = the greedy ids of rows 0..a (room for n), *n_accepted = a, logits_host (optional, vocab floats) = row a.  Afterwards the
+ * context stands at past + a + 1 and its history holds tokens[0..a] at past..past+a; the cache rows behind are stale and are overwritten by
+ * whatever runs next.  Host-synchronous.  Refused before anything is enqueued: past + n > ctx, n out of range, a token id >= vocab
+ * (LH_EINVAL); a layer-shard stage, a shape without an n-row pass on the decode stream (LH_EUNSUPPORTED). */
+int lh_llama_verify(lh_llama* m, const uint32_t* tokens, uint32_t n, uint32_t past, uint32_t* ids_out, uint32_t* n_accepted, float* logits_host);
+/* lh_llama_decode_greedy through verify passes drafted by the rule above: exactly the n_steps ids that loop produces from the same state,
+ * logits_last_host byte-equal to its, the context left as it leaves it (position past + n_steps, every evaluated token in the history; a
+ * context swap at the window's end as there).  Every pass has R = draft_max + 1 rows (lowered to the largest count this plan's shapes
+ * carry; R = 1 = plain greedy steps), the rows behind the draft being filler that never counts.  The loop is device-resident: drafter,
+ * accept step and positions live in device memory, the pass is one captured graph, and the host looks (one 64-byte read) only when its
+ * bounds on the position - `passes` and `passes * R` behind the last look - reach n_steps or the window's end.
+ * stats: rows = R; passes, drafted, accepted = sums over the passes; empty = passes with k = 0.  trace[s] = (k_s << 8) | a_s for
+ * s < trace_cap.  Refused before anything is enqueued (context untouched): draft_max outside 1..7 (block-int8 1..3), bad n-gram bounds,
+ * n_corpus > 65536, a corpus id >= vocab, first_token >= vocab, past > ctx (LH_EINVAL); a layer-shard stage (LH_EUNSUPPORTED). */
+int lh_llama_decode_lookup(lh_llama* m, uint32_t first_token, uint32_t past, uint32_t n_steps, const lh_lookup_params* lp,
+                           uint32_t* out_tokens, float* logits_last_host, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap);
+
 /* ---- pods in ONE weight pass (batched decode) ---------------------------------------------------------------------
  * The reference's only parallelism is request-level: Engine() starts up to MaxPods concurrent Do() goroutines
  * (pkg/server/server.go:84-106), each with its own llama.Context over the shared Model (server.go:151).  On the CPU they share

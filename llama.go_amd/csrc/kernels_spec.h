@@ -1,0 +1,177 @@
+// csrc/kernels_spec.h — lookup-draft speculative decoding (greedy, lossless): the n-gram drafter and the accept step on the device.
+// A pass evaluates [pending, d1..dk] (+ filler rows up to a fixed row count) as one multi-row pass of the stream's own cache (kernels_rows.h:
+// every row bit-identical to its solo one-token step); k_batch_argmax takes the rows' greedy ids; k_spec_accept keeps the longest prefix of the
+// draft the model itself produced, moves the row table on by the accepted count and drafts for the next pass.  The rule is stated in
+// include/llamahip.h (lh_lookup_params) and restated in tests/speculative_ref.py.
+#pragma once
+#include "kernels_common.h"
+
+namespace lh {
+
+constexpr uint32_t SPEC_UNKNOWN = 0xFFFFFFFFu;   // = Plan::HIST_UNKNOWN: a window entry the context does not know
+constexpr int SPEC_TH = 1024;
+constexpr uint32_t SPEC_ROWS_MAX = 8, SPEC_NGRAM_MAX = 8, SPEC_CORPUS_MAX = 65536;
+
+// The loop's state in device memory: a captured pass is replayed for every position and every accepted count.
+struct SpecState {
+    uint32_t pos;        // position of the pending token (= tokens of the window in front of it)
+    uint32_t produced;   // ids in the output list
+    uint32_t n_steps;    // ids asked for: a pass that finds produced == n_steps does nothing
+    uint32_t k;          // draft length of the NEXT pass (its rows 1..k)
+    uint32_t last_a;     // accepted count of the last pass: its row last_a holds the logits behind the last evaluated token
+    uint32_t passes, drafted, accepted, empty;
+    uint32_t pad[7];
+};
+struct SpecLookup {
+    const uint32_t* corpus;   // device, may be nullptr
+    uint32_t n_corpus, draft_max, ngram_max, ngram_min;
+};
+struct SpecToks { uint32_t t[SPEC_ROWS_MAX]; };
+
+// The largest j in [0, n_j) with src[j..j+G) == S, or -1: every thread walks its j ascending (its last hit is its largest), one LDS max over the block.
+// Called by all threads of the block; the result is uniform.
+__device__ __forceinline__ int spec_find_last(const uint32_t* __restrict__ src, uint32_t n_j, uint32_t G, const uint32_t (&S)[SPEC_NGRAM_MAX], int* s_best) {
+    __syncthreads();   // (the readers of the previous search are done)
+    if (threadIdx.x == 0) *s_best = -1;
+    __syncthreads();
+    int best = -1;
+    for (uint32_t j = threadIdx.x; j < n_j; j += SPEC_TH) {
+        bool eq = src[j] == S[0];
+#pragma unroll
+        for (uint32_t g = 1; g < SPEC_NGRAM_MAX; ++g)
+            if (eq && g < G) eq = src[j + g] == S[g];
+        if (eq) best = (int)j;
+    }
+    if (best >= 0) atomicMax(s_best, best);
+    __syncthreads();
+    return *s_best;
+}
+
+// The draft rule (include/llamahip.h) over the window H[0..n) (H[n-1] = the pending token) and the corpus: up to min(draft_max, limit) ids into dst,
+// the count returned (uniform).  An id >= vocab in a continuation (an unknown window entry) ends the draft in front of it.
+__device__ __forceinline__ uint32_t spec_lookup(const uint32_t* __restrict__ H, uint32_t n, const SpecLookup lp, uint32_t limit, uint32_t vocab,
+                                                uint32_t* __restrict__ dst, int* s_best) {
+    uint32_t K = lp.draft_max < limit ? lp.draft_max : limit;
+    if (K > SPEC_ROWS_MAX - 1) K = SPEC_ROWS_MAX - 1;
+    if (K == 0 || n == 0) return 0;
+    for (uint32_t G = lp.ngram_max; G >= lp.ngram_min && G >= 1; --G) {
+        if (n < G) continue;
+        uint32_t S[SPEC_NGRAM_MAX];
+        bool unknown = false;
+#pragma unroll
+        for (uint32_t g = 0; g < SPEC_NGRAM_MAX; ++g) {
+            S[g] = g < G ? H[n - G + g] : 0u;
+            unknown = unknown || (g < G && S[g] == SPEC_UNKNOWN);
+        }
+        if (unknown) continue;
+        const uint32_t* src = H;
+        uint32_t end = n;
+        int j = n > G ? spec_find_last(H, n - G, G, S, s_best) : -1;                      // j <= n - G - 1: the suffix may not match itself
+        if (j < 0) {
+            if (!lp.corpus || lp.n_corpus <= G) continue;
+            j = spec_find_last(lp.corpus, lp.n_corpus - G, G, S, s_best);                 // j + G < n_corpus: at least one id follows
+            if (j < 0) continue;
+            src = lp.corpus; end = lp.n_corpus;
+        }
+        const uint32_t start = (uint32_t)j + G;
+        uint32_t len = end - start;
+        if (len > K) len = K;
+        uint32_t k = 0;
+        while (k < len && src[start + k] < vocab) ++k;   // (every thread reads the same <= 7 words)
+        if (threadIdx.x < k) dst[threadIdx.x] = src[start + threadIdx.x];
+        return k;
+    }
+    return 0;
+}
+
+// limit of the pass that starts with the pending token at position pos: it never leaves the window and never produces more ids than asked
+__device__ __forceinline__ uint32_t spec_limit(uint32_t pos, uint32_t produced, uint32_t n_steps, uint32_t ctx) {
+    const uint32_t n = pos + 1;
+    if (n >= ctx || produced >= n_steps) return 0;
+    const uint32_t a = ctx - n, b = n_steps - produced - 1;
+    return a < b ? a : b;
+}
+
+// The drafter as a launch of its own.  st == nullptr: the op-level twin (lh_draft_lookup) - window, n and limit from the arguments, the count to *k_out.
+// st != nullptr: the first draft of a loop - the window is win[0..st->pos], the limit the loop's; ids into tok[1..], the rows behind them get the pending
+// token as filler, the count into st->k.
+__global__ __launch_bounds__(SPEC_TH) void k_draft_lookup(const uint32_t* __restrict__ win, uint32_t n, const SpecLookup lp, uint32_t limit, uint32_t vocab,
+                                                          uint32_t* __restrict__ dst, uint32_t* __restrict__ k_out, SpecState* st, uint32_t ctx, uint32_t n_rows) {
+    __shared__ int s_best;
+    if (st) {
+        n = st->pos + 1;
+        limit = spec_limit(st->pos, st->produced, st->n_steps, ctx);
+        if (n > ctx + 1) { n = 0; limit = 0; }
+    }
+    const uint32_t k = spec_lookup(win, n, lp, limit, vocab, st ? dst + 1 : dst, &s_best);
+    if (st) {
+        const uint32_t r = threadIdx.x;
+        if (r > k && r < n_rows) dst[r] = dst[0];
+        if (r == 0) st->k = k;
+    } else if (threadIdx.x == 0) {
+        *k_out = k;
+    }
+}
+
+// State, row table and tokens of the next pass from kernel arguments (stream-ordered, nothing on the host to keep alive).  reset: the counters restart.
+__global__ void k_spec_set(SpecState* st, BatchRow* rows, uint32_t* tok, StepParams* sp, float* kc, float* vc, uint32_t pos, uint32_t produced, uint32_t n_steps,
+                           const SpecToks toks, uint32_t k, uint32_t n_rows, uint32_t ctx, int reset) {
+    const uint32_t r = threadIdx.x;
+    if (r < n_rows && r < SPEC_ROWS_MAX) {
+        const uint32_t q = pos + r;
+        rows[r].kc = kc; rows[r].vc = vc; rows[r].pos = q < ctx ? q : ctx - 1; rows[r].step = 0;
+        tok[r] = toks.t[r];
+    }
+    if (r == 0) {
+        st->pos = pos; st->produced = produced; st->n_steps = n_steps; st->k = k; st->last_a = 0;
+        if (reset) { st->passes = 0; st->drafted = 0; st->accepted = 0; st->empty = 0; }
+        sp->token = toks.t[0]; sp->past = pos < ctx ? pos : ctx - 1; sp->step = 0; sp->pad = 0;
+    }
+}
+
+// The accept step behind a pass of R rows whose greedy ids are arg[0..R): a = the leading i < min(k, R - 1) with arg[i] == tok[i + 1] (a filler row never
+// counts); ids arg[0..a] go to the output list and the window; arg[a] is the next pending token; the table's n_rows positions become p + a + 1 ..;
+// counters and trace; then (lookup_next) the draft of the next pass.  One workgroup.  Every index it writes is clamped to its buffer: the host never
+// launches a pass that needs the clamp, and a mistake there must not write outside the cache or the lists.
+__global__ __launch_bounds__(SPEC_TH) void k_spec_accept(const uint32_t* __restrict__ arg, uint32_t R, SpecState* st, BatchRow* rows, uint32_t* tok, StepParams* sp,
+                                                         uint32_t* __restrict__ win, uint32_t ctx, uint32_t vocab, uint32_t* __restrict__ out,
+                                                         uint16_t* __restrict__ trace, uint32_t trace_cap, const SpecLookup lp, uint32_t n_rows, int lookup_next) {
+    __shared__ int s_best;
+    __shared__ uint32_t s_pos, s_done;
+    if (threadIdx.x == 0) {
+        const uint32_t p = st->pos, produced = st->produced, n_steps = st->n_steps;
+        s_done = 1; s_pos = p;
+        if (produced < n_steps && p < ctx && R >= 1) {
+            uint32_t k = st->k;
+            if (k > R - 1) k = R - 1;
+            uint32_t a = 0;
+            while (a < k && arg[a] == tok[a + 1]) ++a;
+            if (a > n_steps - produced - 1) a = n_steps - produced - 1;
+            if (a > ctx - 1 - p) a = ctx - 1 - p;
+            for (uint32_t i = 0; i <= a; ++i) { out[produced + i] = arg[i]; win[p + 1 + i] = arg[i]; }   // win has ctx + 1 entries
+            const uint32_t s = st->passes;
+            if (trace && s < trace_cap) trace[s] = (uint16_t)((k << 8) | a);
+            st->passes = s + 1; st->drafted += k; st->accepted += a; st->empty += k == 0 ? 1u : 0u;
+            st->last_a = a; st->produced = produced + a + 1;
+            const uint32_t np = p + a + 1;
+            st->pos = np;
+            tok[0] = arg[a];
+            sp->token = arg[a]; sp->past = np < ctx ? np : ctx - 1;
+            s_pos = np; s_done = produced + a + 1 >= n_steps ? 1u : 0u;
+        }
+    }
+    __syncthreads();
+    const uint32_t np = s_pos;
+    if (threadIdx.x < n_rows && threadIdx.x < SPEC_ROWS_MAX) {
+        const uint32_t q = np + threadIdx.x;
+        rows[threadIdx.x].pos = q < ctx ? q : ctx - 1;
+    }
+    if (!lookup_next) return;
+    uint32_t k = 0;
+    if (!s_done) k = spec_lookup(win, np + 1, lp, spec_limit(np, st->produced, st->n_steps, ctx), vocab, tok + 1, &s_best);
+    const uint32_t r = threadIdx.x;
+    if (r > k && r < n_rows && r < SPEC_ROWS_MAX) tok[r] = tok[0];
+    if (r == 0) st->k = k;
+}
+
+}  // namespace lh

@@ -7,6 +7,7 @@
 namespace lh {
 
 struct SampleState;
+struct Spec;
 struct AttnBlock;
 
 struct LayerW {
@@ -82,6 +83,7 @@ struct Plan {
     uint32_t smp_topk = 0;                    // topK the sampler launches (and the captured graph) were chosen for
     char* score_dev = nullptr;                // lh_llama_score: [score_cap] lh_row_score, then [score_cap] target ids
     uint32_t score_cap = 0;
+    struct Spec* spec = nullptr;              // lookup-draft speculative decoding (lh_llama_verify, lh_llama_decode_lookup): device state + the captured pass
     uint32_t slot_counter = 0;   // round-robin over the pinned StepParams slots of eager (non-graph) steps
     bool use_graph = true;
     // Context swap of the generation loops (pkg/server/server.go:160-172): the token evaluated at every position of this plan's KV cache, as far as

@@ -14,6 +14,7 @@
 #include "kernels_gemm_b9.h"
 #include "kernels_rows.h"
 #include "kernels_attn_seg.h"
+#include "kernels_spec.h"
 #include "feed_schedule.h"
 #include <math.h>
 #include <string.h>
@@ -1314,6 +1315,7 @@ static void drop_graphs(Plan* p, uint32_t mask) {
 }
 static constexpr uint32_t GM_ADV = (1u << Plan::G_ADV1) | (1u << Plan::G_ADVN), GM_SMP = (1u << Plan::G_SMP1) | (1u << Plan::G_SMPN);
 
+static void spec_free(Plan* p);
 int plan_ensure_rows(Plan* p, uint32_t n) {
     if (n <= p->n_cap) return 0;
     lh_ctx* ctx = p->ctx;
@@ -1391,6 +1393,7 @@ void plan_destroy(Plan* p) {
     if (p->attn_part) hipFree(p->attn_part);
     if (p->s3) hipFree(p->s3);
     if (p->score_dev) hipFree(p->score_dev);
+    spec_free(p);
     delete p;
 }
 
@@ -2557,6 +2560,238 @@ static int batch_feed(Batch* b, const uint32_t* const* tokens, const uint32_t* n
     return 0;
 }
 
+// ---- lookup-draft speculative decoding (kernels_spec.h) -----------------------------------------------------------------------------
+// A pass = the batched plan_eval over a row table whose R rows all name THIS plan's cache at consecutive positions (a causal chunk, as a fed
+// prompt chunk of lh_batch_feed), k_batch_argmax over the R logits rows, k_spec_accept.  Everything a pass depends on lives in device memory, and
+// on the row-table route the attention launches are sized by the window, so a pass is captured once and replayed.
+struct Spec {
+    SpecState* st = nullptr;
+    StepParams* sp = nullptr;          // {pending token, its position}: what the one-row pass at the window's end reads
+    BatchRow* rows = nullptr;          // [SPEC_ROWS_MAX]
+    uint32_t* tok = nullptr;           // [SPEC_ROWS_MAX] pending, draft, filler
+    uint32_t* arg = nullptr;           // [SPEC_ROWS_MAX] greedy ids of the last pass
+    uint32_t* win = nullptr;           // [ctx + 1] the window's tokens, the pending one last
+    uint32_t* corpus = nullptr;
+    uint32_t corpus_cap = 0;
+    uint16_t* trace = nullptr;
+    uint32_t trace_cap = 0;
+    float* part = nullptr;             // split-T attention partials for SPEC_ROWS_MAX rows (plans with ctx > 256)
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    // what the captured pass holds by value
+    uint32_t cap_R = 0, cap_trace_cap = 0;
+    SpecLookup cap_lp = {};
+    uint32_t* cap_out = nullptr;
+    uint16_t* cap_trace = nullptr;
+    uint64_t cap_splitk_gen = 0, cap_scratch_gen = 0;
+    uint32_t warm = 0;                 // bit R: a pass of R rows has run eagerly (it sets kernel attributes a capture must not)
+};
+static void spec_drop_graph(Spec* s) {
+    if (s->exec) { hipGraphExecDestroy(s->exec); s->exec = nullptr; }
+    if (s->graph) { hipGraphDestroy(s->graph); s->graph = nullptr; }
+}
+static void spec_free(Plan* p) {
+    Spec* s = p->spec;
+    if (!s) return;
+    spec_drop_graph(s);
+    void* bufs[] = {s->st, s->sp, s->rows, s->tok, s->arg, s->win, s->corpus, s->trace, s->part};
+    for (void* q : bufs) if (q) hipFree(q);
+    delete s;
+    p->spec = nullptr;
+}
+// every allocation of the route, outside any capture
+static int spec_ensure(Plan* p, uint32_t n_corpus, uint32_t n_trace) {
+    lh_ctx* ctx = p->ctx;
+    const ModelDesc& m = p->md;
+    if (!p->spec) p->spec = new Spec();
+    Spec* s = p->spec;
+    if (!s->st) {
+        LH_HIP(ctx, hipMalloc((void**)&s->st, sizeof(SpecState)));
+        LH_HIP(ctx, hipMalloc((void**)&s->sp, sizeof(StepParams)));
+        LH_HIP(ctx, hipMalloc((void**)&s->rows, sizeof(BatchRow) * SPEC_ROWS_MAX));
+        LH_HIP(ctx, hipMalloc((void**)&s->tok, 4 * SPEC_ROWS_MAX));
+        LH_HIP(ctx, hipMalloc((void**)&s->arg, 4 * SPEC_ROWS_MAX));
+        LH_HIP(ctx, hipMalloc((void**)&s->win, 4 * ((size_t)m.ctx + 1)));
+        if (p->attn_part) LH_HIP(ctx, hipMalloc((void**)&s->part, 4 * (size_t)SPEC_ROWS_MAX * m.H * ((m.ctx + ATT_TC - 1) / ATT_TC) * (m.hd + 2)));
+    }
+    if (n_corpus > s->corpus_cap) {
+        LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (s->corpus) LH_HIP(ctx, hipFree(s->corpus));
+        s->corpus = nullptr; s->corpus_cap = 0;
+        LH_HIP(ctx, hipMalloc((void**)&s->corpus, 4 * (size_t)n_corpus));
+        s->corpus_cap = n_corpus;
+    }
+    if (n_trace > s->trace_cap) {
+        LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (s->trace) LH_HIP(ctx, hipFree(s->trace));
+        s->trace = nullptr; s->trace_cap = 0;
+        const uint32_t cap = std::max(n_trace, 4096u);
+        LH_HIP(ctx, hipMalloc((void**)&s->trace, 2 * (size_t)cap));
+        s->trace_cap = cap;
+    }
+    return 0;
+}
+// the largest row count <= want a pass can take: 1 (the decode step) or a count of the bit-identical rows path
+static uint32_t spec_pass_rows(const Plan* p, uint32_t want) {
+    uint32_t n = std::min(want, gemv_rows_max(p->md.wtype));
+    while (n > 1 && !rows_path_ok(p->ctx, p->md, n)) --n;
+    return std::max(n, 1u);
+}
+// the kernels of one pass of n rows, in stream order (n_table = rows of the table the accept step moves on)
+static int spec_enqueue_pass(Plan* p, uint32_t n, uint32_t n_table, const SpecLookup& lp, int lookup_next) {
+    lh_ctx* ctx = p->ctx;
+    const ModelDesc& m = p->md;
+    Spec* s = p->spec;
+    int rc;
+    if (n == 1) {   // the decode step's own kernels, token and position from the device
+        if ((rc = enqueue_decode(p, s->sp, nullptr, nullptr, 0, nullptr))) return rc;
+    } else {
+        BatchCtx bc = {s->rows, s->tok, p->attn_part ? s->part : nullptr};
+        if ((rc = plan_eval(p, nullptr, nullptr, nullptr, n, 0, false, &bc))) return rc;
+    }
+    LH_LAUNCH(k_batch_argmax, dim3(n), dim3(1024), 0, ctx->stream, (const float*)p->logits, m.V, (BatchRow*)nullptr, (uint32_t*)nullptr, s->arg, (uint32_t*)nullptr, 0u,
+              (StepParams*)nullptr, 0);
+    LH_LAUNCH(k_spec_accept, dim3(1), dim3(SPEC_TH), 0, ctx->stream, (const uint32_t*)s->arg, n, s->st, s->rows, s->tok, s->sp, s->win, m.ctx, m.V, p->out_tokens_dev, s->trace,
+              s->trace_cap, lp, n_table, lookup_next);
+    LH_HIP(ctx, hipGetLastError());
+    return 0;
+}
+// one full-width pass of the loop: eagerly the first time, then the captured graph (re-captured when a value it holds has changed)
+static int spec_pass(Plan* p, uint32_t R, const SpecLookup& lp) {
+    lh_ctx* ctx = p->ctx;
+    Spec* s = p->spec;
+    if (!p->use_graph || !(s->warm & (1u << R))) {
+        s->warm |= 1u << R;
+        return spec_enqueue_pass(p, R, R, lp, 1);
+    }
+    if (s->exec && (s->cap_R != R || memcmp(&s->cap_lp, &lp, sizeof lp) || s->cap_out != p->out_tokens_dev || s->cap_trace != s->trace || s->cap_trace_cap != s->trace_cap ||
+                    s->cap_splitk_gen != ctx->splitk_gen || s->cap_scratch_gen != p->scratch_gen))
+        spec_drop_graph(s);
+    if (!s->exec) {
+        LH_HIP(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeRelaxed));
+        const int rc = spec_enqueue_pass(p, R, R, lp, 1);
+        hipError_t e = hipStreamEndCapture(ctx->stream, &s->graph);
+        if (rc) { if (s->graph) { hipGraphDestroy(s->graph); s->graph = nullptr; } return rc; }
+        if (e != hipSuccess) LH_FAIL(ctx, LH_EHIP, "hipStreamEndCapture (speculative pass): %s", hipGetErrorString(e));
+        LH_HIP(ctx, hipGraphInstantiate(&s->exec, s->graph, nullptr, nullptr, 0));
+        s->cap_R = R; s->cap_lp = lp; s->cap_out = p->out_tokens_dev; s->cap_trace = s->trace; s->cap_trace_cap = s->trace_cap;
+        s->cap_splitk_gen = ctx->splitk_gen; s->cap_scratch_gen = p->scratch_gen;
+    }
+    LH_HIP(ctx, hipGraphLaunch(s->exec, ctx->stream));
+    return 0;
+}
+static int spec_set(Plan* p, uint32_t pos, uint32_t produced, uint32_t n_steps, const SpecToks& toks, uint32_t k, uint32_t n_rows, int reset) {
+    lh_ctx* ctx = p->ctx;
+    Spec* s = p->spec;
+    LH_LAUNCH(k_spec_set, dim3(1), dim3(64), 0, ctx->stream, s->st, s->rows, s->tok, s->sp, p->md.kc, p->md.vc, pos, produced, n_steps, toks, k, n_rows, p->md.ctx, reset);
+    LH_HIP(ctx, hipGetLastError());
+    return 0;
+}
+// window entries [0, pos) from the context's history and the pending token behind them, to the device
+static int spec_upload_window(Plan* p, uint32_t pos, uint32_t pending) {
+    lh_ctx* ctx = p->ctx;
+    int rc;
+    if ((rc = ensure_staging(ctx, ((uint64_t)pos + 1) * 4))) return rc;
+    LH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // staging reuse
+    uint32_t* h = (uint32_t*)ctx->staging;
+    for (uint32_t i = 0; i < pos; ++i) h[i] = (p->hist && i < p->hist->size()) ? (*p->hist)[i] : Plan::HIST_UNKNOWN;
+    h[pos] = pending;
+    LH_HIP(ctx, hipMemcpyAsync(p->spec->win, h, ((size_t)pos + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    return 0;
+}
+static int spec_check_params(lh_ctx* ctx, const ModelDesc& md, const lh_lookup_params* lp, const char* who) {
+    if (!lp) LH_FAIL(ctx, LH_EINVAL, "%s: no lookup parameters", who);
+    const uint32_t kmax = gemv_rows_max(md.wtype) - 1;
+    if (lp->draft_max < 1 || lp->draft_max > kmax) LH_FAIL(ctx, LH_EINVAL, "%s: draft_max %u (1..%u for this weight type)", who, lp->draft_max, kmax);
+    if (lp->ngram_min < 1 || lp->ngram_min > lp->ngram_max || lp->ngram_max > SPEC_NGRAM_MAX)
+        LH_FAIL(ctx, LH_EINVAL, "%s: n-gram bounds %u..%u (1 <= ngram_min <= ngram_max <= %u)", who, lp->ngram_min, lp->ngram_max, SPEC_NGRAM_MAX);
+    if (lp->n_corpus > SPEC_CORPUS_MAX) LH_FAIL(ctx, LH_EINVAL, "%s: a corpus of %u tokens (at most %u)", who, lp->n_corpus, SPEC_CORPUS_MAX);
+    if (lp->n_corpus && lp->corpus)
+        for (uint32_t i = 0; i < lp->n_corpus; ++i)
+            if (lp->corpus[i] >= md.V) LH_FAIL(ctx, LH_EINVAL, "%s: corpus id %u at index %u outside the vocabulary of %u", who, lp->corpus[i], i, md.V);
+    return 0;
+}
+
+static int spec_decode_lookup(Plan* p, uint32_t first_token, uint32_t past, uint32_t n_steps, const lh_lookup_params* lpar, uint32_t R, uint32_t* out_tokens,
+                              float* logits_last_host, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap) {
+    lh_ctx* ctx = p->ctx;
+    const ModelDesc& md = p->md;
+    int rc;
+    const uint32_t n_corpus = lpar->corpus ? lpar->n_corpus : 0;
+    if ((rc = spec_ensure(p, n_corpus, n_steps))) return rc;
+    if ((rc = plan_ensure_rows(p, R))) return rc;
+    if ((rc = ensure_out_tokens(p, n_steps))) return rc;
+    Spec* s = p->spec;
+    if (n_corpus) {
+        if ((rc = ensure_staging(ctx, (uint64_t)n_corpus * 4))) return rc;
+        LH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // staging reuse
+        memcpy(ctx->staging, lpar->corpus, (size_t)n_corpus * 4);
+        LH_HIP(ctx, hipMemcpyAsync(s->corpus, ctx->staging, (size_t)n_corpus * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+    const SpecLookup lp = {n_corpus ? s->corpus : nullptr, n_corpus, R - 1, lpar->ngram_max, lpar->ngram_min};
+    uint32_t pos = past, produced = 0, seg_pos0 = past;
+    SpecState hs = {};
+    std::vector<uint32_t> got, refeed;
+    // the tokens the passes since seg_pos0 evaluated (window entries [seg_pos0, pos)) go into the context's history; returns the pending one
+    auto learn = [&](uint32_t* pending) -> int {
+        got.resize((size_t)pos - seg_pos0 + 1);
+        LH_HIP(ctx, hipMemcpyAsync(got.data(), s->win + seg_pos0, got.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+        LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (uint32_t i = seg_pos0; i < pos; ++i) p->record(i, got[i - seg_pos0]);
+        *pending = got[pos - seg_pos0];
+        return 0;
+    };
+    // state, table and first draft of a run of passes that starts with `pending` at position pos
+    auto start = [&](uint32_t pending, int reset) -> int {
+        if ((rc = spec_upload_window(p, pos, pending))) return rc;
+        SpecToks t;
+        for (uint32_t r = 0; r < SPEC_ROWS_MAX; ++r) t.t[r] = pending;
+        if ((rc = spec_set(p, pos, produced, n_steps, t, 0, R, reset))) return rc;
+        LH_LAUNCH(k_draft_lookup, dim3(1), dim3(SPEC_TH), 0, ctx->stream, (const uint32_t*)s->win, 0u, lp, 0u, md.V, s->tok, (uint32_t*)nullptr, s->st, md.ctx, R);
+        LH_HIP(ctx, hipGetLastError());
+        seg_pos0 = pos;
+        return 0;
+    };
+    if (past < md.ctx && (rc = start(first_token, 1))) return rc;
+    bool started = past < md.ctx;
+    uint32_t pending = first_token;
+    while (produced < n_steps) {
+        if (pos >= md.ctx) {   // the context swap of the resident loops (server.go:160-172, resident_steps_swapping)
+            if (started && (rc = learn(&pending))) return rc;
+            if (p->keep >= md.ctx) LH_FAIL(ctx, LH_EINVAL, "context swap: KeepCount %u leaves no room in a window of %u", p->keep, md.ctx);
+            if (!swap_refeed_tokens(p, pos, pending, &refeed))
+                LH_FAIL(ctx, LH_EINVAL, "context swap at position %u: the tokens of the window are not known to this context (evaluate the prompt through it first)", pos);
+            if (!refeed.empty() && (rc = plan_eval(p, refeed.data(), nullptr, nullptr, (uint32_t)refeed.size(), p->keep, true))) return rc;
+            pos = p->keep + (uint32_t)refeed.size();
+            if ((rc = plan_ensure_rows(p, R))) return rc;
+            if ((rc = start(pending, started ? 0 : 1))) return rc;
+            started = true;
+        }
+        const uint32_t n = spec_pass_rows(p, std::min(R, md.ctx - pos));
+        if (n == R) {
+            // `produced` and `pos` are exact here; q passes move them on by q..q*R: as many as can neither pass n_steps nor leave the window run unseen
+            const uint32_t q = std::max(1u, std::min((n_steps - produced) / R, (md.ctx - pos) / R));
+            for (uint32_t j = 0; j < q; ++j) if ((rc = spec_pass(p, R, lp))) return rc;
+        } else if ((rc = spec_enqueue_pass(p, n, R, lp, 1))) {
+            return rc;
+        }
+        LH_HIP(ctx, hipMemcpyAsync(&hs, s->st, sizeof hs, hipMemcpyDeviceToHost, ctx->stream));
+        LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (hs.produced <= produced) LH_FAIL(ctx, LH_EHIP, "lh_llama_decode_lookup: a pass produced no id");
+        pos = hs.pos; produced = hs.produced;
+    }
+    if ((rc = learn(&pending))) return rc;
+    if (out_tokens) LH_HIP(ctx, hipMemcpyAsync(out_tokens, p->out_tokens_dev, (size_t)n_steps * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (logits_last_host) LH_HIP(ctx, hipMemcpyAsync(logits_last_host, p->logits + (size_t)hs.last_a * md.V, (size_t)md.V * 4, hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<uint16_t> tr;
+    const uint32_t n_tr = trace ? std::min(std::min(trace_cap, hs.passes), s->trace_cap) : 0;
+    if (n_tr) { tr.resize(n_tr); LH_HIP(ctx, hipMemcpyAsync(tr.data(), s->trace, (size_t)n_tr * 2, hipMemcpyDeviceToHost, ctx->stream)); }
+    LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (n_tr) memcpy(trace, tr.data(), (size_t)n_tr * 2);
+    if (stats) { stats->passes = hs.passes; stats->rows = R; stats->drafted = hs.drafted; stats->accepted = hs.accepted; stats->empty = hs.empty; }
+    return 0;
+}
+
 }  // namespace lh
 
 using namespace lh;
@@ -2696,6 +2931,100 @@ int lh_llama_decode_greedy(lh_llama* m, uint32_t first_token, uint32_t past, uin
     if (logits_last_host) LH_HIP(ctx, hipMemcpyAsync(logits_last_host, p->logits, (size_t)md.V * 4, hipMemcpyDeviceToHost, ctx->stream));
     LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return LH_OK;
+}
+
+int lh_draft_lookup(lh_ctx* ctx, const uint32_t* window, uint32_t n_window, const lh_lookup_params* lp, uint32_t limit, uint32_t* draft_out, uint32_t* n_draft) {
+    if (!ctx) return LH_EINVAL;
+    if (!window || !n_window || !lp || !draft_out || !n_draft) LH_FAIL(ctx, LH_EINVAL, "lh_draft_lookup: null argument or empty window");
+    if (lp->draft_max < 1 || lp->draft_max > SPEC_ROWS_MAX - 1) LH_FAIL(ctx, LH_EINVAL, "lh_draft_lookup: draft_max %u (1..%u)", lp->draft_max, SPEC_ROWS_MAX - 1);
+    if (lp->ngram_min < 1 || lp->ngram_min > lp->ngram_max || lp->ngram_max > SPEC_NGRAM_MAX)
+        LH_FAIL(ctx, LH_EINVAL, "lh_draft_lookup: n-gram bounds %u..%u (1 <= ngram_min <= ngram_max <= %u)", lp->ngram_min, lp->ngram_max, SPEC_NGRAM_MAX);
+    if (lp->n_corpus > SPEC_CORPUS_MAX) LH_FAIL(ctx, LH_EINVAL, "lh_draft_lookup: a corpus of %u tokens (at most %u)", lp->n_corpus, SPEC_CORPUS_MAX);
+    if (n_window > (1u << 24)) LH_FAIL(ctx, LH_EINVAL, "lh_draft_lookup: a window of %u tokens", n_window);
+    LH_HIP(ctx, hipSetDevice(ctx->device));
+    const uint32_t nc = lp->corpus ? lp->n_corpus : 0;
+    // one allocation: window | corpus | draft | count
+    const size_t o_c = (size_t)n_window * 4, o_d = o_c + (size_t)nc * 4, o_k = o_d + 4 * SPEC_ROWS_MAX, total = o_k + 4;
+    char* dev = nullptr;
+    LH_HIP(ctx, hipMalloc((void**)&dev, total));
+    uint32_t res[SPEC_ROWS_MAX + 1] = {};
+    hipError_t e = hipMemcpyAsync(dev, window, o_c, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && nc) e = hipMemcpyAsync(dev + o_c, lp->corpus, (size_t)nc * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the caller's arrays are pageable host memory
+    if (e == hipSuccess) {
+        const SpecLookup dl = {nc ? (const uint32_t*)(dev + o_c) : nullptr, nc, lp->draft_max, lp->ngram_max, lp->ngram_min};
+        LH_LAUNCH(k_draft_lookup, dim3(1), dim3(SPEC_TH), 0, ctx->stream, (const uint32_t*)dev, n_window, dl, limit, SPEC_UNKNOWN, (uint32_t*)(dev + o_d), (uint32_t*)(dev + o_k),
+                  (SpecState*)nullptr, 0u, 0u);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(res, dev + o_d, sizeof res, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    }
+    hipFree(dev);
+    if (e != hipSuccess) LH_FAIL(ctx, LH_EHIP, "lh_draft_lookup: %s", hipGetErrorString(e));
+    *n_draft = res[SPEC_ROWS_MAX];
+    for (uint32_t i = 0; i < res[SPEC_ROWS_MAX] && i < lp->draft_max; ++i) draft_out[i] = res[i];
+    return LH_OK;
+}
+
+int lh_llama_verify(lh_llama* m, const uint32_t* tokens, uint32_t n, uint32_t past, uint32_t* ids_out, uint32_t* n_accepted, float* logits_host) {
+    if (!m) return LH_EINVAL;
+    lh_ctx* ctx = m->ctx;
+    Plan* p = m->plan;
+    const ModelDesc& md = p->md;
+    if (!tokens || !ids_out || !n_accepted) LH_FAIL(ctx, LH_EINVAL, "lh_llama_verify: null argument");
+    LH_HIP(ctx, hipSetDevice(ctx->device));
+    if (!md.first_stage() || !md.last_stage()) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_llama_verify needs a whole-model plan (layers [%u, %u) of %u)", md.layer0, md.layer1, md.L);
+    if (n < 1 || n > gemv_rows_max(md.wtype)) LH_FAIL(ctx, LH_EINVAL, "lh_llama_verify: %u rows (1..%u for this weight type)", n, gemv_rows_max(md.wtype));
+    if ((uint64_t)past + n > md.ctx) LH_FAIL(ctx, LH_EINVAL, "lh_llama_verify: past %u + n %u exceeds the context window of %u", past, n, md.ctx);
+    for (uint32_t i = 0; i < n; ++i)
+        if (tokens[i] >= md.V) LH_FAIL(ctx, LH_EINVAL, "lh_llama_verify: token id %u at index %u outside the vocabulary of %u", tokens[i], i, md.V);
+    if (n > 1 && !rows_path_ok(ctx, md, n)) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_llama_verify: this model's shapes have no %u-row pass on the decode stream", n);
+    int rc;
+    if ((rc = spec_ensure(p, 0, n))) return rc;
+    if ((rc = plan_ensure_rows(p, n))) return rc;
+    if ((rc = ensure_out_tokens(p, n))) return rc;
+    Spec* s = p->spec;
+    SpecToks t = {};
+    for (uint32_t i = 0; i < SPEC_ROWS_MAX; ++i) t.t[i] = tokens[i < n ? i : 0];
+    if ((rc = spec_set(p, past, 0, n, t, n - 1, n, 1))) return rc;
+    const SpecLookup none = {nullptr, 0, 0, 1, 1};
+    if ((rc = spec_enqueue_pass(p, n, n, none, 0))) return rc;
+    SpecState hs = {};
+    uint32_t ids[SPEC_ROWS_MAX] = {};
+    LH_HIP(ctx, hipMemcpyAsync(&hs, s->st, sizeof hs, hipMemcpyDeviceToHost, ctx->stream));
+    LH_HIP(ctx, hipMemcpyAsync(ids, p->out_tokens_dev, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const uint32_t a = hs.last_a;
+    if (hs.produced != a + 1 || a >= n) LH_FAIL(ctx, LH_EHIP, "lh_llama_verify: the accept step left an inconsistent state");
+    if (logits_host) {
+        LH_HIP(ctx, hipMemcpyAsync(logits_host, p->logits + (size_t)a * md.V, (size_t)md.V * 4, hipMemcpyDeviceToHost, ctx->stream));
+        LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    for (uint32_t i = 0; i <= a; ++i) { p->record(past + i, tokens[i]); ids_out[i] = ids[i]; }
+    *n_accepted = a;
+    return LH_OK;
+}
+
+int lh_llama_decode_lookup(lh_llama* m, uint32_t first_token, uint32_t past, uint32_t n_steps, const lh_lookup_params* lp, uint32_t* out_tokens, float* logits_last_host,
+                           lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap) {
+    if (!m || !n_steps) return LH_EINVAL;
+    lh_ctx* ctx = m->ctx;
+    Plan* p = m->plan;
+    const ModelDesc& md = p->md;
+    LH_HIP(ctx, hipSetDevice(ctx->device));
+    if (!md.first_stage() || !md.last_stage()) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_llama_decode_lookup needs a whole-model plan (layers [%u, %u) of %u)", md.layer0, md.layer1, md.L);
+    int rc;
+    if ((rc = spec_check_params(ctx, md, lp, "lh_llama_decode_lookup"))) return rc;
+    if (past > md.ctx) LH_FAIL(ctx, LH_EINVAL, "decode: position %u outside the context window of %u", past, md.ctx);
+    if (first_token >= md.V) LH_FAIL(ctx, LH_EINVAL, "decode: token id %u outside the vocabulary of %u", first_token, md.V);
+    const uint32_t R = spec_pass_rows(p, lp->draft_max + 1);
+    if (R == 1) {   // no multi-row pass on this plan's shapes: plain greedy steps, and the stats say so
+        if ((rc = lh_llama_decode_greedy(m, first_token, past, n_steps, out_tokens, logits_last_host))) return rc;
+        if (stats) { stats->passes = n_steps; stats->rows = 1; stats->drafted = 0; stats->accepted = 0; stats->empty = n_steps; }
+        if (trace) for (uint32_t i = 0; i < n_steps && i < trace_cap; ++i) trace[i] = 0;
+        return LH_OK;
+    }
+    return spec_decode_lookup(p, first_token, past, n_steps, lp, R, out_tokens, logits_last_host, stats, trace, trace_cap);
 }
 
 int lh_llama_decode_sample(lh_llama* m, const uint32_t* prompt, uint32_t n_prompt, uint32_t n_predict, uint32_t ring_size, const lh_sample_params* sp,

@@ -157,6 +157,46 @@ func (st *StageHIP) Score(tokens []uint32, pastCount uint32, targets []uint32) [
 	return out
 }
 
+// Verify is one verify pass of lossless speculative decoding (lh_llama_verify): tokens[0] is the pending token at pastCount, tokens[1:] a
+// draft from anywhere (a small model, a cache of earlier answers); 1..8 rows (block-int8: 4).  All rows go through ONE pass over the weights,
+// every row bit-identical to its one-token Eval; ids = the greedy ids of rows 0..a, a = the draft tokens the model itself produced.  The
+// stage then stands at pastCount + a + 1 with ids[a] pending.  C++ twin: llamago_Verify.
+func (st *StageHIP) Verify(tokens []uint32, pastCount uint32) (ids []uint32, accepted uint32) {
+	out := make([]uint32, len(tokens))
+	var a C.uint32_t
+	if rc := C.lh_llama_verify(st.h, (*C.uint32_t)(unsafe.Pointer(&tokens[0])), C.uint32_t(len(tokens)), C.uint32_t(pastCount),
+		(*C.uint32_t)(unsafe.Pointer(&out[0])), &a, nil); rc != 0 {
+		hipHalt(st.ctx.hip.ctx)
+	}
+	return out[:a+1], uint32(a)
+}
+
+// SpecStatsHIP has the layout of lh_spec_stats: passes, rows per pass, and the drafted / accepted / empty-draft totals of a DecodeLookup.
+type SpecStatsHIP struct{ Passes, Rows, Drafted, Accepted, Empty uint32 }
+
+// DecodeLookup is the greedy loop of server.Do (server.go:201-217 with TopK = 1) through verify passes drafted by n-gram lookup over the
+// stage's own window and an optional corpus (lh_llama_decode_lookup; the rule is stated in include/llamahip.h): exactly the nSteps ids the
+// one-token loop produces from (firstToken, pastCount), in fewer passes over the weights wherever the text repeats.  C++ twin: llamago_DecodeLookup.
+func (st *StageHIP) DecodeLookup(firstToken, pastCount, nSteps, draftMax, ngramMax, ngramMin uint32, corpus []uint32) ([]uint32, SpecStatsHIP) {
+	out := make([]uint32, nSteps)
+	var stats SpecStatsHIP
+	lp := C.lh_lookup_params{draft_max: C.uint32_t(draftMax), ngram_max: C.uint32_t(ngramMax), ngram_min: C.uint32_t(ngramMin)}
+	if len(corpus) > 0 { // through C memory: a struct handed to C must not contain Go pointers
+		n := len(corpus)
+		cc := (*[1 << 28]C.uint32_t)(C.malloc(C.size_t(n) * 4))[:n:n]
+		defer C.free(unsafe.Pointer(&cc[0]))
+		for i, t := range corpus {
+			cc[i] = C.uint32_t(t)
+		}
+		lp.corpus, lp.n_corpus = &cc[0], C.uint32_t(n)
+	}
+	if rc := C.lh_llama_decode_lookup(st.h, C.uint32_t(firstToken), C.uint32_t(pastCount), C.uint32_t(nSteps), &lp,
+		(*C.uint32_t)(unsafe.Pointer(&out[0])), nil, (*C.lh_spec_stats)(unsafe.Pointer(&stats)), nil, 0); rc != 0 {
+		hipHalt(st.ctx.hip.ctx)
+	}
+	return out, stats
+}
+
 // ---- the pods of ONE GPU in one weight pass (include/llamahip.h: lh_batch_*) --------------------------------------------
 // server.Engine starts up to MaxPods concurrent Do() goroutines over one Model (server.go:84-106, 151).  With UseHIP the engine
 // instead keeps ONE BatchHIP per GPU: every pod is a row; Prompt() evaluates the pods' prompts, each Tick() advances every pod by

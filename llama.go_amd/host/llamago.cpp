@@ -1202,6 +1202,26 @@ int llamago_Score(llama_context* c, llama_model* m, const uint32_t* tokens, uint
     if (lh_llama_score(r, tokens, n, pastCount, targets_or_null, out)) return halt_rc(lh_last_error(c->mlctx->hip));
     return 0;
 }
+// ---- lookup-draft speculative decoding (lh_draft_lookup / lh_llama_verify / lh_llama_decode_lookup) ----
+int llamago_DraftLookup(const uint32_t* window, uint32_t n_window, const lh_lookup_params* lp, uint32_t limit, uint32_t* draft_out, uint32_t* n_draft) {
+    lh_ctx* h = model_ctx();
+    if (!h) return 1;
+    if (lh_draft_lookup(h, window, n_window, lp, limit, draft_out, n_draft)) return halt_rc(lh_last_error(h));
+    return 0;
+}
+int llamago_Verify(llama_context* c, const uint32_t* tokens, uint32_t n, uint32_t past, uint32_t* ids_out, uint32_t* n_accepted, float* logits) {
+    lh_llama* r = resident(c);
+    if (!r) return 1;
+    if (lh_llama_verify(r, tokens, n, past, ids_out, n_accepted, logits)) return halt_rc(lh_last_error(c->mlctx->hip));
+    return 0;
+}
+int llamago_DecodeLookup(llama_context* c, uint32_t first_token, uint32_t past, uint32_t n_steps, const lh_lookup_params* lp, uint32_t* out_tokens,
+                         float* logits_last, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap) {
+    lh_llama* r = resident(c);
+    if (!r) return 1;
+    if (lh_llama_decode_lookup(r, first_token, past, n_steps, lp, out_tokens, logits_last, stats, trace, trace_cap)) return halt_rc(lh_last_error(c->mlctx->hip));
+    return 0;
+}
 int llamago_Perplexity(llama_context* c, llama_model* m, const uint32_t* tokens, uint32_t n_tokens, uint32_t chunk, double* nll_sum, uint64_t* n_scored) {
     if (!c || c->model != m) return halt_rc("llamago_Perplexity: context does not belong to this model");
     if (!tokens || !nll_sum || !n_scored) return halt_rc("llamago_Perplexity: null argument");

@@ -384,6 +384,36 @@ class Context:
             raise MLError(f"llamago_Score: {self.ml.last_error()}")
         return np.frombuffer(out, dtype=ROW_SCORE_DTYPE, count=n).copy()
 
+    def Verify(self, tokens, past, want_logits=False):
+        """llamago_Verify: one verify pass of [pending token, draft...] on this context's cache at position `past` (lh_llama_verify).
+        -> (ids of rows 0..a, a, logits of row a or None); the context then stands at past + a + 1."""
+        L = self.ml.lib
+        L.llamago_Verify.restype = C.c_int
+        L.llamago_Verify.argtypes = [VP, c_u32p, c_u32, c_u32, c_u32p, c_u32p, c_f32p]
+        n = len(tokens)
+        toks = (c_u32 * max(n, 1))(*[int(t) for t in tokens])
+        ids, a = (c_u32 * max(n, 1))(), c_u32(0)
+        lg = np.empty(self.model.hp.vocabSize, dtype=np.float32) if want_logits else None
+        if L.llamago_Verify(self.h, toks, n, int(past), ids, C.byref(a), lg.ctypes.data_as(c_f32p) if want_logits else None):
+            raise MLError(f"llamago_Verify: {self.ml.last_error()}")
+        return [int(t) for t in ids[:a.value + 1]], int(a.value), lg
+
+    def DecodeLookup(self, first_token, past, n_steps, draft_max, ngram_max=3, ngram_min=1, corpus=None, want_logits=False):
+        """llamago_DecodeLookup: the resident greedy loop through lookup-drafted verify passes (lh_llama_decode_lookup).
+        -> (ids, last logits or None, stats dict(passes, rows, drafted, accepted, empty), trace list of (k, a) per pass)."""
+        L = self.ml.lib
+        L.llamago_DecodeLookup.restype = C.c_int
+        L.llamago_DecodeLookup.argtypes = [VP, c_u32, c_u32, c_u32, C.POINTER(LookupParams), c_u32p, c_f32p, C.POINTER(SpecStats), C.POINTER(C.c_uint16), c_u32]
+        lp, _keep = lookup_params(draft_max, ngram_max, ngram_min, corpus)
+        n = max(int(n_steps), 1)
+        out, st, tr = (c_u32 * n)(), SpecStats(), (C.c_uint16 * n)()
+        lg = np.empty(self.model.hp.vocabSize, dtype=np.float32) if want_logits else None
+        if L.llamago_DecodeLookup(self.h, int(first_token), int(past), int(n_steps), C.byref(lp), out, lg.ctypes.data_as(c_f32p) if want_logits else None,
+                                  C.byref(st), tr, n):
+            raise MLError(f"llamago_DecodeLookup: {self.ml.last_error()}")
+        stats = dict(passes=int(st.passes), rows=int(st.rows), drafted=int(st.drafted), accepted=int(st.accepted), empty=int(st.empty))
+        return [int(t) for t in out[:n_steps]], lg, stats, [(int(v) >> 8, int(v) & 0xFF) for v in tr[:min(st.passes, n)]]
+
     def Perplexity(self, tokens, chunk=0):
         """llamago_Perplexity (convention: include/llamago_ext.h) -> (nll_sum, n_scored); perplexity = exp(nll_sum / n_scored)."""
         L = self.ml.lib
@@ -426,6 +456,35 @@ class RowScore(C.Structure):
 
 
 ROW_SCORE_DTYPE = np.dtype([("logprob", "<f8"), ("lse", "<f8"), ("target_logit", "<f4"), ("max_logit", "<f4"), ("argmax", "<u4"), ("target_rank", "<u4")])
+
+
+class LookupParams(C.Structure):
+    """lh_lookup_params (include/llamahip.h)."""
+    _fields_ = [("draft_max", c_u32), ("ngram_max", c_u32), ("ngram_min", c_u32), ("corpus", c_u32p), ("n_corpus", c_u32)]
+
+
+class SpecStats(C.Structure):
+    """lh_spec_stats (include/llamahip.h)."""
+    _fields_ = [("passes", c_u32), ("rows", c_u32), ("drafted", c_u32), ("accepted", c_u32), ("empty", c_u32)]
+
+
+def lookup_params(draft_max, ngram_max=3, ngram_min=1, corpus=None):
+    """-> (LookupParams, the ctypes array its corpus pointer names: keep it alive for the call)."""
+    arr = (c_u32 * len(corpus))(*[int(t) for t in corpus]) if corpus is not None and len(corpus) else None
+    lp = LookupParams(int(draft_max), int(ngram_max), int(ngram_min), C.cast(arr, c_u32p) if arr is not None else None, len(corpus) if arr is not None else 0)
+    return lp, arr
+
+
+def draft_lookup(ml, window, draft_max, ngram_max=3, ngram_min=1, corpus=None, limit=None):
+    """llamago_DraftLookup: the n-gram drafter alone on the device (lh_draft_lookup) -> the draft ids."""
+    ml.lib.llamago_DraftLookup.restype = C.c_int
+    ml.lib.llamago_DraftLookup.argtypes = [c_u32p, c_u32, C.POINTER(LookupParams), c_u32, c_u32p, c_u32p]
+    lp, _keep = lookup_params(draft_max, ngram_max, ngram_min, corpus)
+    win = (c_u32 * max(len(window), 1))(*[int(t) for t in window])
+    out, k = (c_u32 * 8)(), c_u32(0)
+    if ml.lib.llamago_DraftLookup(win, len(window), C.byref(lp), int(draft_max if limit is None else limit), out, C.byref(k)):
+        raise MLError(f"llamago_DraftLookup: {ml.last_error()}")
+    return [int(t) for t in out[:k.value]]
 
 
 def score_rows(ml, logits, targets):

@@ -1,0 +1,114 @@
+"""Lookup-draft speculative decoding against the routes it rides on, LLaMA-7B shape (results: profiles/speculative.txt).
+Host wall time of the calls (their synchronisations included), median of --reps after a warm-up call.  The weights are synthetic: acceptance
+rates here are those of a replayed or a random text, never a model result.
+  pass    cost of a verify pass of R rows (fp32 2 / 4 / 8, block-int8 2 / 4) behind 100 and behind 1000 cached tokens: the loop's own wall time /
+          passes on a replay workload (corpus = the greedy run itself, so every pass is full), against a tick of R pods of lh_batch_decode at the
+          same positions in the same process (existing code), and against the one-token resident step
+  golden  the 7B golden workload (8-token prompt, ctx 128, 99 ids): the loop with the replay corpus (acceptance 1: the ceiling), without a corpus
+          (the honest side), and lh_llama_decode_greedy, tokens/s each; the break-even mean of accepted ids per pass from the measured times
+usage: python tools/bench_speculative.py [pass golden] [--layers 32] [--reps 5] [--int8] [--out profiles/speculative.txt]"""
+import argparse, json, os, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+from llama_go_amd.mlapi import PROMPT, SHAPES, Batch, decode_greedy_resident, load_product, make_hparams
+
+ap = argparse.ArgumentParser()
+ap.add_argument("parts", nargs="*", default=["pass", "golden"])
+ap.add_argument("--layers", type=int, default=32)
+ap.add_argument("--reps", type=int, default=5)
+ap.add_argument("--int8", action="store_true", help="block-int8 weights too")
+ap.add_argument("--out", default=None, help="append the result lines to this file")
+args = ap.parse_args()
+prod = load_product()
+lines = []
+
+
+def emit(d):
+    s = json.dumps(d)
+    print(s, flush=True)
+    lines.append(s)
+
+
+def med(fn, reps=args.reps):
+    fn()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter(); fn(); ts.append(time.perf_counter() - t0)
+    return sorted(ts)[len(ts) // 2] * 1e3
+
+
+def model(ctx, int8):
+    kw = dict(SHAPES["7B"]); kw["layers"] = args.layers
+    m = prod.NewSyntheticModel(make_hparams(**kw, ctx=ctx), 1234)
+    if int8:
+        m.QuantizeQ8()
+    return m
+
+
+def prompt_state(m, ctx, prompt):
+    c = m.NewContext(ctx, 1)
+    return c, int(np.argmax(c.Eval(prompt, 0)))
+
+
+if "pass" in args.parts:
+    N = 96   # ids per timed call: 12 full passes at R = 8
+    for int8 in ([False, True] if args.int8 else [False]):
+        for cached in (100, 1000):
+            ctx = cached + 2 * N + 16
+            m = model(ctx, int8)
+            rng = np.random.default_rng(cached)
+            prompt = [int(t) for t in rng.integers(0, 32000, cached)]
+            c, first = prompt_state(m, ctx, prompt)
+            g, _ = decode_greedy_resident(c, first, cached, N)
+            step_ms = med(lambda: decode_greedy_resident(c, first, cached, N)) / N
+            for R in ((2, 4) if int8 else (2, 4, 8)):
+                res = {}
+
+                def loop():
+                    ids, _, st, _ = c.DecodeLookup(first, cached, N, R - 1, 3, 1, prompt[-8:] + [first] + g)
+                    assert ids == g and st["rows"] == R, st
+                    res.update(st)
+                loop_ms = med(loop)
+                b = Batch(m, ctx, R)
+                pr, T = [prompt] * R, 48   # resident ticks of lh_batch_decode: the difference of two runs leaves the ticks alone (prompts and set-up cancel)
+                tick_ms = (med(lambda: b.GreedyDecode(pr, 2 + T)) - med(lambda: b.GreedyDecode(pr, 2))) / T
+                b.free()
+                pass_ms = loop_ms / res["passes"]
+                emit(dict(part="pass", int8=int8, layers=args.layers, cached=cached, rows=R, passes=res["passes"], ids=N, pass_ms=round(pass_ms, 3),
+                          tick_of_R_pods_ms=round(tick_ms, 3), pass_over_tick=round(pass_ms / tick_ms, 3), step_ms=round(step_ms, 3),
+                          pass_over_step=round(pass_ms / step_ms, 3)))
+            c.free()
+            m.free()
+
+if "golden" in args.parts:
+    for int8 in ([False, True] if args.int8 else [False]):
+        gold = json.load(open(os.path.join(ROOT, "tests", "golden", "7b_seed1234_int8_ids.json" if int8 else "7b_seed1234_ids.json")))["ids"]
+        K = 3 if int8 else 7
+        m = model(128, int8)
+        c, first = prompt_state(m, 128, PROMPT)
+        n = 99
+        exact = args.layers == 32
+        greedy_ms = med(lambda: decode_greedy_resident(c, first, len(PROMPT), n))
+        g, _ = decode_greedy_resident(c, first, len(PROMPT), n)
+        assert not exact or [first] + g == gold
+        out = dict(part="golden", int8=int8, layers=args.layers, ids=n, rows=K + 1, greedy_ms=round(greedy_ms, 2), greedy_tok_s=round(n / greedy_ms * 1e3, 1))
+        for name, corpus in (("replay", PROMPT + [first] + g), ("no_corpus", None)):
+            res = {}
+
+            def loop():
+                ids, _, st, _ = c.DecodeLookup(first, len(PROMPT), n, K, 3, 1, corpus)
+                assert ids == g and st["rows"] == K + 1, st
+                res.update(st)
+            ms = med(loop)
+            out.update({f"{name}_passes": res["passes"], f"{name}_accepted": res["accepted"], f"{name}_ms": round(ms, 2), f"{name}_tok_s": round(n / ms * 1e3, 1),
+                        f"{name}_pass_ms": round(ms / res["passes"], 3)})
+        # the route wins when ids per pass = 1 + mean accepted > pass time / step time
+        out["break_even_accepted_per_pass"] = round(out["no_corpus_pass_ms"] / (greedy_ms / n) - 1, 3)
+        emit(out)
+        c.free()
+        m.free()
+
+if args.out:
+    with open(args.out, "a") as f:
+        f.write("\n".join(lines) + "\n")
