@@ -72,6 +72,9 @@ int llamago_Stage(llama_context* c, const uint32_t* tokens, const void* tokens_d
                   void* logits_dev, void* argmax_dev);
 /* lh_score_rows on the model context's device: rows of host logits [n_rows][n_logits] scored against targets[row] (op-level parity). */
 int llamago_ScoreRows(const float* logits, uint32_t n_rows, uint32_t n_logits, const uint32_t* targets, lh_row_score* out);
+/* lh_argmax_rows on the model context's device: the greedy id of every row of host logits [n_rows][n_logits], by k_argmax_advance launched once per
+ * row (which = 0) or by one k_batch_argmax launch over all rows (which = 1) - the two kernels every greedy route takes its ids from (op-level parity). */
+int llamago_ArgmaxRows(const float* logits, uint32_t n_rows, uint32_t n_logits, int which, uint32_t* ids_out);
 /* lh_llama_score on the context's own KV cache: llama.Eval of tokens[0..n) at pastCount with the lm_head for all n rows (llama.go:384), every row
  * reduced on the device (softmax arithmetic llama.go:581-609); out[i] belongs to the logits behind tokens[i].  targets_or_null == NULL: row i against
  * tokens[i+1], the last row against its own greedy id.  Leaves the cache as llama_Eval with the same arguments does. */

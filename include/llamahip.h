@@ -172,8 +172,17 @@ int lh_llama_eval(lh_llama* m, const uint32_t* tokens, uint32_t n, uint32_t past
  * that went through it with host token ids and from its own resident loops; otherwise the loop fails with LH_EINVAL at the window's
  * end.  A single Eval past the window (lh_llama_eval, lh_llama_stage, lh_graph_compute) stays an error, as llama.Eval would panic. */
 int lh_llama_set_keep(lh_llama* m, uint32_t keep);
+/* The greedy rule of every route that picks ids on the device (lh_llama_decode_greedy, lh_llama_stage's argmax, lh_llama_verify,
+ * lh_llama_decode_lookup, lh_batch_tick / _prompt / _feed): lowest index on ties; NaN as the checker's argmax_f32, i.e. the reference's
+ * `best = 0; if x[i] > x[best] { best = i }` loop - a NaN at index 0 wins the row, a NaN anywhere else is never taken.  +0 and -0 tie.
+ * lh_argmax_rows is the op-level twin of lh_sample_top_p_top_k / lh_score_rows for the two kernels behind those routes: it uploads host
+ * logits [n_rows][n_logits] packed (rows behind the first are 16-byte aligned only when n_logits % 4 == 0) and returns every row's id;
+ * which = 0: k_argmax_advance, one launch per row (the solo loop's kernel); which = 1: one k_batch_argmax launch, one workgroup per row
+ * (ticks, verify).  Both must return the same id for every row.  n_logits outside 1..65536: LH_ESHAPE; n_rows = 0, a null argument, any
+ * other `which`: LH_EINVAL. */
+int lh_argmax_rows(lh_ctx* ctx, const float* logits_host, uint32_t n_rows, uint32_t n_logits, int which, uint32_t* ids_out_host);
 /* Device-resident greedy decode: step i evaluates one token at position past+i; the argmax (lowest
- * index on ties) is taken on the GPU and feeds step i+1 without a host round trip.  out_tokens[i]
+ * index on ties, the rule above) is taken on the GPU and feeds step i+1 without a host round trip.  out_tokens[i]
  * = id produced by step i.  logits_last_host (optional) receives the final step's logits.  Past the
  * window the loop swaps context (above): one host synchronisation per (ctx - keep) / 2 tokens. */
 int lh_llama_decode_greedy(lh_llama* m, uint32_t first_token, uint32_t past, uint32_t n_steps,

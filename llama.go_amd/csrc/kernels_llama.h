@@ -677,6 +677,9 @@ __global__ __launch_bounds__(256) void k_embed(const float* __restrict__ emb, co
 }
 
 // Greedy argmax over the logits (strict >, lowest index on ties: SURVEY §8c) + advance of the resident loop.
+// NaN as the reference's `best = 0; if x[i] > x[best] { best = i }` loop (the checker's argmax_f32): a NaN at index 0 wins, a NaN anywhere
+// else is never taken.  No thread takes an element unseen: (value, index) pairs merge by "greater value, or equal value and lower index" from
+// (-inf, 0xFFFFFFFF) everywhere - inside a thread, across lanes and across waves - which no NaN passes.
 __global__ __launch_bounds__(1024) void k_argmax_advance(const float* __restrict__ logits, uint32_t n, StepParams* sp, uint32_t* __restrict__ out_tokens,
                                                          uint32_t* __restrict__ argmax_out, int advance) {
     __shared__ float sv[16];
@@ -684,8 +687,9 @@ __global__ __launch_bounds__(1024) void k_argmax_advance(const float* __restrict
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float bv = -INFINITY;
     uint32_t bi = 0xFFFFFFFFu;
-    auto take = [&](float v, uint32_t i) {  // ascending i inside a thread: the first maximum is kept
-        if (v > bv || bi == 0xFFFFFFFFu) { bv = v; bi = i; }
+    const float x0 = logits[0];             // a NaN here wins the row (every thread loads it: no extra round trip behind the reduction)
+    auto take = [&](float v, uint32_t i) {  // ascending i inside a thread: the first maximum is kept; a NaN compares false twice
+        if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
     };
     const uint32_t n4 = (n % 4 == 0 && ((uintptr_t)logits & 15) == 0) ? n / 4 : 0;
     for (uint32_t i0 = tid; i0 < n4; i0 += 1024 * 4) {
@@ -713,6 +717,7 @@ __global__ __launch_bounds__(1024) void k_argmax_advance(const float* __restrict
     if (tid == 0) {
         for (int w = 1; w < 16; ++w)
             if (sv[w] > bv || (sv[w] == bv && si[w] < bi)) { bv = sv[w]; bi = si[w]; }
+        if (x0 != x0) bi = 0;   // (also the row of nothing but NaNs, the only one that leaves bi unset)
         if (argmax_out) *argmax_out = bi;
         if (advance) {
             out_tokens[sp->step] = bi;
@@ -829,9 +834,10 @@ __global__ __launch_bounds__(1024) void k_batch_argmax(const float* __restrict__
     const float* lg = logits + (size_t)row * V;
     float bv = -INFINITY;
     uint32_t bi = 0xFFFFFFFFu;
+    const float x0 = lg[0];                      // a NaN here wins the row, a NaN elsewhere is never taken: k_argmax_advance's rule
     for (uint32_t i = tid; i < V; i += 1024) {   // ascending i inside a thread: the first maximum is kept
         const float v = lg[i];
-        if (v > bv || bi == 0xFFFFFFFFu) { bv = v; bi = i; }
+        if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
     }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) {
@@ -844,6 +850,7 @@ __global__ __launch_bounds__(1024) void k_batch_argmax(const float* __restrict__
     if (tid == 0) {
         for (int w = 1; w < 16; ++w)
             if (sv[w] > bv || (sv[w] == bv && si[w] < bi)) { bv = sv[w]; bi = si[w]; }
+        if (x0 != x0) bi = 0;
         if (ids_out) ids_out[row] = bi;
         if (advance) {
             const uint32_t st = rows[row].step;

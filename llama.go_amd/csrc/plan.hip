@@ -2816,6 +2816,40 @@ void lh_ctx_destroy(lh_ctx* ctx) {
     delete ctx;
 }
 
+// The two greedy kernels on host logits (op-level parity, the twin of lh_sample_top_p_top_k / lh_score_rows).  Rows are packed: with
+// n_logits % 4 != 0 the rows behind the first are not 16-byte aligned, which is what takes k_argmax_advance down its 4-byte path.
+int lh_argmax_rows(lh_ctx* ctx, const float* logits_host, uint32_t n_rows, uint32_t n_logits, int which, uint32_t* ids_out_host) {
+    if (!ctx) return LH_EINVAL;
+    if (!logits_host || !ids_out_host) LH_FAIL(ctx, LH_EINVAL, "lh_argmax_rows: null argument");
+    if (n_logits == 0 || n_logits > 64u * 1024u) LH_FAIL(ctx, LH_ESHAPE, "lh_argmax_rows: vocabulary of %u ids outside the supported 1..65536", n_logits);
+    if (n_rows == 0) LH_FAIL(ctx, LH_EINVAL, "lh_argmax_rows: no rows");
+    if (which != 0 && which != 1) LH_FAIL(ctx, LH_EINVAL, "lh_argmax_rows: which = %d (0 = k_argmax_advance per row, 1 = k_batch_argmax)", which);
+    LH_HIP(ctx, hipSetDevice(ctx->device));
+    // one allocation: logits | ids
+    const size_t o_ids = (((size_t)n_rows * n_logits * 4) + 15) & ~(size_t)15, total = o_ids + (size_t)n_rows * 4;
+    char* dev = nullptr;
+    LH_HIP(ctx, hipMalloc((void**)&dev, total));
+    const float* lg = (const float*)dev;
+    uint32_t* ids = (uint32_t*)(dev + o_ids);
+    hipError_t e = hipMemcpyAsync(dev, logits_host, (size_t)n_rows * n_logits * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the caller's array is pageable host memory
+    if (e == hipSuccess) {
+        if (which == 0) {
+            for (uint32_t r = 0; r < n_rows; ++r)
+                LH_LAUNCH(k_argmax_advance, dim3(1), dim3(1024), 0, ctx->stream, lg + (size_t)r * n_logits, n_logits, (StepParams*)nullptr, (uint32_t*)nullptr, ids + r, 0);
+        } else {
+            LH_LAUNCH(k_batch_argmax, dim3(n_rows), dim3(1024), 0, ctx->stream, lg, n_logits, (BatchRow*)nullptr, (uint32_t*)nullptr, ids, (uint32_t*)nullptr, 0u,
+                      (StepParams*)nullptr, 0);
+        }
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(ids_out_host, ids, (size_t)n_rows * 4, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    }
+    hipFree(dev);
+    if (e != hipSuccess) LH_FAIL(ctx, LH_EHIP, "lh_argmax_rows: %s", hipGetErrorString(e));
+    return LH_OK;
+}
+
 int lh_llama_create(lh_ctx* ctx, const lh_llama_desc* desc, lh_llama** out) {
     if (!ctx || !desc || !out) LH_FAIL(ctx, LH_EINVAL, "lh_llama_create: NULL argument");
     *out = nullptr;

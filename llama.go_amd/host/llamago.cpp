@@ -1194,6 +1194,12 @@ int llamago_ScoreRows(const float* logits, uint32_t n_rows, uint32_t n_logits, c
     if (lh_score_rows(h, logits, n_rows, n_logits, targets, out)) return halt_rc(lh_last_error(h));
     return 0;
 }
+int llamago_ArgmaxRows(const float* logits, uint32_t n_rows, uint32_t n_logits, int which, uint32_t* ids_out) {
+    lh_ctx* h = model_ctx();
+    if (!h) return 1;
+    if (lh_argmax_rows(h, logits, n_rows, n_logits, which, ids_out)) return halt_rc(lh_last_error(h));
+    return 0;
+}
 int llamago_Score(llama_context* c, llama_model* m, const uint32_t* tokens, uint32_t n, uint32_t pastCount, const uint32_t* targets_or_null, lh_row_score* out) {
     if (!c || c->model != m) return halt_rc("llamago_Score: context does not belong to this model");
     if (!tokens || !out) return halt_rc("llamago_Score: null argument");

@@ -503,6 +503,21 @@ def score_rows(ml, logits, targets):
     return np.frombuffer(out, dtype=ROW_SCORE_DTYPE, count=n).copy()
 
 
+def argmax_rows(ml, logits, which):
+    """llamago_ArgmaxRows: the greedy id of every row of host logits [n_rows][V] on the device (lh_argmax_rows); which = 0: k_argmax_advance
+    once per row, which = 1: one k_batch_argmax launch over all rows.  -> uint32 array [n_rows]."""
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    if lg.ndim == 1:
+        lg = lg[None, :]
+    n, V = lg.shape
+    ml.lib.llamago_ArgmaxRows.restype = C.c_int
+    ml.lib.llamago_ArgmaxRows.argtypes = [c_f32p, c_u32, c_u32, C.c_int, c_u32p]
+    out = np.zeros(max(n, 1), dtype=np.uint32)
+    if ml.lib.llamago_ArgmaxRows(lg.ctypes.data_as(c_f32p), n, V, int(which), out.ctypes.data_as(c_u32p)):
+        raise MLError(f"llamago_ArgmaxRows: {ml.last_error()}")
+    return out[:n]
+
+
 def _bind_extensions(ml):
     """Product-only entry points (no counterpart in the reference): resident decode loop, kernel timing, pipeline stage."""
     L = ml.lib

@@ -24,7 +24,8 @@ def sample(logits, ring, topK, topP, temp, penalty, seed, draw):
     l = np.asarray(logits, dtype=f32)
     V = l.size
     scale = f32(1.0) / f32(temp)
-    v = l * scale
+    with np.errstate(over="ignore"):  # 3e38 at temp 1e-3 becomes inf, as in the reference
+        v = l * scale
     member = np.zeros(V, dtype=bool)
     r = np.asarray(list(ring), dtype=np.int64)
     member[r[r < V]] = True
