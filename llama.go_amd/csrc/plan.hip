@@ -19,6 +19,8 @@
 #include <math.h>
 #include <string.h>
 #include <algorithm>
+#include <optional>
+#include <type_traits>
 
 namespace lh {
 
@@ -91,6 +93,22 @@ static int set_lds_once(lh_ctx* ctx, KernT kern, size_t lds, bool* flags) {
 // "This kernel is not built for the shape - take the next one": positive, so it can never be mistaken for an LH_E* code (all negative).
 // Callers fall back ONLY on ST_NA; every other non-zero value is a real failure and is returned as it is.
 static constexpr int ST_NA = 1;
+
+// Grow-only device scratch of floats: waits for the stream (the old buffer may be in use), frees, allocates.  gen, where given, counts the re-allocations:
+// a captured graph that holds the old address compares it and is captured anew.  Where a launch can be part of a stream capture the call stands in
+// front of its prepare-only return, so that the prepare pass before the capture has sized the buffer (hipMalloc is not allowed under a capture).
+static int grow_floats(lh_ctx* ctx, float** buf, uint64_t* cap, uint64_t need, uint64_t* gen = nullptr) {
+    if (need <= *cap) return 0;
+    LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (*buf) LH_HIP(ctx, hipFree(*buf));
+    *buf = nullptr; *cap = 0;
+    if (gen) ++*gen;
+    LH_HIP(ctx, hipMalloc((void**)buf, need * 4));
+    *cap = need;
+    return 0;
+}
+// the context's split-K partial products (lh_ctx::splitk; lh_batch and the verify pass compare splitk_gen)
+static int ensure_splitk(lh_ctx* ctx, uint64_t need_floats) { return grow_floats(ctx, &ctx->splitk, &ctx->splitk_floats, need_floats, &ctx->splitk_gen); }
 
 template <int KI, int U, int PRO, int EPI, int MAP, int THR = TH>
 static int launch_gemv(lh_ctx* ctx, const GemvArgs& a, const char* name, uint64_t bytes) {
@@ -367,14 +385,7 @@ static int launch_gemm(lh_ctx* ctx, const GemmArgs& a0, const char* name, uint32
         if (!a.causal && batch == 1 && a.epi == GEMM_EPI_STORE && a.M % 4 == 0 && a.ldy % 4 == 0)
             splits = pick_splitk(tiles, ncu, a.K / GBK, BN, BM, (uint64_t)a.groups * a.N * a.M, nullptr);
         if (splits > 1) {
-            const uint64_t need = (uint64_t)a.groups * splits * a.N * a.M;
-            if (need > ctx->splitk_floats) {
-                LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                if (ctx->splitk) LH_HIP(ctx, hipFree(ctx->splitk));
-                ctx->splitk = nullptr; ctx->splitk_floats = 0; ctx->splitk_gen++;
-                LH_HIP(ctx, hipMalloc((void**)&ctx->splitk, need * 4));
-                ctx->splitk_floats = need;
-            }
+            if ((rc = ensure_splitk(ctx, (uint64_t)a.groups * splits * a.N * a.M))) return rc;
             a.splits = splits;
             a.part = ctx->splitk;
         }
@@ -450,14 +461,7 @@ static int launch_gemm_q8b3(lh_ctx* ctx, GemmArgs a, const char* name, uint32_t 
     a.xs = xs; a.xs_plane = (uint64_t)a.N * a.K; a.ldxs = a.K;
     a.splits = splits > 1 ? splits : 0; a.part = nullptr;
     if (splits > 1) {
-        const uint64_t need = (uint64_t)a.groups * splits * a.N * a.M;
-        if (need > ctx->splitk_floats) {
-            LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->splitk) LH_HIP(ctx, hipFree(ctx->splitk));
-            ctx->splitk = nullptr; ctx->splitk_floats = 0; ctx->splitk_gen++;
-            LH_HIP(ctx, hipMalloc((void**)&ctx->splitk, need * 4));
-            ctx->splitk_floats = need;
-        }
+        if ((rc = ensure_splitk(ctx, (uint64_t)a.groups * splits * a.N * a.M))) return rc;
         a.part = ctx->splitk;
     }
     if (g_prepare_only) return 0;
@@ -503,14 +507,7 @@ static int gemm_q8_group(lh_ctx* ctx, const float* x, uint32_t ldx, uint32_t gro
             if (c < best * 0.95) { best = c; a.splits = s2; }
         }
         if (a.splits > 1) {
-            const uint64_t need = (uint64_t)groups * a.splits * n * M;
-            if (need > ctx->splitk_floats) {
-                LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                if (ctx->splitk) LH_HIP(ctx, hipFree(ctx->splitk));
-                ctx->splitk = nullptr; ctx->splitk_floats = 0; ctx->splitk_gen++;
-                LH_HIP(ctx, hipMalloc((void**)&ctx->splitk, need * 4));
-                ctx->splitk_floats = need;
-            }
+            if (const int rg = ensure_splitk(ctx, (uint64_t)groups * a.splits * n * M)) return rg;
             a.part = ctx->splitk;
         }
     }
@@ -566,21 +563,9 @@ static int attention_gemm(Plan* p, const float* q, const float* kc, const float*
     const ModelDesc& m = p->md;
     const uint32_t T = past + n, Tp = (T + 31) & ~31u, H = m.H, hd = m.hd, d = m.d;
     const uint64_t need_s = (uint64_t)H * n * Tp, need_v = (uint64_t)H * hd * Tp;
-    if (need_s > p->scores_cap) {
-        LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (p->scores) LH_HIP(ctx, hipFree(p->scores));
-        p->scores = nullptr; p->scores_cap = 0;
-        LH_HIP(ctx, hipMalloc((void**)&p->scores, need_s * 4));
-        p->scores_cap = need_s;
-    }
-    if (need_v > p->vt_cap) {
-        LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (p->vt) LH_HIP(ctx, hipFree(p->vt));
-        p->vt = nullptr; p->vt_cap = 0;
-        LH_HIP(ctx, hipMalloc((void**)&p->vt, need_v * 4));
-        p->vt_cap = need_v;
-    }
     int rc;
+    if ((rc = grow_floats(ctx, &p->scores, &p->scores_cap, need_s))) return rc;
+    if ((rc = grow_floats(ctx, &p->vt, &p->vt_cap, need_v))) return rc;
     LH_TRACE("attention_gemm/hd%u/n%u", hd, n);   // (its four launches follow: the QK GEMM, k_softmax_causal, k_transpose_v, the PV GEMM)
     {   // S[h][j][t] = sum_c Q[j][h*hd + c] * K[t][h*hd + c]
         GemmArgs a = {};
@@ -620,14 +605,7 @@ static int attention_flash(Plan* p, const float* q, const float* kc, const float
     memcpy(a.work, w.work, sizeof(a.work));
     const bool cut = w.chunk != 0 && w.qb_cut < a.nqb;
     if (cut) {
-        const uint64_t need = (uint64_t)m.H * (a.nqb - w.qb_cut) * w.pmax * FA_BQ * FA_PSTRIDE;
-        if (need > p->fa_part_cap) {
-            LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (p->fa_part) LH_HIP(ctx, hipFree(p->fa_part));
-            p->fa_part = nullptr; p->fa_part_cap = 0;
-            LH_HIP(ctx, hipMalloc((void**)&p->fa_part, need * 4));
-            p->fa_part_cap = need;
-        }
+        if (const int rg = grow_floats(ctx, &p->fa_part, &p->fa_part_cap, (uint64_t)m.H * (a.nqb - w.qb_cut) * w.pmax * FA_BQ * FA_PSTRIDE)) return rg;
         a.part = p->fa_part;
     }
     static bool flags[16] = {};
@@ -774,15 +752,24 @@ static int launch_stream_n(lh_ctx* ctx, const StreamArgs& a, const char* name) {
     }
     return ST_NA;
 }
-static int launch_stream_maxt(lh_ctx* ctx, const StreamArgs& a, const char* name, uint32_t maxt) {
-    switch (maxt) {
-        case 1: return launch_stream_n<1>(ctx, a, name);
-        case 2: return launch_stream_n<2>(ctx, a, name);
-        case 3: return launch_stream_n<3>(ctx, a, name);
-        case 4: return launch_stream_n<4>(ctx, a, name);
-        case 5: case 6: return launch_stream_n<6>(ctx, a, name);
-        default: return launch_stream_n<8>(ctx, a, name);
+// Row tiles of a workgroup -> the instantiation built for them: one to four as they are, five and six on the six-tile build, seven and eight on the
+// eight-tile one (0: none; the callers refuse more than eight before they come here, and a matrix has at least one tile).
+static int stream_maxt_built(uint32_t maxt) { return maxt <= 4 ? (int)maxt : maxt <= 6 ? 6 : maxt <= 8 ? 8 : 0; }
+// f(std::integral_constant<int, MAXT>()) for that instantiation: the one switch behind the launchers of k_stream_mm2 / _dma, k_stream_q8b and k_stream_b9
+template <typename F>
+static int with_stream_maxt(uint32_t maxt, F&& f) {
+    switch (stream_maxt_built(maxt)) {
+        case 1: return f(std::integral_constant<int, 1>());
+        case 2: return f(std::integral_constant<int, 2>());
+        case 3: return f(std::integral_constant<int, 3>());
+        case 4: return f(std::integral_constant<int, 4>());
+        case 6: return f(std::integral_constant<int, 6>());
+        case 8: return f(std::integral_constant<int, 8>());
+        default: return ST_NA;
     }
+}
+static int launch_stream_maxt(lh_ctx* ctx, const StreamArgs& a, const char* name, uint32_t maxt) {
+    return with_stream_maxt(maxt, [&](auto mt) { return launch_stream_n<decltype(mt)::value>(ctx, a, name); });
 }
 // returns ST_NA when the shape is not one the kernel is built for (the caller then takes the tile GEMM)
 static int gemm_stream_group(lh_ctx* ctx, const float* x, uint32_t ldx, uint32_t groups, const float* const* w, float* const* y, const float* const* r, uint32_t M,
@@ -793,8 +780,7 @@ static int gemm_stream_group(lh_ctx* ctx, const float* x, uint32_t ldx, uint32_t
     const uint32_t maxt = (fused && fused->epi == ST_EPI_SILU_MUL) ? 2 * ((M / 16 + ncu - 1) / ncu) : (T + ncu - 1) / ncu;
     if (maxt > 8) return ST_NA;
     if (fused && fused->epi != ST_EPI_STORE) {   // the fused epilogues live in the wave-specialised variant only: its two images must fit
-        const int mt = maxt <= 4 ? (int)maxt : (maxt <= 6 ? 6 : 8);
-        if (stream2_lds_bytes(mt, stream_nct(n), stream_kc(n)) > 160 * 1024) return ST_NA;
+        if (stream2_lds_bytes(stream_maxt_built(maxt), stream_nct(n), stream_kc(n)) > 160 * 1024) return ST_NA;
         if (fused->epi == ST_EPI_QKV_ROPE && (fused->hd % 4 || M % fused->hd)) return ST_NA;
     }
     StreamArgs a = {};
@@ -823,16 +809,8 @@ static int gemm_stream_split(lh_ctx* ctx, const float* w, const float* x, uint32
     if (ngrp == 0) return ST_NA;
     const uint32_t maxt = (M / 16 + ngrp - 1) / ngrp;
     if (maxt > 8) return ST_NA;
-    const int mt = maxt <= 4 ? (int)maxt : (maxt <= 6 ? 6 : 8);
-    if (stream2_lds_bytes(mt, stream_nct(n), stream_kc(n)) > 160 * 1024) return ST_NA;
-    const uint64_t need = (uint64_t)S * n * M;
-    if (need > ctx->splitk_floats) {
-        LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->splitk) LH_HIP(ctx, hipFree(ctx->splitk));
-        ctx->splitk = nullptr; ctx->splitk_floats = 0; ctx->splitk_gen++;
-        LH_HIP(ctx, hipMalloc((void**)&ctx->splitk, need * 4));
-        ctx->splitk_floats = need;
-    }
+    if (stream2_lds_bytes(stream_maxt_built(maxt), stream_nct(n), stream_kc(n)) > 160 * 1024) return ST_NA;
+    if (const int rg = ensure_splitk(ctx, (uint64_t)S * n * M)) return rg;
     StreamArgs a = {};
     a.x = x; a.groups = 1; a.M = M; a.K = K; a.n = n; a.ldx = ldx; a.ldy = M; a.w[0] = w; a.y[0] = ctx->splitk;
     a.ksplit = S; a.ysplit = (uint64_t)n * M;
@@ -890,17 +868,9 @@ static int launch_stream_q8b_n(lh_ctx* ctx, const StreamArgs& a, const char* nam
     return ST_NA;
 }
 static int launch_stream_q8b_maxt(lh_ctx* ctx, const StreamArgs& a, const char* name, uint32_t maxt) {
-    switch (maxt) {
-        case 1: return launch_stream_q8b_n<1>(ctx, a, name);
-        case 2: return launch_stream_q8b_n<2>(ctx, a, name);
-        case 3: return launch_stream_q8b_n<3>(ctx, a, name);
-        case 4: return launch_stream_q8b_n<4>(ctx, a, name);
-        case 5: case 6: return launch_stream_q8b_n<6>(ctx, a, name);
-        case 7: case 8: return launch_stream_q8b_n<8>(ctx, a, name);
-        default: return ST_NA;
-    }
+    return with_stream_maxt(maxt, [&](auto mt) { return launch_stream_q8b_n<decltype(mt)::value>(ctx, a, name); });
 }
-// ---- k_stream_b9 (kernels_stream_b9.h, round 6): fp32 weights x the same three bf16 planes, nine exact products per weight on the bf16 matrix pipe.
+// ---- k_stream_b9 (kernels_stream_b9.h, round 6): fp32 weights x the same three bf16 planes, eight of the nine exact bf16 products per weight on the bf16 matrix pipe.
 // Wave-specialised like k_stream_dma (four loader waves, four MFMA waves); up to four column tiles (64 rows), 64-column chunks, as many images
 // as fit (<= 4).  Eight row tiles next to four column tiles are not built (the MFMA waves' 4 x 4 accumulator tiles + operands spill).
 // Eight of the nine products: xl * wl (<= 2^-32 of its product, far below the fp32 accumulator's own rounding) is dropped - against an f64 product max and
@@ -937,15 +907,7 @@ static int launch_stream_b9_n(lh_ctx* ctx, const StreamArgs& a, const char* name
     return ST_NA;
 }
 static int launch_stream_b9_maxt(lh_ctx* ctx, const StreamArgs& a, const char* name, uint32_t maxt) {
-    switch (maxt) {
-        case 1: return launch_stream_b9_n<1>(ctx, a, name);
-        case 2: return launch_stream_b9_n<2>(ctx, a, name);
-        case 3: return launch_stream_b9_n<3>(ctx, a, name);
-        case 4: return launch_stream_b9_n<4>(ctx, a, name);
-        case 5: case 6: return launch_stream_b9_n<6>(ctx, a, name);
-        case 7: case 8: return launch_stream_b9_n<8>(ctx, a, name);
-        default: return ST_NA;
-    }
+    return with_stream_maxt(maxt, [&](auto mt) { return launch_stream_b9_n<decltype(mt)::value>(ctx, a, name); });
 }
 static bool stream_b9_built(uint32_t maxt, uint32_t n) { return maxt >= 1 && maxt <= 8 && n >= 1 && n <= 64 && !(maxt > 6 && n > 48); }
 // groups (<= 3) matrices of equal shape - block-int8 (wsc: their scale planes) or fp32 (wsc[g] == nullptr: k_stream_b9) - times the same activation
@@ -971,23 +933,19 @@ static int gemm_q8b_group(lh_ctx* ctx, const uint16_t* xs, uint64_t xs_plane, ui
 // the residual in fixed order and writes the RMSNorm * gamma rows of the NEXT matmul as planes (and as fp32 rows when h is given) - it
 // stands where that norm's launch stood.  Standalone, 7B (profiles/r05_q8b_probe.txt): wo at 8 / 32 rows 11.5 / 14.5 us in fours against
 // 12.5 / - unsplit, w2 17.5 / 26.2 against 20.3 / 39.6.
+static uint32_t q8b_split_groups(uint32_t nchunks, uint32_t ncu) {   // S: fours, halved while a workgroup's share of the contraction would fall under two chunks
+    uint32_t S = 4;
+    while (S > 1 && (nchunks < 2 * S || ncu / S == 0)) S >>= 1;
+    return S;
+}
 static int gemm_q8b_split(lh_ctx* ctx, const float* wq, const float* wsc, const uint16_t* xs, uint64_t xs_plane, uint32_t ldxs, uint32_t M, uint32_t K, uint32_t n,
                           const float* resid, float* y, const float* gamma, float* h, uint16_t* hs, uint64_t hs_plane, const char* name) {
     if (n == 0 || n > STREAM_ROWS_Q8 || M % 16 || M > 8192 || M % 4 || K % 128 || ldxs % 8 || ((uintptr_t)xs & 15) || (xs_plane * 2) % 16) return ST_NA;
     if ((((uintptr_t)wq | (uintptr_t)y | (uintptr_t)resid | (uintptr_t)gamma | (uintptr_t)h | (uintptr_t)hs | (uintptr_t)wsc) & 15)) return ST_NA;
     const uint32_t ncu = (uint32_t)ctx->ds->num_cu, nchunks = wsc ? K / (K % 256 == 0 ? 256u : 128u) : K / (uint32_t)B9S_KC;
-    uint32_t S = 4;
-    while (S > 1 && (nchunks < 2 * S || ncu / S == 0)) S >>= 1;
-    const uint32_t ngrp = ncu / S, maxt = (M / 16 + ngrp - 1) / ngrp;
+    const uint32_t S = q8b_split_groups(nchunks, ncu), ngrp = ncu / S, maxt = (M / 16 + ngrp - 1) / ngrp;
     if (maxt > 8) return ST_NA;
-    const uint64_t need = (uint64_t)S * n * M;
-    if (need > ctx->splitk_floats) {
-        LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->splitk) LH_HIP(ctx, hipFree(ctx->splitk));
-        ctx->splitk = nullptr; ctx->splitk_floats = 0; ctx->splitk_gen++;
-        LH_HIP(ctx, hipMalloc((void**)&ctx->splitk, need * 4));
-        ctx->splitk_floats = need;
-    }
+    if (const int rg = ensure_splitk(ctx, (uint64_t)S * n * M)) return rg;
     StreamArgs a = {};
     a.xs = xs; a.xs_plane = xs_plane; a.ldxs = ldxs; a.groups = 1; a.M = M; a.K = K; a.n = n; a.ldy = M; a.w[0] = wq; a.ws[0] = wsc; a.y[0] = ctx->splitk;
     a.ksplit = S; a.ysplit = (uint64_t)n * M;
@@ -1019,14 +977,7 @@ static int launch_gemm_b9(lh_ctx* ctx, GemmArgs a, const char* name, uint32_t sp
     a.xs = ctx->xs3; a.xs_plane = (uint64_t)a.N * a.K; a.ldxs = a.K;
     a.splits = splits > 1 ? splits : 0; a.part = nullptr;
     if (splits > 1) {
-        const uint64_t need = (uint64_t)a.groups * splits * a.N * a.M;
-        if (need > ctx->splitk_floats) {
-            LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->splitk) LH_HIP(ctx, hipFree(ctx->splitk));
-            ctx->splitk = nullptr; ctx->splitk_floats = 0; ctx->splitk_gen++;
-            LH_HIP(ctx, hipMalloc((void**)&ctx->splitk, need * 4));
-            ctx->splitk_floats = need;
-        }
+        if ((rc = ensure_splitk(ctx, (uint64_t)a.groups * splits * a.N * a.M))) return rc;
         a.part = ctx->splitk;
     }
     if (g_prepare_only) return 0;
@@ -1173,16 +1124,7 @@ static int launch_skinny(Plan* p, SkinnyArgs a, const char* name) {
     int rc0 = set_lds_once(ctx, kern, 160 * 1024, flags);
     if (rc0) return rc0;
     if (g_prepare_only) return 0;
-    if (nchunks > 1) {
-        const uint64_t need = (uint64_t)SKINNY_NP * a.M;
-        if (need > p->part_cap) {
-            LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (p->part) LH_HIP(ctx, hipFree(p->part));
-            p->part = nullptr; p->part_cap = 0;
-            LH_HIP(ctx, hipMalloc((void**)&p->part, need * 4));
-            p->part_cap = need;
-        }
-    }
+    if (nchunks > 1 && (rc0 = grow_floats(ctx, &p->part, &p->part_cap, (uint64_t)SKINNY_NP * a.M))) return rc0;
     ProfScope ps(ctx->stream, name, (uint64_t)a.M * a.K * 4);
     uint32_t k0 = 0;
     for (uint32_t ch = 0; ch < nchunks; ++ch) {
@@ -1663,11 +1605,6 @@ int plan_decode_step(Plan* p, uint32_t token, uint32_t past) {
 }
 
 // ---- general Eval on the plan (N >= 1) ----------------------------------------------------------------
-
-// Shapes a batched Eval (rows of different streams, BatchCtx) can take in ONE weight pass: every position-dependent kernel on that route
-// reads the row table (k_stream_mm2's RoPE epilogue, k_rope_store, k_attention, k_attention_split).  Routes that do not (k_skinny, the
-// tile GEMM's RoPE epilogue above 64 rows, the flash kernel, block-int8 single-token steps) are excluded here; lh_batch then evaluates
-// the rows one after the other on their own plans.
 // block-int8 on k_stream_q8b: the shapes every launch of an Eval has an instantiation for (kernels_stream_q8b.h; <= 8 row tiles per workgroup
 // in each of wq|wk|wv, w1|w3 pairs, the K-split fours of wo / w2 and the output matrix)
 static bool q8b_shape_ok(lh_ctx* ctx, const ModelDesc& m) {
@@ -1684,10 +1621,8 @@ static bool q8b_shape_ok(lh_ctx* ctx, const ModelDesc& m) {
 static bool b9s_shape_ok(lh_ctx* ctx, const ModelDesc& m, uint32_t n) {
     const uint32_t ncu = (uint32_t)ctx->ds->num_cu, d = m.d, F = m.F;
     if (m.wtype != 0 || ncu < 4 || n < 2 || n > B9S_MAX_ROWS || d > 8192 || d % 128 || F % 128 || m.hd % 4 || d % m.hd) return false;
-    auto split_maxt = [&](uint32_t K) {   // gemm_q8b_split's group size for a contraction of K columns
-        uint32_t S = 4;
-        while (S > 1 && (K / (uint32_t)B9S_KC < 2 * S || ncu / S == 0)) S >>= 1;
-        const uint32_t ngrp = ncu / S;
+    auto split_maxt = [&](uint32_t K) {   // row tiles of a workgroup in gemm_q8b_split's launch of a d x K matrix
+        const uint32_t ngrp = ncu / q8b_split_groups(K / (uint32_t)B9S_KC, ncu);
         return (d / 16 + ngrp - 1) / ngrp;
     };
     return stream_b9_built((3 * d / 16 + ncu - 1) / ncu, n) && stream_b9_built(2 * ((F / 16 + ncu - 1) / ncu), n) && stream_b9_built(split_maxt(d), n) && stream_b9_built(split_maxt(F), n);
@@ -1697,36 +1632,271 @@ static constexpr uint32_t Q8B_PROMPT_ROWS = 88;   // a prompt takes up to two 64
 static bool q8_stream_ok(lh_ctx* ctx, const ModelDesc& m, uint32_t n, uint32_t n_min, bool batch_rows = true) {
     return n >= n_min && n <= (batch_rows ? STREAM_ROWS_Q8 : Q8B_PROMPT_ROWS) && q8b_shape_ok(ctx, m);
 }
+
+// The layer schedules of an Eval.  eval_route picks one from the model's shapes, the row count and whether the rows belong to different streams;
+// plan_eval runs it.
+//   Step     one row: the decode step
+//   Rows     2..8 rows (block-int8: 2..4) on the decode launches with NC activation rows each (kernels_rows.h)
+//   Q8Steps  block-int8 without a k_stream_q8b launch, below the dequantising GEMM's rows or shapes: n single steps
+//   Skinny   fp32, 2..8 rows of one stream where k_stream_* is not built for the shape: k_skinny
+//   Planes   the activations as three bf16 planes: block-int8 on k_stream_q8b (3..64 rows of a batch, 3..88 of a prompt), fp32 at 49..64 rows on k_stream_b9
+//   Prefill  everything else: the fp32 stream kernels and tile GEMMs, the dequantising GEMM, the column kernels
+// Rows of different streams (BatchCtx) take ONE weight pass only on a route whose position-dependent kernels all read the row table: Rows and Planes,
+// and Prefill with fp32 weights (k_stream_mm2's RoPE epilogue, k_rope_store, k_attention, k_attention_split).  Step, Q8Steps and Skinny do not read it, nor
+// do Prefill's tile GEMM RoPE epilogue above 64 rows and its prompt attention kernels, which the at most BATCH_ROWS_MAX rows of a batch never take
+// (plan_batch_rows_ok; lh_batch evaluates what it refuses row by row on the rows' own plans).
+enum class EvalRoute { Step, Rows, Q8Steps, Skinny, Planes, Prefill };
+static EvalRoute eval_route(lh_ctx* ctx, const ModelDesc& m, uint32_t n, bool batched) {
+    if (n == 1) return EvalRoute::Step;
+    if (rows_path_ok(ctx, m, n)) return EvalRoute::Rows;
+    // block-int8: 5..64 rows of a tick / 5..88 of a prompt on k_stream_q8b (two 64-row passes from 65); from 89 rows the tile GEMM k_gemm_q8b3 (Prefill)
+    const bool q8_stream = q8_stream_ok(ctx, m, n, 3, batched);
+    if (m.wtype == 7 && !q8_stream && (n < Q8_GEMM_MIN_ROWS || m.d % GBK || m.F % GBK || m.hd % 32)) return EvalRoute::Q8Steps;
+    if (!batched && skinny_ok(m, n) && !stream_shape_ok(ctx, m)) return EvalRoute::Skinny;   // k_skinny only where the streaming MFMA kernel is not built for the shape
+    if (q8_stream) return EvalRoute::Planes;   // block-int8, up to 64 rows: the bf16 matrix pipe (kernels_stream_q8b.h)
+    static const int b9s_min = getenv("LLAMAHIP_B9S_MIN") ? atoi(getenv("LLAMAHIP_B9S_MIN")) : (int)B9S_MIN_ROWS;   // (A/B switch of round 6's measurements: 65 = off)
+    if (m.wtype == 0 && (int)n >= b9s_min && n <= B9S_MAX_ROWS) return EvalRoute::Planes;   // fp32, 49..64 rows: the same schedule over planes on k_stream_b9
+    return EvalRoute::Prefill;
+}
+// Prefill's grouped MFMA launches: from 9 rows (tile GEMM), fp32 weights from 2 rows on the streaming MFMA kernel
+static bool prefill_mfma(const ModelDesc& m, uint32_t n) { return (n >= MFMA_MIN_ROWS || (n >= 2 && m.wtype == 0)) && m.d % GBK == 0 && m.F % GBK == 0; }
 bool plan_batch_rows_ok(const Plan* p, uint32_t n) {
     const ModelDesc& m = p->md;
     if (n < 2 || n > BATCH_ROWS_MAX) return false;
-    if (rows_path_ok(p->ctx, m, n)) return true;   // two to eight (block-int8: four) rows ride the decode stream itself
+    const EvalRoute route = eval_route(p->ctx, m, n, true);
+    if (route == EvalRoute::Rows) return true;   // two to eight (block-int8: four) rows ride the decode stream itself
     // block-int8 on the stream kernel: from 3 rows (one pass of the dequantising stream kernel costs 4.9 ms on 7B whatever the row count <= 16, a single-row
     // int8 GEMV step 2.04 ms: two rows are faster one after the other - profiles/r03_pods_one_gpu.jsonl)
-    if (m.wtype == 7) return q8_stream_ok(p->ctx, m, n, 3);
-    return m.d % GBK == 0 && m.F % GBK == 0;
+    if (m.wtype == 7) return route == EvalRoute::Planes;
+    return (route == EvalRoute::Planes || route == EvalRoute::Prefill) && prefill_mfma(m, n);   // (fp32 Planes may hand the Eval to Prefill)
 }
 
-// Block-int8, 5..64 rows (a prompt's tokens or the pods of a tick): the layers on k_stream_q8b.  Per layer 7 launches:
+struct EvalCall {   // the arguments of one plan_eval
+    const uint32_t* tokens_host;
+    const float* x_in_dev;
+    float* x_out_dev;
+    uint32_t n, past;
+    bool last_row_only;
+    const BatchCtx* bc;
+};
+static float attn_scale(const ModelDesc& m) { return (float)(1.0 / sqrt((double)m.d / (double)m.H)); }
+// The logits rows of the last stage, first row and count: all n as the reference evaluates them (llama.go:372-384), or the last one alone, which is all
+// llama.Eval reads (llama.go:394-401), for callers that say so (LH_GRAPH_LAST_ROW_LOGITS, the lh_llama_* entry points) - in its usual place.
+struct LogitsRows { uint32_t r0, nr; };
+static LogitsRows logits_rows(const EvalCall& c) { return c.last_row_only ? LogitsRows{c.n - 1, 1} : LogitsRows{0, c.n}; }
+
+// The rows a route's first layer reads (*x): on the first stage the embeddings of the token ids in p->xa - a solo Eval's ids staged up from the host, a
+// batch's already on the device - on a later stage the residual stream it received.  Rows keeps the launch out of a prepare-only pass; the prefill
+// (and, behind the same launch, the planes) route names it for LLAMAHIP_TRACE.
+static int eval_input(Plan* p, const EvalCall& c, EvalRoute route, const float** x) {
+    lh_ctx* ctx = p->ctx;
+    const ModelDesc& m = p->md;
+    if (!m.first_stage()) { *x = c.x_in_dev; return 0; }
+    *x = p->xa;
+    const uint32_t* tok_dev = c.bc ? c.bc->tok_dev : p->tokens_dev;
+    if (!c.bc) {
+        if (const int rc = ensure_staging(ctx, (uint64_t)c.n * 4)) return rc;
+        LH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // staging reuse
+        memcpy(ctx->staging, c.tokens_host, (size_t)c.n * 4);
+        LH_HIP(ctx, hipMemcpyAsync(p->tokens_dev, ctx->staging, (size_t)c.n * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+    std::optional<TraceScope> ts_;
+    if (route == EvalRoute::Planes || route == EvalRoute::Prefill) ts_.emplace(ctx->stream, "embedN");
+    if (!(route == EvalRoute::Rows && g_prepare_only)) LH_LAUNCH(k_embed, dim3(c.n), dim3(256), 0, ctx->stream, m.tok_emb, tok_dev, (const StepParams*)nullptr, p->xa, m.d, m.V);
+    LH_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
+// The attention of a layer's n rows (llama.go:300-333) -> p->attn.  Rows of different streams: one query each, against its own cache up to its own
+// position.  A prompt from 32 rows on, where the grouped MFMA launches run (mfma): one pass with an online softmax (head size 128), or batched MFMA GEMMs
+// over heads with a score tensor (other head sizes).  Fewer queries: the per-query kernel (no score tensor) is cheaper.
+// as != nullptr (Planes): the merged heads also as three bf16 planes of stride as_plane - the row-table and per-query kernels write them themselves, the
+// prompt kernels' rows are split by a pass of their own.
+static int eval_attention(Plan* p, const EvalCall& c, size_t slot, float scale, bool mfma, uint16_t* as = nullptr, uint64_t as_plane = 0) {
+    lh_ctx* ctx = p->ctx;
+    const ModelDesc& m = p->md;
+    const uint32_t d = m.d, n = c.n, past = c.past;
+    int rc;
+    AttnArgs a = {};
+    a.q = p->q; a.out = p->attn; a.d = d; a.hd = m.hd; a.n = n; a.scale = scale; a.out_s3 = as; a.out_plane = as_plane;
+    if (c.bc) {
+        a.rows = c.bc->rows; a.kv_off = slot;
+        return launch_attention_rows(p, a, c.bc);
+    }
+    if (mfma && n >= 32 && (m.hd == FA_HD || m.hd % 32 == 0)) {
+        if (m.hd == FA_HD) rc = attention_flash(p, p->q, m.kc + slot, m.vc + slot, p->attn, n, past, scale);
+        else rc = attention_gemm(p, p->q, m.kc + slot, m.vc + slot, p->attn, n, past, scale);
+        if (rc || !as) return rc;
+        Split3Args sa = {p->attn, as, as_plane, d, d, d};
+        if (!g_prepare_only) { TraceScope ts_(ctx->stream, "split3_rows"); LH_LAUNCH(k_split3_rows, dim3(n), dim3(256), 0, ctx->stream, sa); }
+        return 0;
+    }
+    a.k_cache = m.kc + slot; a.v_cache = m.vc + slot; a.sp = nullptr; a.past_host = past;
+    return launch_attention(ctx, a, past + n);
+}
+
+static int eval_step(Plan* p, const EvalCall& c) {
+    const ModelDesc& m = p->md;
+    if (m.first_stage() && m.last_stage() && p->use_graph) return plan_decode_step(p, c.tokens_host[0], c.past);
+    const uint32_t slot = 1 + (p->slot_counter++ % (SP_SLOTS - 1));
+    if (const int rc = upload_step_params(p, slot, c.tokens_host ? c.tokens_host[0] : 0, c.past, 0)) return rc;
+    return enqueue_decode(p, p->sp_dev + slot, c.x_in_dev, c.x_out_dev, false, nullptr);
+}
+
+// 2..8 rows (block-int8: 2..4) (a prompt of that many tokens, or a tick of that many pods): the decode launches with NC activation rows each
+// (kernels_rows.h): 5 launches per layer like the decode step, every row bit-identical to its solo step
+static int eval_rows(Plan* p, const EvalCall& c, const float* x) {
+    lh_ctx* ctx = p->ctx;
+    const ModelDesc& m = p->md;
+    const uint32_t n = c.n, past = c.past;
+    const BatchRow* rows = c.bc ? c.bc->rows : nullptr;
+    float* x_out_dev = c.x_out_dev;
+    int rc;
+    const float scale = attn_scale(m);
+    const uint32_t d = m.d, F = m.F;
+    for (uint32_t il = m.layer0; il < m.layer1; ++il) {
+        const LayerW& L = m.layers[il];
+        const size_t slot = (size_t)(il - m.cache_layer0) * m.ctx * d;
+        {   // RMSNorm*gamma -> wq|wk|wv -> RoPE(Q, new K rows) -> K, V appended   (llama.go:255-297)
+            GemvRowsArgs a = {};
+            a.w[0] = L.wq; a.w[1] = L.wk; a.w[2] = L.wv; a.ws[0] = L.s_wq; a.ws[1] = L.s_wk; a.ws[2] = L.s_wv; a.rows_per_mat = d; a.M = 3 * d; a.K = d; a.x = x; a.ldx = d; a.n = n; a.gamma = L.attn_norm;
+            a.q_out = p->q; a.k_cache = m.kc + slot; a.v_cache = m.vc + slot; a.rope = p->rope; a.hd = m.hd; a.d = d; a.past = past; a.rows = rows; a.kv_off = slot;
+            if ((rc = gemv_rows<PRO_RMSNORM, EPI_QKV_ROPE, MAP_BLOCK>(ctx, a, "rows_qkv_rope", m.wtype))) return rc;
+        }
+        // scores, scale, mask, softmax, PV, head merge per row   (llama.go:300-333)
+        if ((rc = eval_attention(p, c, slot, scale, false))) return rc;
+        {   // wo + residual   (llama.go:336-340)
+            GemvRowsArgs a = {};
+            a.w[0] = L.wo; a.ws[0] = L.s_wo; a.M = d; a.K = d; a.x = p->attn; a.ldx = d; a.n = n; a.y = p->xb; a.resid = x; a.ldy = d;
+            if ((rc = gemv_rows<PRO_PLAIN, EPI_RESID, MAP_SINGLE>(ctx, a, "rows_wo_resid", m.wtype))) return rc;
+        }
+        {   // RMSNorm*gamma -> w1|w3 -> silu(w1 h) * (w3 h)   (llama.go:346-361)
+            GemvRowsArgs a = {};
+            a.w[0] = L.w1; a.w[1] = L.w3; a.ws[0] = L.s_w1; a.ws[1] = L.s_w3; a.M = 2 * F; a.K = d; a.x = p->xb; a.ldx = d; a.n = n; a.gamma = L.ffn_norm; a.y = p->g; a.ldy = F;
+            if ((rc = gemv_rows<PRO_RMSNORM, EPI_SILU_MUL, MAP_PAIR>(ctx, a, "rows_w1w3_silu", m.wtype))) return rc;
+        }
+        {   // w2 + residual   (llama.go:363-366)
+            const bool last = il + 1 == m.layer1;
+            GemvRowsArgs a = {};
+            a.w[0] = L.w2; a.ws[0] = L.s_w2; a.M = d; a.K = F; a.x = p->g; a.ldx = F; a.n = n; a.resid = p->xb; a.ldy = d;
+            a.y = (last && !m.last_stage()) ? x_out_dev : p->xa;
+            if ((rc = gemv_rows<PRO_PLAIN, EPI_RESID, MAP_SINGLE>(ctx, a, "rows_w2_resid", m.wtype))) return rc;
+        }
+        x = p->xa;
+    }
+    if (m.last_stage()) {   // final RMSNorm*gamma -> lm_head: the rows the caller reads (llama.go:372-384, 394-401)
+        const auto [r0, nr] = logits_rows(c);
+        if (nr == 1) {
+            GemvArgs a = {};
+            a.w[0] = m.output; a.ws[0] = m.s_output; a.M = m.V; a.K = d; a.x = x + (size_t)r0 * d; a.gamma = m.norm; a.y = p->logits + (size_t)r0 * m.V;
+            if ((rc = gemv<PRO_RMSNORM, EPI_STORE, MAP_SINGLE>(ctx, a, "gemv_lmhead", m.wtype))) return rc;
+        } else {
+            GemvRowsArgs a = {};
+            a.w[0] = m.output; a.ws[0] = m.s_output; a.M = m.V; a.K = d; a.x = x + (size_t)r0 * d; a.ldx = d; a.n = nr; a.gamma = m.norm; a.y = p->logits + (size_t)r0 * m.V; a.ldy = m.V;
+            if ((rc = gemv_rows<PRO_RMSNORM, EPI_STORE, MAP_SINGLE>(ctx, a, "rows_lmhead", m.wtype))) return rc;
+        }
+    }
+    LH_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
+// block-int8, short batches: n causal single-token steps on the int8 weight stream (bit-identical to what the decode
+// path produces for them), logits row i from step i like llama.go:384.  n >= 32 takes the dequantising GEMM (Prefill).
+// On a pipeline stage row i of the received / forwarded residual stream stands in for the token id / the logits row.
+static int eval_q8_steps(Plan* p, const EvalCall& c) {
+    const ModelDesc& m = p->md;
+    const uint32_t n = c.n, past = c.past;
+    const uint32_t* tokens_host = c.tokens_host;
+    const float* x_in_dev = c.x_in_dev;
+    float* x_out_dev = c.x_out_dev;
+    int rc;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t slot = 1 + (p->slot_counter++ % (SP_SLOTS - 1));
+        if ((rc = upload_step_params(p, slot, m.first_stage() ? tokens_host[i] : 0, past + i, 0))) return rc;
+        if ((rc = enqueue_decode(p, p->sp_dev + slot, m.first_stage() ? nullptr : x_in_dev + (size_t)i * m.d, m.last_stage() ? nullptr : x_out_dev + (size_t)i * m.d, false,
+                                 nullptr, nullptr, i)))
+            return rc;
+    }
+    return 0;
+}
+
+// short prompt: 4 fused weight passes per layer + the per-query attention kernel (like the decode step, n rows wide)
+static int eval_skinny(Plan* p, const EvalCall& c, const float* x) {
+    lh_ctx* ctx = p->ctx;
+    const ModelDesc& m = p->md;
+    const uint32_t n = c.n, past = c.past;
+    float* x_out_dev = c.x_out_dev;
+    int rc;
+    const float scale = attn_scale(m);
+    const uint32_t d = m.d, F = m.F;
+    for (uint32_t il = m.layer0; il < m.layer1; ++il) {
+        const LayerW& L = m.layers[il];
+        const size_t slot = (size_t)(il - m.cache_layer0) * m.ctx * d;
+        {   // RMSNorm*gamma -> wq|wk|wv -> RoPE(Q, new K rows) -> K,V appended   (llama.go:255-297)
+            SkinnyArgs a = {};
+            a.w[0] = L.wq; a.w[1] = L.wk; a.w[2] = L.wv; a.rows_per_mat = d; a.M = 3 * d; a.K = d; a.x = x; a.ldx = d; a.n = n; a.gamma = L.attn_norm;
+            a.q_out = p->q; a.k_cache = m.kc + slot; a.v_cache = m.vc + slot; a.rope = p->rope; a.hd = m.hd; a.d = d; a.past = past;
+            if ((rc = launch_skinny<PRO_RMSNORM, EPI_QKV_ROPE, MAP_BLOCK>(p, a, "skinny_qkv_rope"))) return rc;
+        }
+        if ((rc = eval_attention(p, c, slot, scale, false))) return rc;
+        {   // wo + residual   (llama.go:336-340)
+            SkinnyArgs a = {};
+            a.w[0] = L.wo; a.M = d; a.K = d; a.x = p->attn; a.ldx = d; a.n = n; a.y = p->xb; a.resid = x; a.ldy = d;
+            if ((rc = launch_skinny<PRO_PLAIN, EPI_RESID, MAP_SINGLE>(p, a, "skinny_wo_resid"))) return rc;
+        }
+        {   // RMSNorm*gamma -> w1|w3 -> silu(w1 h) * (w3 h)   (llama.go:346-361)
+            SkinnyArgs a = {};
+            a.w[0] = L.w1; a.w[1] = L.w3; a.M = 2 * F; a.K = d; a.x = p->xb; a.ldx = d; a.n = n; a.gamma = L.ffn_norm; a.y = p->g; a.ldy = F;
+            if ((rc = launch_skinny<PRO_RMSNORM, EPI_SILU_MUL, MAP_PAIR>(p, a, "skinny_w1w3_silu"))) return rc;
+        }
+        {   // w2 + residual   (llama.go:363-366)
+            const bool last = il + 1 == m.layer1;
+            SkinnyArgs a = {};
+            a.w[0] = L.w2; a.M = d; a.K = F; a.x = p->g; a.ldx = F; a.n = n; a.resid = p->xb; a.ldy = d;
+            a.y = (last && !m.last_stage()) ? x_out_dev : p->xa;
+            if ((rc = launch_skinny<PRO_PLAIN, EPI_RESID, MAP_SINGLE>(p, a, "skinny_w2_resid"))) return rc;
+        }
+        x = p->xa;
+    }
+    if (m.last_stage()) {   // final RMSNorm*gamma -> lm_head: the rows the caller reads (llama.go:372-384, 394-401)
+        const auto [r0, nr] = logits_rows(c);
+        if (nr == 1) {
+            GemvArgs a = {};
+            a.w[0] = m.output; a.M = m.V; a.K = d; a.x = x + (size_t)r0 * d; a.gamma = m.norm; a.y = p->logits + (size_t)r0 * m.V;
+            if ((rc = gemv<PRO_RMSNORM, EPI_STORE, MAP_SINGLE>(ctx, a, "gemv_lmhead", 0))) return rc;
+        } else {
+            SkinnyArgs a = {};
+            a.w[0] = m.output; a.M = m.V; a.K = d; a.x = x; a.ldx = d; a.n = n; a.gamma = m.norm; a.y = p->logits; a.ldy = m.V;
+            if ((rc = launch_skinny<PRO_RMSNORM, EPI_STORE, MAP_SINGLE>(p, a, "skinny_lmhead"))) return rc;
+        }
+    }
+    LH_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
+// The layers over activation planes (three bf16 planes per activation matrix): block-int8 weights on k_stream_q8b, 3..64 rows of a tick or up to 88 of a
+// prompt in two passes, and fp32 weights at 49..64 rows on k_stream_b9.  Per layer 7 launches:
 //   [RMSNorm -> planes] (first layer only; afterwards the w2 reduce pass of the layer before writes them)
 //   wq|wk|wv + RoPE + cache append | attention (merged heads -> planes) | wo as K-split fours | reduce + residual + RMSNorm -> planes |
 //   w1|w3 + silu * mul -> planes | w2 as K-split fours | reduce + residual + the NEXT norm -> planes
-// (llama.go:255-366).  Returns ST_NA before anything is enqueued when a launch of the model has no instantiation (the caller's older route
-// then takes the Eval).
-static int eval_q8b_layers(Plan* p, const float* x, float* x_out_dev, uint32_t n, uint32_t past, bool last_row_only, const BatchCtx* bc) {
+// (llama.go:255-366).  Returns ST_NA before anything is enqueued when a launch of the model has no instantiation (plan_eval then
+// hands an fp32 Eval to Prefill).
+static int eval_planes(Plan* p, const EvalCall& c, const float* x) {
     lh_ctx* ctx = p->ctx;
     const ModelDesc& m = p->md;
+    const uint32_t n = c.n, past = c.past;
+    const BatchRow* rows = c.bc ? c.bc->rows : nullptr;
+    float* x_out_dev = c.x_out_dev;
     const uint32_t d = m.d, F = m.F;
     if (!(m.wtype == 7 ? q8b_shape_ok(ctx, m) : b9s_shape_ok(ctx, m, n))) return ST_NA;
     if (!p->s3 || n > p->s3_rows) return ST_NA;
-    const BatchRow* rows = bc ? bc->rows : nullptr;
-    const float scale = (float)(1.0 / sqrt((double)m.d / (double)m.H));
+    const float scale = attn_scale(m);
     const uint64_t pd = (uint64_t)p->s3_rows * d, pf = (uint64_t)p->s3_rows * F;   // plane strides (elements)
     uint16_t* hs = p->s3;
     uint16_t* as = hs + 3 * pd;
     uint16_t* gs = as + 3 * pd;
     int rc;
-#define Q8B_TRY(expr, what) do { if ((rc = (expr))) { if (rc == ST_NA) LH_FAIL(ctx, LH_ESHAPE, "Eval of %u rows over activation planes: no launch for %s (embd %u, ff %u, weight type %u)", n, what, d, F, m.wtype); return rc; } } while (0)
+#define PLANES_TRY(expr, what) do { if ((rc = (expr))) { if (rc == ST_NA) LH_FAIL(ctx, LH_ESHAPE, "Eval of %u rows over activation planes: no launch for %s (embd %u, ff %u, weight type %u)", n, what, d, F, m.wtype); return rc; } } while (0)
     bool h_ready = false;
     for (uint32_t il = m.layer0; il < m.layer1; ++il) {
         const LayerW& L = m.layers[il];
@@ -1741,30 +1911,13 @@ static int eval_q8b_layers(Plan* p, const float* x, float* x_out_dev, uint32_t n
             for (uint32_t b0 = 0; b0 < n; b0 += STREAM_ROWS_Q8) {   // (a prompt of 65..128 tokens: two passes over the weights, still 1.5x faster than the tile GEMM)
                 const uint32_t nb = std::min(STREAM_ROWS_Q8, n - b0);
                 fq.q_out = p->q + (size_t)b0 * d; fq.past = past + b0;
-                Q8B_TRY(gemm_q8b_group(ctx, hs + (size_t)b0 * d, pd, d, 3, wqkv, sqkv, nullptr, nullptr, d, d, nb, d, m.wtype == 7 ? "q8b_wqkv_rope" : "b9s_wqkv_rope", &fq), "wq|wk|wv");
+                PLANES_TRY(gemm_q8b_group(ctx, hs + (size_t)b0 * d, pd, d, 3, wqkv, sqkv, nullptr, nullptr, d, d, nb, d, m.wtype == 7 ? "q8b_wqkv_rope" : "b9s_wqkv_rope", &fq), "wq|wk|wv");
             }
         }
-        if (rows) {   // rows of different streams: one query each, against its own cache up to its own position
-            AttnArgs a = {};
-            a.q = p->q; a.out = p->attn; a.d = d; a.hd = m.hd; a.n = n; a.scale = scale; a.rows = rows; a.kv_off = slot; a.out_s3 = as; a.out_plane = pd;
-            if ((rc = launch_attention_rows(p, a, bc))) return rc;
-        } else if (n >= 32 && m.hd == FA_HD) {   // a prompt: single pass, online softmax; its rows are split by a pass of their own
-            if ((rc = attention_flash(p, p->q, m.kc + slot, m.vc + slot, p->attn, n, past, scale))) return rc;
-            Split3Args sa = {p->attn, as, pd, d, d, d};
-            if (!g_prepare_only) { TraceScope ts_(ctx->stream, "split3_rows"); LH_LAUNCH(k_split3_rows, dim3(n), dim3(256), 0, ctx->stream, sa); }
-        } else if (n >= 32 && m.hd % 32 == 0) {   // other head sizes: batched MFMA GEMMs over heads with a score tensor (as plan_eval's fp32 route does)
-            if ((rc = attention_gemm(p, p->q, m.kc + slot, m.vc + slot, p->attn, n, past, scale))) return rc;
-            Split3Args sa = {p->attn, as, pd, d, d, d};
-            if (!g_prepare_only) { TraceScope ts_(ctx->stream, "split3_rows"); LH_LAUNCH(k_split3_rows, dim3(n), dim3(256), 0, ctx->stream, sa); }
-        } else {
-            AttnArgs a = {};
-            a.q = p->q; a.k_cache = m.kc + slot; a.v_cache = m.vc + slot; a.out = p->attn; a.d = d; a.hd = m.hd; a.n = n; a.scale = scale; a.sp = nullptr; a.past_host = past;
-            a.out_s3 = as; a.out_plane = pd;
-            if ((rc = launch_attention(ctx, a, past + n))) return rc;
-        }
+        if ((rc = eval_attention(p, c, slot, scale, true, as, pd))) return rc;   // merged heads -> planes (mfma: this route's shapes all have the grouped MFMA launches)
         // wo + residual + RMSNorm * ffn_norm -> planes   (llama.go:336-351)
         for (uint32_t b0 = 0; b0 < n; b0 += STREAM_ROWS_Q8)
-            Q8B_TRY(gemm_q8b_split(ctx, L.wo, L.s_wo, as + (size_t)b0 * d, pd, d, d, d, std::min(STREAM_ROWS_Q8, n - b0), x + (size_t)b0 * d, p->xb + (size_t)b0 * d, L.ffn_norm, nullptr,
+            PLANES_TRY(gemm_q8b_split(ctx, L.wo, L.s_wo, as + (size_t)b0 * d, pd, d, d, d, std::min(STREAM_ROWS_Q8, n - b0), x + (size_t)b0 * d, p->xb + (size_t)b0 * d, L.ffn_norm, nullptr,
                                    hs + (size_t)b0 * d, pd, m.wtype == 7 ? "q8b_wo_ksplit" : "b9s_wo_ksplit"), "wo");
         {   // w1|w3 -> silu(w1 h) * (w3 h) -> planes   (llama.go:354-361)
             const float* w13[2] = {L.w1, L.w3};
@@ -1773,7 +1926,7 @@ static int eval_q8b_layers(Plan* p, const float* x, float* x_out_dev, uint32_t n
             fa.epi = ST_EPI_SILU_MUL; fa.ys = gs; fa.ys_plane = pf; fa.ldys = F;
             for (uint32_t b0 = 0; b0 < n; b0 += STREAM_ROWS_Q8) {
                 fa.ys = gs + (size_t)b0 * F;
-                Q8B_TRY(gemm_q8b_group(ctx, hs + (size_t)b0 * d, pd, d, 2, w13, s13, nullptr, nullptr, F, d, std::min(STREAM_ROWS_Q8, n - b0), F, m.wtype == 7 ? "q8b_w1w3_silu" : "b9s_w1w3_silu", &fa), "w1|w3");
+                PLANES_TRY(gemm_q8b_group(ctx, hs + (size_t)b0 * d, pd, d, 2, w13, s13, nullptr, nullptr, F, d, std::min(STREAM_ROWS_Q8, n - b0), F, m.wtype == 7 ? "q8b_w1w3_silu" : "b9s_w1w3_silu", &fa), "w1|w3");
             }
         }
         {   // w2 + residual (+ the next layer's first norm, or the final norm, on the reduce pass)   (llama.go:363-372)
@@ -1781,7 +1934,7 @@ static int eval_q8b_layers(Plan* p, const float* x, float* x_out_dev, uint32_t n
             float* y = (last && !m.last_stage()) ? x_out_dev : p->xa;
             const float* next_gamma = !last ? m.layers[il + 1].attn_norm : (m.last_stage() ? m.norm : nullptr);
             for (uint32_t b0 = 0; b0 < n; b0 += STREAM_ROWS_Q8)
-                Q8B_TRY(gemm_q8b_split(ctx, L.w2, L.s_w2, gs + (size_t)b0 * F, pf, F, d, F, std::min(STREAM_ROWS_Q8, n - b0), p->xb + (size_t)b0 * d, y + (size_t)b0 * d, next_gamma,
+                PLANES_TRY(gemm_q8b_split(ctx, L.w2, L.s_w2, gs + (size_t)b0 * F, pf, F, d, F, std::min(STREAM_ROWS_Q8, n - b0), p->xb + (size_t)b0 * d, y + (size_t)b0 * d, next_gamma,
                                        (last && m.last_stage()) ? p->h + (size_t)b0 * d : nullptr, next_gamma ? hs + (size_t)b0 * d : nullptr, pd, m.wtype == 7 ? "q8b_w2_ksplit" : "b9s_w2_ksplit"), "w2");
             h_ready = next_gamma != nullptr;
         }
@@ -1789,7 +1942,7 @@ static int eval_q8b_layers(Plan* p, const float* x, float* x_out_dev, uint32_t n
         LH_HIP(ctx, hipGetLastError());
     }
     if (m.last_stage()) {   // lm_head on the rows the caller reads (llama.go:374-384, 394-401); hs / p->h hold RMSNorm * norm of every row
-        const uint32_t r0 = last_row_only ? n - 1 : 0, nr = n - r0;
+        const auto [r0, nr] = logits_rows(c);
         const float* wv = m.output; const float* sv = m.s_output; float* yv = p->logits + (size_t)r0 * m.V;
         for (uint32_t b0 = 0; b0 < nr; b0 += STREAM_ROWS_Q8) {
             float* yb = yv + (size_t)b0 * m.V;
@@ -1811,220 +1964,26 @@ static int eval_q8b_layers(Plan* p, const float* x, float* x_out_dev, uint32_t n
                     rc = gemv<PRO_PLAIN, EPI_STORE, MAP_SINGLE>(ctx, ga, "gemv_lmhead_row", 0);
                 } else rc = gemm_small_n(ctx, m.output, p->h + (size_t)(r0 + b0) * d, yb, nullptr, m.V, d, nb, d, m.V, "gemm_lmhead");
             }
-            Q8B_TRY(rc, "lm_head");
+            PLANES_TRY(rc, "lm_head");
         }
     }
     LH_HIP(ctx, hipGetLastError());
-#undef Q8B_TRY
+#undef PLANES_TRY
     return 0;
 }
 
-int plan_eval(Plan* p, const uint32_t* tokens_host, const float* x_in_dev, float* x_out_dev, uint32_t n, uint32_t past, bool last_row_only, const BatchCtx* bc) {
+// prefill, N > 1 rows (or the rows of a batched Eval: `rows` set, every row at its own position of its own cache): the fp32 stream kernels and tile GEMMs,
+// the dequantising GEMM of block-int8 weights, the column kernels for what neither takes
+static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
     lh_ctx* ctx = p->ctx;
     const ModelDesc& m = p->md;
-    if (n == 0) LH_FAIL(ctx, LH_EINVAL, "Eval: empty token batch");
-    if (bc) {
-        if (!bc->rows || (m.first_stage() && !bc->tok_dev) || !plan_batch_rows_ok(p, n)) LH_FAIL(ctx, LH_EINVAL, "Eval: batched rows need a row table, token ids and a supported shape");
-        if (n > p->n_cap) LH_FAIL(ctx, LH_EINVAL, "Eval: batched rows exceed the plan's scratch (plan_ensure_rows first: a captured graph must not allocate)");
-    } else {
-        if ((uint64_t)past + n > m.ctx) LH_FAIL(ctx, LH_EINVAL, "Eval: past %u + n %u exceeds the context window of %u", past, n, m.ctx);
-        if (m.first_stage() && !tokens_host) LH_FAIL(ctx, LH_EINVAL, "Eval: first stage needs token ids");
-        if (m.first_stage())  // Go panics on tokEmbeddings.Data[id*NE[0]:] past the table (ml.go:1748); the GPU must never gather out of range
-            for (uint32_t i = 0; i < n; ++i)
-                if (tokens_host[i] >= m.V) LH_FAIL(ctx, LH_EINVAL, "Eval: token id %u at index %u outside the vocabulary of %u", tokens_host[i], i, m.V);
-        if (m.first_stage()) for (uint32_t i = 0; i < n; ++i) p->record(past + i, tokens_host[i]);
-    }
-    if (!m.first_stage() && !x_in_dev) LH_FAIL(ctx, LH_EINVAL, "Eval: later stage needs the residual stream");
-    if (!m.last_stage() && !x_out_dev) LH_FAIL(ctx, LH_EINVAL, "Eval: non-final stage needs an output buffer");
-    int rc;
-    if (!bc && (rc = plan_ensure_rows(p, n))) return rc;
+    const uint32_t n = c.n, past = c.past, d = m.d, F = m.F;
+    const BatchCtx* bc = c.bc;
     const BatchRow* rows = bc ? bc->rows : nullptr;
-    if (n == 1) {
-        if (m.first_stage() && m.last_stage() && p->use_graph) return plan_decode_step(p, tokens_host[0], past);
-        const uint32_t slot = 1 + (p->slot_counter++ % (SP_SLOTS - 1));
-        if ((rc = upload_step_params(p, slot, tokens_host ? tokens_host[0] : 0, past, 0))) return rc;
-        return enqueue_decode(p, p->sp_dev + slot, x_in_dev, x_out_dev, false, nullptr);
-    }
-    if (rows_path_ok(ctx, m, n)) {
-        // ---- 2..8 rows (block-int8: 2..4) (a prompt of that many tokens, or a tick of that many pods): the decode launches with NC activation rows each
-        // (kernels_rows.h): 5 launches per layer like the decode step, every row bit-identical to its solo step
-        const float* x = p->xa;
-        if (m.first_stage()) {
-            const uint32_t* tok_dev = bc ? bc->tok_dev : p->tokens_dev;
-            if (!bc) {
-                if ((rc = ensure_staging(ctx, (uint64_t)n * 4))) return rc;
-                LH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // staging reuse
-                memcpy(ctx->staging, tokens_host, (size_t)n * 4);
-                LH_HIP(ctx, hipMemcpyAsync(p->tokens_dev, ctx->staging, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-            }
-            if (!g_prepare_only) LH_LAUNCH(k_embed, dim3(n), dim3(256), 0, ctx->stream, m.tok_emb, tok_dev, (const StepParams*)nullptr, p->xa, m.d, m.V);
-            LH_HIP(ctx, hipGetLastError());
-        } else {
-            x = x_in_dev;
-        }
-        const float scale = (float)(1.0 / sqrt((double)m.d / (double)m.H));
-        const uint32_t d = m.d, F = m.F;
-        for (uint32_t il = m.layer0; il < m.layer1; ++il) {
-            const LayerW& L = m.layers[il];
-            const size_t slot = (size_t)(il - m.cache_layer0) * m.ctx * d;
-            {   // RMSNorm*gamma -> wq|wk|wv -> RoPE(Q, new K rows) -> K, V appended   (llama.go:255-297)
-                GemvRowsArgs a = {};
-                a.w[0] = L.wq; a.w[1] = L.wk; a.w[2] = L.wv; a.ws[0] = L.s_wq; a.ws[1] = L.s_wk; a.ws[2] = L.s_wv; a.rows_per_mat = d; a.M = 3 * d; a.K = d; a.x = x; a.ldx = d; a.n = n; a.gamma = L.attn_norm;
-                a.q_out = p->q; a.k_cache = m.kc + slot; a.v_cache = m.vc + slot; a.rope = p->rope; a.hd = m.hd; a.d = d; a.past = past; a.rows = rows; a.kv_off = slot;
-                if ((rc = gemv_rows<PRO_RMSNORM, EPI_QKV_ROPE, MAP_BLOCK>(ctx, a, "rows_qkv_rope", m.wtype))) return rc;
-            }
-            {   // scores, scale, mask, softmax, PV, head merge per row   (llama.go:300-333)
-                AttnArgs a = {};
-                a.q = p->q; a.out = p->attn; a.d = d; a.hd = m.hd; a.n = n; a.scale = scale;
-                if (rows) {
-                    a.rows = rows; a.kv_off = slot;
-                    if ((rc = launch_attention_rows(p, a, bc))) return rc;
-                } else {
-                    a.k_cache = m.kc + slot; a.v_cache = m.vc + slot; a.sp = nullptr; a.past_host = past;
-                    if ((rc = launch_attention(ctx, a, past + n))) return rc;
-                }
-            }
-            {   // wo + residual   (llama.go:336-340)
-                GemvRowsArgs a = {};
-                a.w[0] = L.wo; a.ws[0] = L.s_wo; a.M = d; a.K = d; a.x = p->attn; a.ldx = d; a.n = n; a.y = p->xb; a.resid = x; a.ldy = d;
-                if ((rc = gemv_rows<PRO_PLAIN, EPI_RESID, MAP_SINGLE>(ctx, a, "rows_wo_resid", m.wtype))) return rc;
-            }
-            {   // RMSNorm*gamma -> w1|w3 -> silu(w1 h) * (w3 h)   (llama.go:346-361)
-                GemvRowsArgs a = {};
-                a.w[0] = L.w1; a.w[1] = L.w3; a.ws[0] = L.s_w1; a.ws[1] = L.s_w3; a.M = 2 * F; a.K = d; a.x = p->xb; a.ldx = d; a.n = n; a.gamma = L.ffn_norm; a.y = p->g; a.ldy = F;
-                if ((rc = gemv_rows<PRO_RMSNORM, EPI_SILU_MUL, MAP_PAIR>(ctx, a, "rows_w1w3_silu", m.wtype))) return rc;
-            }
-            {   // w2 + residual   (llama.go:363-366)
-                const bool last = il + 1 == m.layer1;
-                GemvRowsArgs a = {};
-                a.w[0] = L.w2; a.ws[0] = L.s_w2; a.M = d; a.K = F; a.x = p->g; a.ldx = F; a.n = n; a.resid = p->xb; a.ldy = d;
-                a.y = (last && !m.last_stage()) ? x_out_dev : p->xa;
-                if ((rc = gemv_rows<PRO_PLAIN, EPI_RESID, MAP_SINGLE>(ctx, a, "rows_w2_resid", m.wtype))) return rc;
-            }
-            x = p->xa;
-        }
-        if (m.last_stage()) {   // final RMSNorm*gamma -> lm_head: the rows the caller reads (llama.go:372-384, 394-401)
-            const uint32_t r0 = last_row_only ? n - 1 : 0, nr = n - r0;
-            if (nr == 1) {
-                GemvArgs a = {};
-                a.w[0] = m.output; a.ws[0] = m.s_output; a.M = m.V; a.K = d; a.x = x + (size_t)r0 * d; a.gamma = m.norm; a.y = p->logits + (size_t)r0 * m.V;
-                if ((rc = gemv<PRO_RMSNORM, EPI_STORE, MAP_SINGLE>(ctx, a, "gemv_lmhead", m.wtype))) return rc;
-            } else {
-                GemvRowsArgs a = {};
-                a.w[0] = m.output; a.ws[0] = m.s_output; a.M = m.V; a.K = d; a.x = x + (size_t)r0 * d; a.ldx = d; a.n = nr; a.gamma = m.norm; a.y = p->logits + (size_t)r0 * m.V; a.ldy = m.V;
-                if ((rc = gemv_rows<PRO_RMSNORM, EPI_STORE, MAP_SINGLE>(ctx, a, "rows_lmhead", m.wtype))) return rc;
-            }
-        }
-        LH_HIP(ctx, hipGetLastError());
-        return 0;
-    }
-    // block-int8: 5..64 rows of a tick / 5..88 of a prompt on k_stream_q8b (two 64-row passes from 65); from 89 rows the tile GEMM k_gemm_q8b3 below
-    const bool q8_stream = q8_stream_ok(ctx, m, n, 3, bc != nullptr);
-    if (m.wtype == 7 && !q8_stream && (n < Q8_GEMM_MIN_ROWS || m.d % GBK || m.F % GBK || m.hd % 32)) {
-        // block-int8, short batches: n causal single-token steps on the int8 weight stream (bit-identical to what the decode
-        // path produces for them), logits row i from step i like llama.go:384.  n >= 32 takes the dequantising GEMM below.
-        // On a pipeline stage row i of the received / forwarded residual stream stands in for the token id / the logits row.
-        for (uint32_t i = 0; i < n; ++i) {
-            const uint32_t slot = 1 + (p->slot_counter++ % (SP_SLOTS - 1));
-            if ((rc = upload_step_params(p, slot, m.first_stage() ? tokens_host[i] : 0, past + i, 0))) return rc;
-            if ((rc = enqueue_decode(p, p->sp_dev + slot, m.first_stage() ? nullptr : x_in_dev + (size_t)i * m.d, m.last_stage() ? nullptr : x_out_dev + (size_t)i * m.d, false,
-                                     nullptr, nullptr, i)))
-                return rc;
-        }
-        return 0;
-    }
-    if (!bc && skinny_ok(m, n) && !stream_shape_ok(ctx, m)) {   // k_skinny only where the streaming MFMA kernel is not built for the shape
-        // ---- short prompt: 4 fused weight passes per layer + the per-query attention kernel (like the decode step, n rows wide)
-        const float* x = p->xa;
-        if (m.first_stage()) {
-            if ((rc = ensure_staging(ctx, (uint64_t)n * 4))) return rc;
-            LH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // staging reuse
-            memcpy(ctx->staging, tokens_host, (size_t)n * 4);
-            LH_HIP(ctx, hipMemcpyAsync(p->tokens_dev, ctx->staging, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-            LH_LAUNCH(k_embed, dim3(n), dim3(256), 0, ctx->stream, m.tok_emb, (const uint32_t*)p->tokens_dev, (const StepParams*)nullptr, p->xa, m.d, m.V);
-            LH_HIP(ctx, hipGetLastError());
-        } else {
-            x = x_in_dev;
-        }
-        const float scale = (float)(1.0 / sqrt((double)m.d / (double)m.H));
-        const uint32_t d = m.d, F = m.F;
-        for (uint32_t il = m.layer0; il < m.layer1; ++il) {
-            const LayerW& L = m.layers[il];
-            const size_t slot = (size_t)(il - m.cache_layer0) * m.ctx * d;
-            {   // RMSNorm*gamma -> wq|wk|wv -> RoPE(Q, new K rows) -> K,V appended   (llama.go:255-297)
-                SkinnyArgs a = {};
-                a.w[0] = L.wq; a.w[1] = L.wk; a.w[2] = L.wv; a.rows_per_mat = d; a.M = 3 * d; a.K = d; a.x = x; a.ldx = d; a.n = n; a.gamma = L.attn_norm;
-                a.q_out = p->q; a.k_cache = m.kc + slot; a.v_cache = m.vc + slot; a.rope = p->rope; a.hd = m.hd; a.d = d; a.past = past;
-                if ((rc = launch_skinny<PRO_RMSNORM, EPI_QKV_ROPE, MAP_BLOCK>(p, a, "skinny_qkv_rope"))) return rc;
-            }
-            {
-                AttnArgs a = {};
-                a.q = p->q; a.k_cache = m.kc + slot; a.v_cache = m.vc + slot; a.out = p->attn; a.d = d; a.hd = m.hd; a.n = n; a.scale = scale; a.sp = nullptr; a.past_host = past;
-                if ((rc = launch_attention(ctx, a, past + n))) return rc;
-            }
-            {   // wo + residual   (llama.go:336-340)
-                SkinnyArgs a = {};
-                a.w[0] = L.wo; a.M = d; a.K = d; a.x = p->attn; a.ldx = d; a.n = n; a.y = p->xb; a.resid = x; a.ldy = d;
-                if ((rc = launch_skinny<PRO_PLAIN, EPI_RESID, MAP_SINGLE>(p, a, "skinny_wo_resid"))) return rc;
-            }
-            {   // RMSNorm*gamma -> w1|w3 -> silu(w1 h) * (w3 h)   (llama.go:346-361)
-                SkinnyArgs a = {};
-                a.w[0] = L.w1; a.w[1] = L.w3; a.M = 2 * F; a.K = d; a.x = p->xb; a.ldx = d; a.n = n; a.gamma = L.ffn_norm; a.y = p->g; a.ldy = F;
-                if ((rc = launch_skinny<PRO_RMSNORM, EPI_SILU_MUL, MAP_PAIR>(p, a, "skinny_w1w3_silu"))) return rc;
-            }
-            {   // w2 + residual   (llama.go:363-366)
-                const bool last = il + 1 == m.layer1;
-                SkinnyArgs a = {};
-                a.w[0] = L.w2; a.M = d; a.K = F; a.x = p->g; a.ldx = F; a.n = n; a.resid = p->xb; a.ldy = d;
-                a.y = (last && !m.last_stage()) ? x_out_dev : p->xa;
-                if ((rc = launch_skinny<PRO_PLAIN, EPI_RESID, MAP_SINGLE>(p, a, "skinny_w2_resid"))) return rc;
-            }
-            x = p->xa;
-        }
-        if (m.last_stage()) {   // final RMSNorm*gamma -> lm_head: the rows the caller reads (llama.go:372-384, 394-401)
-            const uint32_t r0 = last_row_only ? n - 1 : 0;
-            if (n - r0 == 1) {
-                GemvArgs a = {};
-                a.w[0] = m.output; a.M = m.V; a.K = d; a.x = x + (size_t)r0 * d; a.gamma = m.norm; a.y = p->logits + (size_t)r0 * m.V;
-                if ((rc = gemv<PRO_RMSNORM, EPI_STORE, MAP_SINGLE>(ctx, a, "gemv_lmhead", 0))) return rc;
-            } else {
-                SkinnyArgs a = {};
-                a.w[0] = m.output; a.M = m.V; a.K = d; a.x = x; a.ldx = d; a.n = n; a.gamma = m.norm; a.y = p->logits; a.ldy = m.V;
-                if ((rc = launch_skinny<PRO_RMSNORM, EPI_STORE, MAP_SINGLE>(p, a, "skinny_lmhead"))) return rc;
-            }
-        }
-        LH_HIP(ctx, hipGetLastError());
-        return 0;
-    }
-    // ---- prefill, N > 1 rows (or the rows of a batched Eval: `rows` set, every row at its own position of its own cache)
+    float* x_out_dev = c.x_out_dev;
     const double2* rope = p->rope;
-    const float* x = p->xa;
-    if (m.first_stage()) {
-        const uint32_t* tok_dev = bc ? bc->tok_dev : p->tokens_dev;
-        if (!bc) {
-            if ((rc = ensure_staging(ctx, (uint64_t)n * 4))) return rc;
-            LH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // staging reuse
-            memcpy(ctx->staging, tokens_host, (size_t)n * 4);
-            LH_HIP(ctx, hipMemcpyAsync(p->tokens_dev, ctx->staging, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-        }
-        TraceScope ts_(ctx->stream, "embedN");
-        LH_LAUNCH(k_embed, dim3(n), dim3(256), 0, ctx->stream, m.tok_emb, tok_dev, (const StepParams*)nullptr, p->xa, m.d, m.V);
-        LH_HIP(ctx, hipGetLastError());
-    } else {
-        x = x_in_dev;
-    }
-    const float scale = (float)(1.0 / sqrt((double)m.d / (double)m.H));
-    const uint32_t d = m.d, F = m.F;
-    if (q8_stream) {   // block-int8, up to 64 rows: the bf16 matrix pipe (kernels_stream_q8b.h)
-        const int rs = eval_q8b_layers(p, x, x_out_dev, n, past, last_row_only, bc);
-        if (rs == ST_NA) LH_FAIL(ctx, LH_ESHAPE, "block-int8 Eval of %u rows: the plan's shape has no k_stream_q8b launch", n);
-        return rs;
-    }
-    static const int b9s_min = getenv("LLAMAHIP_B9S_MIN") ? atoi(getenv("LLAMAHIP_B9S_MIN")) : (int)B9S_MIN_ROWS;   // (A/B switch of round 6's measurements: 65 = off)
-    if (m.wtype == 0 && (int)n >= b9s_min && n <= B9S_MAX_ROWS) {   // fp32, 49..64 rows: the same schedule over planes on k_stream_b9 (eight of the nine exact bf16 products)
-        const int rs = eval_q8b_layers(p, x, x_out_dev, n, past, last_row_only, bc);
-        if (rs != ST_NA) return rs;   // (ST_NA comes back before anything is enqueued: the fp32-MFMA route below takes the Eval)
-    }
+    const float scale = attn_scale(m);
+    int rc;
     // fp32 prompts just past the stream kernels' 128 rows: two passes over the weights, ceil(n / 2) rows each (the rows of a pass are independent of the other
     // pass's in every launch but attention, which runs once over all n as before).  Measurements: STREAM_TWO_PASS_MAX.
     static const uint32_t two_pass_max = getenv("LLAMAHIP_TWO_PASS_MAX") ? (uint32_t)atoi(getenv("LLAMAHIP_TWO_PASS_MAX")) : STREAM_TWO_PASS_MAX;   // (A/B switch: 128 = off)
@@ -2034,7 +1993,7 @@ int plan_eval(Plan* p, const uint32_t* tokens_host, const float* x_in_dev, float
     for (uint32_t il = m.layer0; il < m.layer1; ++il) {
         const LayerW& L = m.layers[il];
         const size_t slot = (size_t)(il - m.cache_layer0) * m.ctx * d;
-        const bool mfma = (n >= MFMA_MIN_ROWS || (n >= 2 && m.wtype == 0)) && d % GBK == 0 && F % GBK == 0;   // grouped MFMA launches: from 9 rows (tile GEMM), from 2 rows on the streaming MFMA kernel
+        const bool mfma = prefill_mfma(m, n);
         const bool q8 = m.wtype == 7;
         bool qkv_roped = false, gated = false;
         // 17..64 rows: wo / w2 as K-split pairs whose reduce pass also writes the next norm's rows into p->h (gemm_stream_split)
@@ -2084,19 +2043,7 @@ int plan_eval(Plan* p, const uint32_t* tokens_host, const float* x_in_dev, float
         }
         if (!qkv_roped) { TraceScope ts_(ctx->stream, "rope_store"); LH_LAUNCH(k_rope_store, dim3(n), dim3(256), 0, ctx->stream, (const float*)p->qraw, (const float*)p->kraw, (const float*)p->vraw, p->q, m.kc + slot,
                            m.vc + slot, rope, d, m.hd, past, rows, (uint64_t)slot); }
-        if (rows) {   // rows of different streams: one query each, against its own cache up to its own position
-            AttnArgs a = {};
-            a.q = p->q; a.out = p->attn; a.d = d; a.hd = m.hd; a.n = n; a.scale = scale; a.rows = rows; a.kv_off = slot;
-            if ((rc = launch_attention_rows(p, a, bc))) return rc;
-        } else if (mfma && n >= 32 && m.hd == FA_HD) {   // single pass, online softmax
-            if ((rc = attention_flash(p, p->q, m.kc + slot, m.vc + slot, p->attn, n, past, scale))) return rc;
-        } else if (mfma && n >= 32 && m.hd % 32 == 0) {  // other head sizes: batched MFMA GEMMs over heads with a score tensor
-            if ((rc = attention_gemm(p, p->q, m.kc + slot, m.vc + slot, p->attn, n, past, scale))) return rc;
-        } else {   // fewer queries: the per-query kernel (no score tensor) is cheaper
-            AttnArgs a = {};
-            a.q = p->q; a.k_cache = m.kc + slot; a.v_cache = m.vc + slot; a.out = p->attn; a.d = d; a.hd = m.hd; a.n = n; a.scale = scale; a.sp = nullptr; a.past_host = past;
-            if ((rc = launch_attention(ctx, a, past + n))) return rc;
-        }
+        if ((rc = eval_attention(p, c, slot, scale, mfma))) return rc;
         int wo_rs = ST_NA;
         if (ksp) {
             for (uint32_t b0 = 0; b0 < n; b0 += sb)
@@ -2164,7 +2111,7 @@ int plan_eval(Plan* p, const uint32_t* tokens_host, const float* x_in_dev, float
     if (m.last_stage()) {
         // the reference evaluates norm + lm_head for all N rows (llama.go:372-384) although only row N-1 is read (llama.go:394-401);
         // callers that say so (LH_GRAPH_LAST_ROW_LOGITS, the lh_llama_* entry points) get that row only, in its usual place
-        const uint32_t r0 = last_row_only ? n - 1 : 0, nr = n - r0;
+        const auto [r0, nr] = logits_rows(c);
         { TraceScope ts_(ctx->stream, "rmsnorm_rows_final"); LH_LAUNCH(k_rmsnorm_rows, dim3(nr), dim3(256), 0, ctx->stream, x + (size_t)r0 * d, m.norm, p->h + (size_t)r0 * d, d); }
         if (m.wtype == 7) {
             if (nr >= Q8_GEMM_MIN_ROWS) {
@@ -2184,6 +2131,44 @@ int plan_eval(Plan* p, const uint32_t* tokens_host, const float* x_in_dev, float
     }
     LH_HIP(ctx, hipGetLastError());
     return 0;
+}
+
+int plan_eval(Plan* p, const uint32_t* tokens_host, const float* x_in_dev, float* x_out_dev, uint32_t n, uint32_t past, bool last_row_only, const BatchCtx* bc) {
+    lh_ctx* ctx = p->ctx;
+    const ModelDesc& m = p->md;
+    if (n == 0) LH_FAIL(ctx, LH_EINVAL, "Eval: empty token batch");
+    if (bc) {
+        if (!bc->rows || (m.first_stage() && !bc->tok_dev) || !plan_batch_rows_ok(p, n)) LH_FAIL(ctx, LH_EINVAL, "Eval: batched rows need a row table, token ids and a supported shape");
+        if (n > p->n_cap) LH_FAIL(ctx, LH_EINVAL, "Eval: batched rows exceed the plan's scratch (plan_ensure_rows first: a captured graph must not allocate)");
+    } else {
+        if ((uint64_t)past + n > m.ctx) LH_FAIL(ctx, LH_EINVAL, "Eval: past %u + n %u exceeds the context window of %u", past, n, m.ctx);
+        if (m.first_stage() && !tokens_host) LH_FAIL(ctx, LH_EINVAL, "Eval: first stage needs token ids");
+        if (m.first_stage())  // Go panics on tokEmbeddings.Data[id*NE[0]:] past the table (ml.go:1748); the GPU must never gather out of range
+            for (uint32_t i = 0; i < n; ++i)
+                if (tokens_host[i] >= m.V) LH_FAIL(ctx, LH_EINVAL, "Eval: token id %u at index %u outside the vocabulary of %u", tokens_host[i], i, m.V);
+        if (m.first_stage()) for (uint32_t i = 0; i < n; ++i) p->record(past + i, tokens_host[i]);
+    }
+    if (!m.first_stage() && !x_in_dev) LH_FAIL(ctx, LH_EINVAL, "Eval: later stage needs the residual stream");
+    if (!m.last_stage() && !x_out_dev) LH_FAIL(ctx, LH_EINVAL, "Eval: non-final stage needs an output buffer");
+    int rc;
+    if (!bc && (rc = plan_ensure_rows(p, n))) return rc;
+    const EvalCall c = {tokens_host, x_in_dev, x_out_dev, n, past, last_row_only, bc};
+    const EvalRoute route = eval_route(ctx, m, n, bc != nullptr);
+    const float* x = nullptr;   // the rows the first layer reads
+    if (route != EvalRoute::Step && route != EvalRoute::Q8Steps && (rc = eval_input(p, c, route, &x))) return rc;   // (the single steps embed their own token)
+    switch (route) {
+        case EvalRoute::Step: return eval_step(p, c);
+        case EvalRoute::Rows: return eval_rows(p, c, x);
+        case EvalRoute::Q8Steps: return eval_q8_steps(p, c);
+        case EvalRoute::Skinny: return eval_skinny(p, c, x);
+        case EvalRoute::Planes:
+            rc = eval_planes(p, c, x);
+            if (rc != ST_NA) return rc;
+            if (m.wtype == 7) LH_FAIL(ctx, LH_ESHAPE, "block-int8 Eval of %u rows: the plan's shape has no k_stream_q8b launch", n);
+            break;   // fp32: ST_NA comes back before anything but the embedding is enqueued, and the fp32-MFMA route takes the Eval
+        case EvalRoute::Prefill: break;
+    }
+    return eval_prefill(p, c, x);
 }
 
 

@@ -155,11 +155,11 @@ def test_attention_rows_within_bound(product, case, wtype):
     for n, past, checked in steps:
         if checked:
             expect_route(case, n, traces[past])
-            # the prompt attention's call site in eval_q8b_layers (layers over activation planes): block-int8 at 5..64 rows, fp32 at 49..64
+            # the prompt attention's call site in eval_planes (layers over activation planes): block-int8 at 5..64 rows, fp32 at 49..64
             if wtype == "q8" and 5 <= n <= 64:
-                assert any(e.startswith("k_stream_q8b") for e in traces[past]), (case, "block-int8 rows must take eval_q8b_layers", traces[past])
+                assert any(e.startswith("k_stream_q8b") for e in traces[past]), (case, "block-int8 rows must take eval_planes", traces[past])
             if wtype == "f32" and 49 <= n <= 64:
-                assert any(e.startswith("k_stream_b9") for e in traces[past]), (case, "fp32 at 49..64 rows must take eval_q8b_layers", traces[past])
+                assert any(e.startswith("k_stream_b9") for e in traces[past]), (case, "fp32 at 49..64 rows must take eval_planes", traces[past])
     # the case as a whole - all rows of all its checked calls - as K_SPREAD was measured (tests/test_attention_bound_cpu.py)
     yc = y[rows].astype(np.float64)
     print(f"{case.name} {wtype}: error / bound {R.bound_ratio(yc, ref):.4g}, E(hip) {R.case_error(yc, ref):.2f}, E(float32) {R.case_error(ref32, ref):.2f}; "
