@@ -30,6 +30,8 @@
 // cost half of the matrix-pipe time and 120 registers here), and the normalisation by the fp32 sum happens once at the end (the
 // reference normalises p before the P.V product and sums in key order): the same value up to a few fp32 roundings per output
 // (~1e-6 relative against the checker, tolerance 1e-4).  Masked keys contribute exactly 0 (ml.go:2476-2477).
+// A NaN or an infinity in a V row reaches only the queries that see its key: the P.V matrix product takes it as 0 and the queries that see
+// that key add it afterwards (the reference's MulMat(VTrans, KQSoftMax) multiplies it with the masked queries' 0 and gives every row a NaN).
 #pragma once
 #include "kernels_llama.h"
 #include "attn_worklist.h"
@@ -54,6 +56,8 @@ struct FlashArgs {
     uint32_t nwork;        // entries of work[]; 0 = no list: blocks in descending order, uncut
     uint16_t work[FA_MAXW];   // (block << 4 | part), longest first; every head runs the same list (attn_worklist.h)
 };
+
+__device__ __forceinline__ bool fa_nonfinite(float x) { return (__builtin_bit_cast(uint32_t, x) & 0x7f800000u) == 0x7f800000u; }
 
 constexpr int FA_TH = 256, FA_HD = 128;
 constexpr int FA_PSTRIDE = FA_HD + 4;   // a partial record per query: 128 O values, m, l, padding to 16 bytes
@@ -183,14 +187,40 @@ __global__ __launch_bounds__(FA_TH) __attribute__((amdgpu_waves_per_eu(2, 2))) v
             dma(true, st + 1 < st1 ? st + 1 : st);             // past the end: a harmless reload (keeps the counts uniform)
             if (live) {
                 const float* Vt = Vsm + pair * (32 * FA_HD) + 4 * lj;
+                // A non-finite V value goes into the matrix product as 0: the product would multiply it with the exact 0 of every query that does
+                // NOT see its key (masked, or a row past the extent) and hand all of them a NaN.  The queries that do see it get it below.
+                // Every tile pays for the test: four exponent compares, four selects and an OR per V float4 next to its four MFMAs (1024-token
+                // prefill of the 13B shape: 34.8 / 35.0 ms before, 34.9 / 34.9 with it); only the repair loop is behind the branch.
+                bool vbad = false;
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
                     const int rr = 8 * (e >> 2) + 4 * lh2 + (e & 3);   // tile row of the key this half-wave supplies in step e
-                    const f4 vf = *(const f4*)(Vt + rr * FA_HD);
+                    f4 vf = *(const f4*)(Vt + rr * FA_HD);
+                    const bool bx = fa_nonfinite(vf.x), by = fa_nonfinite(vf.y), bz = fa_nonfinite(vf.z), bw = fa_nonfinite(vf.w);
+                    vbad |= (bx | by) | (bz | bw);
+                    vf.x = bx ? 0.f : vf.x; vf.y = by ? 0.f : vf.y; vf.z = bz ? 0.f : vf.z; vf.w = bw ? 0.f : vf.w;
                     o[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(vf.x, p[e], o[0], 0, 0, 0); 
                     o[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(vf.y, p[e], o[1], 0, 0, 0); 
                     o[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(vf.z, p[e], o[2], 0, 0, 0); 
                     o[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(vf.w, p[e], o[3], 0, 0, 0); 
+                }
+                if (__any(vbad)) {   // (the wave's lanes read the whole tile between them)  Rare: every key this lane's query sees against its 64 outputs.
+                    const float* Vtile = Vsm + pair * (32 * FA_HD) + 16 * lh2;
+#pragma unroll 1
+                    for (uint32_t r = 0; r < 32; ++r) {
+                        if (!(qok && kt * 32 + r <= qlim)) continue;                   // masked, or a row past the extent
+                        const float* vrow = Vtile + r * FA_HD;
+#pragma unroll
+                        for (int e2 = 0; e2 < 16; ++e2) {
+                            const f4 v = *(const f4*)(vrow + 4 * (8 * (e2 >> 2) + (e2 & 3)));   // the columns of accumulator entry e2
+                            // (weights are positive: adding the value itself gives what p * value gives - an infinity of its sign, or NaN.  One
+                            // difference: a visible key whose weight underflowed to 0 hands on its infinity as such, where 0 * inf would be NaN.)
+                            if (fa_nonfinite(v.x)) o[0][e2] += v.x;
+                            if (fa_nonfinite(v.y)) o[1][e2] += v.y;
+                            if (fa_nonfinite(v.z)) o[2][e2] += v.z;
+                            if (fa_nonfinite(v.w)) o[3][e2] += v.w;
+                        }
+                    }
                 }
             }
             __builtin_amdgcn_s_barrier();                       // every wave is done reading V(st)

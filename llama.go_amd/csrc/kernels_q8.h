@@ -5,6 +5,8 @@
 // in the style of that ggml vintage's Q4_0 ({scale; QK quants} per block):
 //     interchange / registration format: blocks of QK = 32 weights { float d; int8 q[32] } = 36 bytes,  w = d * q
 //     quantiser (ours):                  d = max|w| / 127 (fp32 divide), q = clamp(rint(w / d), -127, 127)   (d = 0 -> q = 0)
+//                                        a block that holds a NaN or an infinity: d = NaN, q = 0 - the whole block dequantises to NaN
+//                                        (one non-finite weight cannot come back as a finite one; the checker's quantiser states the same rule)
 // Semantics the checker uses: dequantise to fp32 (one rounding: fl32(d*q)), then the fp32 MulMat of ml.go:1976-2098.
 //
 // HBM layout (memory laid out for the GPU, not for the file): two planes per matrix — int8 quants [rows][K] and fp32

@@ -15,7 +15,17 @@ __global__ __launch_bounds__(256) void k_quantize_q8(const float* __restrict__ s
         float m = 0.f;
 #pragma unroll
         for (int i = 0; i < 8; ++i) m = fmaxf(fmaxf(fmaxf(m, fabsf(v[i].x)), fabsf(v[i].y)), fmaxf(fabsf(v[i].z), fabsf(v[i].w)));
-        const float d = __fdiv_rn(m, 127.0f);
+        // A block that holds a NaN or an infinity: scale NaN and quants 0 (d > 0 is false below), so the whole block dequantises to NaN.  (fmaxf drops a
+        // NaN from the maximum, and fminf(fmaxf(NaN, -127), 127) is -127: without this a NaN weight would come back as the finite -max|w|.)
+        // Every block pays the scan (32 exponent tests and one select); the arithmetic of a finite block - maximum, divide, rint, clamp - is as it was.
+        bool nonfinite = false;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float f[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) nonfinite |= (__builtin_bit_cast(uint32_t, f[k]) & 0x7f800000u) == 0x7f800000u;
+        }
+        const float d = nonfinite ? __builtin_nanf("") : __fdiv_rn(m, 127.0f);
         unsigned int packed[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
