@@ -92,6 +92,15 @@ int llamago_DraftLookup(const uint32_t* window, uint32_t n_window, const lh_look
 int llamago_Verify(llama_context* c, const uint32_t* tokens, uint32_t n, uint32_t past, uint32_t* ids_out, uint32_t* n_accepted, float* logits);
 int llamago_DecodeLookup(llama_context* c, uint32_t first_token, uint32_t past, uint32_t n_steps, const lh_lookup_params* lp, uint32_t* out_tokens,
                          float* logits_last, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap);
+/* The same for sampled generation (lh_sample_rows, lh_llama_decode_sample_lookup; ring view, draw and commit per row are stated in llamahip.h).
+ * llamago_SampleRows: the multi-row sampler alone on host arrays, on the model context's device - row r of logits [n_rows][n_logits] sampled as
+ * call draw0 + r over the ring behind tokens[1..r].  llamago_SampleDecodeLookup: llama_SampleDecode through verify passes that sample every row -
+ * the same ids, the same state left behind; ring_size = 0 means ctxSize, the reference's ring (server.go:127). */
+int llamago_SampleRows(const float* logits, uint32_t n_rows, uint32_t n_logits, const uint32_t* ring, uint32_t ring_size, uint32_t ring_pos, const uint32_t* tokens,
+                       uint32_t topK, float topP, float temp, float repeatPenalty, uint64_t seed, uint64_t draw0, uint32_t* ids_out);
+int llamago_SampleDecodeLookup(llama_context* c, llama_model* m, const uint32_t* prompt, uint32_t n_prompt, uint32_t n_predict, uint32_t ring_size, uint32_t topK,
+                               float topP, float temp, float repeatPenalty, uint64_t seed, const lh_lookup_params* lp, uint32_t* out_tokens, lh_spec_stats* stats,
+                               uint16_t* trace, uint32_t trace_cap);
 
 /* ModelParams.Embedding (llama.go:52, 88): from now on every llama_Eval also leaves row N-1 of `embeddings` (the final norm * weight rows,
  * llama.go:381, 414-419) in lctx.Embedding; llama_Embedding (llamago.h) returns it ([embd] floats; NULL when not enabled).  On the GPU the fused plan

@@ -289,6 +289,33 @@ int lh_llama_verify(lh_llama* m, const uint32_t* tokens, uint32_t n, uint32_t pa
 int lh_llama_decode_lookup(lh_llama* m, uint32_t first_token, uint32_t past, uint32_t n_steps, const lh_lookup_params* lp,
                            uint32_t* out_tokens, float* logits_last_host, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap);
 
+/* ---- lossless lookup-draft speculative decoding (sampled) ------------------------------------------------------------
+ * The uniforms of the device sampler are counter-based (seed, sampling call, rank), so the id of sampling call s is a pure function of the
+ * logits row, the lastNTokens ring at that moment and s.  A pass over [pending, d1..dk] therefore samples every row at once, and the kept ids
+ * are EXACTLY those of lh_llama_decode_sample - an equality, no rejection sampling.  The rule, with the sampler state {ring, ring_pos = ids
+ * appended so far (next slot = ring_pos % ring_size), draw = index of the next sampling call} in front of the pass:
+ *   ring view of row r: the ring after tok[1..r] were appended in order, ring[(ring_pos + j) % ring_size] = tok[j+1] for j = 0..r-1 (a slot
+ *                        may be overwritten more than once when ring_size < r); the ring itself is not written by the sampler;
+ *   draw of row r:       draw + r;  id of row r -> arg[r];
+ *   commit:              a = the leading i < min(k, R - 1) with arg[i] == tok[i+1] (clipped by the ids still asked for and by the window);
+ *                        arg[0..a] are appended to the ring in order, ring_pos += a + 1, draw += a + 1.
+ * lh_sample_rows is the op-level twin of the multi-row sampler kernels (k_sample_rows, topK <= 1024; k_sample_small_rows, topK <= 64), like
+ * lh_argmax_rows / lh_score_rows: host logits [n_rows][n_logits] packed, ring_host[0..ring_size) with ring_pos, tokens_host[0] ignored (the
+ * pending token is in the ring already), tokens_host[1..n_rows) the draft; ONE launch, ids_out[r] = the id of row r as sampling call
+ * draw0 + r.  Refused with nothing enqueued: n_rows outside 1..8, ring_size == 0, a draft id >= n_logits, bad sampler parameters, a null
+ * argument (LH_EINVAL); n_logits outside 1..65536 (LH_ESHAPE); topK above 1024 (LH_EUNSUPPORTED). */
+int lh_sample_rows(lh_ctx* ctx, const float* logits_host, uint32_t n_rows, uint32_t n_logits, const uint32_t* ring_host, uint32_t ring_size,
+                   uint32_t ring_pos, const uint32_t* tokens_host, const lh_sample_params* sp, uint64_t draw0, uint32_t* ids_out);
+/* lh_llama_decode_sample through verify passes drafted by the lookup rule above: the same ring, prompt Eval and first sample on the last
+ * prompt row, then the n_predict - 1 remaining ids from passes of R = draft_max + 1 rows (lowered as in lh_llama_decode_lookup; R = 1 = plain
+ * sampled steps) that sample every row and commit by the rule above.  out_tokens = exactly the n_predict ids of lh_llama_decode_sample with
+ * the same arguments, and the context is left as that call leaves it (position, history, ring, draw counter, context swaps).  stats / trace
+ * as lh_llama_decode_lookup, over the passes behind the first sample.  Refused before anything is enqueued: everything lh_llama_decode_sample
+ * and lh_llama_decode_lookup refuse (LH_EINVAL); a layer-shard stage (LH_EUNSUPPORTED). */
+int lh_llama_decode_sample_lookup(lh_llama* m, const uint32_t* prompt, uint32_t n_prompt, uint32_t n_predict, uint32_t ring_size,
+                                  const lh_sample_params* sp, const lh_lookup_params* lp, uint32_t* out_tokens, lh_spec_stats* stats,
+                                  uint16_t* trace, uint32_t trace_cap);
+
 /* ---- pods in ONE weight pass (batched decode) ---------------------------------------------------------------------
  * The reference's only parallelism is request-level: Engine() starts up to MaxPods concurrent Do() goroutines
  * (pkg/server/server.go:84-106), each with its own llama.Context over the shared Model (server.go:151).  On the CPU they share

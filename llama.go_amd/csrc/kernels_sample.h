@@ -26,6 +26,9 @@
 //     with ballot/popcount counts.  (Measured at V = 32000: bisection over all elements costs 32 rounds x 32 elements x 16
 //     waves of VALU work on ONE CU = 30 us; this path does one such round.)
 //   k_sample (topK <= 1024): block-wide counts (one barrier per bisection round), LDS-resident candidates.
+//   k_sample_rows / k_sample_small_rows: the same two bodies over the R rows of a verify pass in one launch, one workgroup per row, row r as
+//     sampling call draw + r over the ring as if the draft in front of it had been appended (ring_bitmap<true>); the speculative sampled loop
+//     (include/llamahip.h, lh_llama_decode_sample_lookup).
 #pragma once
 #include "kernels_common.h"
 
@@ -97,10 +100,34 @@ __device__ __forceinline__ void load_keys(uint32_t (&key)[EPT], const float* __r
     }
 }
 
-template <int EPT>
-__global__ __launch_bounds__(1024) void k_sample(const float* __restrict__ logits, uint32_t V, SampleState* st, uint32_t* __restrict__ ring, StepParams* sp,
-                                                 uint32_t* __restrict__ out_tokens, uint32_t* __restrict__ token_out, uint32_t* __restrict__ dbg_ids,
-                                                 float* __restrict__ dbg_probs, uint32_t* __restrict__ dbg_keep, int advance) {
+// Membership bits of the lastNTokens ring (bitmap zeroed and fenced by the caller; the caller fences again before it reads).
+// ROWS: the view of row `row` of a verify pass - the ring as if tok[1..row] had been appended in order behind its ring_pos ids, without
+// writing it: a slot one of those appends overwrites is skipped, and every append that is the LAST writer of its slot (append j is, when
+// j + ring_size >= row) adds its id.  row > ring_size overwrites slots more than once; ring_pos < ring_size leaves initial zeros in place.
+template <bool ROWS>
+__device__ __forceinline__ void ring_bitmap(uint32_t* bitmap, const uint32_t* __restrict__ ring, uint32_t ring_size, uint32_t ring_pos, uint32_t V,
+                                            const uint32_t* __restrict__ tok, uint32_t row, int tid) {
+    const uint32_t base = (ROWS && ring_size) ? ring_pos % ring_size : 0u;
+    for (uint32_t r = tid; r < ring_size; r += 1024) {
+        if (ROWS) {
+            const uint32_t d = r >= base ? r - base : r + ring_size - base;  // appends behind ring_pos that reach slot r first: d < row overwrites it
+            if (d < row) continue;
+        }
+        const uint32_t t = ring[r];
+        if (t < V) atomicOr(&bitmap[t >> 5], 1u << (t & 31));
+    }
+    if (ROWS && (uint32_t)tid < row && (uint32_t)tid + ring_size >= row) {
+        const uint32_t t = tok[tid + 1];
+        if (t < V) atomicOr(&bitmap[t >> 5], 1u << (t & 31));
+    }
+}
+
+// The body of k_sample / k_sample_rows.  ROWS: sampling call st->draw + row over the ring view of that row (ring_bitmap over dtok = the pass's tokens); the caller passes advance = 0.
+template <int EPT, bool ROWS>
+__device__ __forceinline__ void sample_body(const float* __restrict__ logits, uint32_t V, SampleState* st, uint32_t* __restrict__ ring, StepParams* sp,
+                                            uint32_t* __restrict__ out_tokens, uint32_t* __restrict__ token_out, uint32_t* __restrict__ dbg_ids,
+                                            float* __restrict__ dbg_probs, uint32_t* __restrict__ dbg_keep, int advance, const uint32_t* __restrict__ dtok,
+                                            uint32_t row) {
     __shared__ uint32_t bitmap[EPT * 32];  // V <= EPT * 1024 bits
     __shared__ uint32_t cnt[32];
     __shared__ uint32_t cand_key[SAMPLE_MAX_K], cand_idx[SAMPLE_MAX_K], s_idx[SAMPLE_MAX_K];
@@ -115,16 +142,13 @@ __global__ __launch_bounds__(1024) void k_sample(const float* __restrict__ logit
     const float top_p = st->top_p, pen = st->repeat_penalty;
     const float scale = __fdiv_rn(1.0f, st->temp);  // llama.go:497: float32(1.0 / temp) with temp float32 = one fp32 divide
     const uint32_t ring_size = st->ring_size;
-    const uint64_t seed = st->seed, draw = st->draw;
+    const uint64_t seed = st->seed, draw = st->draw + (ROWS ? row : 0u);
     int phase = 0;
 
     for (uint32_t w = tid; w < EPT * 32; w += 1024) bitmap[w] = 0;
     if (tid == 0) ncand = 0;
     __syncthreads();
-    for (uint32_t r = tid; r < ring_size; r += 1024) {
-        const uint32_t t = ring[r];
-        if (t < V) atomicOr(&bitmap[t >> 5], 1u << (t & 31));
-    }
+    ring_bitmap<ROWS>(bitmap, ring, ring_size, ROWS ? st->ring_pos : 0u, V, dtok, row, tid);
     __syncthreads();
 
     uint32_t key[EPT];
@@ -240,6 +264,25 @@ __global__ __launch_bounds__(1024) void k_sample(const float* __restrict__ logit
     }
 }
 
+template <int EPT>
+__global__ __launch_bounds__(1024) void k_sample(const float* __restrict__ logits, uint32_t V, SampleState* st, uint32_t* __restrict__ ring, StepParams* sp,
+                                                 uint32_t* __restrict__ out_tokens, uint32_t* __restrict__ token_out, uint32_t* __restrict__ dbg_ids,
+                                                 float* __restrict__ dbg_probs, uint32_t* __restrict__ dbg_keep, int advance) {
+    sample_body<EPT, false>(logits, V, st, ring, sp, out_tokens, token_out, dbg_ids, dbg_probs, dbg_keep, advance, nullptr, 0u);
+}
+
+// The sampler over the R rows of a verify pass [pending, d1..dk, filler] in ONE launch, workgroup r = row r (include/llamahip.h, lh_sample_rows): logits
+// row r, the ring as if tok[1..r] had been appended, sampling call st->draw + r; the id goes to arg[r].  Nothing else is written - ring, state and step
+// parameters are committed by the accept step (kernels_spec.h) once the accepted count is known.  n_draft (optional) = the draft length k of the
+// pass: rows behind the draft are filler the accept step never reads, and return at once.
+template <int EPT>
+__global__ __launch_bounds__(1024) void k_sample_rows(const float* __restrict__ logits, uint32_t V, SampleState* st, uint32_t* __restrict__ ring,
+                                                      const uint32_t* __restrict__ tok, const uint32_t* __restrict__ n_draft, uint32_t* __restrict__ arg) {
+    const uint32_t row = blockIdx.x;
+    if (n_draft && row > *n_draft) return;
+    sample_body<EPT, true>(logits + (size_t)row * V, V, st, ring, nullptr, nullptr, arg + row, nullptr, nullptr, nullptr, 0, tok, row);
+}
+
 
 // ---- topK <= 64 -----------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t lanes_below(uint64_t m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }
@@ -300,10 +343,12 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
 // Element e of thread t is token id 4 (t + 1024 (e / 4)) + e % 4: four consecutive ids per 16-byte load.
 __device__ __forceinline__ uint32_t small_id(int tid, int e) { return 4u * ((uint32_t)tid + 1024u * (uint32_t)(e >> 2)) + (uint32_t)(e & 3); }
 
-template <int EPT>
-__global__ __launch_bounds__(1024) void k_sample_small(const float* __restrict__ logits, uint32_t V, SampleState* st, uint32_t* __restrict__ ring, StepParams* sp,
-                                                       uint32_t* __restrict__ out_tokens, uint32_t* __restrict__ token_out, uint32_t* __restrict__ dbg_ids,
-                                                       float* __restrict__ dbg_probs, uint32_t* __restrict__ dbg_keep, int advance) {
+// The body of k_sample_small / k_sample_small_rows (ROWS as in sample_body).
+template <int EPT, bool ROWS>
+__device__ __forceinline__ void sample_small_body(const float* __restrict__ logits, uint32_t V, SampleState* st, uint32_t* __restrict__ ring, StepParams* sp,
+                                                  uint32_t* __restrict__ out_tokens, uint32_t* __restrict__ token_out, uint32_t* __restrict__ dbg_ids,
+                                                  float* __restrict__ dbg_probs, uint32_t* __restrict__ dbg_keep, int advance, const uint32_t* __restrict__ dtok,
+                                                  uint32_t row) {
     __shared__ uint32_t bitmap[EPT * 32];
     __shared__ __attribute__((aligned(16))) uint64_t surv[1024 + 8];  // a superset of the top-K, unordered: key << 32 | ~id (bigger = better)
     __shared__ uint32_t win_key[64], win_idx[64];        // the K winners in rank order
@@ -333,10 +378,7 @@ __global__ __launch_bounds__(1024) void k_sample_small(const float* __restrict__
     for (uint32_t w = tid; w < EPT * 32; w += 1024) bitmap[w] = 0;
     if (tid == 0) n_surv = 0;
     __syncthreads();
-    for (uint32_t r = tid; r < ring_size; r += 1024) {
-        const uint32_t t = ring[r];
-        if (t < V) atomicOr(&bitmap[t >> 5], 1u << (t & 31));
-    }
+    ring_bitmap<ROWS>(bitmap, ring, ring_size, ROWS ? st->ring_pos : 0u, V, dtok, row, tid);
     __syncthreads();
 
     uint32_t key[EPT];
@@ -458,7 +500,7 @@ __global__ __launch_bounds__(1024) void k_sample_small(const float* __restrict__
     if ((uint32_t)lane < keep) {
         if (dbg_probs) dbg_probs[lane] = p;
         if (dbg_ids) dbg_ids[lane] = si;
-        const float f = sample_uniform(st->seed, st->draw, (uint32_t)lane);
+        const float f = sample_uniform(st->seed, st->draw + (ROWS ? row : 0u), (uint32_t)lane);
         wv = __fmul_rn(__fmul_rn(__fmul_rn(p, p), f), f);
         wi = (uint32_t)lane;
     }
@@ -482,6 +524,22 @@ __global__ __launch_bounds__(1024) void k_sample_small(const float* __restrict__
             sp->step += 1;
         }
     }
+}
+
+template <int EPT>
+__global__ __launch_bounds__(1024) void k_sample_small(const float* __restrict__ logits, uint32_t V, SampleState* st, uint32_t* __restrict__ ring, StepParams* sp,
+                                                       uint32_t* __restrict__ out_tokens, uint32_t* __restrict__ token_out, uint32_t* __restrict__ dbg_ids,
+                                                       float* __restrict__ dbg_probs, uint32_t* __restrict__ dbg_keep, int advance) {
+    sample_small_body<EPT, false>(logits, V, st, ring, sp, out_tokens, token_out, dbg_ids, dbg_probs, dbg_keep, advance, nullptr, 0u);
+}
+
+// k_sample_rows for topK <= 64.  A row that is not 16-byte aligned (V % 4 != 0) takes the body's 4-byte loads.
+template <int EPT>
+__global__ __launch_bounds__(1024) void k_sample_small_rows(const float* __restrict__ logits, uint32_t V, SampleState* st, uint32_t* __restrict__ ring,
+                                                            const uint32_t* __restrict__ tok, const uint32_t* __restrict__ n_draft, uint32_t* __restrict__ arg) {
+    const uint32_t row = blockIdx.x;
+    if (n_draft && row > *n_draft) return;
+    sample_small_body<EPT, true>(logits + (size_t)row * V, V, st, ring, nullptr, nullptr, arg + row, nullptr, nullptr, nullptr, 0, tok, row);
 }
 
 }  // namespace lh

@@ -1,10 +1,11 @@
-// csrc/kernels_spec.h — lookup-draft speculative decoding (greedy, lossless): the n-gram drafter and the accept step on the device.
+// csrc/kernels_spec.h — lookup-draft speculative decoding (greedy and sampled, lossless): the n-gram drafter and the accept step on the device.
 // A pass evaluates [pending, d1..dk] (+ filler rows up to a fixed row count) as one multi-row pass of the stream's own cache (kernels_rows.h:
-// every row bit-identical to its solo one-token step); k_batch_argmax takes the rows' greedy ids; k_spec_accept keeps the longest prefix of the
+// every row bit-identical to its solo one-token step); k_batch_argmax takes the rows' greedy ids (sampled route: k_sample_rows the rows' sampled ids); k_spec_accept keeps the longest prefix of the
 // draft the model itself produced, moves the row table on by the accepted count and drafts for the next pass.  The rule is stated in
 // include/llamahip.h (lh_lookup_params) and restated in tests/speculative_ref.py.
 #pragma once
 #include "kernels_common.h"
+#include "kernels_sample.h"
 
 namespace lh {
 
@@ -133,9 +134,13 @@ __global__ void k_spec_set(SpecState* st, BatchRow* rows, uint32_t* tok, StepPar
 // counts); ids arg[0..a] go to the output list and the window; arg[a] is the next pending token; the table's n_rows positions become p + a + 1 ..;
 // counters and trace; then (lookup_next) the draft of the next pass.  One workgroup.  Every index it writes is clamped to its buffer: the host never
 // launches a pass that needs the clamp, and a mistake there must not write outside the cache or the lists.
+// ss != nullptr: the sampled route - arg[] are the ids of k_sample_rows / k_sample_small_rows (row i sampled as call ss->draw + i over the ring behind
+// tok[1..i]), so arg[0..a] are the ids of a + 1 consecutive one-token sampling calls; they are appended to the ring in order and ring_pos and draw
+// move on by a + 1.  ss == nullptr: the greedy route, nothing of this.
 __global__ __launch_bounds__(SPEC_TH) void k_spec_accept(const uint32_t* __restrict__ arg, uint32_t R, SpecState* st, BatchRow* rows, uint32_t* tok, StepParams* sp,
                                                          uint32_t* __restrict__ win, uint32_t ctx, uint32_t vocab, uint32_t* __restrict__ out,
-                                                         uint16_t* __restrict__ trace, uint32_t trace_cap, const SpecLookup lp, uint32_t n_rows, int lookup_next) {
+                                                         uint16_t* __restrict__ trace, uint32_t trace_cap, const SpecLookup lp, uint32_t n_rows, int lookup_next,
+                                                         SampleState* ss, uint32_t* __restrict__ ring) {
     __shared__ int s_best;
     __shared__ uint32_t s_pos, s_done;
     if (threadIdx.x == 0) {
@@ -149,6 +154,11 @@ __global__ __launch_bounds__(SPEC_TH) void k_spec_accept(const uint32_t* __restr
             if (a > n_steps - produced - 1) a = n_steps - produced - 1;
             if (a > ctx - 1 - p) a = ctx - 1 - p;
             for (uint32_t i = 0; i <= a; ++i) { out[produced + i] = arg[i]; win[p + 1 + i] = arg[i]; }   // win has ctx + 1 entries
+            if (ss) {
+                const uint32_t rs = ss->ring_size, rp = ss->ring_pos;
+                if (rs) for (uint32_t i = 0; i <= a; ++i) ring[(rp + i) % rs] = arg[i];   // appendToken (server.go:205) per accepted id, in order
+                ss->ring_pos = rp + a + 1; ss->draw += a + 1;
+            }
             const uint32_t s = st->passes;
             if (trace && s < trace_cap) trace[s] = (uint16_t)((k << 8) | a);
             st->passes = s + 1; st->drafted += k; st->accepted += a; st->empty += k == 0 ? 1u : 0u;

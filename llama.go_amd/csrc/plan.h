@@ -133,6 +133,9 @@ void destroy_plans(lh_ctx* ctx);
 int sample_check(lh_ctx* ctx, const lh_sample_params* sp, uint32_t V);
 int sample_launch(lh_ctx* ctx, const float* logits, uint32_t V, SampleState* st, uint32_t* ring, StepParams* sp, uint32_t* out_tokens, uint32_t* token_out,
                   uint32_t* dbg_ids, float* dbg_probs, uint32_t* dbg_keep, int advance, uint32_t topk_hint);
+// the rows of a verify pass in one launch (k_sample_rows / k_sample_small_rows): ids to arg[0..n_rows), nothing else written
+int sample_rows_launch(lh_ctx* ctx, const float* logits, uint32_t V, uint32_t n_rows, SampleState* st, uint32_t* ring, const uint32_t* tok, const uint32_t* n_draft,
+                       uint32_t* arg, uint32_t topk_hint);
 
 // score.hip
 int score_launch(lh_ctx* ctx, const float* logits, uint32_t n, uint32_t V, const uint32_t* targets, lh_row_score* out);

@@ -2549,6 +2549,8 @@ static int batch_feed(Batch* b, const uint32_t* const* tokens, const uint32_t* n
 // A pass = the batched plan_eval over a row table whose R rows all name THIS plan's cache at consecutive positions (a causal chunk, as a fed
 // prompt chunk of lh_batch_feed), k_batch_argmax over the R logits rows, k_spec_accept.  Everything a pass depends on lives in device memory, and
 // on the row-table route the attention launches are sized by the window, so a pass is captured once and replayed.
+// The sampled route (lh_llama_decode_sample_lookup) differs in two launches: k_sample_rows / k_sample_small_rows instead of k_batch_argmax, and
+// the accept step commits the plan's ring and draw counter (ss_dev / ring_dev); its ids land behind the first sample, at out_tokens_dev + 1.
 struct Spec {
     SpecState* st = nullptr;
     StepParams* sp = nullptr;          // {pending token, its position}: what the one-row pass at the window's end reads
@@ -2561,6 +2563,7 @@ struct Spec {
     uint16_t* trace = nullptr;
     uint32_t trace_cap = 0;
     float* part = nullptr;             // split-T attention partials for SPEC_ROWS_MAX rows (plans with ctx > 256)
+    bool smp = false;                  // the passes sample (set by the entry points before they enqueue a pass)
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     // what the captured pass holds by value
@@ -2569,6 +2572,8 @@ struct Spec {
     uint32_t* cap_out = nullptr;
     uint16_t* cap_trace = nullptr;
     uint64_t cap_splitk_gen = 0, cap_scratch_gen = 0;
+    bool cap_smp = false, cap_smp_small = false;   // sampled route: the kernel variant (topK <= 64 or not) and the ring pointer
+    uint32_t* cap_ring = nullptr;
     uint32_t warm = 0;                 // bit R: a pass of R rows has run eagerly (it sets kernel attributes a capture must not)
 };
 static void spec_drop_graph(Spec* s) {
@@ -2622,6 +2627,8 @@ static uint32_t spec_pass_rows(const Plan* p, uint32_t want) {
     while (n > 1 && !rows_path_ok(p->ctx, p->md, n)) --n;
     return std::max(n, 1u);
 }
+// where the accept step's output list starts: the sampled loop's first id (the sample behind the prompt) is entry 0 of out_tokens_dev
+static uint32_t* spec_out(const Plan* p) { return p->out_tokens_dev + (p->spec->smp ? 1 : 0); }
 // the kernels of one pass of n rows, in stream order (n_table = rows of the table the accept step moves on)
 static int spec_enqueue_pass(Plan* p, uint32_t n, uint32_t n_table, const SpecLookup& lp, int lookup_next) {
     lh_ctx* ctx = p->ctx;
@@ -2634,10 +2641,14 @@ static int spec_enqueue_pass(Plan* p, uint32_t n, uint32_t n_table, const SpecLo
         BatchCtx bc = {s->rows, s->tok, p->attn_part ? s->part : nullptr};
         if ((rc = plan_eval(p, nullptr, nullptr, nullptr, n, 0, false, &bc))) return rc;
     }
-    LH_LAUNCH(k_batch_argmax, dim3(n), dim3(1024), 0, ctx->stream, (const float*)p->logits, m.V, (BatchRow*)nullptr, (uint32_t*)nullptr, s->arg, (uint32_t*)nullptr, 0u,
-              (StepParams*)nullptr, 0);
-    LH_LAUNCH(k_spec_accept, dim3(1), dim3(SPEC_TH), 0, ctx->stream, (const uint32_t*)s->arg, n, s->st, s->rows, s->tok, s->sp, s->win, m.ctx, m.V, p->out_tokens_dev, s->trace,
-              s->trace_cap, lp, n_table, lookup_next);
+    if (s->smp) {
+        if ((rc = sample_rows_launch(ctx, p->logits, m.V, n, p->ss_dev, p->ring_dev, s->tok, &s->st->k, s->arg, p->smp_topk))) return rc;
+    } else {
+        LH_LAUNCH(k_batch_argmax, dim3(n), dim3(1024), 0, ctx->stream, (const float*)p->logits, m.V, (BatchRow*)nullptr, (uint32_t*)nullptr, s->arg, (uint32_t*)nullptr, 0u,
+                  (StepParams*)nullptr, 0);
+    }
+    LH_LAUNCH(k_spec_accept, dim3(1), dim3(SPEC_TH), 0, ctx->stream, (const uint32_t*)s->arg, n, s->st, s->rows, s->tok, s->sp, s->win, m.ctx, m.V, spec_out(p), s->trace,
+              s->trace_cap, lp, n_table, lookup_next, s->smp ? p->ss_dev : (SampleState*)nullptr, s->smp ? p->ring_dev : (uint32_t*)nullptr);
     LH_HIP(ctx, hipGetLastError());
     return 0;
 }
@@ -2649,8 +2660,11 @@ static int spec_pass(Plan* p, uint32_t R, const SpecLookup& lp) {
         s->warm |= 1u << R;
         return spec_enqueue_pass(p, R, R, lp, 1);
     }
-    if (s->exec && (s->cap_R != R || memcmp(&s->cap_lp, &lp, sizeof lp) || s->cap_out != p->out_tokens_dev || s->cap_trace != s->trace || s->cap_trace_cap != s->trace_cap ||
-                    s->cap_splitk_gen != ctx->splitk_gen || s->cap_scratch_gen != p->scratch_gen))
+    const bool smp_small = s->smp && p->smp_topk <= 64;
+    uint32_t* const ring = s->smp ? p->ring_dev : nullptr;
+    if (s->exec && (s->cap_R != R || memcmp(&s->cap_lp, &lp, sizeof lp) || s->cap_out != spec_out(p) || s->cap_trace != s->trace || s->cap_trace_cap != s->trace_cap ||
+                    s->cap_splitk_gen != ctx->splitk_gen || s->cap_scratch_gen != p->scratch_gen || s->cap_smp != s->smp || s->cap_smp_small != smp_small ||
+                    s->cap_ring != ring))
         spec_drop_graph(s);
     if (!s->exec) {
         LH_HIP(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeRelaxed));
@@ -2659,8 +2673,9 @@ static int spec_pass(Plan* p, uint32_t R, const SpecLookup& lp) {
         if (rc) { if (s->graph) { hipGraphDestroy(s->graph); s->graph = nullptr; } return rc; }
         if (e != hipSuccess) LH_FAIL(ctx, LH_EHIP, "hipStreamEndCapture (speculative pass): %s", hipGetErrorString(e));
         LH_HIP(ctx, hipGraphInstantiate(&s->exec, s->graph, nullptr, nullptr, 0));
-        s->cap_R = R; s->cap_lp = lp; s->cap_out = p->out_tokens_dev; s->cap_trace = s->trace; s->cap_trace_cap = s->trace_cap;
+        s->cap_R = R; s->cap_lp = lp; s->cap_out = spec_out(p); s->cap_trace = s->trace; s->cap_trace_cap = s->trace_cap;
         s->cap_splitk_gen = ctx->splitk_gen; s->cap_scratch_gen = p->scratch_gen;
+        s->cap_smp = s->smp; s->cap_smp_small = smp_small; s->cap_ring = ring;
     }
     LH_HIP(ctx, hipGraphLaunch(s->exec, ctx->stream));
     return 0;
@@ -2697,16 +2712,19 @@ static int spec_check_params(lh_ctx* ctx, const ModelDesc& md, const lh_lookup_p
     return 0;
 }
 
+// sampled: the passes sample (sampler state and ring = the plan's ss_dev / ring_dev, armed by the caller, whose first id is entry 0 of the device's
+// output list); the n_steps ids land behind it and out_tokens, when given, receives these n_steps ids.
 static int spec_decode_lookup(Plan* p, uint32_t first_token, uint32_t past, uint32_t n_steps, const lh_lookup_params* lpar, uint32_t R, uint32_t* out_tokens,
-                              float* logits_last_host, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap) {
+                              float* logits_last_host, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap, bool sampled = false) {
     lh_ctx* ctx = p->ctx;
     const ModelDesc& md = p->md;
     int rc;
     const uint32_t n_corpus = lpar->corpus ? lpar->n_corpus : 0;
     if ((rc = spec_ensure(p, n_corpus, n_steps))) return rc;
     if ((rc = plan_ensure_rows(p, R))) return rc;
-    if ((rc = ensure_out_tokens(p, n_steps))) return rc;
+    if ((rc = ensure_out_tokens(p, n_steps + (sampled ? 1 : 0)))) return rc;
     Spec* s = p->spec;
+    s->smp = sampled;
     if (n_corpus) {
         if ((rc = ensure_staging(ctx, (uint64_t)n_corpus * 4))) return rc;
         LH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // staging reuse
@@ -2766,7 +2784,7 @@ static int spec_decode_lookup(Plan* p, uint32_t first_token, uint32_t past, uint
         pos = hs.pos; produced = hs.produced;
     }
     if ((rc = learn(&pending))) return rc;
-    if (out_tokens) LH_HIP(ctx, hipMemcpyAsync(out_tokens, p->out_tokens_dev, (size_t)n_steps * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_tokens) LH_HIP(ctx, hipMemcpyAsync(out_tokens, spec_out(p), (size_t)n_steps * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (logits_last_host) LH_HIP(ctx, hipMemcpyAsync(logits_last_host, p->logits + (size_t)hs.last_a * md.V, (size_t)md.V * 4, hipMemcpyDeviceToHost, ctx->stream));
     std::vector<uint16_t> tr;
     const uint32_t n_tr = trace ? std::min(std::min(trace_cap, hs.passes), s->trace_cap) : 0;
@@ -3003,6 +3021,7 @@ int lh_llama_verify(lh_llama* m, const uint32_t* tokens, uint32_t n, uint32_t pa
     if ((rc = plan_ensure_rows(p, n))) return rc;
     if ((rc = ensure_out_tokens(p, n))) return rc;
     Spec* s = p->spec;
+    s->smp = false;
     SpecToks t = {};
     for (uint32_t i = 0; i < SPEC_ROWS_MAX; ++i) t.t[i] = tokens[i < n ? i : 0];
     if ((rc = spec_set(p, past, 0, n, t, n - 1, n, 1))) return rc;
@@ -3046,16 +3065,18 @@ int lh_llama_decode_lookup(lh_llama* m, uint32_t first_token, uint32_t past, uin
     return spec_decode_lookup(p, first_token, past, n_steps, lp, R, out_tokens, logits_last_host, stats, trace, trace_cap);
 }
 
-int lh_llama_decode_sample(lh_llama* m, const uint32_t* prompt, uint32_t n_prompt, uint32_t n_predict, uint32_t ring_size, const lh_sample_params* sp,
-                           uint32_t* out_tokens) {
-    if (!m) return LH_EINVAL;
+}  // extern "C"
+
+// lh_llama_decode_sample (lp == nullptr) and lh_llama_decode_sample_lookup (lp: checked by the caller, R >= 2 rows per pass): the same ring, prompt
+// Eval and first sample; the n_predict - 1 ids behind it by resident steps, or by verify passes that sample every row.
+static int decode_sample(lh_llama* m, const char* who, const uint32_t* prompt, uint32_t n_prompt, uint32_t n_predict, uint32_t ring_size, const lh_sample_params* sp,
+                         uint32_t* out_tokens, const lh_lookup_params* lp, uint32_t R, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap) {
     lh_ctx* ctx = m->ctx;
     Plan* p = m->plan;
     const ModelDesc& md = p->md;
-    LH_HIP(ctx, hipSetDevice(ctx->device));
-    if (!prompt || !n_prompt || !n_predict || !out_tokens) LH_FAIL(ctx, LH_EINVAL, "lh_llama_decode_sample: empty prompt, no tokens to predict or null output");
-    if (!md.first_stage() || !md.last_stage()) LH_FAIL(ctx, LH_EINVAL, "lh_llama_decode_sample needs a whole-model plan");
-    if (ring_size == 0) LH_FAIL(ctx, LH_EINVAL, "lh_llama_decode_sample: the lastNTokens ring needs at least one slot (the reference uses CtxSize, server.go:127)");
+    if (!prompt || !n_prompt || !n_predict || !out_tokens) LH_FAIL(ctx, LH_EINVAL, "%s: empty prompt, no tokens to predict or null output", who);
+    if (!md.first_stage() || !md.last_stage()) LH_FAIL(ctx, LH_EINVAL, "%s needs a whole-model plan", who);
+    if (ring_size == 0) LH_FAIL(ctx, LH_EINVAL, "%s: the lastNTokens ring needs at least one slot (the reference uses CtxSize, server.go:127)", who);
     if (n_prompt > md.ctx) LH_FAIL(ctx, LH_EINVAL, "decode: a prompt of %u tokens exceeds the context window of %u", n_prompt, md.ctx);
     int rc;
     if ((rc = sample_check(ctx, sp, md.V))) return rc;
@@ -3089,15 +3110,55 @@ int lh_llama_decode_sample(lh_llama* m, const uint32_t* prompt, uint32_t n_promp
     if ((rc = upload_step_params(p, 0, 0, n_prompt - 1, 0))) return rc;
     const float* last_row = n_prompt == 1 ? p->logits : p->logits + (size_t)(n_prompt - 1) * md.V;
     if ((rc = sample_launch(ctx, last_row, md.V, p->ss_dev, p->ring_dev, p->sp_dev, p->out_tokens_dev, nullptr, nullptr, nullptr, nullptr, 1, p->smp_topk))) return rc;
-    if (n_predict > 1) {
+    if (n_predict > 1 && lp) {
+        // the passes need the pending token on the host (window upload, first draft): one look per generation, then the loop of spec_decode_lookup
+        // with this plan's sampler state; its ids land behind the first one
+        uint32_t first = 0;
+        LH_HIP(ctx, hipMemcpyAsync(&first, p->out_tokens_dev, 4, hipMemcpyDeviceToHost, ctx->stream));
+        LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if ((rc = spec_decode_lookup(p, first, n_prompt, n_predict - 1, lp, R, nullptr, nullptr, stats, trace, trace_cap, /*sampled=*/true))) return rc;
+    } else if (n_predict > 1) {
         // the first id (entry 0 of the output list) is the first token the resident steps evaluate; past the window the loop swaps context
         // (server.go:160-172)
         uint32_t past = n_prompt;
         if ((rc = resident_steps_swapping(p, 0, &past, 1, n_predict - 1, true, /*first_in_out=*/true))) return rc;
+    } else if (lp && stats) {
+        *stats = lh_spec_stats{0, R, 0, 0, 0};
     }
     LH_HIP(ctx, hipMemcpyAsync(out_tokens, p->out_tokens_dev, (size_t)n_predict * 4, hipMemcpyDeviceToHost, ctx->stream));
     LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return LH_OK;
+}
+
+extern "C" {
+
+int lh_llama_decode_sample(lh_llama* m, const uint32_t* prompt, uint32_t n_prompt, uint32_t n_predict, uint32_t ring_size, const lh_sample_params* sp,
+                           uint32_t* out_tokens) {
+    if (!m) return LH_EINVAL;
+    LH_HIP(m->ctx, hipSetDevice(m->ctx->device));
+    return decode_sample(m, "lh_llama_decode_sample", prompt, n_prompt, n_predict, ring_size, sp, out_tokens, nullptr, 1, nullptr, nullptr, 0);
+}
+
+int lh_llama_decode_sample_lookup(lh_llama* m, const uint32_t* prompt, uint32_t n_prompt, uint32_t n_predict, uint32_t ring_size, const lh_sample_params* sp,
+                                  const lh_lookup_params* lp, uint32_t* out_tokens, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap) {
+    if (!m) return LH_EINVAL;
+    lh_ctx* ctx = m->ctx;
+    Plan* p = m->plan;
+    const ModelDesc& md = p->md;
+    LH_HIP(ctx, hipSetDevice(ctx->device));
+    if (!md.first_stage() || !md.last_stage())
+        LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_llama_decode_sample_lookup needs a whole-model plan (layers [%u, %u) of %u)", md.layer0, md.layer1, md.L);
+    int rc;
+    if ((rc = spec_check_params(ctx, md, lp, "lh_llama_decode_sample_lookup"))) return rc;
+    const uint32_t R = spec_pass_rows(p, lp->draft_max + 1);
+    if (R == 1) {   // no multi-row pass on this plan's shapes: plain sampled steps, and the stats say so
+        if ((rc = decode_sample(m, "lh_llama_decode_sample_lookup", prompt, n_prompt, n_predict, ring_size, sp, out_tokens, nullptr, 1, nullptr, nullptr, 0))) return rc;
+        const uint32_t n = n_predict - 1;
+        if (stats) *stats = lh_spec_stats{n, 1, 0, 0, n};
+        if (trace) for (uint32_t i = 0; i < n && i < trace_cap; ++i) trace[i] = 0;
+        return LH_OK;
+    }
+    return decode_sample(m, "lh_llama_decode_sample_lookup", prompt, n_prompt, n_predict, ring_size, sp, out_tokens, lp, R, stats, trace, trace_cap);
 }
 
 int lh_llama_stage(lh_llama* m, const uint32_t* tokens, const uint32_t* tokens_dev, const float* x_in_dev, float* x_out_dev, uint32_t n, uint32_t past,

@@ -197,6 +197,32 @@ func (st *StageHIP) DecodeLookup(firstToken, pastCount, nSteps, draftMax, ngramM
 	return out, stats
 }
 
+// DecodeSampleLookup is the generation loop of server.Do (server.go:127-217: ring of ringSize zeros, prompt Eval, then sample -> append -> Eval)
+// through lookup-drafted verify passes that sample every row (lh_llama_decode_sample_lookup): row i of a pass is sampled as call draw + i over
+// the lastNTokens ring as if the draft in front of it had been appended, so the kept ids are exactly the nPredict ids of the one-token sampled
+// loop with the same seed.  ringSize = CtxSize in the reference (server.go:127).  C++ twin: llamago_SampleDecodeLookup.
+func (st *StageHIP) DecodeSampleLookup(prompt []uint32, nPredict, ringSize, topK uint32, topP, temp, repeatPenalty float32, seed uint64,
+	draftMax, ngramMax, ngramMin uint32, corpus []uint32) ([]uint32, SpecStatsHIP) {
+	out := make([]uint32, nPredict)
+	var stats SpecStatsHIP
+	sp := C.lh_sample_params{top_k: C.uint32_t(topK), top_p: C.float(topP), temp: C.float(temp), repeat_penalty: C.float(repeatPenalty), seed: C.uint64_t(seed)}
+	lp := C.lh_lookup_params{draft_max: C.uint32_t(draftMax), ngram_max: C.uint32_t(ngramMax), ngram_min: C.uint32_t(ngramMin)}
+	if len(corpus) > 0 { // through C memory: a struct handed to C must not contain Go pointers
+		n := len(corpus)
+		cc := (*[1 << 28]C.uint32_t)(C.malloc(C.size_t(n) * 4))[:n:n]
+		defer C.free(unsafe.Pointer(&cc[0]))
+		for i, t := range corpus {
+			cc[i] = C.uint32_t(t)
+		}
+		lp.corpus, lp.n_corpus = &cc[0], C.uint32_t(n)
+	}
+	if rc := C.lh_llama_decode_sample_lookup(st.h, (*C.uint32_t)(unsafe.Pointer(&prompt[0])), C.uint32_t(len(prompt)), C.uint32_t(nPredict),
+		C.uint32_t(ringSize), &sp, &lp, (*C.uint32_t)(unsafe.Pointer(&out[0])), (*C.lh_spec_stats)(unsafe.Pointer(&stats)), nil, 0); rc != 0 {
+		hipHalt(st.ctx.hip.ctx)
+	}
+	return out, stats
+}
+
 // ---- the pods of ONE GPU in one weight pass (include/llamahip.h: lh_batch_*) --------------------------------------------
 // server.Engine starts up to MaxPods concurrent Do() goroutines over one Model (server.go:84-106, 151).  With UseHIP the engine
 // instead keeps ONE BatchHIP per GPU: every pod is a row; Prompt() evaluates the pods' prompts, each Tick() advances every pod by

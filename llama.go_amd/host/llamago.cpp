@@ -1228,6 +1228,25 @@ int llamago_DecodeLookup(llama_context* c, uint32_t first_token, uint32_t past, 
     if (lh_llama_decode_lookup(r, first_token, past, n_steps, lp, out_tokens, logits_last, stats, trace, trace_cap)) return halt_rc(lh_last_error(c->mlctx->hip));
     return 0;
 }
+int llamago_SampleRows(const float* logits, uint32_t n_rows, uint32_t n_logits, const uint32_t* ring, uint32_t ring_size, uint32_t ring_pos, const uint32_t* tokens,
+                       uint32_t topK, float topP, float temp, float repeatPenalty, uint64_t seed, uint64_t draw0, uint32_t* ids_out) {
+    lh_ctx* h = model_ctx();
+    if (!h) return 1;
+    const lh_sample_params sp = {topK, topP, temp, repeatPenalty, seed};
+    if (lh_sample_rows(h, logits, n_rows, n_logits, ring, ring_size, ring_pos, tokens, &sp, draw0, ids_out)) return halt_rc(lh_last_error(h));
+    return 0;
+}
+int llamago_SampleDecodeLookup(llama_context* c, llama_model* m, const uint32_t* prompt, uint32_t n_prompt, uint32_t n_predict, uint32_t ring_size, uint32_t topK,
+                               float topP, float temp, float repeatPenalty, uint64_t seed, const lh_lookup_params* lp, uint32_t* out_tokens, lh_spec_stats* stats,
+                               uint16_t* trace, uint32_t trace_cap) {
+    if (!c || c->model != m) return halt_rc("llamago_SampleDecodeLookup: context does not belong to this model");
+    lh_llama* r = resident(c);
+    if (!r) return 1;
+    const lh_sample_params sp = {topK, topP, temp, repeatPenalty, seed};
+    if (lh_llama_decode_sample_lookup(r, prompt, n_prompt, n_predict, ring_size ? ring_size : c->ctxSize, &sp, lp, out_tokens, stats, trace, trace_cap))
+        return halt_rc(lh_last_error(c->mlctx->hip));
+    return 0;
+}
 int llamago_Perplexity(llama_context* c, llama_model* m, const uint32_t* tokens, uint32_t n_tokens, uint32_t chunk, double* nll_sum, uint64_t* n_scored) {
     if (!c || c->model != m) return halt_rc("llamago_Perplexity: context does not belong to this model");
     if (!tokens || !nll_sum || !n_scored) return halt_rc("llamago_Perplexity: null argument");

@@ -414,6 +414,24 @@ class Context:
         stats = dict(passes=int(st.passes), rows=int(st.rows), drafted=int(st.drafted), accepted=int(st.accepted), empty=int(st.empty))
         return [int(t) for t in out[:n_steps]], lg, stats, [(int(v) >> 8, int(v) & 0xFF) for v in tr[:min(st.passes, n)]]
 
+    def SampleDecodeLookup(self, prompt, n_predict, draft_max, ngram_max=3, ngram_min=1, corpus=None, ring_size=0, topK=40, topP=0.95, temp=0.8,
+                           repeatPenalty=1.10, seed=0):
+        """llamago_SampleDecodeLookup: SampleDecode through lookup-drafted verify passes that sample every row (lh_llama_decode_sample_lookup);
+        ring_size = 0: the reference's ring of ctxSize ids.  -> (the n_predict ids of SampleDecode, stats dict, trace list of (k, a) per pass)."""
+        L = self.ml.lib
+        L.llamago_SampleDecodeLookup.restype = C.c_int
+        L.llamago_SampleDecodeLookup.argtypes = [VP, VP, c_u32p, c_u32, c_u32, c_u32, c_u32, C.c_float, C.c_float, C.c_float, c_u64, C.POINTER(LookupParams), c_u32p,
+                                                 C.POINTER(SpecStats), C.POINTER(C.c_uint16), c_u32]
+        lp, _keep = lookup_params(draft_max, ngram_max, ngram_min, corpus)
+        toks = (c_u32 * max(len(prompt), 1))(*[int(t) for t in prompt])
+        n = max(int(n_predict), 1)
+        out, st, tr = (c_u32 * n)(), SpecStats(), (C.c_uint16 * n)()
+        if L.llamago_SampleDecodeLookup(self.h, self.model.h, toks, len(prompt), int(n_predict), int(ring_size), int(topK), topP, temp, repeatPenalty, int(seed),
+                                        C.byref(lp), out, C.byref(st), tr, n):
+            raise MLError(f"llamago_SampleDecodeLookup: {self.ml.last_error()}")
+        stats = dict(passes=int(st.passes), rows=int(st.rows), drafted=int(st.drafted), accepted=int(st.accepted), empty=int(st.empty))
+        return [int(t) for t in out[:n_predict]], stats, [(int(v) >> 8, int(v) & 0xFF) for v in tr[:min(st.passes, n)]]
+
     def Perplexity(self, tokens, chunk=0):
         """llamago_Perplexity (convention: include/llamago_ext.h) -> (nll_sum, n_scored); perplexity = exp(nll_sum / n_scored)."""
         L = self.ml.lib
@@ -515,6 +533,26 @@ def argmax_rows(ml, logits, which):
     out = np.zeros(max(n, 1), dtype=np.uint32)
     if ml.lib.llamago_ArgmaxRows(lg.ctypes.data_as(c_f32p), n, V, int(which), out.ctypes.data_as(c_u32p)):
         raise MLError(f"llamago_ArgmaxRows: {ml.last_error()}")
+    return out[:n]
+
+
+def sample_rows(ml, logits, ring, ring_pos, tokens, topK=40, topP=0.95, temp=0.8, repeatPenalty=1.10, seed=0, draw0=0):
+    """llamago_SampleRows: the rows of a verify pass sampled in one launch (lh_sample_rows; k_sample_rows / k_sample_small_rows).  logits [n_rows][V];
+    ring = the lastNTokens ring with ring_pos ids appended so far; tokens[0] = the pending token (ignored), tokens[1..] the draft.  Row r is sampling
+    call draw0 + r over the ring as if tokens[1..r] had been appended.  -> uint32 array [n_rows]."""
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    if lg.ndim == 1:
+        lg = lg[None, :]
+    n, V = lg.shape
+    assert len(tokens) == n, (len(tokens), n)
+    ml.lib.llamago_SampleRows.restype = C.c_int
+    ml.lib.llamago_SampleRows.argtypes = [c_f32p, c_u32, c_u32, c_u32p, c_u32, c_u32, c_u32p, c_u32, C.c_float, C.c_float, C.c_float, c_u64, c_u64, c_u32p]
+    rg = (c_u32 * max(len(ring), 1))(*[int(t) for t in ring])
+    tk = (c_u32 * max(n, 1))(*[int(t) for t in tokens])
+    out = np.zeros(max(n, 8), dtype=np.uint32)
+    if ml.lib.llamago_SampleRows(lg.ctypes.data_as(c_f32p), n, V, rg, len(ring), int(ring_pos), tk, int(topK), topP, temp, repeatPenalty, int(seed), int(draw0),
+                                 out.ctypes.data_as(c_u32p)):
+        raise MLError(f"llamago_SampleRows: {ml.last_error()}")
     return out[:n]
 
 

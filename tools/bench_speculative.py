@@ -6,7 +6,10 @@ rates here are those of a replayed or a random text, never a model result.
           same positions in the same process (existing code), and against the one-token resident step
   golden  the 7B golden workload (8-token prompt, ctx 128, 99 ids): the loop with the replay corpus (acceptance 1: the ceiling), without a corpus
           (the honest side), and lh_llama_decode_greedy, tokens/s each; the break-even mean of accepted ids per pass from the measured times
-usage: python tools/bench_speculative.py [pass golden] [--layers 32] [--reps 5] [--int8] [--out profiles/speculative.txt]"""
+  --sample  the sampled route instead (lh_llama_decode_sample_lookup; results: profiles/sample_lookup.txt): the golden prompt, ctx 128, 100 sampled ids
+          (topK 40, topP 0.95, temp 0.8, penalty 1.1): an R-row sampled pass against one plain sampled step of SampleDecode (prompt Eval and first
+          sample taken off both by a 1-id call), the loop with the replay corpus (the ceiling) and without one, the break-even acceptance
+usage: python tools/bench_speculative.py [pass golden] [--sample] [--layers 32] [--reps 5] [--int8] [--out profiles/speculative.txt]"""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -18,6 +21,7 @@ ap.add_argument("parts", nargs="*", default=["pass", "golden"])
 ap.add_argument("--layers", type=int, default=32)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--int8", action="store_true", help="block-int8 weights too")
+ap.add_argument("--sample", action="store_true", help="the sampled route (SampleDecodeLookup against SampleDecode) instead of the greedy parts")
 ap.add_argument("--out", default=None, help="append the result lines to this file")
 args = ap.parse_args()
 prod = load_product()
@@ -50,6 +54,37 @@ def prompt_state(m, ctx, prompt):
     c = m.NewContext(ctx, 1)
     return c, int(np.argmax(c.Eval(prompt, 0)))
 
+
+if args.sample:
+    args.parts = []
+    SMP = dict(topK=40, topP=0.95, temp=0.8, repeatPenalty=1.1, seed=1234)
+    for int8 in ([False, True] if args.int8 else [False]):
+        K, n = 3 if int8 else 7, 100
+        m = model(128, int8)
+        c = m.NewContext(128, 1)
+        run = c.SampleDecode(PROMPT, n, **SMP)
+        head_ms = med(lambda: c.SampleDecode(PROMPT, 1, **SMP))   # ring upload, prompt Eval, first sample: what both loops start with
+        plain_ms = med(lambda: c.SampleDecode(PROMPT, n, **SMP))
+        step_ms = (plain_ms - head_ms) / (n - 1)
+        out = dict(part="sample", int8=int8, layers=args.layers, ids=n, rows=K + 1, head_ms=round(head_ms, 3), sampled_ms=round(plain_ms, 2),
+                   sampled_tok_s=round(n / plain_ms * 1e3, 1), step_ms=round(step_ms, 3))
+        for name, corpus in (("replay", PROMPT + run), ("no_corpus", None)):
+            res = {}
+
+            def loop():
+                ids, st, _ = c.SampleDecodeLookup(PROMPT, n, K, 3, 1, corpus, **SMP)
+                assert ids == run and st["rows"] == K + 1, st
+                res.update(st)
+            ms = med(loop)
+            pass_ms = (ms - head_ms) / res["passes"]
+            out.update({f"{name}_passes": res["passes"], f"{name}_accepted": res["accepted"], f"{name}_ms": round(ms, 2), f"{name}_tok_s": round(n / ms * 1e3, 1),
+                        f"{name}_pass_ms": round(pass_ms, 3)})
+        out["pass_over_step"] = round(out["replay_pass_ms"] / step_ms, 3)
+        # the route wins when ids per pass = 1 + mean accepted > pass time / step time
+        out["break_even_accepted_per_pass"] = round(out["no_corpus_pass_ms"] / step_ms - 1, 3)
+        emit(out)
+        c.free()
+        m.free()
 
 if "pass" in args.parts:
     N = 96   # ids per timed call: 12 full passes at R = 8
