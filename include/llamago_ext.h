@@ -135,6 +135,17 @@ int llamago_BatchFeed(llama_batch* b, const uint32_t* const* tokens, const uint3
 /* lh_batch_set_sampler on the batch: the following ticks pick every pod's id with SampleTopPTopK (llama.go:455-707) instead of the argmax, every
  * pod seeded like a solo run; ringSize slots of lastNTokens per pod, empty.  May be called mid-stream (behind llamago_BatchPrompt and ticks). */
 int llamago_BatchSetSampler(llama_batch* b, uint32_t topK, float topP, float temp, float repeatPenalty, uint64_t seed, uint32_t ringSize);
+int llamago_BatchClearSampler(llama_batch* b);   /* lh_batch_set_sampler(NULL): the following ticks take the argmax again */
+/* lh_batch_feed_sample: llamago_BatchFeed on a batch whose ticks sample - a job joins (flags[i] = LH_FEED_NEW: pod i's ring and draw counter restart, its
+ * prompt in ONE feed), a pod takes a next turn (0) or its own pending id (LH_FEED_PENDING) while the other pods go on sampling.  Every fed pod's last row
+ * is sampled over its ring behind the fed tokens (the rule is stated in llamahip.h); ids_out[i] = that id, which the pod's next tick evaluates.
+ * flags NULL = all 0.  llamago_BatchFeed on such a batch stays refused. */
+int llamago_BatchFeedSample(llama_batch* b, const uint32_t* const* tokens, const uint32_t* n_tokens, const uint32_t* past, const uint32_t* flags, uint32_t* ids_out,
+                            float* logits_last, float* logits_rows);
+/* lh_sample_pods: the multi-pod sampler of a sampled tick alone on host arrays, on the model context's device - row i of logits [n][n_logits] over ring i
+ * of rings [n][ring_size] (ring_pos[i] ids appended so far) as sampling call draws[i]; rings_out / ring_pos_out (optional) = the rings behind the ids. */
+int llamago_SamplePods(const float* logits, uint32_t n, uint32_t n_logits, const uint32_t* rings, uint32_t ring_size, const uint32_t* ring_pos, const uint64_t* draws,
+                       uint32_t topK, float topP, float temp, float repeatPenalty, uint64_t seed, uint32_t* ids_out, uint32_t* rings_out, uint32_t* ring_pos_out);
 
 /* ---- [product] pods as pipeline streams over a layer-sharded model ---------------------------- */
 typedef struct llama_pipeline llama_pipeline;

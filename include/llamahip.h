@@ -306,6 +306,14 @@ int lh_llama_decode_lookup(lh_llama* m, uint32_t first_token, uint32_t past, uin
  * argument (LH_EINVAL); n_logits outside 1..65536 (LH_ESHAPE); topK above 1024 (LH_EUNSUPPORTED). */
 int lh_sample_rows(lh_ctx* ctx, const float* logits_host, uint32_t n_rows, uint32_t n_logits, const uint32_t* ring_host, uint32_t ring_size,
                    uint32_t ring_pos, const uint32_t* tokens_host, const lh_sample_params* sp, uint64_t draw0, uint32_t* ids_out);
+/* lh_sample_pods is the op-level twin of the multi-pod sampler kernels (k_sample_pods, topK <= 1024; k_sample_small_pods, topK <= 64): what a sampled
+ * tick of an lh_batch runs.  Host logits [n][n_logits] packed, rings_host [n][ring_size] with ring_pos[i] ids appended to pod i's ring so far, draws[i] =
+ * the index of pod i's sampling call, one set of parameters; ONE launch, one workgroup per pod.  ids_out[i] = SampleTopPTopK of row i over ring i as call
+ * draws[i]; rings_out [n][ring_size] / ring_pos_out [n] (both optional) = the rings with that id appended.  Refusals as lh_sample_rows, with n outside
+ * 1..64 in place of the row count. */
+int lh_sample_pods(lh_ctx* ctx, const float* logits_host, uint32_t n, uint32_t n_logits, const uint32_t* rings_host, uint32_t ring_size,
+                   const uint32_t* ring_pos, const uint64_t* draws, const lh_sample_params* sp, uint32_t* ids_out, uint32_t* rings_out,
+                   uint32_t* ring_pos_out);
 /* lh_llama_decode_sample through verify passes drafted by the lookup rule above: the same ring, prompt Eval and first sample on the last
  * prompt row, then the n_predict - 1 remaining ids from passes of R = draft_max + 1 rows (lowered as in lh_llama_decode_lookup; R = 1 = plain
  * sampled steps) that sample every row and commit by the rule above.  out_tokens = exactly the n_predict ids of lh_llama_decode_sample with
@@ -353,6 +361,8 @@ int lh_batch_stage(lh_batch* b, const float* x_in_dev, float* x_out_dev, float* 
 /* From now on the last stage draws every row's id with SampleTopPTopK (llama.go:455-707; same device sampler and counter-based
  * uniforms as lh_llama_decode_sample, every row seeded like a solo run) instead of the argmax.  ring_init[i][0..n_init[i]) = ids
  * already appended to row i's lastNTokens ring of ring_size slots (the prompt, server.go:193-197).  sp = NULL: back to greedy. */
+/* A sampled tick is ONE sampler launch over all rows (k_sample_pods / k_sample_small_pods, one workgroup per row); LLAMAHIP_SAMPLE_PER_POD=1 (debug / A-B,
+ * read when the tick is captured) keeps one launch per row - ids, rings and draw counters are the same either way. */
 int lh_batch_set_sampler(lh_batch* b, const lh_sample_params* sp, uint32_t ring_size, const uint32_t* const* ring_init, const uint32_t* n_init);
 /* Whole-model pods: n_steps device-resident ticks from (first_tokens[i], past[i]); out_tokens[i * n_steps + s] = id row i
  * produced at step s; logits_last_host (optional) = [rows][vocab] logits of the final tick.
@@ -374,7 +384,7 @@ int lh_batch_decode(lh_batch* b, const uint32_t* first_tokens, const uint32_t* p
  * reads them.  Which rows share which pass is lh_feed_schedule's fixed partition (below), so results never depend on timing.
  * Refused before anything is enqueued, the batch left exactly as it was: past[i] + n_tokens[i] > ctx, a token id >= vocab, all n_tokens[i] == 0,
  * tokens[i] == NULL with n_tokens[i] > 0 (LH_EINVAL); a batch with a sampler set, a batch of layer-shard stages (LH_EUNSUPPORTED).
- * Out of scope: sampler rings across a feed; layer shards and the pipeline; a context swap INSIDE a feed (a feed never leaves the window: the
+ * Out of scope: sampler rings across a feed (lh_batch_feed_sample below); layer shards and the pipeline; a context swap INSIDE a feed (a feed never leaves the window: the
  * swap happens in the ticks behind it); lh_batch_prompt keeps its own route (one Eval per pod).
  * Switches (read per call): LLAMAHIP_FEED_SOLO_MIN (rows from which a pod's feed is an Eval of its own, default 129), LLAMAHIP_FEED_QB (query rows
  * per attention block: 2, 4 or 8), LLAMAHIP_FEED_ROW_ATTN=1 (debug / A-B: the per-row attention kernels on the pass's row table). */
@@ -382,6 +392,30 @@ int lh_batch_feed(lh_batch* b, const uint32_t* const* tokens, const uint32_t* n_
                   uint32_t* ids_host,          /* optional [rows]: greedy id of each FED pod's last row; other entries not written */
                   float* logits_last_host,     /* optional [rows][vocab]: logits of each fed pod's last row; other rows not written */
                   float* logits_rows_host);    /* optional [sum n_tokens][vocab]: every fed row, pods in index order */
+/* lh_batch_feed on a batch whose ticks SAMPLE (lh_batch_set_sampler): jobs join and leave a running sampled batch as server.Do takes them
+ * (pkg/server/server.go:127-217).  Schedule, passes, caches, histories, positions and output-list conventions are lh_batch_feed's; what differs is
+ * the id behind a fed pod's last row and the pod's sampler state {ring, ring_pos, draw}.  The rule, for a fed pod i (tests/feed_sample_ref.py restates it):
+ *   1. flags[i] & LH_FEED_NEW: a new job (server.go:127-138) - the ring becomes ring_size zeros, ring_pos = 0, draw = 0; seed and parameters stay the batch's;
+ *   2. its fed tokens are appended to the ring in order (server.go:189-190).  With LH_FEED_PENDING the first one is NOT appended: tokens[i][0] is then
+ *      the pod's pending id, which its last sampling call appended already.  It requires past[i] == the pod's position and tokens[i][0] == its pending id,
+ *      both known to the host once the stream has been waited for: a feed with a PENDING flag therefore waits for the stream and reads what the ticks so
+ *      far produced BEFORE it is checked (a refused one has done that much, and nothing else); otherwise the call returns LH_EINVAL;
+ *   3. its last fed row is sampled as call `draw` over that ring; the id is appended, ring_pos and draw move on by one.  The id is the pod's pending
+ *      token: lh_batch_ids_dev, lh_batch_tokens_dev, entry 0 of its output list and ids_host[i];
+ *   4. a pod that is not fed keeps its ring, counters, pending token and cache.
+ * Every feed of a pod ends in exactly ONE sampling call, so a prompt must arrive in ONE feed to draw what lh_llama_decode_sample draws for it: NEW + the
+ * prompt, then ticks, makes the same sampler calls over the same ring.  Where the rows of the pass are bit-identical to solo rows (up to 8 rows per pass
+ * for fp32, 4 for block-int8) the ids are equal; beyond, they are the sampler's on logits within the feed's tolerance.
+ * Per pass: one k_feed_ring launch over its segments, one k_sample_pods / k_sample_small_pods launch over the segments that end in it.
+ * Refused before anything is enqueued, the batch - sampler state included - left as it was: everything lh_batch_feed refuses except a set sampler; no
+ * sampler set (LH_EINVAL: use lh_batch_feed); an unknown flag bit; NEW | PENDING together; a failed PENDING check (LH_EINVAL).
+ * Out of scope: chunked prompts on a sampling batch, per-job seeds, layer shards. */
+enum { LH_FEED_NEW = 1, LH_FEED_PENDING = 2 };
+int lh_batch_feed_sample(lh_batch* b, const uint32_t* const* tokens, const uint32_t* n_tokens, const uint32_t* past,
+                         const uint32_t* flags,       /* [rows] or NULL = all 0 */
+                         uint32_t* ids_host,          /* optional [rows]: sampled id of each FED pod; other entries not written */
+                         float* logits_last_host,     /* optional [rows][vocab]: logits of each fed pod's last row; other rows not written */
+                         float* logits_rows_host);    /* optional [sum n_tokens][vocab]: every fed row, pods in index order */
 /* The pass schedule of a feed: the pure function (no GPU) lh_batch_feed executes.  A pod with n_tokens >= solo_min is a solo pass (an Eval on
  * its own plan); the other fed rows, in pod order with ascending positions, are cut into batched passes of <= 64 rows (a pod's rows in a pass
  * are one segment; a segment may continue in the next pass); a pass of one row, and the segments of a pass whose row count n has bit n - 1 of

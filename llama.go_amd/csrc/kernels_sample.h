@@ -29,6 +29,9 @@
 //   k_sample_rows / k_sample_small_rows: the same two bodies over the R rows of a verify pass in one launch, one workgroup per row, row r as
 //     sampling call draw + r over the ring as if the draft in front of it had been appended (ring_bitmap<true>); the speculative sampled loop
 //     (include/llamahip.h, lh_llama_decode_sample_lookup).
+//   k_sample_pods / k_sample_small_pods: the single-row bodies over the pods of a batch in one launch, one workgroup per job {pod, logits row}, every pod on
+//     its own state, ring, step parameters and output list (the sampled tick of lh_batch and lh_batch_feed_sample; the workgroups run on separate CUs).
+//   k_feed_ring: the lastNTokens bookkeeping of a fed segment (server.go:127-138, 189-190) in front of that pod's sampling call.
 #pragma once
 #include "kernels_common.h"
 
@@ -281,6 +284,46 @@ __global__ __launch_bounds__(1024) void k_sample_rows(const float* __restrict__ 
     const uint32_t row = blockIdx.x;
     if (n_draft && row > *n_draft) return;
     sample_body<EPT, true>(logits + (size_t)row * V, V, st, ring, nullptr, nullptr, arg + row, nullptr, nullptr, nullptr, 0, tok, row);
+}
+
+// One job of a multi-pod launch: pod `pod` samples logits row `row` (a null table: job e = {e, e}, the tick of a batch).
+struct SampleJob { uint32_t pod, row; };
+
+// k_sample over the pods of a batch in ONE launch, workgroup e = job e: exactly what k_sample does for that pod alone (sampling call st->draw, the id appended
+// to the pod's ring, ring_pos and draw moved on, the id to the pod's output list, step parameters and ids[pod]).  A pod is touched by its own workgroup only.
+template <int EPT>
+__global__ __launch_bounds__(1024) void k_sample_pods(const float* __restrict__ logits, uint32_t V, SampleState* ss, uint32_t* __restrict__ ring, uint32_t ring_cap,
+                                                      StepParams* sp, uint32_t* __restrict__ out, uint32_t out_cap, uint32_t* __restrict__ ids,
+                                                      const SampleJob* __restrict__ jobs) {
+    const uint32_t e = blockIdx.x, q = jobs ? jobs[e].pod : e, r = jobs ? jobs[e].row : e;
+    sample_body<EPT, false>(logits + (size_t)r * V, V, ss + q, ring + (size_t)q * ring_cap, sp + q, out + (size_t)q * out_cap, ids + q, nullptr, nullptr, nullptr, 1,
+                            nullptr, 0u);
+}
+
+// The ring of a fed segment (lh_batch_feed_sample), one workgroup per segment of a pass: `restart` makes the pod a new job (ring = ring_size zeros, ring_pos = 0,
+// draw = 0: server.go:127-138), then tok[tok0 .. tok0 + n) are appended in order (server.go:189-190).  Of several appends to one slot (n > ring_size) only the
+// last is stored, and a restart zeroes only the slots no append reaches: every slot has one writer, so nothing here depends on the order of the threads.
+// (static: not a template, and this header is part of two translation units.)
+struct FeedRingSeg { uint32_t pod, tok0, n, restart; };
+static __global__ __launch_bounds__(256) void k_feed_ring(const FeedRingSeg* __restrict__ segs, const uint32_t* __restrict__ tok, SampleState* ss, uint32_t* __restrict__ ring,
+                                                   uint32_t ring_cap) {
+    const FeedRingSeg sg = segs[blockIdx.x];
+    SampleState* st = ss + sg.pod;
+    uint32_t* rg = ring + (size_t)sg.pod * ring_cap;
+    const uint32_t rs = st->ring_size, pos0 = sg.restart ? 0u : st->ring_pos, base = rs ? pos0 % rs : 0u;
+    if (sg.restart)
+        for (uint32_t r = threadIdx.x; r < rs; r += 256) {
+            const uint32_t d = r >= base ? r - base : r + rs - base;   // the first append that reaches slot r
+            if (d >= sg.n) rg[r] = 0u;
+        }
+    if (rs)
+        for (uint32_t j = threadIdx.x; j < sg.n; j += 256)
+            if (j + rs >= sg.n) rg[(base + j % rs) % rs] = tok[sg.tok0 + j];   // the last writer of its slot
+    __syncthreads();   // every thread has read ring_pos
+    if (threadIdx.x == 0) {
+        st->ring_pos = pos0 + sg.n;
+        if (sg.restart) st->draw = 0;
+    }
 }
 
 
@@ -540,6 +583,16 @@ __global__ __launch_bounds__(1024) void k_sample_small_rows(const float* __restr
     const uint32_t row = blockIdx.x;
     if (n_draft && row > *n_draft) return;
     sample_small_body<EPT, true>(logits + (size_t)row * V, V, st, ring, nullptr, nullptr, arg + row, nullptr, nullptr, nullptr, 0, tok, row);
+}
+
+// k_sample_pods for topK <= 64.
+template <int EPT>
+__global__ __launch_bounds__(1024) void k_sample_small_pods(const float* __restrict__ logits, uint32_t V, SampleState* ss, uint32_t* __restrict__ ring, uint32_t ring_cap,
+                                                            StepParams* sp, uint32_t* __restrict__ out, uint32_t out_cap, uint32_t* __restrict__ ids,
+                                                            const SampleJob* __restrict__ jobs) {
+    const uint32_t e = blockIdx.x, q = jobs ? jobs[e].pod : e, r = jobs ? jobs[e].row : e;
+    sample_small_body<EPT, false>(logits + (size_t)r * V, V, ss + q, ring + (size_t)q * ring_cap, sp + q, out + (size_t)q * out_cap, ids + q, nullptr, nullptr, nullptr,
+                                  1, nullptr, 0u);
 }
 
 }  // namespace lh

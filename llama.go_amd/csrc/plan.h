@@ -136,6 +136,13 @@ int sample_launch(lh_ctx* ctx, const float* logits, uint32_t V, SampleState* st,
 // the rows of a verify pass in one launch (k_sample_rows / k_sample_small_rows): ids to arg[0..n_rows), nothing else written
 int sample_rows_launch(lh_ctx* ctx, const float* logits, uint32_t V, uint32_t n_rows, SampleState* st, uint32_t* ring, const uint32_t* tok, const uint32_t* n_draft,
                        uint32_t* arg, uint32_t topk_hint);
+// the single-row sampler over n_jobs pods of a batch in one launch (k_sample_pods / k_sample_small_pods): job e = jobs[e] {pod, logits row}, or {e, e} without a table
+struct SampleJob;
+struct FeedRingSeg;
+int sample_pods_launch(lh_ctx* ctx, const float* logits, uint32_t V, uint32_t n_jobs, const SampleJob* jobs, SampleState* ss, uint32_t* ring, uint32_t ring_cap,
+                       StepParams* sp, uint32_t* out, uint32_t out_cap, uint32_t* ids, uint32_t topk_hint);
+// the rings of the fed segments of one pass (k_feed_ring), in front of their pods' sampling calls
+int feed_ring_launch(lh_ctx* ctx, const FeedRingSeg* segs, uint32_t n_segs, const uint32_t* tok, SampleState* ss, uint32_t* ring, uint32_t ring_cap);
 
 // score.hip
 int score_launch(lh_ctx* ctx, const float* logits, uint32_t n, uint32_t V, const uint32_t* targets, lh_row_score* out);

@@ -2208,6 +2208,7 @@ struct Batch {
     uint64_t cap_splitk_gen = 0, cap_scratch_gen = 0;
     uint64_t scratch_gen() const { uint64_t g = 0; for (const Plan* p : pods) g += p->scratch_gen; return g; }   // grows when any pod's scratch moved
     bool cap_sampling = false;
+    bool per_pod = false, cap_per_pod = false;   // LLAMAHIP_SAMPLE_PER_POD=1: one sampler launch per row (read where the tick is captured)
     bool warm = false;
     // host mirror of the rows' positions (rows_dev[i].pos): the tick kernels advance them in device memory with no bound of their own, so
     // the window check of every other Eval entry point (plan_eval: past + n <= ctx) is made here before a tick is enqueued
@@ -2251,11 +2252,18 @@ static int batch_enqueue_tick(Batch* b, const float* x_in, float* x_out) {
         }
     }
     if (m.last_stage() && b->sampling) {
-        // SampleTopPTopK per row (llama.go:455-707) on the row's own ring / draw counter; the rows' step parameters carry the output index
-        for (uint32_t i = 0; i < B; ++i)
-            if ((rc = sample_launch(ctx, b->logits() + (size_t)i * m.V, m.V, b->ss_dev + i, b->ring_dev + (size_t)i * b->ring_cap, b->sp_dev + i, b->out_dev + (size_t)i * b->out_cap,
-                                    nullptr, nullptr, nullptr, nullptr, 1, b->smp_topk)))
-                return rc;
+        // SampleTopPTopK per row (llama.go:455-707) on the row's own ring / draw counter; the rows' step parameters carry the output index.
+        // One launch, a workgroup per row (they run on separate CUs); the per-row launches stay as the A/B switch the tests compare against.
+        if (!b->per_pod) {
+            if ((rc = sample_pods_launch(ctx, b->logits(), m.V, B, nullptr, b->ss_dev, b->ring_dev, b->ring_cap, b->sp_dev, b->out_dev, b->out_cap, b->ids_dev, b->smp_topk))) return rc;
+        } else {
+            for (uint32_t i = 0; i < B; ++i) {
+                LH_TRACE("%s", b->smp_topk <= 64 ? "k_sample_small" : "k_sample");
+                if ((rc = sample_launch(ctx, b->logits() + (size_t)i * m.V, m.V, b->ss_dev + i, b->ring_dev + (size_t)i * b->ring_cap, b->sp_dev + i,
+                                        b->out_dev + (size_t)i * b->out_cap, nullptr, nullptr, nullptr, nullptr, 1, b->smp_topk)))
+                    return rc;
+            }
+        }
         LH_LAUNCH(k_batch_from_sp, dim3(1), dim3(64), 0, ctx->stream, b->rows_dev, b->tok_dev, b->ids_dev, (const StepParams*)b->sp_dev, B);
     } else if (m.last_stage()) {
         LH_LAUNCH(k_batch_argmax, dim3(B), dim3(1024), 0, ctx->stream, (const float*)b->logits(), m.V, b->rows_dev, b->tok_dev, b->ids_dev, b->out_dev, b->out_cap,
@@ -2289,11 +2297,14 @@ static int batch_tick_unchecked(Batch* b, const float* x_in, float* x_out) {
     lh_ctx* ctx = b->ctx;
     Plan* p0 = b->pods[0];
     int rc;
+    const char* pp = getenv("LLAMAHIP_SAMPLE_PER_POD");
+    b->per_pod = pp && pp[0] == '1';
     if (!p0->use_graph || !b->warm) {
         b->warm = true;
         return batch_enqueue_tick(b, x_in, x_out);
     }
-    if (b->exec && (b->cap_x_in != x_in || b->cap_x_out != x_out || b->cap_splitk_gen != ctx->splitk_gen || b->cap_scratch_gen != b->scratch_gen() || b->cap_sampling != b->sampling))
+    if (b->exec && (b->cap_x_in != x_in || b->cap_x_out != x_out || b->cap_splitk_gen != ctx->splitk_gen || b->cap_scratch_gen != b->scratch_gen() || b->cap_sampling != b->sampling ||
+                    b->cap_per_pod != b->per_pod))
         batch_drop_graph(b);
     if (!b->exec) {
         LH_HIP(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeRelaxed));
@@ -2303,6 +2314,7 @@ static int batch_tick_unchecked(Batch* b, const float* x_in, float* x_out) {
         if (e != hipSuccess) LH_FAIL(ctx, LH_EHIP, "hipStreamEndCapture (batch tick): %s", hipGetErrorString(e));
         LH_HIP(ctx, hipGraphInstantiate(&b->exec, b->graph, nullptr, nullptr, 0));
         b->cap_x_in = x_in; b->cap_x_out = x_out; b->cap_splitk_gen = ctx->splitk_gen; b->cap_scratch_gen = b->scratch_gen(); b->cap_sampling = b->sampling;
+        b->cap_per_pod = b->per_pod;
     }
     LH_HIP(ctx, hipGraphLaunch(b->exec, ctx->stream));
     return 0;
@@ -2405,31 +2417,55 @@ static uint32_t env_u32(const char* name, uint32_t dflt) {
     return (e && *e) ? (uint32_t)strtoul(e, nullptr, 10) : dflt;
 }
 
-static int batch_feed(Batch* b, const uint32_t* const* tokens, const uint32_t* n_tokens, const uint32_t* past, uint32_t* ids_host, float* logits_last_host,
-                      float* logits_rows_host) {
+// sample: lh_batch_feed_sample - the same feed on a batch whose ticks sample; the fed pods' rings (k_feed_ring) and the id behind a pod's last row
+// (the pods sampler in place of the argmax) are all that differs.
+static int batch_feed(Batch* b, const uint32_t* const* tokens, const uint32_t* n_tokens, const uint32_t* past, const uint32_t* flags, bool sample, uint32_t* ids_host,
+                      float* logits_last_host, float* logits_rows_host) {
     lh_ctx* ctx = b->ctx;
     Plan* p0 = b->pods[0];
     const ModelDesc& m = p0->md;
     const uint32_t B = b->B;
+    const char* who = sample ? "lh_batch_feed_sample" : "lh_batch_feed";
     // ---- everything is checked before anything is enqueued or any host state moves
-    if (!m.first_stage() || !m.last_stage()) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_batch_feed needs whole-model pods (a layer shard's prompts are driven by the pipeline)");
-    if (b->sampling) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_batch_feed: the batch has a sampler set (sampler rings across a feed are out of scope; lh_batch_set_sampler(NULL) first)");
+    if (!m.first_stage() || !m.last_stage()) LH_FAIL(ctx, LH_EUNSUPPORTED, "%s needs whole-model pods (a layer shard's prompts are driven by the pipeline)", who);
+    if (sample && !b->sampling) LH_FAIL(ctx, LH_EINVAL, "lh_batch_feed_sample: the batch has no sampler set (lh_batch_feed feeds a greedy batch)");
+    if (!sample && b->sampling) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_batch_feed: the batch has a sampler set (sampler rings across a feed are out of scope; lh_batch_set_sampler(NULL) first)");
     uint64_t total = 0;
     for (uint32_t i = 0; i < B; ++i) {
         const uint32_t n = n_tokens[i];
         if (!n) {
-            if (!b->pos_known) LH_FAIL(ctx, LH_EINVAL, "lh_batch_feed: the first feed of a fresh batch must feed every row (row %u has no position yet)", i);
+            if (!b->pos_known) LH_FAIL(ctx, LH_EINVAL, "%s: the first feed of a fresh batch must feed every row (row %u has no position yet)", who, i);
             continue;
         }
-        if (!tokens || !tokens[i]) LH_FAIL(ctx, LH_EINVAL, "lh_batch_feed: row %u has %u tokens to feed and no token array", i, n);
-        if (!past || (uint64_t)past[i] + n > m.ctx) LH_FAIL(ctx, LH_EINVAL, "lh_batch_feed: row %u: past %u + n %u exceeds the context window of %u", i, past ? past[i] : 0u, n, m.ctx);
+        if (!tokens || !tokens[i]) LH_FAIL(ctx, LH_EINVAL, "%s: row %u has %u tokens to feed and no token array", who, i, n);
+        if (!past || (uint64_t)past[i] + n > m.ctx) LH_FAIL(ctx, LH_EINVAL, "%s: row %u: past %u + n %u exceeds the context window of %u", who, i, past ? past[i] : 0u, n, m.ctx);
         for (uint32_t j = 0; j < n; ++j)
-            if (tokens[i][j] >= m.V) LH_FAIL(ctx, LH_EINVAL, "lh_batch_feed: row %u: token id %u at index %u outside the vocabulary of %u", i, tokens[i][j], j, m.V);
+            if (tokens[i][j] >= m.V) LH_FAIL(ctx, LH_EINVAL, "%s: row %u: token id %u at index %u outside the vocabulary of %u", who, i, tokens[i][j], j, m.V);
         total += n;
     }
-    if (!total) LH_FAIL(ctx, LH_EINVAL, "lh_batch_feed: no row is fed");
+    if (!total) LH_FAIL(ctx, LH_EINVAL, "%s: no row is fed", who);
+    int rc;
+    if (sample) {
+        bool pending = false;
+        for (uint32_t i = 0; i < B; ++i) {
+            const uint32_t fl = (flags && n_tokens[i]) ? flags[i] : 0u;
+            if (fl & ~(uint32_t)(LH_FEED_NEW | LH_FEED_PENDING)) LH_FAIL(ctx, LH_EINVAL, "lh_batch_feed_sample: row %u: unknown flag bits 0x%x", i, fl);
+            if ((fl & LH_FEED_NEW) && (fl & LH_FEED_PENDING)) LH_FAIL(ctx, LH_EINVAL, "lh_batch_feed_sample: row %u: LH_FEED_NEW and LH_FEED_PENDING exclude each other", i);
+            pending = pending || (fl & LH_FEED_PENDING);
+        }
+        if (pending) {   // the pod's position and pending id, as the host knows them once the ticks so far are read (a stream wait and the host mirror's histories: neither device state nor positions move)
+            if (!b->pos_known) LH_FAIL(ctx, LH_EINVAL, "lh_batch_feed_sample: LH_FEED_PENDING on a fresh batch (no row has a pending id yet)");
+            if ((rc = batch_drain(b))) return rc;
+            for (uint32_t i = 0; i < B; ++i) {
+                if (!n_tokens[i] || !(flags[i] & LH_FEED_PENDING)) continue;
+                if (past[i] != b->pos[i] || b->pending[i] == Plan::HIST_UNKNOWN || tokens[i][0] != b->pending[i])
+                    LH_FAIL(ctx, LH_EINVAL, "lh_batch_feed_sample: row %u: LH_FEED_PENDING needs past = the row's position %u and tokens[0] = its pending id (got past %u, id %u)", i,
+                            b->pos[i], past[i], tokens[i][0]);
+            }
+        }
+    }
     const uint32_t solo_min = env_u32("LLAMAHIP_FEED_SOLO_MIN", FEED_SOLO_MIN), qb = env_u32("LLAMAHIP_FEED_QB", FEED_QB);
-    if (qb != 2 && qb != 4 && qb != 8) LH_FAIL(ctx, LH_EINVAL, "lh_batch_feed: LLAMAHIP_FEED_QB = %u (2, 4 or 8)", qb);
+    if (qb != 2 && qb != 4 && qb != 8) LH_FAIL(ctx, LH_EINVAL, "%s: LLAMAHIP_FEED_QB = %u (2, 4 or 8)", who, qb);
     const char* ra = getenv("LLAMAHIP_FEED_ROW_ATTN");
     const bool row_attn = ra && ra[0] == '1';
     uint64_t sizes_ok = 0;   // the row counts that may share one weight pass on this plan
@@ -2438,6 +2474,8 @@ static int batch_feed(Batch* b, const uint32_t* const* tokens, const uint32_t* n
     FeedSchedule fs;
     feed_schedule(n_tokens, past, B, solo_min, qb, sizes_ok, &fs);
     // ---- the passes' tables: [BatchRow x rows | token id x rows | AttnBlock x blocks] per batched pass, one upload through the pinned staging buffer
+    std::vector<uint64_t> row_off(B, 0);   // logits_rows_host, and the token table of a sampled feed: every fed row, pods in index order
+    for (uint32_t i = 1; i < B; ++i) row_off[i] = row_off[i - 1] + n_tokens[i - 1];
     std::vector<size_t> pass_off(fs.passes.size(), 0);
     size_t bytes = 0;
     for (size_t k = 0; k < fs.passes.size(); ++k) {
@@ -2446,9 +2484,14 @@ static int batch_feed(Batch* b, const uint32_t* const* tokens, const uint32_t* n
         pass_off[k] = bytes;
         bytes += (sizeof(BatchRow) * ps.rows + 4 * (size_t)ps.rows + sizeof(AttnBlock) * ps.nblk + 15) & ~(size_t)15;
     }
-    int rc;
+    const size_t pass_bytes = bytes;
+    // a sampled feed: [FeedRingSeg x segments | SampleJob x segments (per pass, from its first segment's index: the segments that END in it) | every fed token]
+    const size_t n_segs = fs.segs.size(), o_rseg = bytes, o_jobs = o_rseg + sizeof(FeedRingSeg) * n_segs, o_toks = o_jobs + sizeof(SampleJob) * n_segs;
+    std::vector<uint32_t> n_end(fs.passes.size(), 0);
+    std::vector<SampleJob> jobs(sample ? n_segs : 0);   // (kept on the host too: a solo pass reuses the staging buffer)
+    if (sample) bytes = (o_toks + 4 * (size_t)total + 15) & ~(size_t)15;
+    if (pass_bytes && (rc = plan_ensure_rows(p0, FEED_PASS_ROWS))) return rc;   // (the captured tick re-captures on scratch_gen)
     if (bytes) {
-        if ((rc = plan_ensure_rows(p0, FEED_PASS_ROWS))) return rc;   // (the captured tick re-captures on scratch_gen)
         if ((rc = ensure_staging(ctx, bytes))) return rc;
         if (bytes > b->feed_cap) {
             LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -2457,7 +2500,7 @@ static int batch_feed(Batch* b, const uint32_t* const* tokens, const uint32_t* n
             LH_HIP(ctx, hipMalloc((void**)&b->feed_dev, bytes));
             b->feed_cap = bytes;
         }
-        if (p0->attn_part && !b->feed_part)
+        if (pass_bytes && p0->attn_part && !b->feed_part)
             LH_HIP(ctx, hipMalloc((void**)&b->feed_part, 4 * (size_t)FEED_PASS_ROWS * m.H * ((m.ctx + ATT_TC - 1) / ATT_TC) * (m.hd + 2)));
     }
     // what the ticks so far did goes into the pods' histories (and waits for the stream: the staging buffer is free)
@@ -2483,18 +2526,51 @@ static int batch_feed(Batch* b, const uint32_t* const* tokens, const uint32_t* n
                 for (uint32_t q = 0; q < ps.nblk; ++q)
                     if ((fs.blocks[ps.blk0 + q].n == 1) == (one == 1)) hb[w++] = AttnBlock{fs.blocks[ps.blk0 + q].row0, fs.blocks[ps.blk0 + q].n};
         }
+        if (sample) {
+            FeedRingSeg* hs = (FeedRingSeg*)(ctx->staging + o_rseg);
+            uint32_t* ht = (uint32_t*)(ctx->staging + o_toks);
+            for (uint32_t i = 0; i < B; ++i)
+                for (uint32_t j = 0; j < n_tokens[i]; ++j) ht[row_off[i] + j] = tokens[i][j];
+            for (size_t k = 0; k < fs.passes.size(); ++k) {
+                const lh_feed_pass& ps = fs.passes[k];
+                for (uint32_t s = ps.seg0; s < ps.seg0 + ps.nseg; ++s) {
+                    const lh_feed_seg& sg = fs.segs[s];
+                    const uint32_t fl = flags ? flags[sg.pod] : 0u, t0 = sg.pos0 - past[sg.pod];
+                    const uint32_t skip = (t0 == 0 && (fl & LH_FEED_PENDING)) ? 1u : 0u;   // the pending id is in the ring already
+                    hs[s] = FeedRingSeg{sg.pod, (uint32_t)row_off[sg.pod] + t0 + skip, sg.n - skip, (t0 == 0 && (fl & LH_FEED_NEW)) ? 1u : 0u};
+                    if (t0 + sg.n == n_tokens[sg.pod])   // a solo pass hands its last row to the sampler as row 0
+                        jobs[ps.seg0 + n_end[k]++] = SampleJob{sg.pod, ps.kind == LH_FEED_SOLO ? 0u : sg.row0 + sg.n - 1};
+                }
+            }
+            memcpy(ctx->staging + o_jobs, jobs.data(), sizeof(SampleJob) * n_segs);
+        }
         LH_HIP(ctx, hipMemcpyAsync(b->feed_dev, ctx->staging, bytes, hipMemcpyHostToDevice, ctx->stream));
     }
-    std::vector<uint64_t> row_off(B, 0);   // logits_rows_host: every fed row, pods in index order
-    for (uint32_t i = 1; i < B; ++i) row_off[i] = row_off[i - 1] + n_tokens[i - 1];
+    // a sampled pass: the rings of its segments in front of it, one sampler launch over the pods whose feed ends in it behind it
+    auto pass_rings = [&](const lh_feed_pass& ps) -> int {
+        return feed_ring_launch(ctx, (const FeedRingSeg*)(b->feed_dev + o_rseg) + ps.seg0, ps.nseg, (const uint32_t*)(b->feed_dev + o_toks), b->ss_dev, b->ring_dev, b->ring_cap);
+    };
+    auto pass_sample = [&](size_t k, const float* lg) -> int {
+        const lh_feed_pass& ps = fs.passes[k];
+        if (!n_end[k]) return 0;
+        int r = sample_pods_launch(ctx, lg, m.V, n_end[k], (const SampleJob*)(b->feed_dev + o_jobs) + ps.seg0, b->ss_dev, b->ring_dev, b->ring_cap, b->sp_dev, b->out_dev,
+                                   b->out_cap, b->ids_dev, b->smp_topk);
+        if (r) return r;
+        const SampleJob* hj = jobs.data() + ps.seg0;
+        for (uint32_t e = 0; e < n_end[k]; ++e)
+            LH_HIP(ctx, hipMemcpyAsync(b->tok_dev + hj[e].pod, b->ids_dev + hj[e].pod, 4, hipMemcpyDeviceToDevice, ctx->stream));
+        return 0;
+    };
     // rows [r0, r0 + n) of `lg` are tokens tok0.. of pod's feed: the copies the caller asked for, and the pod's next id behind its last row
     auto rows_done = [&](uint32_t pod, uint32_t tok0, uint32_t n, const float* lg) -> int {
         if (logits_rows_host)
             LH_HIP(ctx, hipMemcpyAsync(logits_rows_host + (row_off[pod] + tok0) * m.V, lg, (size_t)n * m.V * 4, hipMemcpyDeviceToHost, ctx->stream));
         if (tok0 + n != n_tokens[pod]) return 0;   // (the pod's feed continues in the next pass)
         const float* last_row = lg + (size_t)(n - 1) * m.V;
-        LH_LAUNCH(k_argmax_advance, dim3(1), dim3(1024), 0, ctx->stream, last_row, m.V, (StepParams*)nullptr, b->out_dev + (size_t)pod * b->out_cap, b->ids_dev + pod, 0);
-        LH_HIP(ctx, hipMemcpyAsync(b->tok_dev + pod, b->ids_dev + pod, 4, hipMemcpyDeviceToDevice, ctx->stream));
+        if (!sample) {   // (a sampled pass draws the ids of all its ending pods in one launch: pass_sample)
+            LH_LAUNCH(k_argmax_advance, dim3(1), dim3(1024), 0, ctx->stream, last_row, m.V, (StepParams*)nullptr, b->out_dev + (size_t)pod * b->out_cap, b->ids_dev + pod, 0);
+            LH_HIP(ctx, hipMemcpyAsync(b->tok_dev + pod, b->ids_dev + pod, 4, hipMemcpyDeviceToDevice, ctx->stream));
+        }
         if (logits_last_host) LH_HIP(ctx, hipMemcpyAsync(logits_last_host + (size_t)pod * m.V, last_row, (size_t)m.V * 4, hipMemcpyDeviceToHost, ctx->stream));
         return 0;
     };
@@ -2505,10 +2581,12 @@ static int batch_feed(Batch* b, const uint32_t* const* tokens, const uint32_t* n
             Plan* pp = b->pods[sg.pod];
             const uint32_t tok0 = sg.pos0 - past[sg.pod];
             LH_TRACE("feed_pass/solo/n%u", sg.n);
+            if (sample && (rc = pass_rings(ps))) return rc;
             if ((rc = plan_eval(pp, tokens[sg.pod] + tok0, nullptr, nullptr, sg.n, sg.pos0, logits_rows_host == nullptr))) return rc;
             // (last_row_only leaves the last row in its usual place, row n - 1; the rows in front of it are then not the caller's)
             if (logits_rows_host) { if ((rc = rows_done(sg.pod, tok0, sg.n, pp->logits))) return rc; }
             else if ((rc = rows_done(sg.pod, tok0 + sg.n - 1, 1, pp->logits + (size_t)(sg.n - 1) * m.V))) return rc;
+            if (sample && (rc = pass_sample(k, pp->logits + (size_t)(sg.n - 1) * m.V))) return rc;
             continue;
         }
         char* base = b->feed_dev + pass_off[k];
@@ -2526,11 +2604,13 @@ static int batch_feed(Batch* b, const uint32_t* const* tokens, const uint32_t* n
             for (uint32_t q = 0; q < ps.nblk; ++q) bc.n_blocks1 += fs.blocks[ps.blk0 + q].n == 1;
         }
         LH_TRACE("feed_pass/batched/n%u", ps.rows);
+        if (sample && (rc = pass_rings(ps))) return rc;
         if ((rc = plan_eval(p0, nullptr, nullptr, nullptr, ps.rows, 0, false, &bc))) return rc;
         for (uint32_t s = ps.seg0; s < ps.seg0 + ps.nseg; ++s) {   // before the next pass overwrites p0->logits
             const lh_feed_seg& sg = fs.segs[s];
             if ((rc = rows_done(sg.pod, sg.pos0 - past[sg.pod], sg.n, p0->logits + (size_t)sg.row0 * m.V))) return rc;
         }
+        if (sample && (rc = pass_sample(k, p0->logits))) return rc;
     }
     LH_LAUNCH(k_batch_feed_heads, dim3(1), dim3(64), 0, ctx->stream, b->out_dev, b->out_cap, (const uint32_t*)b->tok_dev, B);
     LH_HIP(ctx, hipGetLastError());
@@ -3409,7 +3489,14 @@ int lh_batch_feed(lh_batch* h, const uint32_t* const* tokens, const uint32_t* n_
                   float* logits_rows_host) {
     if (!h || !n_tokens) return LH_EINVAL;
     LH_HIP(h->b->ctx, hipSetDevice(h->b->ctx->device));
-    return batch_feed(h->b, tokens, n_tokens, past, ids_host, logits_last_host, logits_rows_host);
+    return batch_feed(h->b, tokens, n_tokens, past, nullptr, false, ids_host, logits_last_host, logits_rows_host);
+}
+
+int lh_batch_feed_sample(lh_batch* h, const uint32_t* const* tokens, const uint32_t* n_tokens, const uint32_t* past, const uint32_t* flags, uint32_t* ids_host,
+                         float* logits_last_host, float* logits_rows_host) {
+    if (!h || !n_tokens) return LH_EINVAL;
+    LH_HIP(h->b->ctx, hipSetDevice(h->b->ctx->device));
+    return batch_feed(h->b, tokens, n_tokens, past, flags, true, ids_host, logits_last_host, logits_rows_host);
 }
 
 int lh_feed_schedule(const uint32_t* n_tokens, const uint32_t* past, uint32_t rows, uint32_t solo_min, uint32_t qb, uint64_t sizes_ok, lh_feed_pass* passes,

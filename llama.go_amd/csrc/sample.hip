@@ -46,6 +46,28 @@ int sample_rows_launch(lh_ctx* ctx, const float* logits, uint32_t V, uint32_t n_
     return 0;
 }
 
+int sample_pods_launch(lh_ctx* ctx, const float* logits, uint32_t V, uint32_t n_jobs, const SampleJob* jobs, SampleState* ss, uint32_t* ring, uint32_t ring_cap,
+                       StepParams* sp, uint32_t* out, uint32_t out_cap, uint32_t* ids, uint32_t topk_hint) {
+    const bool small_k = topk_hint && topk_hint <= 64;
+    LH_TRACE("%s/n%u", small_k ? "k_sample_small_pods" : "k_sample_pods", n_jobs);
+    if (small_k && V <= 32u * 1024u)
+        LH_LAUNCH(k_sample_small_pods<32>, dim3(n_jobs), dim3(1024), 0, ctx->stream, logits, V, ss, ring, ring_cap, sp, out, out_cap, ids, jobs);
+    else if (small_k)
+        LH_LAUNCH(k_sample_small_pods<64>, dim3(n_jobs), dim3(1024), 0, ctx->stream, logits, V, ss, ring, ring_cap, sp, out, out_cap, ids, jobs);
+    else if (V <= 32u * 1024u)
+        LH_LAUNCH(k_sample_pods<32>, dim3(n_jobs), dim3(1024), 0, ctx->stream, logits, V, ss, ring, ring_cap, sp, out, out_cap, ids, jobs);
+    else
+        LH_LAUNCH(k_sample_pods<64>, dim3(n_jobs), dim3(1024), 0, ctx->stream, logits, V, ss, ring, ring_cap, sp, out, out_cap, ids, jobs);
+    LH_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
+int feed_ring_launch(lh_ctx* ctx, const FeedRingSeg* segs, uint32_t n_segs, const uint32_t* tok, SampleState* ss, uint32_t* ring, uint32_t ring_cap) {
+    LH_LAUNCH(k_feed_ring, dim3(n_segs), dim3(256), 0, ctx->stream, segs, tok, ss, ring, ring_cap);
+    LH_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
 }  // namespace lh
 
 using namespace lh;
@@ -119,5 +141,47 @@ extern "C" int lh_sample_top_p_top_k(lh_ctx* ctx, const float* logits, uint32_t 
     }
     hipFree(dev);
     if (e != hipSuccess) LH_FAIL(ctx, LH_EHIP, "lh_sample_top_p_top_k: %s", hipGetErrorString(e));
+    return LH_OK;
+}
+
+extern "C" int lh_sample_pods(lh_ctx* ctx, const float* logits_host, uint32_t n, uint32_t n_logits, const uint32_t* rings_host, uint32_t ring_size,
+                              const uint32_t* ring_pos, const uint64_t* draws, const lh_sample_params* sp, uint32_t* ids_out, uint32_t* rings_out,
+                              uint32_t* ring_pos_out) {
+    if (!ctx) return LH_EINVAL;
+    if (!logits_host || !rings_host || !ring_pos || !draws || !ids_out) LH_FAIL(ctx, LH_EINVAL, "lh_sample_pods: null argument");
+    if (n == 0 || n > 64) LH_FAIL(ctx, LH_EINVAL, "lh_sample_pods: %u pods outside 1..64", n);
+    if (ring_size == 0) LH_FAIL(ctx, LH_EINVAL, "lh_sample_pods: the lastNTokens ring needs at least one slot");
+    int rc;
+    if ((rc = sample_check(ctx, sp, n_logits))) return rc;
+    LH_HIP(ctx, hipSetDevice(ctx->device));
+    // one allocation: logits | rings | states | step parameters | output lists (one entry each) | ids
+    const size_t b_lg = (size_t)n * n_logits * 4, b_ring = (size_t)n * ring_size * 4;
+    const size_t o_ring = b_lg, o_st = (o_ring + b_ring + 15) & ~(size_t)15, o_sp = o_st + sizeof(SampleState) * 64, o_out = o_sp + sizeof(StepParams) * 64,
+                 o_ids = o_out + 4 * 64, total = o_ids + 4 * 64;
+    char* dev = nullptr;
+    LH_HIP(ctx, hipMalloc((void**)&dev, total));
+    SampleState st[64];
+    for (uint32_t i = 0; i < n; ++i) st[i] = SampleState{sp->top_k, sp->top_p, sp->temp, sp->repeat_penalty, sp->seed, draws[i], ring_size, ring_pos[i]};
+    uint32_t ids[64] = {};
+    hipError_t e = hipMemcpyAsync(dev, logits_host, b_lg, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dev + o_ring, rings_host, b_ring, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dev + o_st, st, sizeof(SampleState) * n, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(dev + o_sp, 0, o_ids - o_sp, ctx->stream);   // step 0 of a one-entry output list per pod
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // st and the caller's arrays are pageable host memory
+    if (e == hipSuccess) {
+        rc = sample_pods_launch(ctx, (const float*)dev, n_logits, n, nullptr, (SampleState*)(dev + o_st), (uint32_t*)(dev + o_ring), ring_size, (StepParams*)(dev + o_sp),
+                                (uint32_t*)(dev + o_out), 1, (uint32_t*)(dev + o_ids), sp->top_k);
+        if (rc) { hipFree(dev); return rc; }
+        e = hipMemcpyAsync(ids, dev + o_ids, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && rings_out) e = hipMemcpyAsync(rings_out, dev + o_ring, b_ring, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && ring_pos_out) e = hipMemcpyAsync(st, dev + o_st, sizeof(SampleState) * n, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    }
+    hipFree(dev);
+    if (e != hipSuccess) LH_FAIL(ctx, LH_EHIP, "lh_sample_pods: %s", hipGetErrorString(e));
+    for (uint32_t i = 0; i < n; ++i) {
+        ids_out[i] = ids[i];
+        if (ring_pos_out) ring_pos_out[i] = st[i].ring_pos;
+    }
     return LH_OK;
 }

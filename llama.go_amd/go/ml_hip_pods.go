@@ -298,12 +298,34 @@ func (bt *BatchHIP) Tick() []uint32 {
 // Feed: llama.Eval for any subset of the pods, packed into shared weight passes (lh_batch_feed): pod i evaluates tokens[i] at position
 // past[i] of its own cache; a pod with no tokens is not fed and goes on as if nothing had happened.  This is how a new job's prompt (past 0),
 // a next turn or a chunk of a long prompt enters a running batch without the other pods leaving the one-pass route.  Returns the ids of the
-// batch: for a fed pod the greedy id of its last fed row, which its next Tick evaluates.  Greedy batches only (no SetSampler).
+// batch: for a fed pod the greedy id of its last fed row, which its next Tick evaluates.  Greedy batches only (a batch behind SetSampler: FeedSample).
 func (bt *BatchHIP) Feed(tokens [][]uint32, past []uint32) []uint32 {
 	pp, nn, free := cPrompts(tokens)
 	defer free()
 	out := make([]uint32, len(bt.stages))
 	if rc := C.lh_batch_feed(bt.b, pp, nn, (*C.uint32_t)(unsafe.Pointer(&past[0])), (*C.uint32_t)(unsafe.Pointer(&out[0])), nil, nil); rc != 0 {
+		hipHalt(bt.ctx.hip.ctx)
+	}
+	return out
+}
+
+// FeedSample: Feed on a batch that samples (SetSampler), lh_batch_feed_sample.  flags[i] = C.LH_FEED_NEW makes pod i a new job (its lastNTokens ring
+// and draw counter restart, server.go:127-138; the prompt must arrive in this ONE call), C.LH_FEED_PENDING says tokens[i][0] is the pod's pending id
+// (in its ring already), 0 appends every fed token; flags == nil: all 0.  Returns the ids of the batch: for a fed pod the id sampled behind its last
+// fed row, which its next Tick evaluates.  Pods that are not fed keep their rings, counters and pending ids.
+func (bt *BatchHIP) FeedSample(tokens [][]uint32, past []uint32, flags []uint32) []uint32 {
+	pp, nn, free := cPrompts(tokens)
+	defer free()
+	out := make([]uint32, len(bt.stages))
+	if len(tokens) != len(bt.stages) || len(past) != len(bt.stages) || (len(flags) != 0 && len(flags) != len(bt.stages)) {
+		fmt.Printf("\n[HALT] FeedSample: tokens, past and flags (or no flags) need one entry per pod (%d)", len(bt.stages))
+		os.Exit(1)
+	}
+	var fl *C.uint32_t
+	if len(flags) > 0 {
+		fl = (*C.uint32_t)(unsafe.Pointer(&flags[0]))
+	}
+	if rc := C.lh_batch_feed_sample(bt.b, pp, nn, (*C.uint32_t)(unsafe.Pointer(&past[0])), fl, (*C.uint32_t)(unsafe.Pointer(&out[0])), nil, nil); rc != 0 {
 		hipHalt(bt.ctx.hip.ctx)
 	}
 	return out

@@ -1236,6 +1236,14 @@ int llamago_SampleRows(const float* logits, uint32_t n_rows, uint32_t n_logits, 
     if (lh_sample_rows(h, logits, n_rows, n_logits, ring, ring_size, ring_pos, tokens, &sp, draw0, ids_out)) return halt_rc(lh_last_error(h));
     return 0;
 }
+int llamago_SamplePods(const float* logits, uint32_t n, uint32_t n_logits, const uint32_t* rings, uint32_t ring_size, const uint32_t* ring_pos, const uint64_t* draws,
+                       uint32_t topK, float topP, float temp, float repeatPenalty, uint64_t seed, uint32_t* ids_out, uint32_t* rings_out, uint32_t* ring_pos_out) {
+    lh_ctx* h = model_ctx();
+    if (!h) return 1;
+    const lh_sample_params sp = {topK, topP, temp, repeatPenalty, seed};
+    if (lh_sample_pods(h, logits, n, n_logits, rings, ring_size, ring_pos, draws, &sp, ids_out, rings_out, ring_pos_out)) return halt_rc(lh_last_error(h));
+    return 0;
+}
 int llamago_SampleDecodeLookup(llama_context* c, llama_model* m, const uint32_t* prompt, uint32_t n_prompt, uint32_t n_predict, uint32_t ring_size, uint32_t topK,
                                float topP, float temp, float repeatPenalty, uint64_t seed, const lh_lookup_params* lp, uint32_t* out_tokens, lh_spec_stats* stats,
                                uint16_t* trace, uint32_t trace_cap) {
@@ -1360,6 +1368,11 @@ int llamago_BatchSetSampler(llama_batch* p, uint32_t topK, float topP, float tem
     if (lh_batch_set_sampler(p->b, &sp, ringSize, nullptr, nullptr)) return halt_rc(lh_last_error(hip));
     return 0;
 }
+int llamago_BatchClearSampler(llama_batch* p) {
+    if (!p) return halt_rc("llamago_BatchClearSampler: bad arguments");
+    if (lh_batch_set_sampler(p->b, nullptr, 0, nullptr, nullptr)) return halt_rc(lh_last_error(p->mlctx->hip));
+    return 0;
+}
 int llamago_BatchTick(llama_batch* p, uint32_t* ids_out) {
     if (!p || !ids_out) return halt_rc("llamago_BatchTick: bad arguments");
     lh_ctx* hip = p->mlctx->hip;
@@ -1381,6 +1394,14 @@ int llamago_BatchFeed(llama_batch* p, const uint32_t* const* tokens, const uint3
     if (!p || !n_tokens) return halt_rc("llamago_BatchFeed: bad arguments");
     lh_ctx* hip = p->mlctx->hip;
     if (lh_batch_feed(p->b, tokens, n_tokens, past, ids_out, logits_last, logits_rows)) return halt_rc(lh_last_error(hip));
+    return 0;
+}
+// lh_batch_feed_sample: the same on a batch whose ticks sample; flags [pods] (LH_FEED_NEW / LH_FEED_PENDING) or NULL
+int llamago_BatchFeedSample(llama_batch* p, const uint32_t* const* tokens, const uint32_t* n_tokens, const uint32_t* past, const uint32_t* flags, uint32_t* ids_out,
+                            float* logits_last, float* logits_rows) {
+    if (!p || !n_tokens) return halt_rc("llamago_BatchFeedSample: bad arguments");
+    lh_ctx* hip = p->mlctx->hip;
+    if (lh_batch_feed_sample(p->b, tokens, n_tokens, past, flags, ids_out, logits_last, logits_rows)) return halt_rc(lh_last_error(hip));
     return 0;
 }
 

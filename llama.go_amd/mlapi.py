@@ -556,6 +556,34 @@ def sample_rows(ml, logits, ring, ring_pos, tokens, topK=40, topP=0.95, temp=0.8
     return out[:n]
 
 
+def SamplePods(ml, logits, rings, ring_pos, draws, topK=40, topP=0.95, temp=0.8, repeatPenalty=1.10, seed=0):
+    """llamago_SamplePods: the pods of a sampled tick in one launch (lh_sample_pods; k_sample_pods / k_sample_small_pods).  logits [n][V]; rings [n][ring_size]
+    with ring_pos[i] ids appended so far; draws[i] = pod i's sampling call.  -> (ids [n], the rings behind the ids [n][ring_size], their ring_pos [n])."""
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    if lg.ndim == 1:
+        lg = lg[None, :]
+    n, V = lg.shape
+    rg = np.ascontiguousarray(rings, dtype=np.uint32)
+    rs = rg.size // n if n else 0
+    rg = rg.reshape(n, rs)
+    assert len(ring_pos) == n and len(draws) == n
+    f = ml.lib.llamago_SamplePods
+    f.restype = C.c_int
+    f.argtypes = [c_f32p, c_u32, c_u32, c_u32p, c_u32, c_u32p, C.POINTER(c_u64), c_u32, C.c_float, C.c_float, C.c_float, c_u64, c_u32p, c_u32p, c_u32p]
+    rp = (c_u32 * max(n, 1))(*[int(x) for x in ring_pos])
+    dr = (c_u64 * max(n, 1))(*[int(x) for x in draws])
+    out = np.zeros(max(n, 64), dtype=np.uint32)
+    rout = np.zeros((max(n, 1), max(rs, 1)), dtype=np.uint32)
+    pout = np.zeros(max(n, 64), dtype=np.uint32)
+    if f(lg.ctypes.data_as(c_f32p), n, V, rg.ctypes.data_as(c_u32p), rs, rp, dr, int(topK), topP, temp, repeatPenalty, int(seed), out.ctypes.data_as(c_u32p),
+         rout.ctypes.data_as(c_u32p), pout.ctypes.data_as(c_u32p)):
+        raise MLError(f"llamago_SamplePods: {ml.last_error()}")
+    return out[:n], rout[:n, :rs], pout[:n]
+
+
+FEED_NEW, FEED_PENDING = 1, 2   # include/llamahip.h: LH_FEED_NEW, LH_FEED_PENDING
+
+
 def _bind_extensions(ml):
     """Product-only entry points (no counterpart in the reference): resident decode loop, kernel timing, pipeline stage."""
     L = ml.lib
@@ -602,6 +630,8 @@ def _bind_extensions(ml):
     L.llamago_BatchSet.argtypes = [VP, c_u32p, c_u32p]
     L.llamago_BatchFeed.restype = C.c_int
     L.llamago_BatchFeed.argtypes = [VP, C.POINTER(c_u32p), c_u32p, c_u32p, c_u32p, c_f32p, c_f32p]
+    L.llamago_BatchFeedSample.restype = C.c_int
+    L.llamago_BatchFeedSample.argtypes = [VP, C.POINTER(c_u32p), c_u32p, c_u32p, c_u32p, c_u32p, c_f32p, c_f32p]
     L.llamago_FreePipeline.restype = None
     L.llamago_FreePipeline.argtypes = [VP]
     L.llamago_PipelineRun.restype = C.c_int
@@ -767,11 +797,8 @@ class Batch:
         if self.ml.lib.llamago_BatchSet(self.h, tk, ps):
             raise MLError(f"llamago_BatchSet: {self.ml.last_error()}")
 
-    def Feed(self, tokens_per_pod, past, want_logits=False, want_rows=False):
-        """lh_batch_feed: llama.Eval of tokens_per_pod[i] at position past[i] of pod i's cache for every pod with a non-empty list, packed into
-        shared weight passes; pods with an empty list are not fed.  Returns the list of ids (the greedy id of each fed pod's last row, None for
-        pods that were not fed), then - if asked for - the [pods][vocab] logits of the fed pods' last rows (other rows NaN) and the
-        [sum n][vocab] logits of every fed row, pods in index order."""
+    def _feed(self, name, tokens_per_pod, past, flags, want_logits, want_rows):
+        """The marshalling of llamago_BatchFeed / llamago_BatchFeedSample (flags is None: the entry point takes none)."""
         assert len(tokens_per_pod) == self.pods and len(past) == self.pods
         arrs = [(c_u32 * max(len(p), 1))(*[int(t) for t in p]) for p in tokens_per_pod]
         pp = (c_u32p * self.pods)(*[C.cast(a, c_u32p) if len(p) else None for a, p in zip(arrs, tokens_per_pod)])
@@ -781,9 +808,10 @@ class Batch:
         V = self.model.hp.vocabSize
         last = np.full((self.pods, V), np.nan, dtype=np.float32) if want_logits else None
         rows = np.empty((sum(len(p) for p in tokens_per_pod), V), dtype=np.float32) if want_rows else None
-        if self.ml.lib.llamago_BatchFeed(self.h, pp, nn, ps, out, last.ctypes.data_as(c_f32p) if want_logits else None,
-                                         rows.ctypes.data_as(c_f32p) if want_rows and rows.size else None):
-            raise MLError(f"llamago_BatchFeed: {self.ml.last_error()}")
+        args = [self.h, pp, nn, ps] + ([] if flags is None else [flags[0]])
+        args += [out, last.ctypes.data_as(c_f32p) if want_logits else None, rows.ctypes.data_as(c_f32p) if want_rows and rows.size else None]
+        if getattr(self.ml.lib, name)(*args):
+            raise MLError(f"{name}: {self.ml.last_error()}")
         res = ([int(out[i]) if len(p) else None for i, p in enumerate(tokens_per_pod)],)
         if want_logits:
             res += (last,)
@@ -791,12 +819,34 @@ class Batch:
             res += (rows,)
         return res if len(res) > 1 else res[0]
 
+    def Feed(self, tokens_per_pod, past, want_logits=False, want_rows=False):
+        """lh_batch_feed: llama.Eval of tokens_per_pod[i] at position past[i] of pod i's cache for every pod with a non-empty list, packed into
+        shared weight passes; pods with an empty list are not fed.  Returns the list of ids (the greedy id of each fed pod's last row, None for
+        pods that were not fed), then - if asked for - the [pods][vocab] logits of the fed pods' last rows (other rows NaN) and the
+        [sum n][vocab] logits of every fed row, pods in index order."""
+        return self._feed("llamago_BatchFeed", tokens_per_pod, past, None, want_logits, want_rows)
+
+    def FeedSample(self, tokens_per_pod, past, flags=None, want_logits=False, want_rows=False):
+        """lh_batch_feed_sample: Feed on a batch behind SetSampler.  flags[i]: FEED_NEW (pod i is a new job: ring and draw counter restart), FEED_PENDING
+        (tokens[i][0] is the pod's pending id, in its ring already) or 0; None = all 0.  Returns as Feed, the ids being the ones sampled behind each fed
+        pod's last row."""
+        assert flags is None or len(flags) == self.pods
+        fl = (c_u32 * self.pods)(*[int(x) for x in flags]) if flags is not None else None
+        return self._feed("llamago_BatchFeedSample", tokens_per_pod, past, (fl,), want_logits, want_rows)
+
     def SetSampler(self, topK=40, topP=0.95, temp=0.8, repeatPenalty=1.10, seed=0, ringSize=64):
         """lh_batch_set_sampler: the following ticks sample (SampleTopPTopK on the device) instead of taking the argmax; allowed mid-stream."""
         f = self.ml.lib.llamago_BatchSetSampler
         f.restype, f.argtypes = C.c_int, [VP, c_u32, C.c_float, C.c_float, C.c_float, C.c_uint64, c_u32]
         if f(self.h, topK, topP, temp, repeatPenalty, seed, ringSize):
             raise MLError(f"llamago_BatchSetSampler: {self.ml.last_error()}")
+
+    def ClearSampler(self):
+        """lh_batch_set_sampler(NULL): back to greedy ticks."""
+        f = self.ml.lib.llamago_BatchClearSampler
+        f.restype, f.argtypes = C.c_int, [VP]
+        if f(self.h):
+            raise MLError(f"llamago_BatchClearSampler: {self.ml.last_error()}")
 
     def Tick(self):
         """BatchHIP.Tick: one decode step of every pod in one pass over the weights; returns the ids produced."""

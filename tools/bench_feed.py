@@ -7,7 +7,14 @@
   c  one 64-token chunk behind 1984 cached tokens (ctx 2048): segment attention with QB = 2 / 4 / 8, the per-row kernels (LLAMAHIP_FEED_ROW_ATTN=1) and
      the pod's own Eval (LLAMAHIP_FEED_SOLO_MIN=1)
   d  one pod's n-token prompt, n = 65..256: batched passes against its solo Eval (sets FEED_SOLO_MIN)
+  --sample  the sampled batch (lh_batch_feed_sample, the one-launch sampled tick; results: profiles/feed_sample.txt), instead of the parts above:
+     sa  a sampled tick of 2 / 8 / 32 / 64 pods, topK 40: ONE sampler launch against LLAMAHIP_SAMPLE_PER_POD=1, same process and batch, alternating;
+         per variant the median over --reps (>= 5) runs of --ticks ticks from the same positions, and the spread (max - min) between the runs
+         (lh_batch_set rewinds the positions only: rings and draw counters go on, so the runs sample different states - the time does not depend on them)
+     sb  a 24-token job joins 32 sampled pods: one lh_batch_feed_sample against what there was before it - sampler off, lh_batch_feed, sampler on again
+         (which also empties every pod's ring and restarts its draw counter)
 usage: python tools/bench_feed.py [a b c d] [--layers 32] [--layers-c 8] [--reps 3] [--int8]
+       python tools/bench_feed.py --sample [--layers 32] [--reps 5] [--ticks 20]
 BENCH_B_ONLY=feed|tick (environment): part b measures that variant only - one variant per process under a profiler"""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,7 +28,12 @@ ap.add_argument("--layers", type=int, default=32)
 ap.add_argument("--layers-c", type=int, default=8)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--int8", action="store_true", help="part a on block-int8 weights too")
+ap.add_argument("--sample", action="store_true", help="the sampled-batch leg (sa, sb) instead of parts a-d")
+ap.add_argument("--ticks", type=int, default=20, help="--sample: ticks per timed run")
 args = ap.parse_args()
+if args.sample:
+    args.parts = ["sa", "sb"]
+    args.reps = max(args.reps, 5)
 prod = load_product()
 rng = np.random.default_rng(0)
 
@@ -90,6 +102,58 @@ if "b" in args.parts:
     only = os.environ.get("BENCH_B_ONLY", "")   # (profiling: one variant per process)
     print(json.dumps({"part": "b", "layers": args.layers, "pods": 32, "cached": 1000, "prompt_len": 24, "one_feed_ms": med(one_feed) if only != "tick" else None,
                       "eval_plus_tick_ms": med(eval_and_tick) if only != "feed" else None}), flush=True)
+    b.free()
+    m.free()
+
+if args.sample:
+    from llama_go_amd.mlapi import FEED_NEW
+    ctx, SMP = 256, dict(topK=40, topP=0.95, temp=0.8, repeatPenalty=1.1, seed=1)
+    m, hp = model(args.layers, ctx)
+
+    def switch(per_pod):
+        if per_pod:
+            os.environ["LLAMAHIP_SAMPLE_PER_POD"] = "1"
+        else:
+            os.environ.pop("LLAMAHIP_SAMPLE_PER_POD", None)
+
+    for P in (2, 8, 32, 64):
+        b = Batch(m, ctx, P)
+        b.Feed([toks(hp, 8) for _ in range(P)], [0] * P)
+        b.SetSampler(ringSize=ctx, **SMP)
+        runs = {False: [], True: []}
+        for rep in range(args.reps):
+            for per_pod in (False, True):
+                switch(per_pod)
+                b.Set(None, [8] * P)          # every run from the same positions
+                b.Tick(); b.Tick()            # the switch drops the captured tick: capture, one replay
+                t0 = time.perf_counter()
+                for _ in range(args.ticks):
+                    b.Tick()
+                runs[per_pod].append((time.perf_counter() - t0) / args.ticks * 1e3)
+        switch(False)
+        b.free()
+        mid = {k: sorted(v)[len(v) // 2] for k, v in runs.items()}
+        spread = {k: max(v) - min(v) for k, v in runs.items()}
+        print(json.dumps({"part": "sa", "layers": args.layers, "pods": P, "ticks_per_run": args.ticks, "runs": args.reps, "one_launch_tick_ms": round(mid[False], 4),
+                          "per_pod_tick_ms": round(mid[True], 4), "one_launch_spread_ms": round(spread[False], 4), "per_pod_spread_ms": round(spread[True], 4),
+                          "gain_us": round((mid[True] - mid[False]) * 1e3, 1),
+                          "one_launch_slower_than_spread": bool(mid[False] - mid[True] > max(spread.values()))}), flush=True)
+
+    b = Batch(m, ctx, 33)
+    b.SetSampler(ringSize=ctx, **SMP)
+    b.FeedSample([toks(hp, 64) for _ in range(32)] + [toks(hp, 24)], [0] * 33, [FEED_NEW] * 33)
+    new = toks(hp, 24)
+
+    def feed_sample():
+        b.FeedSample([[]] * 32 + [new], [0] * 33, [0] * 32 + [FEED_NEW])
+
+    def off_feed_on():
+        b.ClearSampler()
+        b.Feed([[]] * 32 + [new], [0] * 33)
+        b.SetSampler(ringSize=ctx, **SMP)
+
+    print(json.dumps({"part": "sb", "layers": args.layers, "pods": 32, "cached": 64, "prompt_len": 24, "runs": args.reps, "feed_sample_ms": med(feed_sample),
+                      "sampler_off_feed_on_ms": med(off_feed_on)}), flush=True)
     b.free()
     m.free()
 

@@ -33,6 +33,6 @@ bad = [k for k in kernels if k["scratch"] not in ("0", "?") or k["vspill"] not i
 for k in kernels:
     if flt and flt not in k["name"]:
         continue
-    print(f'{k["name"][:90]:90s} vgpr {k["vgpr"]:>4s} sgpr {k["sgpr"]:>4s} scratch {k["scratch"]:>5s} vgpr_spill {k["vspill"]:>3s} sgpr_spill {k["sspill"]:>3s}')
+    print(f'{k["name"][:90]:90s} vgpr {k["vgpr"]:>4s} sgpr {k["sgpr"]:>4s} lds {k["lds"]:>6s} scratch {k["scratch"]:>5s} vgpr_spill {k["vspill"]:>3s} sgpr_spill {k["sspill"]:>3s}')
 print(f"{len(kernels)} kernels, {len(bad)} with scratch or VGPR spills")
 sys.exit(1 if bad else 0)
