@@ -142,6 +142,14 @@ int llamago_BatchClearSampler(llama_batch* b);   /* lh_batch_set_sampler(NULL): 
  * flags NULL = all 0.  llamago_BatchFeed on such a batch stays refused. */
 int llamago_BatchFeedSample(llama_batch* b, const uint32_t* const* tokens, const uint32_t* n_tokens, const uint32_t* past, const uint32_t* flags, uint32_t* ids_out,
                             float* logits_last, float* logits_rows);
+/* lh_batch_decode_lookup: n_steps greedy ids per pod from (first_tokens[i], past[i]) through lookup-drafted verify passes of pods x R rows (the rule,
+ * the window condition past + n_steps + R - 1 <= ctxSize and the state left behind are stated in llamahip.h).  out [pods][n_steps]; optional: logits_last
+ * [pods][vocab] (the logits behind each pod's last id), stats [pods], trace [pods][trace_cap].  llamago_SpecAcceptPods: lh_spec_accept_pods, the accept
+ * step of such a pass alone on host arrays, on the model context's device. */
+int llamago_BatchDecodeLookup(llama_batch* b, const uint32_t* first_tokens, const uint32_t* past, uint32_t n_steps, const lh_lookup_params* lp, uint32_t* out,
+                              float* logits_last, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap);
+int llamago_SpecAcceptPods(const uint32_t* arg, const uint32_t* tok, uint32_t n_pods, uint32_t n_rows, const uint32_t* k, const uint32_t* pos, const uint32_t* produced,
+                           uint32_t n_steps, uint32_t ctx_size, uint32_t* a_out, uint32_t* pos_out, uint32_t* produced_out, uint32_t* pending_out, uint32_t* ids_out);
 /* lh_sample_pods: the multi-pod sampler of a sampled tick alone on host arrays, on the model context's device - row i of logits [n][n_logits] over ring i
  * of rings [n][ring_size] (ring_pos[i] ids appended so far) as sampling call draws[i]; rings_out / ring_pos_out (optional) = the rings behind the ids. */
 int llamago_SamplePods(const float* logits, uint32_t n, uint32_t n_logits, const uint32_t* rings, uint32_t ring_size, const uint32_t* ring_pos, const uint64_t* draws,

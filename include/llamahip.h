@@ -173,7 +173,7 @@ int lh_llama_eval(lh_llama* m, const uint32_t* tokens, uint32_t n, uint32_t past
  * end.  A single Eval past the window (lh_llama_eval, lh_llama_stage, lh_graph_compute) stays an error, as llama.Eval would panic. */
 int lh_llama_set_keep(lh_llama* m, uint32_t keep);
 /* The greedy rule of every route that picks ids on the device (lh_llama_decode_greedy, lh_llama_stage's argmax, lh_llama_verify,
- * lh_llama_decode_lookup, lh_batch_tick / _prompt / _feed): lowest index on ties; NaN as the checker's argmax_f32, i.e. the reference's
+ * lh_llama_decode_lookup, lh_batch_decode_lookup, lh_batch_tick / _prompt / _feed): lowest index on ties; NaN as the checker's argmax_f32, i.e. the reference's
  * `best = 0; if x[i] > x[best] { best = i }` loop - a NaN at index 0 wins the row, a NaN anywhere else is never taken.  +0 and -0 tie.
  * lh_argmax_rows is the op-level twin of lh_sample_top_p_top_k / lh_score_rows for the two kernels behind those routes: it uploads host
  * logits [n_rows][n_logits] packed (rows behind the first are 16-byte aligned only when n_logits % 4 == 0) and returns every row's id;
@@ -259,7 +259,7 @@ int lh_llama_score(lh_llama* m, const uint32_t* tokens, uint32_t n, uint32_t pas
  * is cut to k = min(len, limit); in the loop limit = min(ctx - n, remaining - 1), remaining = n_steps - ids produced so far, so a pass
  * never leaves the window and never produces more ids than asked. */
 typedef struct lh_lookup_params {
-    uint32_t draft_max;            /* K: 1..7 (block-int8: 1..3) */
+    uint32_t draft_max;            /* K: 1..7 (block-int8: 1..3; lh_batch_decode_lookup: 1..7 for both) */
     uint32_t ngram_max, ngram_min; /* 1 <= ngram_min <= ngram_max <= 8 */
     const uint32_t* corpus;        /* optional host tokens searched behind the window; NULL / 0 = none */
     uint32_t n_corpus;             /* <= 65536 */
@@ -372,6 +372,47 @@ int lh_batch_set_sampler(lh_batch* b, const lh_sample_params* sp, uint32_t ring_
  * row's prompt ran through lh_batch_prompt (or its Evals through its lh_llama with host ids); otherwise, and for a stage of a layer shard,
  * such a tick fails with LH_EINVAL before anything is enqueued. */
 int lh_batch_decode(lh_batch* b, const uint32_t* first_tokens, const uint32_t* past, uint32_t n_steps, uint32_t* out_tokens, float* logits_last_host);
+/* lh_batch_decode through lookup-drafted verify passes (the draft rule of lh_lookup_params, per pod over the pod's own window; ONE corpus for all pods):
+ * speculation and the shared weight stream at once.  Greedy only, whole-model batches, weight_dtype 0 and 7.  With P = the number of pods, every pass has
+ * P * R rows: row i * R + r is row r of pod i, on pod i's cache at position pos_i + r, holding [pending_i, d_1..d_k, filler = pending_i] - the order in
+ * which lh_batch_feed lays out P pods fed R tokens each.  R = draft_max + 1, lowered to the largest R with P * R <= 64 whose row count shares one weight
+ * pass on this plan (the predicate behind the feed's sizes_ok); a batch of two or more pods that is not lh_batch_batched takes R = 1.  R = 1 = plain
+ * ticks (the lh_batch_decode route); stats[i].rows reports R.  draft_max is 1..7 for both weight types.
+ * Per pod and pass: limit = min(ctx - n, remaining_i - 1); a = the leading i < k with argmax(row i) == tok[i + 1] (fillers never count), clipped by what
+ * the pod still needs; ids arg[0..a] go to its output list and window.  A pod with n_steps ids is finished: its rows stay in the pass as filler (they
+ * re-evaluate the tokens of its finishing pass at their positions) and its state, output list and window no longer change.  Every pass gives every
+ * unfinished pod 1..R ids, so the host enqueues ceil((n_steps - min_i produced_i) / R) passes - one captured graph: the batched Eval, k_batch_argmax,
+ * k_spec_accept_pods - reads 16 bytes per pod and repeats; it never enqueues a pass that could find every pod finished.
+ * The loop never leaves the window and never swaps context: past[i] + n_steps + R - 1 <= ctx must hold for every pod (LH_EINVAL otherwise), so no row
+ * of any pass stands past the window; the caller takes the last R - 1 positions with ticks.
+ * Contract:
+ *  1. the rows of a pass are byte-equal to the rows lh_batch_feed computes for the same tokens and positions with LLAMAHIP_FEED_ROW_ATTN=1 (the same
+ *     launch sequence);
+ *  2. where P * R <= 8 (fp32) or <= 4 (block-int8) the ids equal lh_batch_decode's and each pod's solo lh_llama_decode_greedy, and for fp32
+ *     logits_last_host is byte-equal too (the bit-identity of the rows path);
+ *  3. beyond, the ids are the greedy ids of the passes' own logits, at the tolerance of ticks of more than 8 pods.  No more is claimed.
+ * out_tokens [rows][n_steps] as lh_batch_decode; logits_last_host (optional) [rows][vocab] = the logits behind each pod's LAST id (row a of its finishing
+ * pass); stats (optional) [rows]; trace (optional) [rows][trace_cap]: (k << 8) | a per pass of that pod.
+ * Afterwards the batch stands as lh_batch_decode(first_tokens, past, n_steps) leaves it: positions past + n_steps (host mirror included), each pod's last
+ * id pending in lh_batch_tokens_dev, lh_batch_ids_dev and entry 0 of its output list (lh_batch_feed's conventions), every evaluated token in the pods'
+ * histories; cache rows behind each position are stale and are overwritten by whatever runs next.
+ * Refused before anything is enqueued, the batch left exactly as it was: the window condition, bad lookup parameters, a corpus id or first token >= vocab,
+ * n_steps == 0, a null required argument (LH_EINVAL); a batch with a sampler set, a batch of layer-shard stages (LH_EUNSUPPORTED).
+ * Out of scope: sampled batches, a context swap or shrinking passes at the window's end, segment attention for the pass, per-pod n_steps or corpora. */
+int lh_batch_decode_lookup(lh_batch* b, const uint32_t* first_tokens, const uint32_t* past, uint32_t n_steps, const lh_lookup_params* lp,
+                           uint32_t* out_tokens,        /* [rows][n_steps], as lh_batch_decode */
+                           float* logits_last_host,     /* optional [rows][vocab] */
+                           lh_spec_stats* stats,        /* optional [rows] */
+                           uint16_t* trace,             /* optional [rows][trace_cap] */
+                           uint32_t trace_cap);
+/* The accept step of such a pass on its own (op-level twin of k_spec_accept_pods, host in / host out like lh_draft_lookup): arg [n_pods][n_rows] = the
+ * greedy ids of the pass's rows, tok [n_pods][n_rows] = the tokens they evaluated, k[i] = pod i's draft length, pos[i] / produced[i] its state in front
+ * of the pass.  ONE launch, no drafting.  a_out[i] = the accepted count, pos_out / produced_out / pending_out the state behind the pass, ids_out
+ * [n_pods][n_rows] = the ids appended to pod i's list (entries behind them 0xFFFFFFFF).  A finished pod (produced[i] >= n_steps) comes back unchanged.
+ * n_pods outside 1..64, n_rows outside 1..8, n_pods * n_rows > 64, ctx_size == 0, a null argument: LH_EINVAL. */
+int lh_spec_accept_pods(lh_ctx* ctx, const uint32_t* arg, const uint32_t* tok, uint32_t n_pods, uint32_t n_rows, const uint32_t* k, const uint32_t* pos,
+                        const uint32_t* produced, uint32_t n_steps, uint32_t ctx_size, uint32_t* a_out, uint32_t* pos_out, uint32_t* produced_out,
+                        uint32_t* pending_out, uint32_t* ids_out);
 /* llama.Eval for any subset of the pods, packed into shared weight passes of <= 64 rows (whole-model batches, greedy).
  * Pod i evaluates tokens[i][0..n_tokens[i]) at positions past[i].. of ITS cache.
  * n_tokens[i] == 0: pod i is not fed (tokens[i], past[i] ignored).

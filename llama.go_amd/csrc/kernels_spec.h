@@ -184,4 +184,116 @@ __global__ __launch_bounds__(SPEC_TH) void k_spec_accept(const uint32_t* __restr
     if (r == 0) st->k = k;
 }
 
+// ---- the pods of a batch (lh_batch_decode_lookup): pod i owns rows [i * R, (i + 1) * R) of the pass's table, state st[i] and window win[i][ctx + 1] ----
+// What the host reads between runs of passes: 16 bytes per pod.
+struct SpecPodSum { uint32_t pos, produced, passes, last_a; };
+struct SpecPodsArgs {
+    const uint32_t* arg;      // [P * R] greedy ids of the pass's rows
+    SpecState* st;            // [P]
+    BatchRow* rows;           // [P * R]
+    uint32_t* tok;            // [P * R] per pod: pending, draft, filler
+    uint32_t* win;            // [P][ctx + 1]; nullptr (op-level twin): no window is kept
+    uint32_t* out;            // [P][out_cap] output lists
+    uint16_t* trace;          // [P][trace_cap], may be nullptr
+    const float* logits;      // [P * R][vocab] of the pass, may be nullptr
+    float* last;              // [P][vocab]: the logits behind each pod's last id, may be nullptr
+    uint32_t* pend;           // [P] the pods' pending ids (the batch's token array), may be nullptr
+    uint32_t* ids;            // [P] the same (the batch's array of produced ids), may be nullptr
+    SpecPodSum* sum;          // [P]
+    uint32_t R, ctx, vocab, out_cap, trace_cap;
+};
+struct SpecPodsSet { uint32_t pos[64]; uint32_t tok[64]; };
+
+// State, table rows and tokens of every pod from kernel arguments; the caches come from the batch's own row table.  One workgroup per pod.
+__global__ void k_spec_set_pods(const SpecPodsArgs A, const BatchRow* __restrict__ pods, const SpecPodsSet v, uint32_t n_steps) {
+    const uint32_t i = blockIdx.x, r = threadIdx.x, pos = v.pos[i];
+    if (r < A.R) {
+        const uint32_t q = pos + r;
+        BatchRow* row = A.rows + (size_t)i * A.R + r;
+        row->kc = pods[i].kc; row->vc = pods[i].vc; row->pos = q < A.ctx ? q : A.ctx - 1; row->step = 0;
+        A.tok[(size_t)i * A.R + r] = v.tok[i];
+    }
+    if (r == 0) {
+        SpecState* st = A.st + i;
+        st->pos = pos; st->produced = 0; st->n_steps = n_steps; st->k = 0; st->last_a = 0;
+        st->passes = 0; st->drafted = 0; st->accepted = 0; st->empty = 0;
+        A.sum[i] = SpecPodSum{pos, 0u, 0u, 0u};
+    }
+}
+
+// The first draft of every pod: the rule over win[i][0..pos_i], ids into the pod's rows 1.., the pending token as filler behind them.
+__global__ __launch_bounds__(SPEC_TH) void k_draft_lookup_pods(const SpecPodsArgs A, const SpecLookup lp) {
+    __shared__ int s_best;
+    const uint32_t i = blockIdx.x;
+    SpecState* st = A.st + i;
+    uint32_t* tok = A.tok + (size_t)i * A.R;
+    uint32_t n = st->pos + 1, limit = spec_limit(st->pos, st->produced, st->n_steps, A.ctx);
+    if (n > A.ctx + 1) { n = 0; limit = 0; }
+    const uint32_t k = spec_lookup(A.win + (size_t)i * (A.ctx + 1), n, lp, limit, A.vocab, tok + 1, &s_best);
+    const uint32_t r = threadIdx.x;
+    if (r > k && r < A.R) tok[r] = tok[0];
+    if (r == 0) st->k = k;
+}
+
+// k_spec_accept for every pod of a pass, one workgroup per pod: the same accept rule over the pod's R ids, its output list, window, counters and trace.
+// A pod that still needs ids moves its R table rows and its pending token on and (lookup_next) drafts its next pass.  A pod that FINISHES in this pass
+// copies logits row a (the logits behind its last id) to last[i] and leaves its table rows and tokens where they are: as filler of the later passes they
+// re-evaluate the same tokens at the same positions, so no row ever stands past the window.  A finished pod changes nothing.  Every index written is
+// clamped to its buffer, as in k_spec_accept.
+__global__ __launch_bounds__(SPEC_TH) void k_spec_accept_pods(const SpecPodsArgs A, const SpecLookup lp, int lookup_next) {
+    __shared__ int s_best;
+    __shared__ uint32_t s_pos, s_done, s_fin, s_a;
+    const uint32_t i = blockIdx.x, R = A.R;
+    SpecState* st = A.st + i;
+    const uint32_t* arg = A.arg + (size_t)i * R;
+    uint32_t* tok = A.tok + (size_t)i * R;
+    uint32_t* win = A.win ? A.win + (size_t)i * (A.ctx + 1) : nullptr;
+    if (threadIdx.x == 0) {
+        const uint32_t p = st->pos, produced = st->produced, n_steps = st->n_steps;
+        s_done = 1; s_fin = 0; s_a = 0; s_pos = p;
+        if (produced < n_steps && p < A.ctx && R >= 1) {
+            uint32_t k = st->k;
+            if (k > R - 1) k = R - 1;
+            uint32_t a = 0;
+            while (a < k && arg[a] == tok[a + 1]) ++a;
+            if (a > n_steps - produced - 1) a = n_steps - produced - 1;
+            if (a > A.ctx - 1 - p) a = A.ctx - 1 - p;
+            for (uint32_t j = 0; j <= a; ++j) {
+                if (produced + j < A.out_cap) A.out[(size_t)i * A.out_cap + produced + j] = arg[j];
+                if (win) win[p + 1 + j] = arg[j];   // win has ctx + 1 entries
+            }
+            const uint32_t s = st->passes;
+            if (A.trace && s < A.trace_cap) A.trace[(size_t)i * A.trace_cap + s] = (uint16_t)((k << 8) | a);
+            st->passes = s + 1; st->drafted += k; st->accepted += a; st->empty += k == 0 ? 1u : 0u;
+            st->last_a = a; st->produced = produced + a + 1;
+            const uint32_t np = p + a + 1;
+            st->pos = np;
+            if (A.pend) A.pend[i] = arg[a];
+            if (A.ids) A.ids[i] = arg[a];
+            const bool fin = produced + a + 1 >= n_steps;
+            if (!fin) tok[0] = arg[a];
+            s_pos = np; s_a = a; s_done = fin ? 1u : 0u; s_fin = fin ? 1u : 0u;
+        }
+    }
+    __syncthreads();
+    const uint32_t np = s_pos;
+    if (s_fin && A.logits && A.last) {
+        const float* src = A.logits + ((size_t)i * R + s_a) * A.vocab;
+        float* dst = A.last + (size_t)i * A.vocab;
+        for (uint32_t j = threadIdx.x; j < A.vocab; j += SPEC_TH) dst[j] = src[j];
+    }
+    if (!s_done && threadIdx.x < R) {
+        const uint32_t q = np + threadIdx.x;
+        A.rows[(size_t)i * R + threadIdx.x].pos = q < A.ctx ? q : A.ctx - 1;
+    }
+    uint32_t k = 0;
+    if (lookup_next && !s_done && win) k = spec_lookup(win, np + 1, lp, spec_limit(np, st->produced, st->n_steps, A.ctx), A.vocab, tok + 1, &s_best);
+    const uint32_t r = threadIdx.x;
+    if (lookup_next && !s_done && r > k && r < R) tok[r] = tok[0];
+    if (r == 0) {
+        if (lookup_next && !s_done) st->k = k;
+        A.sum[i] = SpecPodSum{st->pos, st->produced, st->passes, st->last_a};
+    }
+}
+
 }  // namespace lh

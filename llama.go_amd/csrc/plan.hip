@@ -2182,6 +2182,7 @@ int plan_eval(Plan* p, const uint32_t* tokens_host, const float* x_in_dev, float
 // tiles accumulates on its own), so a stream decodes the same ids whoever shares its tick.
 // One tick = one captured hipGraph (token ids, positions and the residual stream live at fixed device addresses; the graph itself moves the
 // positions on), so a tick costs the host one hipGraphLaunch whatever the stage's length.
+struct BatchSpec;
 struct Batch {
     lh_ctx* ctx = nullptr;
     std::vector<Plan*> pods;
@@ -2226,6 +2227,7 @@ struct Batch {
     char* feed_dev = nullptr;
     size_t feed_cap = 0;
     float* feed_part = nullptr;
+    BatchSpec* spec = nullptr;     // lh_batch_decode_lookup: device state + the captured pass
     float* logits() const { return batched || B == 1 ? pods[0]->logits : logits_own; }
 };
 
@@ -2320,11 +2322,13 @@ static int batch_tick_unchecked(Batch* b, const float* x_in, float* x_out) {
     return 0;
 }
 
+static void batch_spec_free(Batch* b);
 static void batch_free(Batch* b) {
     if (!b) return;
     hipSetDevice(b->ctx->device);
     hipStreamSynchronize(b->ctx->stream);
     batch_drop_graph(b);
+    batch_spec_free(b);
     void* bufs[] = {b->rows_dev, b->tok_dev, b->ids_dev, b->out_dev, b->sp_dev, b->logits_own, b->attn_part, b->ss_dev, b->ring_dev, b->feed_dev, b->feed_part};
     for (void* q : bufs) if (q) hipFree(q);
     delete b;
@@ -2872,6 +2876,218 @@ static int spec_decode_lookup(Plan* p, uint32_t first_token, uint32_t past, uint
     LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (n_tr) memcpy(trace, tr.data(), (size_t)n_tr * 2);
     if (stats) { stats->passes = hs.passes; stats->rows = R; stats->drafted = hs.drafted; stats->accepted = hs.accepted; stats->empty = hs.empty; }
+    return 0;
+}
+
+// ---- lh_batch_decode_lookup: the same loop for the pods of a batch -------------------------------------------------------------------
+// A pass = the batched plan_eval of P * R rows on pod 0's plan (row i * R + r = row r of pod i, on pod i's cache: the table lh_batch_feed lays out for
+// P pods fed R tokens each, with the per-row attention kernels), k_batch_argmax over the P * R logits rows, k_spec_accept_pods.  One captured graph.
+struct BatchSpec {
+    SpecState* st = nullptr;           // [B]
+    SpecPodSum* sum = nullptr;         // [B]
+    BatchRow* rows = nullptr;          // [BATCH_ROWS_MAX]
+    uint32_t* tok = nullptr;           // [BATCH_ROWS_MAX]
+    uint32_t* arg = nullptr;           // [BATCH_ROWS_MAX]
+    uint32_t* win = nullptr;           // [B][ctx + 1]
+    float* last = nullptr;             // [B][V]
+    float* part = nullptr;             // split-T attention partials for BATCH_ROWS_MAX rows (plans with ctx > 256)
+    uint32_t* corpus = nullptr;
+    uint32_t corpus_cap = 0;
+    uint16_t* trace = nullptr;         // [B][trace_cap]
+    uint32_t trace_cap = 0;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    // what the captured pass holds by value
+    uint32_t cap_R = 0, cap_trace_cap = 0;
+    SpecLookup cap_lp = {};
+    uint16_t* cap_trace = nullptr;
+    uint64_t cap_splitk_gen = 0, cap_scratch_gen = 0;
+    uint64_t warm = 0;                 // bit n - 1: a pass of n rows has run eagerly
+};
+static void batch_spec_drop_graph(BatchSpec* s) {
+    if (s->exec) { hipGraphExecDestroy(s->exec); s->exec = nullptr; }
+    if (s->graph) { hipGraphDestroy(s->graph); s->graph = nullptr; }
+}
+static void batch_spec_free(Batch* b) {
+    BatchSpec* s = b->spec;
+    if (!s) return;
+    batch_spec_drop_graph(s);
+    void* bufs[] = {s->st, s->sum, s->rows, s->tok, s->arg, s->win, s->last, s->part, s->corpus, s->trace};
+    for (void* q : bufs) if (q) hipFree(q);
+    delete s;
+    b->spec = nullptr;
+}
+// every allocation of the route, outside any capture
+static int batch_spec_ensure(Batch* b, uint32_t n_corpus, uint32_t n_trace) {
+    lh_ctx* ctx = b->ctx;
+    Plan* p0 = b->pods[0];
+    const ModelDesc& m = p0->md;
+    const uint32_t B = b->B;
+    if (!b->spec) b->spec = new BatchSpec();
+    BatchSpec* s = b->spec;
+    if (!s->st) {
+        LH_HIP(ctx, hipMalloc((void**)&s->st, sizeof(SpecState) * B));
+        LH_HIP(ctx, hipMalloc((void**)&s->sum, sizeof(SpecPodSum) * B));
+        LH_HIP(ctx, hipMalloc((void**)&s->rows, sizeof(BatchRow) * BATCH_ROWS_MAX));
+        LH_HIP(ctx, hipMalloc((void**)&s->tok, 4 * (size_t)BATCH_ROWS_MAX));
+        LH_HIP(ctx, hipMalloc((void**)&s->arg, 4 * (size_t)BATCH_ROWS_MAX));
+        LH_HIP(ctx, hipMalloc((void**)&s->win, 4 * (size_t)B * ((size_t)m.ctx + 1)));
+        LH_HIP(ctx, hipMalloc((void**)&s->last, 4 * (size_t)B * m.V));
+        if (p0->attn_part) LH_HIP(ctx, hipMalloc((void**)&s->part, 4 * (size_t)BATCH_ROWS_MAX * m.H * ((m.ctx + ATT_TC - 1) / ATT_TC) * (m.hd + 2)));
+    }
+    if (n_corpus > s->corpus_cap) {
+        LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (s->corpus) LH_HIP(ctx, hipFree(s->corpus));
+        s->corpus = nullptr; s->corpus_cap = 0;
+        LH_HIP(ctx, hipMalloc((void**)&s->corpus, 4 * (size_t)n_corpus));
+        s->corpus_cap = n_corpus;
+    }
+    if (n_trace > s->trace_cap) {
+        LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (s->trace) LH_HIP(ctx, hipFree(s->trace));
+        s->trace = nullptr; s->trace_cap = 0;
+        const uint32_t cap = std::max(n_trace, 256u);
+        LH_HIP(ctx, hipMalloc((void**)&s->trace, 2 * (size_t)B * cap));
+        s->trace_cap = cap;
+    }
+    return 0;
+}
+// rows per pod and pass: draft_max + 1, lowered to the largest R whose P * R rows share one weight pass on this plan; 1 = plain ticks.
+// (A batch of one pod is never `batched` - one row needs no table - but its R rows are a batched Eval like any other.)
+static uint32_t batch_spec_rows(const Batch* b, uint32_t draft_max) {
+    if (!b->batched && b->B > 1) return 1;
+    uint32_t R = draft_max + 1;
+    while (R > 1 && (b->B * R > BATCH_ROWS_MAX || !plan_batch_rows_ok(b->pods[0], b->B * R))) --R;
+    return R;
+}
+static SpecPodsArgs batch_spec_args(const Batch* b, uint32_t R) {
+    const BatchSpec* s = b->spec;
+    const ModelDesc& m = b->pods[0]->md;
+    SpecPodsArgs a = {};
+    a.arg = s->arg; a.st = s->st; a.rows = s->rows; a.tok = s->tok; a.win = s->win; a.out = b->out_dev; a.trace = s->trace;
+    a.logits = b->pods[0]->logits; a.last = s->last; a.pend = b->tok_dev; a.ids = b->ids_dev; a.sum = s->sum;
+    a.R = R; a.ctx = m.ctx; a.vocab = m.V; a.out_cap = b->out_cap; a.trace_cap = s->trace_cap;
+    return a;
+}
+// the kernels of one pass, in stream order
+static int batch_spec_enqueue_pass(Batch* b, uint32_t R, const SpecLookup& lp) {
+    lh_ctx* ctx = b->ctx;
+    Plan* p0 = b->pods[0];
+    const ModelDesc& m = p0->md;
+    BatchSpec* s = b->spec;
+    const uint32_t n = b->B * R;
+    int rc;
+    BatchCtx bc = {s->rows, s->tok, p0->attn_part ? s->part : nullptr};
+    if ((rc = plan_eval(p0, nullptr, nullptr, nullptr, n, 0, false, &bc))) return rc;
+    LH_LAUNCH(k_batch_argmax, dim3(n), dim3(1024), 0, ctx->stream, (const float*)p0->logits, m.V, (BatchRow*)nullptr, (uint32_t*)nullptr, s->arg, (uint32_t*)nullptr, 0u,
+              (StepParams*)nullptr, 0);
+    LH_LAUNCH(k_spec_accept_pods, dim3(b->B), dim3(SPEC_TH), 0, ctx->stream, batch_spec_args(b, R), lp, 1);
+    LH_HIP(ctx, hipGetLastError());
+    return 0;
+}
+// one pass: eagerly the first time, then the captured graph (re-captured when a value it holds has changed)
+static int batch_spec_pass(Batch* b, uint32_t R, const SpecLookup& lp) {
+    lh_ctx* ctx = b->ctx;
+    BatchSpec* s = b->spec;
+    const uint64_t bit = 1ull << (b->B * R - 1);
+    if (!b->pods[0]->use_graph || !(s->warm & bit)) {
+        s->warm |= bit;
+        return batch_spec_enqueue_pass(b, R, lp);
+    }
+    if (s->exec && (s->cap_R != R || memcmp(&s->cap_lp, &lp, sizeof lp) || s->cap_trace != s->trace || s->cap_trace_cap != s->trace_cap || s->cap_splitk_gen != ctx->splitk_gen ||
+                    s->cap_scratch_gen != b->scratch_gen()))
+        batch_spec_drop_graph(s);
+    if (!s->exec) {
+        LH_HIP(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeRelaxed));
+        const int rc = batch_spec_enqueue_pass(b, R, lp);
+        hipError_t e = hipStreamEndCapture(ctx->stream, &s->graph);
+        if (rc) { if (s->graph) { hipGraphDestroy(s->graph); s->graph = nullptr; } return rc; }
+        if (e != hipSuccess) LH_FAIL(ctx, LH_EHIP, "hipStreamEndCapture (batch speculative pass): %s", hipGetErrorString(e));
+        LH_HIP(ctx, hipGraphInstantiate(&s->exec, s->graph, nullptr, nullptr, 0));
+        s->cap_R = R; s->cap_lp = lp; s->cap_trace = s->trace; s->cap_trace_cap = s->trace_cap; s->cap_splitk_gen = ctx->splitk_gen; s->cap_scratch_gen = b->scratch_gen();
+    }
+    LH_HIP(ctx, hipGraphLaunch(s->exec, ctx->stream));
+    return 0;
+}
+
+// The loop behind lh_batch_decode_lookup; the caller has checked every argument and R >= 2.
+static int batch_decode_lookup(Batch* b, const uint32_t* first_tokens, const uint32_t* past, uint32_t n_steps, const lh_lookup_params* lpar, uint32_t R, uint32_t* out_tokens,
+                               float* logits_last_host, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap) {
+    lh_ctx* ctx = b->ctx;
+    Plan* p0 = b->pods[0];
+    const ModelDesc& m = p0->md;
+    const uint32_t B = b->B, W = m.ctx + 1;
+    int rc;
+    const uint32_t n_corpus = lpar->corpus ? lpar->n_corpus : 0;
+    // ---- every allocation first: none inside a capture
+    if ((rc = batch_spec_ensure(b, n_corpus, n_steps))) return rc;
+    if ((rc = plan_ensure_rows(p0, B * R))) return rc;   // (the captured tick re-captures on scratch_gen)
+    const size_t win_bytes = 4 * (size_t)B * W;
+    if ((rc = ensure_staging(ctx, win_bytes + 4 * (size_t)n_corpus))) return rc;
+    BatchSpec* s = b->spec;
+    // what the ticks so far did goes into the pods' histories (and waits for the stream: the staging buffer is free)
+    if (b->pos_known) { if ((rc = batch_drain(b))) return rc; }
+    else LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    // ---- windows (positions [0, past_i) from the pod's history, the pending token behind them) and corpus: one upload each
+    uint32_t* hw = (uint32_t*)ctx->staging;
+    SpecPodsSet v = {};
+    for (uint32_t i = 0; i < B; ++i) {
+        const Plan* p = b->pods[i];
+        uint32_t* h = hw + (size_t)i * W;
+        for (uint32_t j = 0; j < W; ++j) h[j] = (j < past[i] && p->hist && j < p->hist->size()) ? (*p->hist)[j] : Plan::HIST_UNKNOWN;
+        h[past[i]] = first_tokens[i];
+        v.pos[i] = past[i]; v.tok[i] = first_tokens[i];
+    }
+    LH_HIP(ctx, hipMemcpyAsync(s->win, hw, win_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (n_corpus) {
+        memcpy(ctx->staging + win_bytes, lpar->corpus, (size_t)n_corpus * 4);
+        LH_HIP(ctx, hipMemcpyAsync(s->corpus, ctx->staging + win_bytes, (size_t)n_corpus * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+    const SpecLookup lp = {n_corpus ? s->corpus : nullptr, n_corpus, R - 1, lpar->ngram_max, lpar->ngram_min};
+    const SpecPodsArgs args = batch_spec_args(b, R);
+    LH_LAUNCH(k_spec_set_pods, dim3(B), dim3(64), 0, ctx->stream, args, (const BatchRow*)b->rows_dev, v, n_steps);
+    LH_LAUNCH(k_draft_lookup_pods, dim3(B), dim3(SPEC_TH), 0, ctx->stream, args, lp);
+    LH_HIP(ctx, hipGetLastError());
+    // ---- the passes.  Every pass gives every unfinished pod 1..R ids, so with `low` = the least count any pod has for certain, ceil((n_steps - low) / R)
+    // passes cannot find every pod finished before the last of them; then one look at 16 bytes per pod.
+    std::vector<SpecPodSum> hs(B);
+    uint32_t low = 0;
+    while (low < n_steps) {
+        const uint32_t q = (n_steps - low + R - 1) / R;
+        for (uint32_t j = 0; j < q; ++j) if ((rc = batch_spec_pass(b, R, lp))) return rc;
+        LH_HIP(ctx, hipMemcpyAsync(hs.data(), s->sum, sizeof(SpecPodSum) * B, hipMemcpyDeviceToHost, ctx->stream));
+        LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        uint32_t now = n_steps;
+        for (uint32_t i = 0; i < B; ++i) now = std::min(now, hs[i].produced);
+        if (now < std::min(n_steps, low + q)) LH_FAIL(ctx, LH_EHIP, "lh_batch_decode_lookup: a pass produced no id for a pod");
+        low = now;
+    }
+    // ---- results, then the state lh_batch_feed leaves: every pod behind its last evaluated token, its last id pending
+    std::vector<uint32_t> out((size_t)B * n_steps);
+    std::vector<SpecState> st(B);
+    LH_HIP(ctx, hipMemcpy2DAsync(out.data(), (size_t)n_steps * 4, b->out_dev, (size_t)b->out_cap * 4, (size_t)n_steps * 4, B, hipMemcpyDeviceToHost, ctx->stream));
+    LH_HIP(ctx, hipMemcpyAsync(st.data(), s->st, sizeof(SpecState) * B, hipMemcpyDeviceToHost, ctx->stream));
+    if (logits_last_host) LH_HIP(ctx, hipMemcpyAsync(logits_last_host, s->last, 4 * (size_t)B * m.V, hipMemcpyDeviceToHost, ctx->stream));
+    const uint32_t n_tr = trace ? std::min(std::min(trace_cap, n_steps), s->trace_cap) : 0;
+    std::vector<uint16_t> tr((size_t)B * n_tr);
+    if (n_tr) LH_HIP(ctx, hipMemcpy2DAsync(tr.data(), (size_t)n_tr * 2, s->trace, (size_t)s->trace_cap * 2, (size_t)n_tr * 2, B, hipMemcpyDeviceToHost, ctx->stream));
+    LH_LAUNCH(k_batch_feed_heads, dim3(1), dim3(64), 0, ctx->stream, b->out_dev, b->out_cap, (const uint32_t*)b->tok_dev, B);
+    LH_HIP(ctx, hipGetLastError());
+    std::vector<uint32_t> newpos(B);
+    for (uint32_t i = 0; i < B; ++i) newpos[i] = past[i] + n_steps;
+    if ((rc = batch_set(b, nullptr, newpos.data(), 1))) return rc;
+    LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint32_t i = 0; i < B; ++i) {
+        if (st[i].produced != n_steps || st[i].pos != newpos[i]) LH_FAIL(ctx, LH_EHIP, "lh_batch_decode_lookup: the accept step left pod %u in an inconsistent state", i);
+        const uint32_t* o = out.data() + (size_t)i * n_steps;
+        for (uint32_t t = 0; t < n_steps; ++t) b->pods[i]->record(past[i] + t, t ? o[t - 1] : first_tokens[i]);
+        memcpy(out_tokens + (size_t)i * n_steps, o, (size_t)n_steps * 4);
+        if (stats) stats[i] = lh_spec_stats{st[i].passes, R, st[i].drafted, st[i].accepted, st[i].empty};
+        if (n_tr) {
+            const uint32_t np = std::min(n_tr, st[i].passes);
+            memcpy(trace + (size_t)i * trace_cap, tr.data() + (size_t)i * n_tr, (size_t)np * 2);
+        }
+    }
     return 0;
 }
 
@@ -3482,6 +3698,94 @@ int lh_batch_decode(lh_batch* h, const uint32_t* first_tokens, const uint32_t* p
         for (uint32_t i = 0; i < b->B; ++i) memcpy(out_tokens + (size_t)i * n_steps, b->gen[i].data(), (size_t)n_steps * 4);
     if (logits_last_host) LH_HIP(ctx, hipMemcpyAsync(logits_last_host, b->logits(), (size_t)b->B * m.V * 4, hipMemcpyDeviceToHost, ctx->stream));
     LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LH_OK;
+}
+
+int lh_batch_decode_lookup(lh_batch* h, const uint32_t* first_tokens, const uint32_t* past, uint32_t n_steps, const lh_lookup_params* lp, uint32_t* out_tokens,
+                           float* logits_last_host, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap) {
+    if (!h) return LH_EINVAL;
+    Batch* b = h->b;
+    lh_ctx* ctx = b->ctx;
+    const ModelDesc& m = b->pods[0]->md;
+    LH_HIP(ctx, hipSetDevice(ctx->device));
+    // ---- everything is checked before anything is enqueued or any host state moves
+    if (!first_tokens || !past || !out_tokens) LH_FAIL(ctx, LH_EINVAL, "lh_batch_decode_lookup: null argument");
+    if (!n_steps) LH_FAIL(ctx, LH_EINVAL, "lh_batch_decode_lookup: no ids asked for");
+    if (!m.first_stage() || !m.last_stage()) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_batch_decode_lookup needs whole-model pods (layers [%u, %u) of %u)", m.layer0, m.layer1, m.L);
+    if (b->sampling) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_batch_decode_lookup: the batch has a sampler set (greedy only; lh_batch_set_sampler(NULL) first)");
+    int rc;
+    {   // draft_max is 1..7 for both weight types here: beyond the bit-identical rows the passes are batched Evals like a feed's
+        if (!lp) LH_FAIL(ctx, LH_EINVAL, "lh_batch_decode_lookup: no lookup parameters");
+        if (lp->draft_max < 1 || lp->draft_max > SPEC_ROWS_MAX - 1) LH_FAIL(ctx, LH_EINVAL, "lh_batch_decode_lookup: draft_max %u (1..%u)", lp->draft_max, SPEC_ROWS_MAX - 1);
+        lh_lookup_params one = *lp;
+        one.draft_max = 1;
+        if ((rc = spec_check_params(ctx, m, &one, "lh_batch_decode_lookup"))) return rc;
+    }
+    const uint32_t R = batch_spec_rows(b, lp->draft_max);
+    for (uint32_t i = 0; i < b->B; ++i) {
+        if (first_tokens[i] >= m.V) LH_FAIL(ctx, LH_EINVAL, "lh_batch_decode_lookup: token id %u of row %u outside the vocabulary of %u", first_tokens[i], i, m.V);
+        if ((uint64_t)past[i] + n_steps + R - 1 > m.ctx)
+            LH_FAIL(ctx, LH_EINVAL, "lh_batch_decode_lookup: row %u: past %u + n_steps %u + %u rows per pass - 1 exceeds the context window of %u (the loop never leaves the window)",
+                    i, past[i], n_steps, R, m.ctx);
+    }
+    if (R == 1) {   // no multi-row pass for this pod count on this plan's shapes: plain ticks, and the stats say so
+        if ((rc = lh_batch_decode(h, first_tokens, past, n_steps, out_tokens, logits_last_host))) return rc;
+        for (uint32_t i = 0; i < b->B; ++i) {
+            if (stats) stats[i] = lh_spec_stats{n_steps, 1, 0, 0, n_steps};
+            if (trace) for (uint32_t t = 0; t < n_steps && t < trace_cap; ++t) trace[(size_t)i * trace_cap + t] = 0;
+        }
+        return LH_OK;
+    }
+    return batch_decode_lookup(b, first_tokens, past, n_steps, lp, R, out_tokens, logits_last_host, stats, trace, trace_cap);
+}
+
+int lh_spec_accept_pods(lh_ctx* ctx, const uint32_t* arg, const uint32_t* tok, uint32_t n_pods, uint32_t n_rows, const uint32_t* k, const uint32_t* pos,
+                        const uint32_t* produced, uint32_t n_steps, uint32_t ctx_size, uint32_t* a_out, uint32_t* pos_out, uint32_t* produced_out, uint32_t* pending_out,
+                        uint32_t* ids_out) {
+    if (!ctx) return LH_EINVAL;
+    if (!arg || !tok || !k || !pos || !produced || !a_out || !pos_out || !produced_out || !pending_out || !ids_out) LH_FAIL(ctx, LH_EINVAL, "lh_spec_accept_pods: null argument");
+    const uint32_t P = n_pods, R = n_rows;
+    if (P < 1 || P > BATCH_ROWS_MAX || R < 1 || R > SPEC_ROWS_MAX || P * R > BATCH_ROWS_MAX)
+        LH_FAIL(ctx, LH_EINVAL, "lh_spec_accept_pods: %u pods x %u rows (1..%u pods, 1..%u rows, at most %u rows in all)", P, R, BATCH_ROWS_MAX, SPEC_ROWS_MAX, BATCH_ROWS_MAX);
+    if (!ctx_size) LH_FAIL(ctx, LH_EINVAL, "lh_spec_accept_pods: an empty window");
+    LH_HIP(ctx, hipSetDevice(ctx->device));
+    // one allocation: arg | tok | pending | output lists [P][R] | states | summaries | row table
+    const size_t n = (size_t)P * R, o_tok = 4 * n, o_pend = o_tok + 4 * n, o_out = o_pend + 4 * (size_t)P, o_st = (o_out + 4 * n + 63) & ~(size_t)63,
+                 o_sum = o_st + sizeof(SpecState) * P, o_rows = o_sum + sizeof(SpecPodSum) * P, total = o_rows + sizeof(BatchRow) * n;
+    std::vector<char> hb(total, 0);
+    memcpy(hb.data(), arg, 4 * n);
+    memcpy(hb.data() + o_tok, tok, 4 * n);
+    std::vector<uint32_t> base(P);   // a pod's list holds only what this pass appends: entry `produced` of the loop's list is entry 0 here
+    for (uint32_t i = 0; i < P; ++i) {
+        ((uint32_t*)(hb.data() + o_pend))[i] = tok[(size_t)i * R];
+        SpecState* st = (SpecState*)(hb.data() + o_st) + i;
+        base[i] = std::min(produced[i], n_steps);
+        st->pos = pos[i]; st->produced = produced[i] - base[i]; st->n_steps = n_steps - base[i]; st->k = k[i];
+    }
+    char* dev = nullptr;
+    LH_HIP(ctx, hipMalloc((void**)&dev, total));
+    hipError_t e = hipMemcpyAsync(dev, hb.data(), total, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) {
+        SpecPodsArgs a = {};
+        a.arg = (const uint32_t*)dev; a.tok = (uint32_t*)(dev + o_tok); a.pend = (uint32_t*)(dev + o_pend); a.out = (uint32_t*)(dev + o_out); a.st = (SpecState*)(dev + o_st);
+        a.sum = (SpecPodSum*)(dev + o_sum); a.rows = (BatchRow*)(dev + o_rows);
+        a.R = R; a.ctx = ctx_size; a.vocab = SPEC_UNKNOWN; a.out_cap = R;
+        const SpecLookup none = {nullptr, 0, 0, 1, 1};
+        LH_LAUNCH(k_spec_accept_pods, dim3(P), dim3(SPEC_TH), 0, ctx->stream, a, none, 0);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(hb.data(), dev, total, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    }
+    hipFree(dev);
+    if (e != hipSuccess) LH_FAIL(ctx, LH_EHIP, "lh_spec_accept_pods: %s", hipGetErrorString(e));
+    for (uint32_t i = 0; i < P; ++i) {
+        const SpecState* st = (const SpecState*)(hb.data() + o_st) + i;
+        a_out[i] = st->last_a; pos_out[i] = st->pos; produced_out[i] = st->produced + base[i];
+        pending_out[i] = ((const uint32_t*)(hb.data() + o_pend))[i];
+        const uint32_t appended = st->produced - (produced[i] - base[i]);
+        for (uint32_t j = 0; j < R; ++j) ids_out[(size_t)i * R + j] = j < appended ? ((const uint32_t*)(hb.data() + o_out))[(size_t)i * R + j] : SPEC_UNKNOWN;
+    }
     return LH_OK;
 }
 

@@ -331,6 +331,39 @@ func (bt *BatchHIP) FeedSample(tokens [][]uint32, past []uint32, flags []uint32)
 	return out
 }
 
+// DecodeLookup is lh_batch_decode through lookup-drafted verify passes (lh_batch_decode_lookup; the rule is stated in include/llamahip.h): nSteps
+// greedy ids per pod from (firstTokens[i], past[i]), every pass evaluating pods x R rows in ONE pass over the weights - speculation and the shared weight
+// stream at once.  The loop never leaves the window: past[i] + nSteps + R - 1 <= CtxSize must hold (the caller takes the last positions with Tick).
+// Returns the ids per pod and the stats per pod; afterwards every pod's last id is pending, as behind Feed.  C++ twin: llamago_BatchDecodeLookup.
+func (bt *BatchHIP) DecodeLookup(firstTokens, past []uint32, nSteps, draftMax, ngramMax, ngramMin uint32, corpus []uint32) ([][]uint32, []SpecStatsHIP) {
+	n := len(bt.stages)
+	if len(firstTokens) != n || len(past) != n || nSteps == 0 {
+		fmt.Printf("\n[HALT] DecodeLookup: firstTokens and past need one entry per pod (%d), nSteps at least 1", n)
+		os.Exit(1)
+	}
+	flat := make([]uint32, n*int(nSteps))
+	stats := make([]SpecStatsHIP, n)
+	lp := C.lh_lookup_params{draft_max: C.uint32_t(draftMax), ngram_max: C.uint32_t(ngramMax), ngram_min: C.uint32_t(ngramMin)}
+	if len(corpus) > 0 { // through C memory: a struct handed to C must not contain Go pointers
+		m := len(corpus)
+		cc := (*[1 << 28]C.uint32_t)(C.malloc(C.size_t(m) * 4))[:m:m]
+		defer C.free(unsafe.Pointer(&cc[0]))
+		for i, t := range corpus {
+			cc[i] = C.uint32_t(t)
+		}
+		lp.corpus, lp.n_corpus = &cc[0], C.uint32_t(m)
+	}
+	if rc := C.lh_batch_decode_lookup(bt.b, (*C.uint32_t)(unsafe.Pointer(&firstTokens[0])), (*C.uint32_t)(unsafe.Pointer(&past[0])), C.uint32_t(nSteps), &lp,
+		(*C.uint32_t)(unsafe.Pointer(&flat[0])), nil, (*C.lh_spec_stats)(unsafe.Pointer(&stats[0])), nil, 0); rc != 0 {
+		hipHalt(bt.ctx.hip.ctx)
+	}
+	out := make([][]uint32, n)
+	for i := range out {
+		out[i] = flat[i*int(nSteps) : (i+1)*int(nSteps)]
+	}
+	return out, stats
+}
+
 func (bt *BatchHIP) ids() []uint32 {
 	out := make([]uint32, len(bt.stages))
 	if rc := C.lh_batch_read_ids(bt.b, (*C.uint32_t)(unsafe.Pointer(&out[0]))); rc != 0 {

@@ -1405,6 +1405,21 @@ int llamago_BatchFeedSample(llama_batch* p, const uint32_t* const* tokens, const
     return 0;
 }
 
+// lh_batch_decode_lookup: lh_batch_decode through lookup-drafted verify passes of pods x R rows; lh_spec_accept_pods: its accept step alone
+int llamago_BatchDecodeLookup(llama_batch* p, const uint32_t* first_tokens, const uint32_t* past, uint32_t n_steps, const lh_lookup_params* lp, uint32_t* out,
+                              float* logits_last, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap) {
+    if (!p) return halt_rc("llamago_BatchDecodeLookup: bad arguments");
+    if (lh_batch_decode_lookup(p->b, first_tokens, past, n_steps, lp, out, logits_last, stats, trace, trace_cap)) return halt_rc(lh_last_error(p->mlctx->hip));
+    return 0;
+}
+int llamago_SpecAcceptPods(const uint32_t* arg, const uint32_t* tok, uint32_t n_pods, uint32_t n_rows, const uint32_t* k, const uint32_t* pos, const uint32_t* produced,
+                           uint32_t n_steps, uint32_t ctx_size, uint32_t* a_out, uint32_t* pos_out, uint32_t* produced_out, uint32_t* pending_out, uint32_t* ids_out) {
+    lh_ctx* h = model_ctx();
+    if (!h) return 1;
+    if (lh_spec_accept_pods(h, arg, tok, n_pods, n_rows, k, pos, produced, n_steps, ctx_size, a_out, pos_out, produced_out, pending_out, ids_out)) return halt_rc(lh_last_error(h));
+    return 0;
+}
+
 // ---- pods as pipeline streams over a layer-sharded model (server.go:84-106, 151) ----------------------
 // One ml.Context (= one HIP stream) per rank carries every pod's stage and the RCCL p2p; each pod owns its KV cache like a
 // llama.Context does (llama.go:91-98).  All scheduling happens below the C-ABI (lh_pipeline_run).

@@ -505,6 +505,27 @@ def draft_lookup(ml, window, draft_max, ngram_max=3, ngram_min=1, corpus=None, l
     return [int(t) for t in out[:k.value]]
 
 
+def spec_accept_pods(ml, arg, tok, k, pos, produced, n_steps, ctx):
+    """llamago_SpecAcceptPods: the accept step of one pass of pods x R rows alone on the device (lh_spec_accept_pods; k_spec_accept_pods).  arg / tok
+    [pods][R] = the rows' greedy ids / the tokens they evaluated; k, pos, produced [pods] = the pods' state in front of the pass.
+    -> (a [pods], pos [pods], produced [pods], pending [pods], the ids appended per pod)."""
+    arg = np.ascontiguousarray(arg, dtype=np.uint32)
+    tok = np.ascontiguousarray(tok, dtype=np.uint32)
+    P, R = (arg.shape if arg.ndim == 2 else (0, 0))
+    assert tok.shape == arg.shape and len(k) == len(pos) == len(produced) == P, (arg.shape, tok.shape, len(k), len(pos), len(produced))
+    f = ml.lib.llamago_SpecAcceptPods
+    f.restype = C.c_int
+    f.argtypes = [c_u32p, c_u32p, c_u32, c_u32, c_u32p, c_u32p, c_u32p, c_u32, c_u32, c_u32p, c_u32p, c_u32p, c_u32p, c_u32p]
+    m = max(P, 1)
+    kk, pp, pr = ((c_u32 * m)(*[int(x) for x in v]) for v in (k, pos, produced))
+    a, npos, nprod, pend = ((c_u32 * m)() for _ in range(4))
+    ids = (c_u32 * max(P * R, 1))()
+    if f(arg.ctypes.data_as(c_u32p), tok.ctypes.data_as(c_u32p), P, R, kk, pp, pr, int(n_steps), int(ctx), a, npos, nprod, pend, ids):
+        raise MLError(f"llamago_SpecAcceptPods: {ml.last_error()}")
+    appended = [[int(t) for t in ids[i * R:i * R + (nprod[i] - int(produced[i]))]] for i in range(P)]
+    return [int(x) for x in a[:P]], [int(x) for x in npos[:P]], [int(x) for x in nprod[:P]], [int(x) for x in pend[:P]], appended
+
+
 def score_rows(ml, logits, targets):
     """llamago_ScoreRows: every row of host logits [n_rows][V] scored against targets[row] on the device (lh_score_rows)."""
     lg = np.ascontiguousarray(logits, dtype=np.float32)
@@ -847,6 +868,27 @@ class Batch:
         f.restype, f.argtypes = C.c_int, [VP]
         if f(self.h):
             raise MLError(f"llamago_BatchClearSampler: {self.ml.last_error()}")
+
+    def DecodeLookup(self, first_tokens, past, n_steps, draft_max, ngram_max=3, ngram_min=1, corpus=None, want_logits=False):
+        """llamago_BatchDecodeLookup: n_steps greedy ids per pod from (first_tokens[i], past[i]) through lookup-drafted verify passes of pods x R rows
+        (lh_batch_decode_lookup).  -> (ids per pod, [pods][vocab] logits behind each pod's last id or None, per pod a stats dict(passes, rows, drafted,
+        accepted, empty), per pod the trace list of (k, a) per pass)."""
+        assert len(first_tokens) == self.pods and len(past) == self.pods
+        L = self.ml.lib
+        L.llamago_BatchDecodeLookup.restype = C.c_int
+        L.llamago_BatchDecodeLookup.argtypes = [VP, c_u32p, c_u32p, c_u32, C.POINTER(LookupParams), c_u32p, c_f32p, C.POINTER(SpecStats), C.POINTER(C.c_uint16), c_u32]
+        lp, _keep = lookup_params(draft_max, ngram_max, ngram_min, corpus)
+        n = max(int(n_steps), 1)
+        tk = (c_u32 * self.pods)(*[int(t) for t in first_tokens])
+        ps = (c_u32 * self.pods)(*[int(x) for x in past])
+        out, st, tr = (c_u32 * (self.pods * n))(), (SpecStats * self.pods)(), (C.c_uint16 * (self.pods * n))()
+        lg = np.empty((self.pods, self.model.hp.vocabSize), dtype=np.float32) if want_logits else None
+        if L.llamago_BatchDecodeLookup(self.h, tk, ps, int(n_steps), C.byref(lp), out, lg.ctypes.data_as(c_f32p) if want_logits else None, st, tr, n):
+            raise MLError(f"llamago_BatchDecodeLookup: {self.ml.last_error()}")
+        ids = [[int(t) for t in out[i * n:i * n + n_steps]] for i in range(self.pods)]
+        stats = [dict(passes=int(s.passes), rows=int(s.rows), drafted=int(s.drafted), accepted=int(s.accepted), empty=int(s.empty)) for s in st]
+        traces = [[(int(v) >> 8, int(v) & 0xFF) for v in tr[i * n:i * n + min(st[i].passes, n)]] for i in range(self.pods)]
+        return ids, lg, stats, traces
 
     def Tick(self):
         """BatchHIP.Tick: one decode step of every pod in one pass over the weights; returns the ids produced."""

@@ -9,7 +9,11 @@ rates here are those of a replayed or a random text, never a model result.
   --sample  the sampled route instead (lh_llama_decode_sample_lookup; results: profiles/sample_lookup.txt): the golden prompt, ctx 128, 100 sampled ids
           (topK 40, topP 0.95, temp 0.8, penalty 1.1): an R-row sampled pass against one plain sampled step of SampleDecode (prompt Eval and first
           sample taken off both by a 1-id call), the loop with the replay corpus (the ceiling) and without one, the break-even acceptance
-usage: python tools/bench_speculative.py [pass golden] [--sample] [--layers 32] [--reps 5] [--int8] [--out profiles/speculative.txt]"""
+  --pods P  the pods of a batch instead (lh_batch_decode_lookup; results: profiles/batch_lookup.txt): P pods behind the golden prompt, ctx 256, 96 ids
+          per pod, draft_max 1 / 3 / 7 (R lowered to what P pods leave room for): a pass of P * R rows against a tick of P rows of lh_batch_decode, same
+          process, alternating; aggregate tokens/s with the replay corpus (acceptance 1 by construction: a CEILING, not a model result), without a
+          corpus, and of the plain ticks; the break-even mean of accepted ids per pod and pass
+usage: python tools/bench_speculative.py [pass golden] [--sample] [--pods P] [--layers 32] [--reps 5] [--int8] [--out profiles/speculative.txt]"""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -22,6 +26,7 @@ ap.add_argument("--layers", type=int, default=32)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--int8", action="store_true", help="block-int8 weights too")
 ap.add_argument("--sample", action="store_true", help="the sampled route (SampleDecodeLookup against SampleDecode) instead of the greedy parts")
+ap.add_argument("--pods", type=int, default=0, help="the pods of a batch (Batch.DecodeLookup against the ticks of lh_batch_decode) instead of the solo parts")
 ap.add_argument("--out", default=None, help="append the result lines to this file")
 args = ap.parse_args()
 prod = load_product()
@@ -84,6 +89,59 @@ if args.sample:
         out["break_even_accepted_per_pass"] = round(out["no_corpus_pass_ms"] / step_ms - 1, 3)
         emit(out)
         c.free()
+        m.free()
+
+if args.pods:
+    args.parts = []
+    P, ctx, n = args.pods, 256, 96
+    prompts = [[PROMPT[0]] + [(t + 17 * i) % 32000 for t in PROMPT[1:]] for i in range(P)]
+    past = [len(p) for p in prompts]
+    for int8 in ([False, True] if args.int8 else [False]):
+        m = model(ctx, int8)
+        b = Batch(m, ctx, P)
+        g = b.GreedyDecode(prompts, n + 1)
+        first = [gi[0] for gi in g]
+        replay = [t for p, gi in zip(prompts, g) for t in list(p) + gi]
+        for K in (1, 3, 7):
+            res = {}
+
+            def loop(corpus):
+                b.Prompt(prompts)
+                _, _, st, _ = b.DecodeLookup(first, past, n, K, 3, 1, corpus)
+                res.update(rows=st[0]["rows"], passes=max(s["passes"] for s in st), accepted=sum(s["accepted"] for s in st), pod_passes=sum(s["passes"] for s in st))
+
+            def ticks():
+                b.GreedyDecode(prompts, n + 1)
+            head = lambda: b.Prompt(prompts)   # noqa: E731  (what all three start with)
+            # alternating: replay, ticks, no corpus per repetition; medians per leg
+            ts = {"head": [], "replay": [], "ticks": [], "no_corpus": []}
+            legs = (("head", head), ("replay", lambda: loop(replay)), ("ticks", ticks), ("no_corpus", lambda: loop(None)))
+            for _, fn in legs:
+                fn()
+            shape = {}
+            for _ in range(args.reps):
+                for name, fn in legs:
+                    t0 = time.perf_counter(); fn(); ts[name].append((time.perf_counter() - t0) * 1e3)
+                    if name in ("replay", "no_corpus"):
+                        shape[name] = dict(res)
+            md = {k: sorted(v)[len(v) // 2] for k, v in ts.items()}
+            R = shape["replay"]["rows"]
+            if R == 1:
+                emit(dict(part="pods", int8=int8, layers=args.layers, pods=P, draft_max=K, rows=1, note="no room for a second row: plain ticks"))
+                continue
+            tick_ms = (md["ticks"] - md["head"]) / n
+            out = dict(part="pods", int8=int8, layers=args.layers, pods=P, draft_max=K, rows=R, pass_rows=P * R, ids_per_pod=n, tick_ms=round(tick_ms, 3),
+                       ticks_tok_s=round(P * n / (md["ticks"] - md["head"]) * 1e3, 1))
+            for name in ("replay", "no_corpus"):
+                ms = md[name] - md["head"]
+                out.update({f"{name}_passes": shape[name]["passes"], f"{name}_accepted_per_pod_pass": round(shape[name]["accepted"] / shape[name]["pod_passes"], 3),
+                            f"{name}_pass_ms": round(ms / shape[name]["passes"], 3), f"{name}_tok_s": round(P * n / ms * 1e3, 1)})
+            out["replay_is"] = "acceptance-1 ceiling (the corpus is the run itself), not a model result"
+            out["pass_over_tick"] = round(out["no_corpus_pass_ms"] / tick_ms, 3)
+            # the route wins when ids per pod and pass = 1 + mean accepted > pass time / tick time
+            out["break_even_accepted_per_pod_pass"] = round(out["no_corpus_pass_ms"] / tick_ms - 1, 3)
+            emit(out)
+        b.free()
         m.free()
 
 if "pass" in args.parts:
