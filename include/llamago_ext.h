@@ -59,6 +59,15 @@ int llamago_SetModelTensor(llama_model* m, const char* name, const float* data, 
  * pastBuild >= 0: from the graph llama_Eval KEEPS between one-token calls, learnt around pastBuild and moved to pastQuery (host/llamago.cpp,
  * eval_cache) - tests require both to be identical.  Returns the tensor count, -1 bad arguments, -2 the kept graph declined. */
 int llamago_DescribeEvalArray(const llama_hparams* hp, uint32_t ctxSize, uint32_t N, int64_t pastBuild, uint32_t pastQuery, int64_t* out, uint32_t cap_tensors, uint32_t* n_leafs);
+/* Flattened graphs as real lh_tensor records with storage, view_off and buf - what lh_graph_check takes.  Host values (token ids, op parameters,
+ * caller-filled leafs) are copied to host_vals, where the records' host pointers then point.  Both return the tensor count; out = NULL asks for
+ * the counts only; -1 on bad arguments or arrays that are too small.
+ * llamago_GraphRecords: any graph built with the mirror's constructors (ctx = NULL serves all of them).
+ * llamago_EvalGraphRecords: the graph llama_Eval builds for N tokens (ids 1..N) at pastCount, built fresh; every weight and cache of the shape model
+ * gets a buffer id of its own (1, 2, ...) and an lh_buf_extent that says what a registration of it would hold. */
+int llamago_GraphRecords(ml_graph* g, lh_tensor* out, uint32_t cap_tensors, uint32_t* n_leafs, float* host_vals, uint32_t cap_vals, uint32_t* n_vals);
+int llamago_EvalGraphRecords(const llama_hparams* hp, uint32_t ctxSize, uint32_t N, uint32_t pastCount, lh_tensor* out, uint32_t cap_tensors, uint32_t* n_leafs,
+                             lh_buf_extent* bufs, uint32_t cap_bufs, uint32_t* n_bufs, float* host_vals, uint32_t cap_vals, uint32_t* n_vals);
 /* 0: every llama_Eval builds its graph anew (what LLAMAGO_NO_EVAL_CACHE=1 sets at load); 1 (default): one-token Evals move the kept graph. */
 void llamago_KeepDecodeGraph(int on);
 

@@ -111,6 +111,14 @@ enum {
 };
 
 int lh_graph_compute(lh_ctx* ctx, const lh_tensor* tensors, uint32_t n_leafs, uint32_t n_nodes, uint32_t flags);
+/* What lh_graph_compute refuses before it enqueues anything, as a pure host function (csrc/graph_check.h; needs no context and no device): LH_OK,
+ * or the negative code lh_graph_compute returns for this array, with the message in msg (cap bytes, may be NULL).  Two levels: the structural
+ * checks every call makes (counts, storage owners, source indices and order, arity, strides that are whole floats, no extent of 0 - an empty
+ * tensor is refused, not skipped), then what a node-by-node walk checks in front of its first launch: every op's shape rules and parameter leafs
+ * and the furthest float its kernel touches in every operand, which must lie inside the owner.  bufs names what the registered buffers the array
+ * refers to hold (lh_buf_nfloats; dtype as at registration); a host leaf holds its nelem floats, any other owner its own strided span. */
+typedef struct lh_buf_extent { lh_buf id; uint64_t nfloats; int dtype; } lh_buf_extent;
+int lh_graph_check(const lh_tensor* tensors, uint32_t n_leafs, uint32_t n_nodes, const lh_buf_extent* bufs, uint32_t n_bufs, char* msg, uint64_t cap);
 /* Read elements of a tensor of the LAST computed graph (flat, in storage order from the tensor's first
  * element).  Replaces the host's direct reads of Tensor.Data after GraphCompute (llama.go:394-401). */
 int lh_node_read(lh_ctx* ctx, uint32_t index, uint64_t off_floats, float* dst, uint64_t n);

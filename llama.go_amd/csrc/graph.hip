@@ -8,6 +8,7 @@
 #include "plan.h"
 #include <chrono>
 #include "kernels_generic.h"
+#include "graph_check.h"
 #include <math.h>
 #include <algorithm>
 
@@ -22,12 +23,6 @@ enum { OP_NONE = 0, OP_ADD = 2, OP_MUL = 4, OP_REPEAT = 10, OP_SILU = 17, OP_RMS
 static inline uint64_t nelem(const lh_tensor& t) { return (uint64_t)t.ne[0] * t.ne[1] * t.ne[2] * t.ne[3]; }
 static inline bool contiguous(const lh_tensor& t) {  // ml.go:206-211
     return t.nb[0] == 4 && t.nb[1] == t.nb[0] * t.ne[0] && t.nb[2] == t.nb[1] * t.ne[1] && t.nb[3] == t.nb[2] * t.ne[2];
-}
-// furthest element touched + 1 (floats) through the tensor's strides
-static inline uint64_t extent(const lh_tensor& t) {
-    uint64_t e = 1;
-    for (int i = 0; i < 4; ++i) e += (uint64_t)(t.ne[i] - 1) * (t.nb[i] / 4);
-    return e;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -382,16 +377,18 @@ static int run_node(lh_ctx* ctx, const lh_tensor* T, const std::vector<float*>& 
             break;
         }
         case OP_ROPE: {
-            const lh_tensor& b = T[t.src1];
+            // src0's NE and NB address both sides (ml.go:2274-2281); dst is a ViewTensor of src0 (ml.go:1016): the same data, under packed strides
+            // of its own when src0 is a permuted view, and those are never read
+            const lh_tensor &a = T[t.src0], &b = T[t.src1];
             if (nelem(b) != 3 || !b.host) LH_FAIL(ctx, LH_ESHAPE, "[HALT] ComputeForwardRopeFP32 : src1 has NOT EXACT 3 elements!");
             const uint32_t past = (uint32_t)b.host[0], dims = (uint32_t)b.host[1], mode = (uint32_t)b.host[2];
-            if (dims == 0 || dims % 2 || dims > t.ne[0]) LH_FAIL(ctx, LH_ESHAPE, "Rope: dims %u not supported", dims);
-            const uint32_t maxpos = (mode == 0 ? past : 0) + t.ne[2];
+            if (dims == 0 || dims % 2 || dims > a.ne[0]) LH_FAIL(ctx, LH_ESHAPE, "Rope: dims %u not supported", dims);
+            const uint32_t maxpos = (mode == 0 ? past : 0) + a.ne[2];
             const double2* table = nullptr;
             int rc = ensure_rope_table(ctx, maxpos + 1, dims, &table);
             if (rc) return rc;
-            const uint64_t total = (uint64_t)t.ne[3] * t.ne[2] * t.ne[1] * (dims / 2);
-            LH_LAUNCH(g_rope, grid_for(total), dim3(256), 0, st, V(i), table, past, dims, mode);
+            const uint64_t total = (uint64_t)a.ne[3] * a.ne[2] * a.ne[1] * (dims / 2);
+            LH_LAUNCH(g_rope, grid_for(total), dim3(256), 0, st, view_of(a, P[i]), table, past, dims, mode);
             break;
         }
         case OP_MUL_MAT: {
@@ -438,8 +435,8 @@ int lh_graph_compute(lh_ctx* ctx, const lh_tensor* T, uint32_t n_leafs, uint32_t
     auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return (long)std::chrono::duration_cast<std::chrono::nanoseconds>(b - a).count() / 1000.0; };
     const auto tq0 = now();
     LH_HIP(ctx, hipSetDevice(ctx->device));
-    const uint32_t total = n_leafs + n_nodes;
-    if (total == 0) return LH_OK;
+    if (!n_leafs && !n_nodes) return LH_OK;
+    const uint32_t total = n_leafs + n_nodes;   // counts whose sum wraps are refused by the structural check below, before total is used
     // lh_ctx_time_computes: one event in front of everything this call puts on the stream, one behind it (mark_end, in front of the call's
     // last wait); the sums are taken when the call returns with both recorded
     struct ComputeTimer {
@@ -455,17 +452,13 @@ int lh_graph_compute(lh_ctx* ctx, const lh_tensor* T, uint32_t n_leafs, uint32_t
     ctx->tc_end = false;
     if (ctx->tc_on) LH_HIP(ctx, hipEventRecord(ctx->tc_ev0, ctx->stream));
     auto mark_end = [&]() { if (ctx->tc_on && hipEventRecord(ctx->tc_ev1, ctx->stream) == hipSuccess) ctx->tc_end = true; };
-    // ---- validate indices
-    for (uint32_t i = 0; i < total; ++i) {
-        const lh_tensor& t = T[i];
-        if (t.storage < 0 || (uint32_t)t.storage >= total) LH_FAIL(ctx, LH_EINVAL, "tensor %u: storage index %d out of range", i, t.storage);
-        if (t.src0 >= (int)total || t.src1 >= (int)total) LH_FAIL(ctx, LH_EINVAL, "tensor %u: source index out of range", i);
-        if (T[t.storage].storage != t.storage) LH_FAIL(ctx, LH_EINVAL, "tensor %u: storage owner %d is itself a view", i, t.storage);
-        if (i >= n_leafs && (t.src0 >= (int)i || t.src1 >= (int)i)) {
-            // nodes must come after their sources (post-order, ml.go:647-697) except leaf sources
-            if ((t.src0 >= (int)i && (uint32_t)t.src0 >= n_leafs) || (t.src1 >= (int)i && (uint32_t)t.src1 >= n_leafs))
-                LH_FAIL(ctx, LH_EINVAL, "node %u is listed before one of its sources", i);
-        }
+    // ---- structural checks (graph_check.h): every index run_node, the matcher and the storage pass below use is in range after this
+    ctx->last_ptr.clear();   // a refused graph leaves nothing for lh_node_read
+    ctx->last_len.clear();
+    {
+        char why[256];
+        const int bad = gc::graph_check_structure(T, n_leafs, n_nodes, why, sizeof why);
+        if (bad) LH_FAIL(ctx, bad, "%s", why);
     }
     ctx->last_ptr.assign(total, nullptr);
     ctx->last_len.assign(total, 0);
@@ -520,12 +513,22 @@ int lh_graph_compute(lh_ctx* ctx, const lh_tensor* T, uint32_t n_leafs, uint32_t
         }
     }
 
-    // ---- generic path: storage for every owner
-    std::vector<uint64_t> need(total, 0);  // floats needed per owner
-    for (uint32_t i = 0; i < total; ++i) {
-        const lh_tensor& t = T[i];
-        const uint64_t e = t.view_off + extent(t);
-        need[t.storage] = std::max(need[t.storage], e);
+    // ---- generic path: what every op will touch lies inside its owner (graph_check.h), then storage for every owner
+    std::vector<uint64_t> need;  // floats per owner: a registered buffer's size, the nelem a host leaf uploads, a scratch owner's own span
+    {
+        std::vector<lh_buf_extent> ext;
+        for (uint32_t i = 0; i < total; ++i) {
+            if ((uint32_t)T[i].storage != i || !T[i].buf) continue;
+            const Buffer* b = find_buffer(ctx->ds, T[i].buf);
+            if (b) ext.push_back(lh_buf_extent{T[i].buf, b->nfloats, b->dtype});
+        }
+        char why[256];
+        const int bad = gc::graph_check_reach(T, n_leafs, n_nodes, ext.data(), (uint32_t)ext.size(), why, sizeof why, &need);
+        if (bad) {
+            ctx->last_ptr.clear();
+            ctx->last_len.clear();
+            LH_FAIL(ctx, bad, "%s", why);
+        }
     }
     std::vector<uint64_t> offs(total, 0);
     uint64_t arena = 0, stage = 0;
@@ -538,7 +541,6 @@ int lh_graph_compute(lh_ctx* ctx, const lh_tensor* T, uint32_t n_leafs, uint32_t
             Buffer* b = find_buffer(ctx->ds, T[i].buf);
             if (!b) LH_FAIL(ctx, LH_EINVAL, "tensor %u: unknown buffer %llu", i, (unsigned long long)T[i].buf);
             if (written[i]) b->unchecked.store(true, std::memory_order_relaxed);
-            if (b->nfloats < need[i]) LH_FAIL(ctx, LH_ESHAPE, "tensor %u: views reach %llu floats, buffer holds %llu", i, (unsigned long long)need[i], (unsigned long long)b->nfloats);
             continue;
         }
         offs[i] = arena;
@@ -574,6 +576,10 @@ int lh_graph_compute(lh_ctx* ctx, const lh_tensor* T, uint32_t n_leafs, uint32_t
     mark_end();
     LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return LH_OK;
+}
+
+int lh_graph_check(const lh_tensor* T, uint32_t n_leafs, uint32_t n_nodes, const lh_buf_extent* bufs, uint32_t n_bufs, char* msg, uint64_t cap) {
+    return gc::graph_check(T, n_leafs, n_nodes, bufs, n_bufs, msg, cap);
 }
 
 int lh_node_read(lh_ctx* ctx, uint32_t index, uint64_t off, float* dst, uint64_t n) {

@@ -1046,6 +1046,77 @@ int llamago_DescribeEvalArray(const llama_hparams* hp, uint32_t ctxSize, uint32_
     return count;
 }
 
+// Harness extensions (no GPU): flattened graphs as real lh_tensor records - what lh_graph_check takes.  Host values (token ids, op parameters,
+// caller-filled leafs) are copied to host_vals and the records' host pointers point there.  `weight` (optional) names tensors that stand for
+// registered buffers: each gets a buffer id of its own (1 + its number) and bufs[] says how many floats a registration of it would hold.
+}  // extern "C"
+static int records_out(ml_context* scratch, uint32_t nl, uint32_t nn, const std::unordered_map<const ml_tensor*, uint32_t>* weight, lh_tensor* out, uint32_t cap_tensors,
+                       uint32_t* n_leafs, lh_buf_extent* bufs, uint32_t cap_bufs, uint32_t* n_bufs, float* host_vals, uint32_t cap_vals, uint32_t* n_vals) {
+    uint32_t nb = 0;
+    uint64_t nv = 0;
+    bool fits = true;
+    for (uint32_t i = 0; i < nl + nn; ++i) {
+        lh_tensor t = scratch->flat[i];
+        const uint64_t n = (uint64_t)t.ne[0] * t.ne[1] * t.ne[2] * t.ne[3];
+        const bool is_weight = weight && i < nl && (uint32_t)t.storage == i && weight->count(scratch->flat_leafs[i]);
+        if (is_weight) {
+            t.buf = weight->at(scratch->flat_leafs[i]) + 1;
+            t.host = nullptr;
+            if (bufs && nb < cap_bufs) bufs[nb] = lh_buf_extent{t.buf, nelements(scratch->flat_leafs[i]), 0};
+            else if (out) fits = false;
+            nb++;
+        } else if (t.host) {
+            if (host_vals && nv + n <= cap_vals) { memcpy(host_vals + nv, t.host, n * 4); t.host = host_vals + nv; }
+            else if (out) fits = false;
+            nv += n;
+        }
+        if (out && i < cap_tensors) out[i] = t;
+        else if (out) fits = false;
+    }
+    if (n_leafs) *n_leafs = nl;
+    if (n_bufs) *n_bufs = nb;
+    if (n_vals) *n_vals = (uint32_t)std::min<uint64_t>(nv, 0xffffffffu);
+    return fits && nv <= 0xffffffffu ? (int)(nl + nn) : -1;
+}
+extern "C" {
+// any graph built with the mirror's constructors (ctx = NULL works for all of them)
+int llamago_GraphRecords(ml_graph* g, lh_tensor* out, uint32_t cap_tensors, uint32_t* n_leafs, float* host_vals, uint32_t cap_vals, uint32_t* n_vals) {
+    g_err.clear();
+    if (!g) return -1;
+    ml_context scratch;
+    scratch.maxThreads = 1; scratch.hip = nullptr;
+    uint32_t nl = 0, nn = 0;
+    flatten_graph(&scratch, g, &nl, &nn);
+    return records_out(&scratch, nl, nn, nullptr, out, cap_tensors, n_leafs, nullptr, 0, nullptr, host_vals, cap_vals, n_vals);
+}
+// the graph llama_Eval builds for N tokens (ids 1..N) at pastCount over a model of shape hp, built fresh; weights and caches become buffers
+int llamago_EvalGraphRecords(const llama_hparams* hp, uint32_t ctxSize, uint32_t N, uint32_t pastCount, lh_tensor* out, uint32_t cap_tensors, uint32_t* n_leafs,
+                             lh_buf_extent* bufs, uint32_t cap_bufs, uint32_t* n_bufs, float* host_vals, uint32_t cap_vals, uint32_t* n_vals) {
+    g_err.clear();
+    if (!hp || !N || (uint64_t)pastCount + N > ctxSize) return -1;
+    shape_model sm(hp, ctxSize);
+    std::vector<uint32_t> tokens(N);
+    for (uint32_t i = 0; i < N; i++) tokens[i] = i + 1;
+    ml_context scratch;
+    scratch.maxThreads = 1; scratch.hip = nullptr;
+    const bool save = g_gc_enabled;
+    ml_tensor* const gc_mark = g_gc_head;
+    ml_graph* g = ml_NewGraph();
+    g_gc_enabled = true;
+    int count = -1;
+    if (build_eval_graph(&scratch, &sm.m, sm.kK, sm.kV, ctxSize, tokens.data(), N, pastCount, g)) {
+        uint32_t nl = 0, nn = 0;
+        flatten_graph(&scratch, g, &nl, &nn);
+        std::unordered_map<const ml_tensor*, uint32_t> weight;
+        for (size_t k = 0; k < sm.mine.size(); ++k) weight[sm.mine[k]] = (uint32_t)k;
+        count = records_out(&scratch, nl, nn, &weight, out, cap_tensors, n_leafs, bufs, cap_bufs, n_bufs, host_vals, cap_vals, n_vals);
+    }
+    ml_FreeGraph(g);
+    gc_free_down_to(gc_mark);
+    g_gc_enabled = save;
+    return count;
+}
+
 static uint32_t argmax_f32(const float* x, uint32_t n) {  // strict >, lowest index wins ties
     // two passes: the maximum over eight independent lanes (vectorises; the one-pass `x[i] > x[best]` chain cost ~40 us on 32000 logits, a
     // tenth of what a token's whole host side may cost), then the first index that holds it.  NaNs as the reference's `x[i] > x[best]` loop treats

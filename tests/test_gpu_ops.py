@@ -179,6 +179,14 @@ def test_rms_norm_repeat_mul(pair, d, N):
 
     out = pair.run(build)
     assert_close(out, 2e-6)
+    # element by element against float64 (tests/graph_ops_ref.py): RMSNorm is within 3 u |n| of the f64 norm n (squares rounded in fp32, ml.go:1792),
+    # Repeat copies, Mul rounds once more: |out - g n| <= 3 u |g n| + u (1 + 3 u) |g n|
+    import graph_ops_ref as R
+    n64, _ = R.rms_norm64(x)
+    y64 = n64 * g.astype(np.float64)
+    err = np.abs(out["hip"][0].reshape(N, d).astype(np.float64) - y64)
+    bound = 4 * R.U * (1 + 2.0 ** -20) * np.abs(y64)
+    assert np.all(err <= bound), f"{np.count_nonzero(err > bound)} elements outside 4 u |y|, worst {np.max(err / np.maximum(bound, 1e-300)):.2f} bounds"
 
 
 @pytest.mark.parametrize("mode,past,N", [(0, 0, 1), (0, 5, 3), (1, 0, 4), (1, 6, 2), (0, 100, 1)])
