@@ -52,6 +52,12 @@ int llamago_GraphComputeNoFusion(ml_context* ctx, ml_graph* g);   /* ml_GraphCom
  * `n` host floats, row-major as llama_ModelTensor / ml_TensorRead show it (lh_buf_upload).  Fails (non-zero, ml_LastError) on an unknown name, n different from
  * the tensor's element count, a block-int8 tensor, or a model with live contexts / batches / pipelines (their plans may hold derived copies). */
 int llamago_SetModelTensor(llama_model* m, const char* name, const float* data, uint64_t n);
+/* Test instrumentation: floats [off_floats, off_floats + n) of a context's KV cache (which: 0 = K, 1 = V) read to the host / overwritten from it, after
+ * waiting for the context's stream.  The cache is [layer1 - layer0][ctxSize][embd] floats: slot = layer - layer0, then position, then channel, K and V
+ * alike.  Fails (non-zero, ml_LastError) on a null argument, which outside 0 / 1, or a range outside the cache.  llamago_BatchCache*: pod `pod` of a batch
+ * (declared with the batch below). */
+int llamago_CacheRead(llama_context* c, int which, uint64_t off_floats, float* dst, uint64_t n);
+int llamago_CacheWrite(llama_context* c, int which, uint64_t off_floats, const float* src, uint64_t n);
 
 /* ---- [product] harness helper of the kept decode graph (no GPU needed) -------------------------------------------------- */
 /* The array llama_Eval hands to lh_graph_compute for N tokens (ids 1..N) at pastQuery, as numbers: per tensor 16 int64 = op, dtype, flags, ne[4],
@@ -125,6 +131,9 @@ typedef struct llama_batch llama_batch;
 llama_batch* llamago_NewBatch(llama_model* m, uint32_t ctxSize, uint32_t pods);
 void llamago_FreeBatch(llama_batch* b);
 int llamago_BatchBatched(llama_batch* b);            /* lh_batch_batched */
+/* Test instrumentation: llamago_CacheRead / llamago_CacheWrite on the KV cache of pod `pod` (also fails on a pod outside the batch). */
+int llamago_BatchCacheRead(llama_batch* b, uint32_t pod, int which, uint64_t off_floats, float* dst, uint64_t n);
+int llamago_BatchCacheWrite(llama_batch* b, uint32_t pod, int which, uint64_t off_floats, const float* src, uint64_t n);
 /* Every pod: its prompt as one Eval, then n_predict - 1 greedy steps of ALL pods per weight pass.  out[i * n_predict + s] = s-th id
  * of pod i (= llama_GreedyDecode of that prompt alone); logits (optional): [pods][vocab] of the last tick. */
 int llamago_BatchGreedyDecode(llama_batch* b, const uint32_t* const* prompts, const uint32_t* n_prompt, uint32_t n_predict, uint32_t* out, float* logits);

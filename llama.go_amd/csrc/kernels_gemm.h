@@ -594,10 +594,11 @@ __global__ __launch_bounds__(256) void k_gemm_q8(const GemmArgs a) {
 
 // Scale + causal mask + softmax on the full score block S[h][j][0..Tp) in place (Scale ml.go:2331-2374, DiagMaskInf
 // ml.go:2377-2414, SoftMax ml.go:2432-2505): row j keeps keys t <= past + j; masked and padding columns become exactly 0.
-__global__ __launch_bounds__(256) void k_softmax_causal(float* __restrict__ S, uint32_t N, uint32_t Tp, uint32_t past, float scale) {
+__global__ __launch_bounds__(256) void k_softmax_causal(float* __restrict__ S, uint32_t N, uint32_t Tp, uint32_t past, float scale, uint32_t* __restrict__ v_nonfinite) {
     __shared__ float scratch[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t j = blockIdx.x, h = blockIdx.y;
+    if (j == 0 && h == 0 && tid == 0) *v_nonfinite = 0u;   // k_transpose_v, next on the stream, raises it
     float* p = S + ((size_t)h * N + j) * Tp;
     const uint32_t T = past + j + 1;
     float m = -INFINITY;
@@ -626,18 +627,44 @@ __global__ __launch_bounds__(256) void k_softmax_causal(float* __restrict__ S, u
 
 // V cache rows [t][h*hd + c] -> VT[h][c][t] (t padded to Tp with zeros): the reference's VTrans copy (llama.go:315-322),
 // needed because the MFMA GEMM wants both operands contiguous along the contraction (here: keys).
-__global__ __launch_bounds__(256) void k_transpose_v(const float* __restrict__ v_cache, float* __restrict__ vt, uint32_t T, uint32_t Tp, uint32_t d, uint32_t hd) {
+// A non-finite V value goes into VT as 0 and raises *v_nonfinite: in the P V product it would meet the exact 0 of every query that does not see its
+// key (0 x NaN = NaN in all rows of the call); k_attn_gemm_repair adds it to the queries that do.
+__global__ __launch_bounds__(256) void k_transpose_v(const float* __restrict__ v_cache, float* __restrict__ vt, uint32_t T, uint32_t Tp, uint32_t d, uint32_t hd,
+                                                      uint32_t* __restrict__ v_nonfinite) {
     __shared__ float tile[32][33];
     const uint32_t h = blockIdx.z, t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
+    bool bad = false;
     for (int r = ty; r < 32; r += 8) {
         const uint32_t t = t0 + r;
-        tile[r][tx] = t < T ? v_cache[(size_t)t * d + h * hd + c0 + tx] : 0.f;
+        float v = t < T ? v_cache[(size_t)t * d + h * hd + c0 + tx] : 0.f;
+        if ((__builtin_bit_cast(uint32_t, v) & 0x7f800000u) == 0x7f800000u) { v = 0.f; bad = true; }
+        tile[r][tx] = v;
     }
+    if (bad) atomicOr(v_nonfinite, 1u);
     __syncthreads();
     for (int r = ty; r < 32; r += 8) {
         const uint32_t c = c0 + r, t = t0 + tx;
         if (t < Tp) vt[((size_t)h * hd + c) * Tp + t] = tile[tx][r];
+    }
+}
+
+// Behind the P V GEMM of attention_gemm, one workgroup per (query, head); leaves at once unless k_transpose_v met a non-finite V value.  Then: query j
+// gets, per output column, the products P[j][t] v of the non-finite values among the keys it sees (t <= past + j), in key order - as the reference's
+// MulMat(V, softmax) gives that query (NaN, or an infinity), and nothing to the queries that do not see the key.
+__global__ __launch_bounds__(64) void k_attn_gemm_repair(const float* __restrict__ P, const float* __restrict__ v_cache, float* __restrict__ out,
+                                                          const uint32_t* __restrict__ v_nonfinite, uint32_t N, uint32_t Tp, uint32_t past, uint32_t d, uint32_t hd) {
+    if (*v_nonfinite == 0u) return;
+    const uint32_t j = blockIdx.x, h = blockIdx.y, T = past + j + 1;
+    const float* p = P + ((size_t)h * N + j) * Tp;
+    for (uint32_t c = threadIdx.x; c < hd; c += 64) {
+        float add = 0.f;
+        bool any = false;
+        for (uint32_t t = 0; t < T; ++t) {
+            const float v = v_cache[(size_t)t * d + h * hd + c];
+            if ((__builtin_bit_cast(uint32_t, v) & 0x7f800000u) == 0x7f800000u) { add = __fadd_rn(add, __fmul_rn(p[t], v)); any = true; }
+        }
+        if (any) out[(size_t)j * d + h * hd + c] = __fadd_rn(out[(size_t)j * d + h * hd + c], add);
     }
 }
 

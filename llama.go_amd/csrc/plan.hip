@@ -564,9 +564,10 @@ static int attention_gemm(Plan* p, const float* q, const float* kc, const float*
     const uint32_t T = past + n, Tp = (T + 31) & ~31u, H = m.H, hd = m.hd, d = m.d;
     const uint64_t need_s = (uint64_t)H * n * Tp, need_v = (uint64_t)H * hd * Tp;
     int rc;
-    if ((rc = grow_floats(ctx, &p->scores, &p->scores_cap, need_s))) return rc;
+    if ((rc = grow_floats(ctx, &p->scores, &p->scores_cap, need_s + 32))) return rc;   // (+ the non-finite-V flag behind the scores)
     if ((rc = grow_floats(ctx, &p->vt, &p->vt_cap, need_v))) return rc;
-    LH_TRACE("attention_gemm/hd%u/n%u", hd, n);   // (its four launches follow: the QK GEMM, k_softmax_causal, k_transpose_v, the PV GEMM)
+    uint32_t* v_nonfinite = (uint32_t*)(p->scores + need_s);
+    LH_TRACE("attention_gemm/hd%u/n%u", hd, n);   // (its four launches follow: the QK GEMM, k_softmax_causal, k_transpose_v, the PV GEMM; then k_attn_gemm_repair)
     {   // S[h][j][t] = sum_c Q[j][h*hd + c] * K[t][h*hd + c]
         GemmArgs a = {};
         a.x = q; a.w[0] = kc; a.y[0] = p->scores; a.groups = 1; a.N = n; a.M = T; a.K = hd; a.ldx = d; a.ldw = d; a.ldy = Tp;
@@ -575,9 +576,9 @@ static int attention_gemm(Plan* p, const float* q, const float* kc, const float*
         if ((rc = launch_gemm<2, 2, 2, 2>(ctx, a, "attn_qk_gemm", H))) return rc;
     }
     LH_TRACE("k_softmax_causal");
-    LH_LAUNCH(k_softmax_causal, dim3(n, H), dim3(256), 0, ctx->stream, p->scores, n, Tp, past, scale);
+    LH_LAUNCH(k_softmax_causal, dim3(n, H), dim3(256), 0, ctx->stream, p->scores, n, Tp, past, scale, v_nonfinite);
     LH_TRACE("k_transpose_v");
-    LH_LAUNCH(k_transpose_v, dim3(Tp / 32, hd / 32, H), dim3(256), 0, ctx->stream, vc, p->vt, T, Tp, d, hd);
+    LH_LAUNCH(k_transpose_v, dim3(Tp / 32, hd / 32, H), dim3(256), 0, ctx->stream, vc, p->vt, T, Tp, d, hd, v_nonfinite);
     LH_HIP(ctx, hipGetLastError());
     {   // O[j][h*hd + c] = sum_t P[h][j][t] * VT[h][c][t]
         GemmArgs a = {};
@@ -586,6 +587,9 @@ static int attention_gemm(Plan* p, const float* q, const float* kc, const float*
         a.causal = 2; a.past = past;
         if ((rc = launch_gemm<2, 2, 2, 1>(ctx, a, "attn_pv_gemm", H))) return rc;
     }
+    // a non-finite V value (k_transpose_v passed it on as 0) goes to the queries that see its key, and to no other row of the call
+    LH_LAUNCH(k_attn_gemm_repair, dim3(n, H), dim3(64), 0, ctx->stream, (const float*)p->scores, vc, out, (const uint32_t*)v_nonfinite, n, Tp, past, d, hd);
+    LH_HIP(ctx, hipGetLastError());
     return 0;
 }
 

@@ -1636,6 +1636,41 @@ int llamago_SetModelTensor(llama_model* m, const char* name, const float* data, 
     if (lh_buf_upload(h, t->buf, 0, data, n) || lh_ctx_sync(h)) return halt_rc(lh_last_error(h));
     return 0;
 }
+// Test instrumentation (tests/test_gpu_cache_probe.py): floats [off, off + n) of a KV cache read to / overwritten from the host, behind everything the
+// owner's stream holds.  which: 0 = K, 1 = V.  The cache is [layer1 - layer0][ctxSize][embd] floats (slot = layer - layer0).
+static int cache_io(const char* who, ml_context* mc, ml_tensor* t, int which, uint64_t off, float* dst, const float* src, uint64_t n) {
+    char msg[256];
+    if (!mc || !mc->hip || !t || !(dst || src)) { snprintf(msg, sizeof msg, "%s: null argument", who); return halt_rc(msg); }
+    if (which != 0 && which != 1) { snprintf(msg, sizeof msg, "%s: which = %d (0 = K, 1 = V)", who, which); return halt_rc(msg); }
+    const uint64_t ne = nelements(t);
+    if (off > ne || n > ne - off) {
+        snprintf(msg, sizeof msg, "%s: floats [%llu, %llu + %llu) outside the cache of %llu floats", who, (unsigned long long)off, (unsigned long long)off, (unsigned long long)n, (unsigned long long)ne);
+        return halt_rc(msg);
+    }
+    if (!n) return 0;
+    lh_ctx* h = mc->hip;
+    if (lh_ctx_sync(h)) return halt_rc(lh_last_error(h));
+    if (dst ? lh_buf_read(h, t->buf, off, dst, n) : (lh_buf_upload(h, t->buf, off, src, n) || lh_ctx_sync(h))) return halt_rc(lh_last_error(h));
+    return 0;
+}
+int llamago_CacheRead(llama_context* c, int which, uint64_t off_floats, float* dst, uint64_t n) {
+    if (!c || !dst) return halt_rc("llamago_CacheRead: null argument");
+    return cache_io("llamago_CacheRead", c->mlctx, which == 1 ? c->V : c->K, which, off_floats, dst, nullptr, n);
+}
+int llamago_CacheWrite(llama_context* c, int which, uint64_t off_floats, const float* src, uint64_t n) {
+    if (!c || !src) return halt_rc("llamago_CacheWrite: null argument");
+    return cache_io("llamago_CacheWrite", c->mlctx, which == 1 ? c->V : c->K, which, off_floats, nullptr, src, n);
+}
+int llamago_BatchCacheRead(llama_batch* p, uint32_t pod, int which, uint64_t off_floats, float* dst, uint64_t n) {
+    if (!p || !dst) return halt_rc("llamago_BatchCacheRead: null argument");
+    if (pod >= p->K.size() || pod >= p->V.size()) return halt_rc("llamago_BatchCacheRead: pod outside the batch");
+    return cache_io("llamago_BatchCacheRead", p->mlctx, which == 1 ? p->V[pod] : p->K[pod], which, off_floats, dst, nullptr, n);
+}
+int llamago_BatchCacheWrite(llama_batch* p, uint32_t pod, int which, uint64_t off_floats, const float* src, uint64_t n) {
+    if (!p || !src) return halt_rc("llamago_BatchCacheWrite: null argument");
+    if (pod >= p->K.size() || pod >= p->V.size()) return halt_rc("llamago_BatchCacheWrite: pod outside the batch");
+    return cache_io("llamago_BatchCacheWrite", p->mlctx, which == 1 ? p->V[pod] : p->K[pod], which, off_floats, nullptr, src, n);
+}
 int llamago_TimeComputes(llama_context* c, int on) { return c && c->mlctx && c->mlctx->hip ? lh_ctx_time_computes(c->mlctx->hip, on) : 1; }
 int llamago_ComputeStats(llama_context* c, uint64_t* calls, double* wall_us, double* device_us) {
     lh_compute_stats st = {};

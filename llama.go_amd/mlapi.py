@@ -285,6 +285,23 @@ class Model:
             self.h = None
 
 
+def _cache_read(ml, name, head, which, off, n):
+    f = getattr(ml.lib, name)
+    f.restype, f.argtypes = C.c_int, [VP] + [c_u32] * (len(head) - 1) + [C.c_int, c_u64, c_f32p, c_u64]
+    out = np.empty(int(n), dtype=np.float32)
+    if f(*head, int(which), int(off), out.ctypes.data_as(c_f32p), int(n)):
+        raise MLError(f"{name}: {ml.last_error()}")
+    return out
+
+
+def _cache_write(ml, name, head, which, off, values):
+    f = getattr(ml.lib, name)
+    f.restype, f.argtypes = C.c_int, [VP] + [c_u32] * (len(head) - 1) + [C.c_int, c_u64, c_f32p, c_u64]
+    a = np.ascontiguousarray(values, dtype=np.float32).ravel()
+    if f(*head, int(which), int(off), a.ctypes.data_as(c_f32p), a.size):
+        raise MLError(f"{name}: {ml.last_error()}")
+
+
 class Context:
     """llama.Context (llama.go:83-88)."""
 
@@ -442,6 +459,15 @@ class Context:
         if L.llamago_Perplexity(self.h, self.model.h, toks, len(tokens), int(chunk), C.byref(nll), C.byref(cnt)):
             raise MLError(f"llamago_Perplexity: {self.ml.last_error()}")
         return float(nll.value), int(cnt.value)
+
+    def CacheRead(self, which, off, n):
+        """llamago_CacheRead (product only, test instrumentation): n floats at float offset `off` of the K (which = 0) or V (1) cache, behind everything
+        the context's stream holds.  Layout [layer - layer0][position][channel]; raises on a range outside the cache."""
+        return _cache_read(self.ml, "llamago_CacheRead", (self.h,), which, off, n)
+
+    def CacheWrite(self, which, off, values):
+        """llamago_CacheWrite (product only, test instrumentation): the floats `values` written at float offset `off` of the K / V cache."""
+        _cache_write(self.ml, "llamago_CacheWrite", (self.h,), which, off, values)
 
     def free(self):
         if self.h:
@@ -896,6 +922,14 @@ class Batch:
         if self.ml.lib.llamago_BatchTick(self.h, out):
             raise MLError(f"llamago_BatchTick: {self.ml.last_error()}")
         return list(out)
+
+    def CacheRead(self, pod, which, off, n):
+        """llamago_BatchCacheRead (test instrumentation): Context.CacheRead on pod `pod`'s cache."""
+        return _cache_read(self.ml, "llamago_BatchCacheRead", (self.h, int(pod)), which, off, n)
+
+    def CacheWrite(self, pod, which, off, values):
+        """llamago_BatchCacheWrite (test instrumentation): Context.CacheWrite on pod `pod`'s cache."""
+        _cache_write(self.ml, "llamago_BatchCacheWrite", (self.h, int(pod)), which, off, values)
 
     def free(self):
         if self.h:
