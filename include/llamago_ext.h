@@ -168,6 +168,19 @@ int llamago_BatchDecodeLookup(llama_batch* b, const uint32_t* first_tokens, cons
                               float* logits_last, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap);
 int llamago_SpecAcceptPods(const uint32_t* arg, const uint32_t* tok, uint32_t n_pods, uint32_t n_rows, const uint32_t* k, const uint32_t* pos, const uint32_t* produced,
                            uint32_t n_steps, uint32_t ctx_size, uint32_t* a_out, uint32_t* pos_out, uint32_t* produced_out, uint32_t* pending_out, uint32_t* ids_out);
+/* lh_batch_decode: n_steps ticks of every pod from (first_tokens[i], past[i]) in one call; out [pods][n_steps], logits_last (optional) [pods][vocab]:
+ * the logits of the last tick (llamago_BatchTick returns ids only). */
+int llamago_BatchDecode(llama_batch* b, const uint32_t* first_tokens, const uint32_t* past, uint32_t n_steps, uint32_t* out, float* logits_last);
+/* lh_batch_fork: cache rows [0, n_pos) of every layer, K and V, and the token history of pod src copied into the pods dst[0..n_dst), which then form a
+ * sharing group of length n_pos with src: the ticks read the group's prefix once per block of member rows, every logit byte-equal to a batch that never
+ * forked (the rule, the leave predicate, the refusals and what is out of scope are stated in llamahip.h).  Nothing else moves: feed each destination at
+ * past = n_pos or place it with llamago_BatchSet.  llamago_BatchCacheWrite into rows below the shared length makes the pod leave its group.
+ * llamago_BatchShareInfo: lh_batch_share_info - per pod the lowest pod of its group and the shared length (its own index and 0 without a group).
+ * llamago_ShareSchedule: lh_share_schedule, the block table a tick derives from that state, alone on host arrays (no GPU). */
+int llamago_BatchFork(llama_batch* b, uint32_t src, const uint32_t* dst, uint32_t n_dst, uint32_t n_pos);
+int llamago_BatchShareInfo(llama_batch* b, uint32_t* group, uint32_t* len);
+int llamago_ShareSchedule(const uint32_t* group, const uint32_t* len, uint32_t rows, uint32_t qb, uint32_t min_rows, lh_share_block* blocks, uint32_t cap,
+                          uint32_t* row_block);
 /* lh_sample_pods: the multi-pod sampler of a sampled tick alone on host arrays, on the model context's device - row i of logits [n][n_logits] over ring i
  * of rings [n][ring_size] (ring_pos[i] ids appended so far) as sampling call draws[i]; rings_out / ring_pos_out (optional) = the rings behind the ids. */
 int llamago_SamplePods(const float* logits, uint32_t n, uint32_t n_logits, const uint32_t* rings, uint32_t ring_size, const uint32_t* ring_pos, const uint64_t* draws,

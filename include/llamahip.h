@@ -477,6 +477,54 @@ typedef struct lh_feed_block { uint32_t row0, n; } lh_feed_block;               
 int lh_feed_schedule(const uint32_t* n_tokens, const uint32_t* past, uint32_t rows, uint32_t solo_min, uint32_t qb, uint64_t sizes_ok,
                      lh_feed_pass* passes, uint32_t pass_cap, lh_feed_seg* segs, uint32_t seg_cap, lh_feed_block* blocks, uint32_t block_cap, uint32_t* counts);
 
+/* ---- a common prompt prefix shared by pods of a batch ---------------------------------------------------------------
+ * The pods of a server usually stand behind one identical prefix (a system prompt in front of every job, several continuations of one prompt).
+ * lh_batch_fork gives pods the prefix another pod has evaluated, and the ticks then read the prefix's keys and values ONCE per block of member rows
+ * instead of once per row.
+ * The rule.  In stream order, cache rows [0, n_pos) of every layer slot, K and V, of pod src are copied into every pod of dst[0..n_dst) (device to
+ * device; every member keeps a full copy of its own), and entries [0, n_pos) of the source's token history into the destinations' histories, so that
+ * a later context swap knows them.  Nothing else moves: positions, pending tokens, output lists, sampler rings and draw counters of all pods stay as
+ * they are (a fork is allowed on a sampling batch).  The caller then feeds each destination at past = n_pos (lh_batch_feed / lh_batch_feed_sample) or
+ * places it with lh_batch_set.
+ * Sharing groups.  The fork records {src} + dst as a group of shared length n_pos.  A pod is in at most one group.  If src already stands in a group of
+ * exactly that length the destinations join it; otherwise src and the destinations leave whatever groups they were in and form a new one.  The
+ * invariant of a member is "my cache rows [0, len) are byte-equal to every other member's"; ONE predicate keeps it: a pod leaves its group when
+ * anything writes its cache below len - lh_batch_feed / lh_batch_feed_sample with past[i] < len, lh_batch_prompt, a tick or lh_batch_set that places it
+ * at a position < len, lh_batch_decode_lookup with past[i] < len, the re-fed Eval of a context swap, anything that evaluates a token below len on the
+ * pod's own lh_llama (lh_llama_eval, lh_llama_stage, lh_llama_score, the one-token step and the resident greedy, sampled, lookup and verify loops;
+ * seen when the batch next looks), and whoever writes the cache from outside says so with lh_batch_share_written.  A group of one member dissolves.
+ * A fork first reads the ids of the ticks so far into the pods' histories (a stream wait, only if there are such ticks), so that no later read
+ * records a destination's old tokens over the history it was given.
+ * Ticks.  Where the batch shares one weight pass and its plan has split attention partials (ctx > 256, head size 128) a tick runs
+ * k_attention_split_shared on k_attention_split's grid: the full 128-key chunks inside a group's prefix are loaded once per block of member rows (the
+ * blocks: lh_share_schedule below) from the block's first row's OWN cache, every other chunk and every row without a block as before, the partial
+ * records in the same slots, k_attention_combine unchanged.  Per query row the operations and their order are k_attention_split's, so every logit of
+ * every tick is byte-equal to the per-row kernels' (LLAMAHIP_SHARE_ROW_ATTN=1 keeps those: the A/B switch).  Elsewhere a fork still copies and ticks
+ * run as before.  Feeds, lh_batch_decode_lookup passes and prompt Evals keep their own attention routes.
+ * State left behind: the destinations' cache rows [0, n_pos) and histories as the source's; rows >= n_pos of every cache untouched; the group state.
+ * Refused before anything is enqueued, the batch left exactly as it was: src or a dst[i] outside the batch, dst naming src or a pod twice, n_dst == 0,
+ * n_pos == 0, n_pos beyond the source's position in the host mirror or the mirror not placed yet (LH_EINVAL); a batch of layer-shard stages
+ * (LH_EUNSUPPORTED).
+ * Out of scope: freeing or never allocating the members' own copies (copy-on-write), shared reads in feeds, in lookup passes and in the single-pass
+ * k_attention (ctx <= 256), layer shards and the pipeline, per-pod sampler seeds, detecting equal prefixes by itself.
+ * Switches (read per tick; a change that alters the tick's launches re-captures it): LLAMAHIP_SHARE_ROW_ATTN=1, LLAMAHIP_SHARE_QB = 2 | 4 | 8 (rows
+ * per block), LLAMAHIP_SHARE_MIN (smallest group that gets blocks). */
+int lh_batch_fork(lh_batch* b, uint32_t src, const uint32_t* dst, uint32_t n_dst, uint32_t n_pos);
+/* Per pod the lowest pod index of its sharing group and the shared length; a pod that shares nothing: its own index and 0.  Host state only (no
+ * stream wait).  Both arrays [rows]. */
+int lh_batch_share_info(lh_batch* b, uint32_t* group_out, uint32_t* len_out);
+/* The leave rule for writers the batch cannot see (a host upload into a pod's cache): something wrote pod's cache rows from position pos_lo on.  The
+ * pod leaves its group if pos_lo lies below the shared length.  Host state only.  pod outside the batch: LH_EINVAL. */
+int lh_batch_share_written(lh_batch* b, uint32_t pod, uint32_t pos_lo);
+/* The block table of a tick: the pure function (no GPU) the tick executes.  group / len [rows] as lh_batch_share_info returns them.  Groups in
+ * ascending order of their lowest member, members ascending, cut into blocks of at most qb rows (2, 4 or 8); chunks = len / 128 full key chunks lie
+ * inside the prefix; a group with chunks == 0 or fewer than min_rows members, and a trailing block of one row, get no block.  row_block[j] (optional,
+ * [rows]) = the block of row j or 0xFFFFFFFF.  blocks == NULL: the sizing call.  Returns the block count; -1: a null group / len, rows outside 1..64,
+ * another qb, a group index that is not its group's lowest member, members of one group with different lengths, cap below the count (nothing written). */
+typedef struct lh_share_block { uint32_t n, chunks, row[8]; } lh_share_block;   /* rows row[0..n) share the first `chunks` key chunks */
+int lh_share_schedule(const uint32_t* group, const uint32_t* len, uint32_t rows, uint32_t qb, uint32_t min_rows, lh_share_block* blocks, uint32_t cap,
+                      uint32_t* row_block);
+
 /* ---- multi-GPU: layer shard over RCCL point-to-point ------------------------------------------------
  * The reference's only parallel dimension is request-level "pods" (pkg/server/server.go:84-106: Engine() starts up to
  * MaxPods concurrent Do() goroutines; server.go:151: each with its own llama.Context over the shared Model).  Layers

@@ -9,6 +9,7 @@ namespace lh {
 struct SampleState;
 struct Spec;
 struct AttnBlock;
+struct ShareTable;
 
 struct LayerW {
     const float *attn_norm = nullptr, *wq = nullptr, *wk = nullptr, *wv = nullptr, *wo = nullptr, *ffn_norm = nullptr, *w1 = nullptr, *w2 = nullptr, *w3 = nullptr;
@@ -92,7 +93,15 @@ struct Plan {
     static constexpr uint32_t HIST_UNKNOWN = 0xFFFFFFFFu;
     std::shared_ptr<std::vector<uint32_t>> hist;   // shared by every plan over the same KV cache (Buffer::kv_hist)
     uint32_t keep = 0;
-    void record(uint32_t pos, uint32_t tok) { if (hist && pos < hist->size()) (*hist)[pos] = tok; }
+    // Prefix sharing (lh_batch_fork): while this plan's pod is a member of a sharing group its cache rows [0, share_len) must stay byte-equal to
+    // the other members'.  Whatever evaluates a token on this plan's own cache below share_len notes it here - plan_eval, and through record() the
+    // one-token step, the resident greedy / sampled loops, the lookup loops and the verify pass; the batch drops the pod from its group when it next looks.
+    uint32_t share_len = 0;
+    bool share_broken = false;
+    void record(uint32_t pos, uint32_t tok) {
+        if (pos < share_len) share_broken = true;
+        if (hist && pos < hist->size()) (*hist)[pos] = tok;
+    }
 };
 
 // The re-fed run of a context swap (server.go:166-171) for a stream whose window is full: positions [0, past) hold hist[], `pending` is the
@@ -112,6 +121,10 @@ struct BatchCtx {
     uint32_t n_blocks = 0, qb = 0;
     uint32_t n_blocks1 = 0;              // the first n_blocks1 blocks hold ONE row each (decode rows, one-token tails): they take the QB = 1 instantiation
     uint32_t max_T = 0;                  // keys the pass's longest row sees (its highest position + 1): LDS of the single pass, chunk grid of the split
+    // a tick whose pods share a prompt prefix (lh_batch_fork): the device table {row -> block, blocks} k_attention_split_shared<share_qb> reads
+    // (kernels_attn_share.h); share_blocks / share_rows = what the table held when the tick was captured (route trace only).  nullptr: the per-row kernels.
+    const ShareTable* share = nullptr;
+    uint32_t share_qb = 0, share_blocks = 0, share_rows = 0;
 };
 
 int plan_create(lh_ctx* ctx, const ModelDesc& md, Plan** out);

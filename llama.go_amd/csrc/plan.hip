@@ -14,8 +14,10 @@
 #include "kernels_gemm_b9.h"
 #include "kernels_rows.h"
 #include "kernels_attn_seg.h"
+#include "kernels_attn_share.h"
 #include "kernels_spec.h"
 #include "feed_schedule.h"
+#include "share_schedule.h"
 #include <math.h>
 #include <string.h>
 #include <algorithm>
@@ -1231,9 +1233,41 @@ static int launch_attention_seg_qb(Plan* p, const AttnArgs& a, const BatchCtx* b
 static constexpr size_t ATT_SEG_LDS_MAX = 48 * 1024;   // the single-pass segment kernel stays inside the LDS a launch gets without an attribute
 static bool attention_seg_fits(uint32_t qb, uint32_t max_T) { return ((size_t)2 * qb * ((max_T + 63) & ~63u) + (size_t)qb * ATT_TH) * 4 <= ATT_SEG_LDS_MAX; }
 
+// a tick whose pods share a prompt prefix (lh_batch_fork; kernels_attn_share.h): k_attention_split's grid, the full chunks inside a group's prefix read
+// once per block of up to QB member rows.  The same partial records at the same addresses, so the combine is launch_attention_split's.
+template <int QB>
+static int launch_attention_split_shared(Plan* p, const AttnArgs& a, const BatchCtx* bc) {
+    lh_ctx* ctx = p->ctx;
+    const ModelDesc& m = p->md;
+    if (a.hd != 128) LH_FAIL(ctx, LH_EUNSUPPORTED, "split attention: head dim %u", a.hd);
+    if (a.n > SHARE_ROWS_MAX) LH_FAIL(ctx, LH_EINVAL, "shared attention: %u rows (the table holds %u)", a.n, SHARE_ROWS_MAX);
+    const uint32_t nch = (m.ctx + ATT_TC - 1) / ATT_TC;
+    if (g_prepare_only || g_only) return 0;
+    {
+        ProfScope ps(ctx->stream, "attention_split_shared", (uint64_t)2 * m.ctx * a.d * 4 * a.n);
+        LH_TRACE("k_attention_split_shared/c%u/qb%u/b%u/n%u", nch, (uint32_t)QB, bc->share_blocks, bc->share_rows);
+        LH_LAUNCH_AS("k_attention_split_shared", k_attention_split_shared<QB>, dim3(m.H, nch, a.n), dim3(ATT_TH), 0, ctx->stream, a, bc->share, bc->attn_part);
+    }
+    {
+        ProfScope ps(ctx->stream, "attention_combine", (uint64_t)m.H * nch * (a.hd + 2) * 4 * a.n);
+        LH_TRACE("k_attention_combine/c%u/n%u", nch, a.n);
+        LH_LAUNCH(k_attention_combine, dim3(m.H, a.n), dim3(128), 0, ctx->stream, a, (const float*)bc->attn_part, nch);
+    }
+    LH_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
 // the attention of a batched Eval's rows: query blocks (a feed), else row by row (ticks; LLAMAHIP_FEED_ROW_ATTN)
 static int launch_attention_rows(Plan* p, const AttnArgs& a, const BatchCtx* bc) {
     lh_ctx* ctx = p->ctx;
+    if (bc->share && bc->attn_part) {
+        switch (bc->share_qb) {
+            case 2: return launch_attention_split_shared<2>(p, a, bc);
+            case 4: return launch_attention_split_shared<4>(p, a, bc);
+            case 8: return launch_attention_split_shared<8>(p, a, bc);
+            default: LH_FAIL(ctx, LH_EINVAL, "shared attention: blocks of %u rows (2, 4 or 8)", bc->share_qb);
+        }
+    }
     if (bc->blocks) {
         if (a.hd > ATT_TH || ATT_TH % a.hd || a.hd % 4) LH_FAIL(ctx, LH_EUNSUPPORTED, "attention: head dim %u unsupported (needs to divide %d)", a.hd, ATT_TH);
         // (a single pass whose score rows outgrow the LDS budget - wide blocks on a head size without the split kernel - keeps the per-row kernel)
@@ -2151,6 +2185,7 @@ int plan_eval(Plan* p, const uint32_t* tokens_host, const float* x_in_dev, float
             for (uint32_t i = 0; i < n; ++i)
                 if (tokens_host[i] >= m.V) LH_FAIL(ctx, LH_EINVAL, "Eval: token id %u at index %u outside the vocabulary of %u", tokens_host[i], i, m.V);
         if (m.first_stage()) for (uint32_t i = 0; i < n; ++i) p->record(past + i, tokens_host[i]);
+        if (past < p->share_len) p->share_broken = true;   // this Eval writes cache rows of a shared prefix: the pod's batch drops it from its group (lh_batch_fork)
     }
     if (!m.first_stage() && !x_in_dev) LH_FAIL(ctx, LH_EINVAL, "Eval: later stage needs the residual stream");
     if (!m.last_stage() && !x_out_dev) LH_FAIL(ctx, LH_EINVAL, "Eval: non-final stage needs an output buffer");
@@ -2232,8 +2267,50 @@ struct Batch {
     size_t feed_cap = 0;
     float* feed_part = nullptr;
     BatchSpec* spec = nullptr;     // lh_batch_decode_lookup: device state + the captured pass
+    // Prefix sharing (lh_batch_fork).  Host state: pod i is a member of group sh_gid[i] (SH_NONE: of none) of shared length sh_len[i];
+    // the invariant of a member is "my cache rows [0, len) are byte-equal to every other member's" (share_written enforces it).
+    // Device: the block table the shared tick kernel reads (batched, split partials), the table last sent, and what the captured tick was captured for.
+    static constexpr uint32_t SH_NONE = 0xFFFFFFFFu;
+    std::vector<uint32_t> sh_gid, sh_len;
+    uint32_t sh_next_gid = 0;
+    ShareTable* share_dev = nullptr;
+    ShareTable share_sent;         // (set to "no block" where share_dev is allocated)
+    uint32_t share_sent_blocks = 0;
+    bool shared = false, cap_shared = false;   // the tick takes k_attention_split_shared (some block in the table, LLAMAHIP_SHARE_ROW_ATTN unset)
+    uint32_t share_qb = 0, cap_share_qb = 0;
     float* logits() const { return batched || B == 1 ? pods[0]->logits : logits_own; }
 };
+
+// ---- prefix sharing: group state (host only) ---------------------------------------------------------------------------------------------------
+static void share_set(Batch* b, uint32_t pod, uint32_t gid, uint32_t len) {
+    b->sh_gid[pod] = gid; b->sh_len[pod] = len;
+    b->pods[pod]->share_len = len; b->pods[pod]->share_broken = false;
+}
+// pod leaves its group; a group of one member dissolves
+static void share_leave(Batch* b, uint32_t pod) {
+    const uint32_t gid = b->sh_gid[pod];
+    if (gid == Batch::SH_NONE) return;
+    share_set(b, pod, Batch::SH_NONE, 0);
+    uint32_t n = 0, last = 0;
+    for (uint32_t i = 0; i < b->B; ++i) if (b->sh_gid[i] == gid) { ++n; last = i; }
+    if (n == 1) share_set(b, last, Batch::SH_NONE, 0);
+}
+// THE predicate: something writes pod's cache from position pos_lo on
+static void share_written(Batch* b, uint32_t pod, uint32_t pos_lo) {
+    if (b->sh_gid[pod] != Batch::SH_NONE && pos_lo < b->sh_len[pod]) share_leave(b, pod);
+}
+// Evals on the pods' own plans since the batch last looked (Plan::share_broken: a solo feed pass, the re-fed Eval of a context swap, lh_llama_eval)
+static void share_sync(Batch* b) {
+    for (uint32_t i = 0; i < b->B; ++i) if (b->pods[i]->share_broken) share_leave(b, i);
+}
+static void share_info(Batch* b, uint32_t* group, uint32_t* len) {
+    share_sync(b);
+    for (uint32_t i = 0; i < b->B; ++i) {
+        uint32_t lo = i;
+        if (b->sh_gid[i] != Batch::SH_NONE) for (uint32_t j = 0; j < i; ++j) if (b->sh_gid[j] == b->sh_gid[i]) { lo = j; break; }
+        group[i] = lo; len[i] = b->sh_len[i];
+    }
+}
 
 static void batch_drop_graph(Batch* b) {
     if (b->exec) { hipGraphExecDestroy(b->exec); b->exec = nullptr; }
@@ -2249,6 +2326,10 @@ static int batch_enqueue_tick(Batch* b, const float* x_in, float* x_out) {
     int rc;
     if (b->batched) {
         BatchCtx bc = {b->rows_dev, b->tok_dev, b->attn_part};
+        if (b->shared) {   // some pods share a prefix: the shared tick kernel on the table share_prepare sent (with no block: exactly the launches of a batch that never forked)
+            bc.share = b->share_dev; bc.share_qb = b->share_qb; bc.share_blocks = b->share_sent_blocks;
+            for (uint32_t i = 0; i < B; ++i) bc.share_rows += b->share_sent.row_block[i] != SHARE_NO_BLOCK;
+        }
         if ((rc = plan_eval(p0, nullptr, x_in, x_out, B, 0, false, &bc))) return rc;
     } else {
         for (uint32_t i = 0; i < B; ++i) {
@@ -2285,6 +2366,7 @@ static int batch_enqueue_tick(Batch* b, const float* x_in, float* x_out) {
 // captured graph, re-captured when an address it holds has changed.
 static int batch_tick_unchecked(Batch* b, const float* x_in, float* x_out);
 static int batch_swap(Batch* b);
+static int share_prepare(Batch* b);
 static int batch_tick(Batch* b, const float* x_in, float* x_out) {
     lh_ctx* ctx = b->ctx;
     const ModelDesc& m = b->pods[0]->md;
@@ -2295,6 +2377,8 @@ static int batch_tick(Batch* b, const float* x_in, float* x_out) {
     for (uint32_t i = 0; i < b->B; ++i) full = full || b->pos[i] >= m.ctx;
     int rc;
     if (full && (rc = batch_swap(b))) return rc;   // whole-model batches swap context like server.Do; a stage's batch fails here
+    share_sync(b);
+    for (uint32_t i = 0; i < b->B; ++i) share_written(b, i, b->pos[i]);   // the tick appends row i's K / V at pos[i]: below a shared length the pod leaves its group
     rc = batch_tick_unchecked(b, x_in, x_out);
     if (rc == 0) { for (uint32_t i = 0; i < b->B; ++i) b->pos[i] += 1; b->ticks += 1; }
     return rc;
@@ -2305,12 +2389,13 @@ static int batch_tick_unchecked(Batch* b, const float* x_in, float* x_out) {
     int rc;
     const char* pp = getenv("LLAMAHIP_SAMPLE_PER_POD");
     b->per_pod = pp && pp[0] == '1';
+    if ((rc = share_prepare(b))) return rc;   // the block table of the pods that share a prefix, re-sent when it changed (outside the captured graph)
     if (!p0->use_graph || !b->warm) {
         b->warm = true;
         return batch_enqueue_tick(b, x_in, x_out);
     }
     if (b->exec && (b->cap_x_in != x_in || b->cap_x_out != x_out || b->cap_splitk_gen != ctx->splitk_gen || b->cap_scratch_gen != b->scratch_gen() || b->cap_sampling != b->sampling ||
-                    b->cap_per_pod != b->per_pod))
+                    b->cap_per_pod != b->per_pod || b->cap_shared != b->shared || (b->shared && b->cap_share_qb != b->share_qb)))
         batch_drop_graph(b);
     if (!b->exec) {
         LH_HIP(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeRelaxed));
@@ -2320,7 +2405,7 @@ static int batch_tick_unchecked(Batch* b, const float* x_in, float* x_out) {
         if (e != hipSuccess) LH_FAIL(ctx, LH_EHIP, "hipStreamEndCapture (batch tick): %s", hipGetErrorString(e));
         LH_HIP(ctx, hipGraphInstantiate(&b->exec, b->graph, nullptr, nullptr, 0));
         b->cap_x_in = x_in; b->cap_x_out = x_out; b->cap_splitk_gen = ctx->splitk_gen; b->cap_scratch_gen = b->scratch_gen(); b->cap_sampling = b->sampling;
-        b->cap_per_pod = b->per_pod;
+        b->cap_per_pod = b->per_pod; b->cap_shared = b->shared; b->cap_share_qb = b->share_qb;
     }
     LH_HIP(ctx, hipGraphLaunch(b->exec, ctx->stream));
     return 0;
@@ -2333,7 +2418,7 @@ static void batch_free(Batch* b) {
     hipStreamSynchronize(b->ctx->stream);
     batch_drop_graph(b);
     batch_spec_free(b);
-    void* bufs[] = {b->rows_dev, b->tok_dev, b->ids_dev, b->out_dev, b->sp_dev, b->logits_own, b->attn_part, b->ss_dev, b->ring_dev, b->feed_dev, b->feed_part};
+    void* bufs[] = {b->rows_dev, b->tok_dev, b->ids_dev, b->out_dev, b->sp_dev, b->logits_own, b->attn_part, b->ss_dev, b->ring_dev, b->feed_dev, b->feed_part, b->share_dev};
     for (void* q : bufs) if (q) hipFree(q);
     delete b;
 }
@@ -2423,6 +2508,43 @@ static constexpr uint32_t FEED_QB = 4;           // query rows per attention blo
 static uint32_t env_u32(const char* name, uint32_t dflt) {
     const char* e = getenv(name);
     return (e && *e) ? (uint32_t)strtoul(e, nullptr, 10) : dflt;
+}
+
+// ---- prefix sharing: the tick's block table ---------------------------------------------------------------------------------------------------------
+// Before a tick is enqueued the batch derives the table from the pods' group state (share_schedule.h: a pure function, B <= 64 rows), compares it with
+// the table last sent and re-sends it on change (k_share_set, the table as kernel arguments, in stream order in front of the tick: the captured graph
+// reads it from a fixed address, so a changed table needs no new capture).  Only "no block" <-> "some block" changes the tick's launches (cap_shared).
+// Switches, read per tick: LLAMAHIP_SHARE_ROW_ATTN=1 (the per-row kernels: the A/B switch and the tests' reference), LLAMAHIP_SHARE_QB, LLAMAHIP_SHARE_MIN.
+static constexpr uint32_t SHARE_QB = 4;    // rows per block (LLAMAHIP_SHARE_QB: 2, 4, 8).  Measured (profiles/shared_prefix.txt, 7B fp32, ctx 2048): 4 beats 8 in every case - 64 pods
+                                           // behind 1920 shared keys 18.15 ms per tick at 4 (two workgroups per CU), 20.71 at 8 (one), 29.19 on the per-row kernels
+static constexpr uint32_t SHARE_MIN = 2;   // smallest group that gets blocks (LLAMAHIP_SHARE_MIN).  Measured: 16 pairs behind 1024 / 1920 keys 10.29 / 12.79 ms against 11.73 / 16.40
+                                           // per-row.  Behind 256 keys every group size loses (pairs 4.6 %, larger groups 0.6-1.6 %): a matter of the length, not of this value
+static int share_prepare(Batch* b) {
+    lh_ctx* ctx = b->ctx;
+    b->shared = false;
+    if (!b->share_dev) return 0;   // row-by-row batches and plans without split partials (ctx <= 256, hd != 128): ticks run as they always did
+    const char* ra = getenv("LLAMAHIP_SHARE_ROW_ATTN");
+    const bool row_attn = ra && ra[0] == '1';
+    const uint32_t qb = env_u32("LLAMAHIP_SHARE_QB", SHARE_QB), min_rows = env_u32("LLAMAHIP_SHARE_MIN", SHARE_MIN);
+    if (qb != 2 && qb != 4 && qb != 8) LH_FAIL(ctx, LH_EINVAL, "lh_batch: LLAMAHIP_SHARE_QB = %u (2, 4 or 8)", qb);
+    ShareTable t;
+    memset(&t, 0, sizeof t);
+    for (uint32_t j = 0; j < SHARE_ROWS_MAX; ++j) t.row_block[j] = SHARE_NO_BLOCK;
+    int nb = 0;
+    if (!row_attn) {
+        uint32_t group[SHARE_ROWS_MAX], len[SHARE_ROWS_MAX];
+        share_info(b, group, len);
+        nb = share_schedule(group, len, b->B, qb, min_rows, t.blocks, SHARE_BLOCKS_MAX, t.row_block);
+        if (nb < 0) LH_FAIL(ctx, LH_EINVAL, "lh_batch: the sharing groups of the batch are inconsistent (internal)");
+    }
+    if (memcmp(&t, &b->share_sent, sizeof t) != 0) {
+        LH_TRACE("share_table/b%u", (uint32_t)nb);
+        LH_LAUNCH(k_share_set, dim3(1), dim3(512), 0, ctx->stream, b->share_dev, t);
+        LH_HIP(ctx, hipGetLastError());
+        b->share_sent = t; b->share_sent_blocks = (uint32_t)nb;
+    }
+    b->shared = nb > 0; b->share_qb = qb;
+    return 0;
 }
 
 // sample: lh_batch_feed_sample - the same feed on a batch whose ticks sample; the fed pods' rings (k_feed_ring) and the id behind a pod's last row
@@ -2554,6 +2676,9 @@ static int batch_feed(Batch* b, const uint32_t* const* tokens, const uint32_t* n
         }
         LH_HIP(ctx, hipMemcpyAsync(b->feed_dev, ctx->staging, bytes, hipMemcpyHostToDevice, ctx->stream));
     }
+    // a batched pass runs on pod 0's plan over a row table and writes OTHER pods' caches, so the batch applies the sharing predicate here (a solo pass also
+    // notes itself on its pod's plan): a pod fed below its group's shared length leaves the group
+    for (uint32_t i = 0; i < B; ++i) if (n_tokens[i]) share_written(b, i, past[i]);
     // a sampled pass: the rings of its segments in front of it, one sampler launch over the pods whose feed ends in it behind it
     auto pass_rings = [&](const lh_feed_pass& ps) -> int {
         return feed_ring_launch(ctx, (const FeedRingSeg*)(b->feed_dev + o_rseg) + ps.seg0, ps.nseg, (const uint32_t*)(b->feed_dev + o_toks), b->ss_dev, b->ring_dev, b->ring_cap);
@@ -3475,6 +3600,7 @@ int lh_llama_stage(lh_llama* m, const uint32_t* tokens, const uint32_t* tokens_d
         const uint32_t slot = 1 + (p->slot_counter++ % (SP_SLOTS - 1));
         if (md.first_stage() && !tokens && !tokens_dev) LH_FAIL(ctx, LH_EINVAL, "stage: first stage needs a token id (host or device)");
         if (md.first_stage() && tokens && tokens[0] >= md.V) LH_FAIL(ctx, LH_EINVAL, "stage: token id %u outside the vocabulary of %u", tokens[0], md.V);
+        if (past < p->share_len) p->share_broken = true;   // (this path records no token: the note of Plan::record, made here)
         if ((rc = upload_step_params(p, slot, tokens ? tokens[0] : 0, past, 0))) return rc;
         if ((rc = enqueue_decode(p, p->sp_dev + slot, x_in_dev, x_out_dev, false, md.last_stage() ? argmax_dev : nullptr, tokens ? nullptr : tokens_dev))) return rc;
     } else {
@@ -3529,6 +3655,13 @@ int lh_batch_create(lh_ctx* ctx, lh_llama* const* pods, uint32_t n_pods, lh_batc
     if (ok && m.last_stage()) ok = al((void**)&b->out_dev, 4 * (size_t)n_pods * b->out_cap);
     if (ok && m.last_stage() && !b->batched && n_pods > 1) ok = al((void**)&b->logits_own, 4 * (size_t)n_pods * m.V);
     if (ok && b->batched && p0->attn_part) ok = al((void**)&b->attn_part, 4 * (size_t)n_pods * m.H * ((m.ctx + ATT_TC - 1) / ATT_TC) * (m.hd + 2));
+    // prefix sharing: the block table of the shared tick kernel, where ticks have split partials to share (elsewhere a fork still copies and ticks run as ever)
+    b->sh_gid.assign(n_pods, Batch::SH_NONE);
+    b->sh_len.assign(n_pods, 0u);
+    memset(&b->share_sent, 0, sizeof b->share_sent);
+    for (uint32_t j = 0; j < SHARE_ROWS_MAX; ++j) b->share_sent.row_block[j] = SHARE_NO_BLOCK;
+    if (ok && b->attn_part && m.first_stage() && m.last_stage())
+        ok = al((void**)&b->share_dev, sizeof(ShareTable)) && hipMemsetAsync(b->share_dev, 0xFF, sizeof(ShareTable), ctx->stream) == hipSuccess;   // every row: no block
     if (ok) {
         // The zero fills above run on the context's stream, which is non-blocking: a synchronous copy (null stream) is NOT ordered behind
         // them.  Without this wait the fill of rows_dev could land after the table below and leave null cache pointers in it (seen as a GPU
@@ -3568,7 +3701,9 @@ int lh_batch_read_ids(lh_batch* h, uint32_t* ids_host) {
 int lh_batch_set(lh_batch* h, const uint32_t* tokens, const uint32_t* past) {
     if (!h || !past) return LH_EINVAL;
     LH_HIP(h->b->ctx, hipSetDevice(h->b->ctx->device));
-    return batch_set(h->b, tokens, past);
+    int rc = batch_set(h->b, tokens, past);
+    if (rc == 0) for (uint32_t i = 0; i < h->b->B; ++i) share_written(h->b, i, past[i]);   // placed below a shared length: the next tick writes there
+    return rc;
 }
 
 int lh_batch_set_sampler(lh_batch* h, const lh_sample_params* sp, uint32_t ring_size, const uint32_t* const* ring_init, const uint32_t* n_init) {
@@ -3641,6 +3776,7 @@ int lh_batch_prompt(lh_batch* h, const uint32_t* const* prompts, const uint32_t*
         past[i] = n_prompt[i];
     }
     int rc;
+    for (uint32_t i = 0; i < b->B; ++i) share_written(b, i, 0);   // every pod's cache is rewritten from position 0: the sharing groups end
     LH_HIP(ctx, hipMemsetAsync(b->sp_dev, 0, sizeof(StepParams) * b->B, ctx->stream));   // sampling: the prompt's id is entry 0 of the row's output list
     size_t off = 0;   // rows of the pods, one after the other, in the residual stream buffers
     for (uint32_t i = 0; i < b->B; ++i) {
@@ -3740,6 +3876,7 @@ int lh_batch_decode_lookup(lh_batch* h, const uint32_t* first_tokens, const uint
         }
         return LH_OK;
     }
+    for (uint32_t i = 0; i < b->B; ++i) share_written(b, i, past[i]);   // the passes write every pod's cache from past[i] on
     return batch_decode_lookup(b, first_tokens, past, n_steps, lp, R, out_tokens, logits_last_host, stats, trace, trace_cap);
 }
 
@@ -3817,6 +3954,77 @@ int lh_feed_schedule(const uint32_t* n_tokens, const uint32_t* past, uint32_t ro
     for (size_t i = 0; blocks && i < fs.blocks.size() && i < block_cap; ++i) blocks[i] = fs.blocks[i];
     if (counts) { counts[0] = (uint32_t)fs.passes.size(); counts[1] = (uint32_t)fs.segs.size(); counts[2] = (uint32_t)fs.blocks.size(); }
     return (int)fs.passes.size();
+}
+
+// ---- lh_batch_fork: a pod's evaluated prefix for other pods of the batch (llamahip.h states the rule) -------------------------------------------------
+int lh_batch_fork(lh_batch* h, uint32_t src, const uint32_t* dst, uint32_t n_dst, uint32_t n_pos) {
+    if (!h) return LH_EINVAL;
+    Batch* b = h->b;
+    lh_ctx* ctx = b->ctx;
+    const ModelDesc& m = b->pods[0]->md;
+    LH_HIP(ctx, hipSetDevice(ctx->device));
+    // ---- everything is checked before anything is enqueued or any host state moves
+    if (!m.first_stage() || !m.last_stage()) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_batch_fork needs whole-model pods (layers [%u, %u) of %u)", m.layer0, m.layer1, m.L);
+    if (!dst || !n_dst) LH_FAIL(ctx, LH_EINVAL, "lh_batch_fork: no destination pod");
+    if (!n_pos) LH_FAIL(ctx, LH_EINVAL, "lh_batch_fork: no position to copy");
+    if (src >= b->B) LH_FAIL(ctx, LH_EINVAL, "lh_batch_fork: source pod %u outside the batch of %u", src, b->B);
+    uint64_t seen = 1ull << src;
+    for (uint32_t i = 0; i < n_dst; ++i) {
+        if (dst[i] >= b->B) LH_FAIL(ctx, LH_EINVAL, "lh_batch_fork: destination pod %u outside the batch of %u", dst[i], b->B);
+        if (seen & (1ull << dst[i])) LH_FAIL(ctx, LH_EINVAL, "lh_batch_fork: pod %u is the source or named twice", dst[i]);
+        seen |= 1ull << dst[i];
+    }
+    if (!b->pos_known || n_pos > b->pos[src])
+        LH_FAIL(ctx, LH_EINVAL, "lh_batch_fork: %u positions, the source pod %u stands at %u (the host mirror; not placed yet: 0)", n_pos, src, b->pos_known ? b->pos[src] : 0u);
+    int rc;
+    // Tokens the ticks evaluated are recorded in the histories only when the host next reads the ids (batch_drain).  Read them NOW, whatever the
+    // positions: the source's copied range may need them, and a destination's undrained ticks would otherwise be recorded LATER, at its old positions,
+    // over the history copied below - a later context swap would then re-feed tokens its cache no longer holds.
+    if (b->ticks > b->drained && (rc = batch_drain(b))) return rc;
+    share_sync(b);
+    // ---- the copy, in stream order: rows [0, n_pos) of every layer slot of [layers][ctx][d], K and V
+    const Plan* sp = b->pods[src];
+    const size_t pitch = (size_t)m.ctx * m.d * 4, width = (size_t)n_pos * m.d * 4, layers = m.layer1 - m.layer0;
+    for (uint32_t i = 0; i < n_dst; ++i) {
+        Plan* dp = b->pods[dst[i]];
+        LH_HIP(ctx, hipMemcpy2DAsync(dp->md.kc, pitch, sp->md.kc, pitch, width, layers, hipMemcpyDeviceToDevice, ctx->stream));
+        LH_HIP(ctx, hipMemcpy2DAsync(dp->md.vc, pitch, sp->md.vc, pitch, width, layers, hipMemcpyDeviceToDevice, ctx->stream));
+        if (sp->hist && dp->hist)
+            for (uint32_t k = 0; k < n_pos && k < sp->hist->size() && k < dp->hist->size(); ++k) (*dp->hist)[k] = (*sp->hist)[k];
+    }
+    // ---- the group {src} + dst of shared length n_pos: the destinations join src's group if it has exactly that length, else a new group forms
+    if (b->sh_gid[src] != Batch::SH_NONE && b->sh_len[src] == n_pos) {
+        const uint32_t gid = b->sh_gid[src];
+        for (uint32_t i = 0; i < n_dst; ++i) {
+            if (b->sh_gid[dst[i]] == gid) continue;
+            // (leaving cannot dissolve src's group: a group that is not src's loses the pod)
+            share_leave(b, dst[i]);
+            share_set(b, dst[i], gid, n_pos);
+        }
+    } else {
+        share_leave(b, src);
+        for (uint32_t i = 0; i < n_dst; ++i) share_leave(b, dst[i]);
+        const uint32_t gid = b->sh_next_gid++;
+        share_set(b, src, gid, n_pos);
+        for (uint32_t i = 0; i < n_dst; ++i) share_set(b, dst[i], gid, n_pos);
+    }
+    return LH_OK;
+}
+
+int lh_batch_share_info(lh_batch* h, uint32_t* group_out, uint32_t* len_out) {
+    if (!h || !group_out || !len_out) return LH_EINVAL;
+    share_info(h->b, group_out, len_out);
+    return LH_OK;
+}
+
+int lh_batch_share_written(lh_batch* h, uint32_t pod, uint32_t pos_lo) {
+    if (!h || pod >= h->b->B) return LH_EINVAL;
+    share_written(h->b, pod, pos_lo);
+    return LH_OK;
+}
+
+int lh_share_schedule(const uint32_t* group, const uint32_t* len, uint32_t rows, uint32_t qb, uint32_t min_rows, lh_share_block* blocks, uint32_t cap, uint32_t* row_block) {
+    return share_schedule(group, len, rows, qb, min_rows, blocks, cap, row_block);
 }
 
 int lh_llama_profile_decode(lh_llama* m, uint32_t token, uint32_t past, uint32_t repeats, lh_kernel_time* out, uint32_t cap) {

@@ -331,6 +331,31 @@ func (bt *BatchHIP) FeedSample(tokens [][]uint32, past []uint32, flags []uint32)
 	return out
 }
 
+// Fork gives the pods of dst the prefix pod src has evaluated (lh_batch_fork; the rule is stated in include/llamahip.h): cache rows [0, nPos) of every
+// layer and the token history are copied, nothing else moves, and {src} + dst become a sharing group whose ticks read the prefix's keys once per block
+// of member rows - every id and logit what it is without the fork.  Feed each destination at past = nPos afterwards (Feed / FeedSample).  One system
+// prompt in front of every job, several continuations of one prompt: evaluate it once.  C++ twin: llamago_BatchFork.
+func (bt *BatchHIP) Fork(src uint32, dst []uint32, nPos uint32) {
+	if len(dst) == 0 {
+		fmt.Printf("\n[HALT] Fork: no destination pod")
+		os.Exit(1)
+	}
+	if rc := C.lh_batch_fork(bt.b, C.uint32_t(src), (*C.uint32_t)(unsafe.Pointer(&dst[0])), C.uint32_t(len(dst)), C.uint32_t(nPos)); rc != 0 {
+		hipHalt(bt.ctx.hip.ctx)
+	}
+}
+
+// ShareInfo returns per pod the lowest pod index of its sharing group and the shared length (its own index and 0: the pod shares nothing);
+// lh_batch_share_info, host state only.  C++ twin: llamago_BatchShareInfo.
+func (bt *BatchHIP) ShareInfo() (group, length []uint32) {
+	group = make([]uint32, len(bt.stages))
+	length = make([]uint32, len(bt.stages))
+	if rc := C.lh_batch_share_info(bt.b, (*C.uint32_t)(unsafe.Pointer(&group[0])), (*C.uint32_t)(unsafe.Pointer(&length[0]))); rc != 0 {
+		hipHalt(bt.ctx.hip.ctx)
+	}
+	return group, length
+}
+
 // DecodeLookup is lh_batch_decode through lookup-drafted verify passes (lh_batch_decode_lookup; the rule is stated in include/llamahip.h): nSteps
 // greedy ids per pod from (firstTokens[i], past[i]), every pass evaluating pods x R rows in ONE pass over the weights - speculation and the shared weight
 // stream at once.  The loop never leaves the window: past[i] + nSteps + R - 1 <= CtxSize must hold (the caller takes the last positions with Tick).

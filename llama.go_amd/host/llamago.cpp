@@ -1490,6 +1490,27 @@ int llamago_SpecAcceptPods(const uint32_t* arg, const uint32_t* tok, uint32_t n_
     if (lh_spec_accept_pods(h, arg, tok, n_pods, n_rows, k, pos, produced, n_steps, ctx_size, a_out, pos_out, produced_out, pending_out, ids_out)) return halt_rc(lh_last_error(h));
     return 0;
 }
+// lh_batch_decode: n_steps ticks of every pod from (first_tokens[i], past[i]); out [pods][n_steps], logits_last (optional) [pods][vocab] of the last tick
+int llamago_BatchDecode(llama_batch* p, const uint32_t* first_tokens, const uint32_t* past, uint32_t n_steps, uint32_t* out, float* logits_last) {
+    if (!p || !first_tokens || !past || !n_steps) return halt_rc("llamago_BatchDecode: bad arguments");
+    if (lh_batch_decode(p->b, first_tokens, past, n_steps, out, logits_last)) return halt_rc(lh_last_error(p->mlctx->hip));
+    return 0;
+}
+// lh_batch_fork / lh_batch_share_info: a pod's evaluated prefix for other pods of the batch, and the sharing groups that follow from it;
+// lh_share_schedule: the block table a tick derives from them, alone on host arrays (no GPU)
+int llamago_BatchFork(llama_batch* p, uint32_t src, const uint32_t* dst, uint32_t n_dst, uint32_t n_pos) {
+    if (!p) return halt_rc("llamago_BatchFork: bad arguments");
+    if (lh_batch_fork(p->b, src, dst, n_dst, n_pos)) return halt_rc(lh_last_error(p->mlctx->hip));
+    return 0;
+}
+int llamago_BatchShareInfo(llama_batch* p, uint32_t* group, uint32_t* len) {
+    if (!p || !group || !len) return halt_rc("llamago_BatchShareInfo: bad arguments");
+    if (lh_batch_share_info(p->b, group, len)) return halt_rc("llamago_BatchShareInfo: lh_batch_share_info failed");
+    return 0;
+}
+int llamago_ShareSchedule(const uint32_t* group, const uint32_t* len, uint32_t rows, uint32_t qb, uint32_t min_rows, lh_share_block* blocks, uint32_t cap, uint32_t* row_block) {
+    return lh_share_schedule(group, len, rows, qb, min_rows, blocks, cap, row_block);
+}
 
 // ---- pods as pipeline streams over a layer-sharded model (server.go:84-106, 151) ----------------------
 // One ml.Context (= one HIP stream) per rank carries every pod's stage and the RCCL p2p; each pod owns its KV cache like a
@@ -1669,7 +1690,13 @@ int llamago_BatchCacheRead(llama_batch* p, uint32_t pod, int which, uint64_t off
 int llamago_BatchCacheWrite(llama_batch* p, uint32_t pod, int which, uint64_t off_floats, const float* src, uint64_t n) {
     if (!p || !src) return halt_rc("llamago_BatchCacheWrite: null argument");
     if (pod >= p->K.size() || pod >= p->V.size()) return halt_rc("llamago_BatchCacheWrite: pod outside the batch");
-    return cache_io("llamago_BatchCacheWrite", p->mlctx, which == 1 ? p->V[pod] : p->K[pod], which, off_floats, nullptr, src, n);
+    int rc = cache_io("llamago_BatchCacheWrite", p->mlctx, which == 1 ? p->V[pod] : p->K[pod], which, off_floats, nullptr, src, n);
+    if (rc == 0 && n) {   // the leave rule of lh_batch_fork: the lowest cache position (of any layer slot of [layers][ctxSize][embd]) the write touched
+        const uint64_t slot = (uint64_t)p->ctxSize * p->model->hp.embdSize, first = off_floats % slot;
+        const uint32_t pos_lo = first + n > slot ? 0u : (uint32_t)(first / p->model->hp.embdSize);   // (a write that runs into the next slot starts that one at 0)
+        lh_batch_share_written(p->b, pod, pos_lo);
+    }
+    return rc;
 }
 int llamago_TimeComputes(llama_context* c, int on) { return c && c->mlctx && c->mlctx->hip ? lh_ctx_time_computes(c->mlctx->hip, on) : 1; }
 int llamago_ComputeStats(llama_context* c, uint64_t* calls, double* wall_us, double* device_us) {

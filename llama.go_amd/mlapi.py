@@ -679,6 +679,14 @@ def _bind_extensions(ml):
     L.llamago_BatchFeed.argtypes = [VP, C.POINTER(c_u32p), c_u32p, c_u32p, c_u32p, c_f32p, c_f32p]
     L.llamago_BatchFeedSample.restype = C.c_int
     L.llamago_BatchFeedSample.argtypes = [VP, C.POINTER(c_u32p), c_u32p, c_u32p, c_u32p, c_u32p, c_f32p, c_f32p]
+    L.llamago_BatchDecode.restype = C.c_int
+    L.llamago_BatchDecode.argtypes = [VP, c_u32p, c_u32p, c_u32, c_u32p, c_f32p]
+    L.llamago_BatchFork.restype = C.c_int
+    L.llamago_BatchFork.argtypes = [VP, c_u32, c_u32p, c_u32, c_u32]
+    L.llamago_BatchShareInfo.restype = C.c_int
+    L.llamago_BatchShareInfo.argtypes = [VP, c_u32p, c_u32p]
+    L.llamago_ShareSchedule.restype = C.c_int
+    L.llamago_ShareSchedule.argtypes = [c_u32p, c_u32p, c_u32, c_u32, c_u32, C.POINTER(ShareBlock), c_u32, c_u32p]
     L.llamago_FreePipeline.restype = None
     L.llamago_FreePipeline.argtypes = [VP]
     L.llamago_PipelineRun.restype = C.c_int
@@ -693,6 +701,29 @@ def _bind_extensions(ml):
 
 
 COMM_ID_BYTES = 128
+
+
+class ShareBlock(C.Structure):
+    """lh_share_block: rows row[0..n) of a tick share the first `chunks` 128-key chunks of their caches."""
+    _fields_ = [("n", c_u32), ("chunks", c_u32), ("row", c_u32 * 8)]
+
+
+SHARE_NO_BLOCK = 0xFFFFFFFF
+
+
+def share_schedule(ml, group, length, qb, min_rows, cap=None, sizing=False):
+    """llamago_ShareSchedule (lh_share_schedule; no GPU): the block table a tick derives from the sharing groups of a batch.  group / length per pod
+    as Batch.ShareInfo returns them.  -> (count, blocks as (chunks, [rows]) tuples, row_block list); count is -1 on bad arguments (blocks and row_block
+    are then whatever was there: nothing is written).  sizing: the call without a block array; cap: the capacity handed over (default 32)."""
+    rows = len(group)
+    g = (c_u32 * max(rows, 1))(*[int(x) for x in group])
+    ln = (c_u32 * max(rows, 1))(*[int(x) for x in length])
+    cap = 32 if cap is None else int(cap)
+    blocks = (ShareBlock * max(cap, 1))()
+    rb = (c_u32 * max(rows, 1))(*([0xDEADBEEF] * max(rows, 1)))
+    n = ml.lib.llamago_ShareSchedule(g, ln, rows, int(qb), int(min_rows), None if sizing else blocks, cap, rb)
+    got = [] if sizing or n < 0 else [(int(blocks[i].chunks), [int(blocks[i].row[k]) for k in range(blocks[i].n)]) for i in range(min(n, cap))]
+    return int(n), got, [int(x) for x in rb[:rows]]
 
 
 def comm_unique_id(ml):
@@ -915,6 +946,33 @@ class Batch:
         stats = [dict(passes=int(s.passes), rows=int(s.rows), drafted=int(s.drafted), accepted=int(s.accepted), empty=int(s.empty)) for s in st]
         traces = [[(int(v) >> 8, int(v) & 0xFF) for v in tr[i * n:i * n + min(st[i].passes, n)]] for i in range(self.pods)]
         return ids, lg, stats, traces
+
+    def Decode(self, first_tokens, past, n_steps, want_logits=False):
+        """lh_batch_decode: n_steps ticks of every pod from (first_tokens[i], past[i]).  -> ids per pod (and the [pods][vocab] logits of the last tick)."""
+        assert len(first_tokens) == self.pods and len(past) == self.pods
+        tk = (c_u32 * self.pods)(*[int(t) for t in first_tokens])
+        ps = (c_u32 * self.pods)(*[int(x) for x in past])
+        out = (c_u32 * (self.pods * n_steps))()
+        lg = np.empty((self.pods, self.model.hp.vocabSize), dtype=np.float32) if want_logits else None
+        if self.ml.lib.llamago_BatchDecode(self.h, tk, ps, int(n_steps), out, lg.ctypes.data_as(c_f32p) if want_logits else None):
+            raise MLError(f"llamago_BatchDecode: {self.ml.last_error()}")
+        ids = [[int(t) for t in out[i * n_steps:(i + 1) * n_steps]] for i in range(self.pods)]
+        return (ids, lg) if want_logits else ids
+
+    def Fork(self, src, dst, n_pos):
+        """lh_batch_fork: cache rows [0, n_pos) and the token history of pod src copied into the pods of dst, which then share that prefix with src in
+        the ticks (byte-equal results, the prefix's keys read once per block of member rows).  Feed each destination at past = n_pos, or Set it."""
+        dst = [int(x) for x in dst]
+        arr = (c_u32 * max(len(dst), 1))(*dst)
+        if self.ml.lib.llamago_BatchFork(self.h, int(src), arr, len(dst), int(n_pos)):
+            raise MLError(f"llamago_BatchFork: {self.ml.last_error()}")
+
+    def ShareInfo(self):
+        """lh_batch_share_info -> (group, length) per pod: the lowest pod index of the pod's sharing group and the shared length (own index, 0: none)."""
+        g, ln = (c_u32 * self.pods)(), (c_u32 * self.pods)()
+        if self.ml.lib.llamago_BatchShareInfo(self.h, g, ln):
+            raise MLError(f"llamago_BatchShareInfo: {self.ml.last_error()}")
+        return list(g), list(ln)
 
     def Tick(self):
         """BatchHIP.Tick: one decode step of every pod in one pass over the weights; returns the ids produced."""
