@@ -119,6 +119,22 @@ int lh_graph_compute(lh_ctx* ctx, const lh_tensor* tensors, uint32_t n_leafs, ui
  * refers to hold (lh_buf_nfloats; dtype as at registration); a host leaf holds its nelem floats, any other owner its own strided span. */
 typedef struct lh_buf_extent { lh_buf id; uint64_t nfloats; int dtype; } lh_buf_extent;
 int lh_graph_check(const lh_tensor* tensors, uint32_t n_leafs, uint32_t n_nodes, const lh_buf_extent* bufs, uint32_t n_bufs, char* msg, uint64_t cap);
+/* The gate of lh_graph_compute as a pure host function (csrc/graph_match.h; needs no context and no device): 1 when the array is recognised as
+ * the graph llama.Eval builds and would run as the fused plan, 0 when it would run node by node, or the negative code of the structural checks.
+ * lh_graph_compute runs the same matcher over its buffer table; here bufs says what the registered buffers hold, as for lh_graph_check.  An
+ * extent carries no rows / cols, so a block-int8 (dtype 7) weight must hold exactly ne0 * ne1 logical elements here, where the device entry
+ * compares the rows and cols of the quantised buffer.  On 1, *out (may be NULL) receives everything the fused result depends on besides the
+ * data: the geometry, N and past, the cache owners, the token leaf, llama.Eval's `embeddings` node, and the leaf index of every weight -
+ * weights[9 * layer + k] for k = attention_norm, wq, wk, wv, wo, ffn_norm, w1, w2, w3, then tok_embeddings, norm, output.  n_weights is set to
+ * 9 * L + 3; at most cap_weights entries are written (weights may be NULL). */
+typedef struct lh_match_info {
+    uint32_t N, past, V, d, H, hd, L, F, ctx;
+    int32_t wtype;
+    int32_t kc_owner, vc_owner, tokens_leaf, emb_node;
+    int32_t* weights;
+    uint32_t cap_weights, n_weights;
+} lh_match_info;
+int lh_graph_match(const lh_tensor* tensors, uint32_t n_leafs, uint32_t n_nodes, const lh_buf_extent* bufs, uint32_t n_bufs, lh_match_info* out);
 /* Read elements of a tensor of the LAST computed graph (flat, in storage order from the tensor's first
  * element).  Replaces the host's direct reads of Tensor.Data after GraphCompute (llama.go:394-401). */
 int lh_node_read(lh_ctx* ctx, uint32_t index, uint64_t off_floats, float* dst, uint64_t n);

@@ -9,6 +9,7 @@
 #include <chrono>
 #include "kernels_generic.h"
 #include "graph_check.h"
+#include "graph_match.h"
 #include <math.h>
 #include <algorithm>
 
@@ -26,282 +27,50 @@ static inline bool contiguous(const lh_tensor& t) {  // ml.go:206-211
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Structural matcher for the graph of llama.Eval
+// Structural matcher for the graph of llama.Eval: csrc/graph_match.h (pure host code, also behind lh_graph_match).  Here its buffer lookup is
+// the context's snapshot of the device's table, and what it extracted is resolved to device pointers.
 // ---------------------------------------------------------------------------------------------------
-struct Matcher {
+struct CtxLookup {
     lh_ctx* ctx;
-    const lh_tensor* T;
-    uint32_t total, n_leafs;
-    ModelDesc md;
-    uint32_t N = 0, past = 0;
-    int kc_owner = -1, vc_owner = -1;
-    int tokens_leaf = -1;
-    int emb_node = -1;   // `embeddings` of llama.Eval (llama.go:381): the final norm * weight rows, source of the lm_head
-    std::vector<uint32_t> tokens;
-
-    // Every node the pattern walks over is marked; the match only holds if ALL nodes of the graph were claimed (extra outputs or
-    // side-effect copies expanded into the same graph would otherwise be silently skipped by the fused plan).
-    mutable std::vector<uint8_t> claimed;
-    std::vector<uint32_t> cpy_nodes;
-    bool is(int i, int op) const {
-        if (i < 0 || (uint32_t)i >= total || T[i].op != op) return false;
-        claimed[i] = 1;
-        return true;
-    }
-    // shape + byte strides of a (permuted) view
-    bool view_is(int i, uint32_t n0, uint32_t n1, uint32_t n2, uint64_t b0, uint64_t b1, uint64_t b2) const {
-        const lh_tensor& t = T[i];
-        return t.ne[0] == n0 && t.ne[1] == n1 && t.ne[2] == n2 && t.ne[3] == 1 && t.nb[0] == b0 && t.nb[1] == b1 && t.nb[2] == b2;
-    }
-    int s0(int i) const { return T[i].src0; }
-    int s1(int i) const { return T[i].src1; }
-    // persistent weight leaf with the expected shape -> device pointer.  Matrices may be f32 or block-int8 (all the same
-    // dtype within a model: `want`); norm vectors are always f32.
-    const float* weight(int i, uint32_t ne0, uint32_t ne1, const float** scales = nullptr, bool matrix = false) {
-        if (i < 0 || (uint32_t)i >= n_leafs) return nullptr;
-        const lh_tensor& t = T[i];
-        if (t.op != OP_NONE || t.storage != i || !t.buf) return nullptr;
-        if (t.ne[0] != ne0 || t.ne[1] != ne1 || t.ne[2] != 1 || t.ne[3] != 1) return nullptr;
-        Buffer* b = find_buffer_fast(ctx, t.buf);
-        if (!b || b->nfloats < (uint64_t)ne0 * ne1 || b->dtype != (int)t.dtype) return nullptr;
-        if (!matrix) return b->dtype == 0 && contiguous(t) ? b->dev : nullptr;
-        if (b->dtype != 0 && b->dtype != 7) return nullptr;
-        if (b->dtype == 0 && !contiguous(t)) return nullptr;
-        if (b->dtype == 7 && (b->rows != ne1 || b->cols != ne0)) return nullptr;
-        if (wtype_seen < 0) wtype_seen = b->dtype;
-        else if (wtype_seen != b->dtype) return nullptr;
-        if (scales) *scales = b->scales;
-        return b->dev;
-    }
-    int wtype_seen = -1;
-    // h = Mul(gamma or Repeat(gamma, .), RMSNorm(x))  ->  returns x index, gamma pointer
-    bool norm_mul(int h, int* x, const float** gamma) {
-        if (!is(h, OP_MUL)) return false;
-        int g = s0(h), r = s1(h);
-        if (!is(r, OP_RMS_NORM)) return false;
-        if (is(g, OP_REPEAT)) g = s0(g);
-        *gamma = weight(g, md.d, 1);
-        if (!*gamma) return false;
-        *x = s0(r);
-        return true;
-    }
-    const float* host_param(int i, uint32_t n) const {
-        if (i < 0 || (uint32_t)i >= total) return nullptr;
-        const lh_tensor& t = T[i];
-        if (t.op != OP_NONE || !t.host || nelem(t) != n) return nullptr;
-        return t.host;
-    }
-    // View1D(cache) -> Reshape3D -> [Rope] : returns the cache owner and the view offset
-    bool cache_view3d(int r3, int* owner, uint64_t* off, uint32_t* ne2) const {
-        if (!is(r3, OP_RESHAPE)) return false;
-        const int v = s0(r3);
-        if (!is(v, OP_VIEW)) return false;
-        const lh_tensor& t = T[r3];
-        if (t.ne[0] != md.hd || t.ne[1] != md.H) return false;
-        *owner = T[v].storage;
-        *off = T[v].view_off;
-        *ne2 = t.ne[2];
-        return T[*owner].buf != 0;
-    }
-
-    bool match_layer(int x_out, uint32_t il, int* x_in) {
-        const uint32_t d = md.d, F = md.F, hd = md.hd, H = md.H;
-        LayerW& L = md.layers[il];
-        // x_out = Add(MulMat(w2, Mul(Silu(MulMat(w1,h2)), MulMat(w3,h2))), inpFF)      llama.go:354-366
-        if (!is(x_out, OP_ADD)) return false;
-        const int mm2 = s0(x_out), inpFF = s1(x_out);
-        if (!is(mm2, OP_MUL_MAT)) return false;
-        if (!(L.w2 = weight(s0(mm2), F, d, &L.s_w2, true))) return false;
-        const int gm = s1(mm2);
-        if (!is(gm, OP_MUL)) return false;
-        const int sl = s0(gm), mm3 = s1(gm);
-        if (!is(sl, OP_SILU) || !is(mm3, OP_MUL_MAT)) return false;
-        const int mm1 = s0(sl);
-        if (!is(mm1, OP_MUL_MAT)) return false;
-        if (!(L.w1 = weight(s0(mm1), d, F, &L.s_w1, true)) || !(L.w3 = weight(s0(mm3), d, F, &L.s_w3, true))) return false;
-        const int h2 = s1(mm1);
-        if (s1(mm3) != h2) return false;
-        int xff;
-        if (!norm_mul(h2, &xff, &L.ffn_norm) || xff != inpFF) return false;
-        // inpFF = Add(MulMat(wo, A), inpSA)                                             llama.go:336-340
-        if (!is(inpFF, OP_ADD)) return false;
-        const int mmo = s0(inpFF), inpSA = s1(inpFF);
-        if (!is(mmo, OP_MUL_MAT) || !(L.wo = weight(s0(mmo), d, d, &L.s_wo, true))) return false;
-        // A = Cpy(Permute(KQV), new2D)                                                  llama.go:328-333
-        const int A = s1(mmo);
-        if (!is(A, OP_CPY) || !is(s0(A), OP_PERMUTE)) return false;
-        const int kqv = s0(s0(A));
-        if (!is(kqv, OP_MUL_MAT)) return false;
-        // KQV = MulMat(VTrans, S);  VTrans = Cpy(Permute(Reshape3D(View1D(V))), new3D) llama.go:315-325
-        const int vt = s0(kqv), S = s1(kqv);
-        if (!is(vt, OP_CPY) || !is(s0(vt), OP_PERMUTE)) return false;
-        int vo; uint64_t voff; uint32_t vT;
-        if (!cache_view3d(s0(s0(vt)), &vo, &voff, &vT)) return false;
-        // S = SoftMax(DiagMaskInf(Scale(KQ, sc), past))                                 llama.go:303-313
-        if (!is(S, OP_SOFT_MAX) || !is(s0(S), OP_DIAG_MASK_INF)) return false;
-        const int dm = s0(S);
-        if (!is(s0(dm), OP_SCALE)) return false;
-        const int scn = s0(dm), kq = s0(scn);
-        const float* pastp = host_param(s1(dm), 1);
-        const float* scp = host_param(s1(scn), 1);
-        if (!pastp || !scp || !is(kq, OP_MUL_MAT)) return false;
-        if (*scp != (float)(1.0 / sqrt((double)d / (double)H))) return false;
-        // KQ = MulMat(Permute(Rope(Reshape3D(View1D(K)), mode 1)), Permute(Rope(Cpy(MulMat(wq,h1), new3D), mode 0)))   llama.go:281-300
-        const int Kp = s0(kq), Qp = s1(kq);
-        if (!is(Kp, OP_PERMUTE) || !is(Qp, OP_PERMUTE) || !is(s0(Kp), OP_ROPE) || !is(s0(Qp), OP_ROPE)) return false;
-        const int kr = s0(Kp), qr = s0(Qp);
-        const float* kpar = host_param(s1(kr), 3);
-        const float* qpar = host_param(s1(qr), 3);
-        if (!kpar || !qpar) return false;
-        int ko; uint64_t koff; uint32_t kT;
-        if (!cache_view3d(s0(kr), &ko, &koff, &kT)) return false;
-        const int qc = s0(qr);
-        if (!is(qc, OP_CPY) || !is(s0(qc), OP_MUL_MAT)) return false;
-        const int mmq = s0(qc);
-        if (!(L.wq = weight(s0(mmq), d, d, &L.s_wq, true))) return false;
-        const int h1 = s1(mmq);
-        int xsa;
-        if (!norm_mul(h1, &xsa, &L.attn_norm) || xsa != inpSA) return false;
-        // shapes / parameters
-        const lh_tensor& q3 = T[qc];
-        const uint32_t n = q3.ne[2];
-        if (q3.ne[0] != hd || q3.ne[1] != H) return false;
-        const uint32_t p = (uint32_t)qpar[0];
-        if ((uint32_t)kpar[0] != p || (uint32_t)*pastp != p) return false;
-        if ((uint32_t)qpar[1] != hd || (uint32_t)kpar[1] != hd || (uint32_t)qpar[2] != 0 || (uint32_t)kpar[2] != 1) return false;
-        if (kT != p + n || vT != p + n) return false;
-        // the views must be the reference's permutations, not look-alikes: Q/K Permute(0,2,1,3) of [hd,H,*] (llama.go:288, 297),
-        // V Permute(1,2,0,3) (llama.go:319), KQV [hd,N,H] merged back with Permute(0,2,1,3) (llama.go:328); all K-contiguous copies
-        const uint64_t e4 = 4, dB = (uint64_t)d * 4, hB = (uint64_t)hd * 4;
-        if (!view_is(Qp, hd, n, H, e4, dB, hB) || !view_is(Kp, hd, p + n, H, e4, dB, hB)) return false;
-        if (!view_is(s0(vt), p + n, hd, H, dB, e4, hB)) return false;
-        if (!view_is(kqv, hd, n, H, e4, hB, hB * n) || !view_is(s0(A), hd, H, n, e4, hB * n, hB)) return false;
-        if (!view_is(kq, p + n, n, H, e4, (uint64_t)(p + n) * 4, (uint64_t)(p + n) * n * 4)) return false;
-        if (il + 1 == md.L) { N = n; past = p; kc_owner = ko; vc_owner = vo; }
-        else if (N != n || past != p || kc_owner != ko || vc_owner != vo) return false;
-        if (koff != (uint64_t)il * md.ctx * d || voff != koff) return false;
-        // K / V stores: Cpy(MulMat(wk|wv, h1), View1D(cache, d*(il*ctx + past)))         llama.go:274-278
-        bool gotk = false, gotv = false;
-        for (const uint32_t i : cpy_nodes) {   // (every Cpy node of the graph, in graph order: collected once - scanning all nodes here for every layer was
-                                               // most of the 25 us a one-token match took)
-            const int src = T[i].src0;
-            if (!is(src, OP_MUL_MAT) || s1(src) != h1 || src == mmq) continue;
-            const int dstv = T[i].src1;
-            if (!is(dstv, OP_VIEW)) continue;
-            const int own = T[dstv].storage;
-            if (T[dstv].view_off != (uint64_t)d * ((uint64_t)il * md.ctx + p) || T[dstv].ne[0] != n * d) continue;
-            const float* wsc = nullptr;
-            const float* w = weight(s0(src), d, d, &wsc, true);
-            if (!w) continue;
-            if (own == ko && !gotk) { L.wk = w; L.s_wk = wsc; gotk = true; claimed[i] = 1; }
-            else if (own == vo && !gotv) { L.wv = w; L.s_wv = wsc; gotv = true; claimed[i] = 1; }
-        }
-        if (!gotk || !gotv) return false;
-        *x_in = inpSA;
-        return true;
-    }
-
-    bool run() {
-        claimed.assign(total, 0);
-        if (!run_pattern()) return false;
-        for (uint32_t i = n_leafs; i < total; ++i)
-            if (!claimed[i]) return false;  // a node outside the Eval pattern: run the graph node by node
-        // LH_T_OUTPUT: the host wants to read this node back (in the reference every Tensor.Data is readable after GraphCompute, ml.go:1411-1528).
-        // A fused plan materialises the final node and `embeddings` (llama.go:381, read at llama.go:414-419); any other flagged intermediate
-        // never exists in it, so such a graph runs node by node.
-        for (uint32_t i = n_leafs; i + 1 < total; ++i)
-            if ((T[i].flags & LH_T_OUTPUT) && (int)i != emb_node) return false;
-        return true;
-    }
-    bool run_pattern() {
-        const int fin = (int)total - 1;
-        if (!is(fin, OP_MUL_MAT)) return false;
-        const lh_tensor& ft = T[fin];
-        const int wout = s0(fin);
-        if (wout < 0 || (uint32_t)wout >= n_leafs) return false;
-        md.d = T[wout].ne[0];
-        md.V = T[wout].ne[1];
-        if (!md.d || !md.V || ft.ne[0] != md.V) return false;
-        if (!(md.output = weight(wout, md.d, md.V, &md.s_output, true))) return false;
-        int x;
-        if (!norm_mul(s1(fin), &x, &md.norm)) return false;
-        emb_node = s1(fin);
-        // count layers by walking the residual chain down to GetRows
-        std::vector<int> outs;
-        int cur = x;
-        while (is(cur, OP_ADD)) {
-            outs.push_back(cur);
-            const int inpFF = s1(cur);
-            if (!is(inpFF, OP_ADD)) return false;
-            cur = s1(inpFF);
-            if (outs.size() > 4096) return false;
-        }
-        if (!is(cur, OP_GET_ROWS) || outs.empty()) return false;
-        md.L = (uint32_t)outs.size();
-        md.layer0 = 0; md.layer1 = md.L; md.cache_layer0 = 0;
-        md.layers.assign(md.L, LayerW());
-        // head geometry from the last layer's Q copy: find it through the pattern of layer L-1
-        {
-            const int inpFF = s1(outs[0]);
-            const int mmo = s0(inpFF);
-            if (!is(mmo, OP_MUL_MAT)) return false;
-            const int A = s1(mmo);
-            if (!is(A, OP_CPY) || !is(s0(A), OP_PERMUTE)) return false;
-            const int kqv = s0(s0(A));
-            if (!is(kqv, OP_MUL_MAT)) return false;
-            const lh_tensor& k = T[kqv];  // [hd, N, H]
-            md.hd = k.ne[0];
-            md.H = k.ne[2];
-            if (!md.hd || md.hd * md.H != md.d) return false;
-            const int mm2 = s0(outs[0]);
-            if (!is(mm2, OP_MUL_MAT)) return false;
-            md.F = T[s0(mm2)].ne[0];
-        }
-        // context size from the KV cache extent: embd*layers*ctx floats (llama.go:93)
-        {
-            const int inpFF = s1(outs[0]);
-            const int kqv = s0(s0(s1(s0(inpFF))));
-            const int vt = s0(kqv);
-            if (!is(vt, OP_CPY) || !is(s0(vt), OP_PERMUTE) || !is(s0(s0(vt)), OP_RESHAPE) || !is(s0(s0(s0(vt))), OP_VIEW)) return false;
-            const int own = T[s0(s0(s0(vt)))].storage;
-            if (own < 0 || !T[own].buf) return false;
-            Buffer* b = find_buffer_fast(ctx, T[own].buf);
-            if (!b) return false;
-            const uint64_t per = (uint64_t)md.d * md.L;
-            if (b->nfloats % per) return false;
-            md.ctx = (uint32_t)(b->nfloats / per);
-        }
-        cpy_nodes.clear();
-        for (uint32_t i = n_leafs; i < total; ++i)
-            if (T[i].op == OP_CPY) cpy_nodes.push_back(i);
-        int xin = -1;
-        for (uint32_t k = 0; k < md.L; ++k) {
-            const uint32_t il = md.L - 1 - k;
-            if (!match_layer(outs[k], il, &xin)) return false;
-            if (il > 0 && xin != outs[k + 1]) return false;
-        }
-        // x_0 = GetRows(tok_embeddings, embd)                                         llama.go:239-244
-        if (!is(xin, OP_GET_ROWS)) return false;
-        if (!(md.tok_emb = weight(s0(xin), md.d, md.V))) return false;
-        const float* ids = host_param(s1(xin), N);
-        if (!ids) return false;
-        tokens.resize(N);
-        for (uint32_t i = 0; i < N; ++i) {
-            tokens[i] = (uint32_t)ids[i];  // ids travel as fp32 (ml.go:1739)
-            if (tokens[i] >= md.V) return false;
-        }
-        Buffer* kb = find_buffer_fast(ctx, T[kc_owner].buf);
-        Buffer* vb = find_buffer_fast(ctx, T[vc_owner].buf);
-        if (!kb || !vb || kb == vb || vb->nfloats != kb->nfloats) return false;
-        md.kc = kb->dev;
-        md.vc = vb->dev;
-        if (!kb->kv_hist) kb->kv_hist = std::make_shared<std::vector<uint32_t>>();
-        md.kv_hist = kb->kv_hist;   // the cache's token history (context swap of the generation loops): shared by every plan over this buffer
-        md.wtype = wtype_seen < 0 ? 0 : wtype_seen;
-        if ((uint64_t)past + N > md.ctx) return false;
+    bool operator()(lh_buf id, gm::BufInfo* out) const {
+        const Buffer* b = find_buffer_fast(ctx, id);
+        if (!b) return false;
+        out->nfloats = b->nfloats; out->dtype = b->dtype; out->rows = b->rows; out->cols = b->cols; out->has_shape = true;
         return true;
     }
 };
+static bool model_desc_of(lh_ctx* ctx, const lh_tensor* T, const gm::MatchInfo& mi, ModelDesc* out) {
+    ModelDesc& md = *out;
+    md.V = mi.V; md.d = mi.d; md.H = mi.H; md.hd = mi.hd; md.L = mi.L; md.F = mi.F; md.ctx = mi.ctx;
+    md.layer0 = 0; md.layer1 = md.L; md.cache_layer0 = 0;
+    md.wtype = mi.wtype;
+    bool ok = true;
+    auto dev = [&](int32_t leaf, const float** scales) -> const float* {
+        Buffer* b = find_buffer_fast(ctx, T[leaf].buf);
+        if (!b) { ok = false; return nullptr; }
+        if (scales) *scales = b->scales;
+        return b->dev;
+    };
+    md.layers.assign(md.L, LayerW());
+    for (uint32_t il = 0; il < md.L; ++il) {
+        const int32_t* W = &mi.weights[(size_t)il * gm::W_PER_LAYER];
+        LayerW& L = md.layers[il];
+        L.attn_norm = dev(W[gm::W_ATTN_NORM], nullptr); L.ffn_norm = dev(W[gm::W_FFN_NORM], nullptr);
+        L.wq = dev(W[gm::W_WQ], &L.s_wq); L.wk = dev(W[gm::W_WK], &L.s_wk); L.wv = dev(W[gm::W_WV], &L.s_wv); L.wo = dev(W[gm::W_WO], &L.s_wo);
+        L.w1 = dev(W[gm::W_W1], &L.s_w1); L.w2 = dev(W[gm::W_W2], &L.s_w2); L.w3 = dev(W[gm::W_W3], &L.s_w3);
+    }
+    const int32_t* tail = &mi.weights[(size_t)md.L * gm::W_PER_LAYER];
+    md.tok_emb = dev(tail[gm::W_TOK_EMB], nullptr); md.norm = dev(tail[gm::W_NORM], nullptr); md.output = dev(tail[gm::W_OUTPUT], &md.s_output);
+    Buffer* kb = find_buffer_fast(ctx, T[mi.kc_owner].buf);
+    Buffer* vb = find_buffer_fast(ctx, T[mi.vc_owner].buf);
+    if (!ok || !kb || !vb || kb == vb) return false;
+    md.kc = kb->dev;
+    md.vc = vb->dev;
+    if (!kb->kv_hist) kb->kv_hist = std::make_shared<std::vector<uint32_t>>();
+    md.kv_hist = kb->kv_hist;   // the cache's token history (context swap of the generation loops): shared by every plan over this buffer
+    return true;
+}
+
 
 // ---------------------------------------------------------------------------------------------------
 // generic node-by-node execution
@@ -467,26 +236,27 @@ int lh_graph_compute(lh_ctx* ctx, const lh_tensor* T, uint32_t n_leafs, uint32_t
 
     // ---- fused LLaMA plan?
     if (!(flags & LH_GRAPH_NO_FUSION)) {
-        Matcher m;
-        m.ctx = ctx; m.T = T; m.total = total; m.n_leafs = n_leafs;
+        gm::Matcher<CtxLookup> mt(T, n_leafs, n_nodes, CtxLookup{ctx});
+        const gm::MatchInfo& m = mt.mi;
+        ModelDesc md;
         const auto tq1 = now();
-        if (m.run()) {
+        if (mt.run() && model_desc_of(ctx, T, m, &md)) {
             int rc = 0;
             const auto tq2 = now();
-            Plan* p = plan_find_or_create(ctx, m.md, &rc);
+            Plan* p = plan_find_or_create(ctx, md, &rc);
             const auto tq3 = now();
             if (p) rc = plan_eval(p, m.tokens.data(), nullptr, nullptr, m.N, m.past, (flags & LH_GRAPH_LAST_ROW_LOGITS) != 0);
             const auto tq4 = now();
             if (!rc && m.emb_node >= 0 && (T[m.emb_node].flags & LH_T_OUTPUT)) {
                 float* emb = nullptr;
                 rc = plan_embeddings(p, m.N, &emb);   // the final norm * weight rows [N][embd] (the fused lm_head launches never write them out)
-                if (!rc) { ctx->last_ptr[m.emb_node] = emb; ctx->last_len[m.emb_node] = (uint64_t)m.N * m.md.d; }
+                if (!rc) { ctx->last_ptr[m.emb_node] = emb; ctx->last_len[m.emb_node] = (uint64_t)m.N * m.d; }
             }
             if (!rc && (flags & LH_GRAPH_LAST_ROW_LOGITS)) {
                 // this caller reads row N - 1 of the final node and nothing else (llama.go:394-401): the row follows the kernels into pinned host
                 // memory in front of the Eval's one synchronisation, and lh_node_read of that range is then a host copy (round 5: a second
                 // synchronise + copy + synchronise cost ~20 us of the 4.5 ms a token takes through this route)
-                const uint64_t V = m.md.V;
+                const uint64_t V = m.V;
                 if (ctx->out_pinned_floats < V) {
                     if (ctx->out_pinned) hipHostFree(ctx->out_pinned);
                     ctx->out_pinned = nullptr; ctx->out_pinned_floats = 0;
@@ -501,7 +271,7 @@ int lh_graph_compute(lh_ctx* ctx, const lh_tensor* T, uint32_t n_leafs, uint32_t
                 LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
                 if (timing) fprintf(stderr, "[llamahip] graph_compute N=%u: validate %.1f us, match %.1f, find plan %.1f, enqueue %.1f, wait %.1f\n", m.N, us(tq0, tq1), us(tq1, tq2), us(tq2, tq3), us(tq3, tq4), us(tq4, now()));
                 ctx->last_ptr[total - 1] = p->logits;  // [N][V], the final node's layout (ne0 = V, ne1 = N)
-                ctx->last_len[total - 1] = (uint64_t)m.N * m.md.V;
+                ctx->last_len[total - 1] = (uint64_t)m.N * m.V;
                 ctx->last_fused = 1;
                 return LH_OK;
             }
@@ -580,6 +350,10 @@ int lh_graph_compute(lh_ctx* ctx, const lh_tensor* T, uint32_t n_leafs, uint32_t
 
 int lh_graph_check(const lh_tensor* T, uint32_t n_leafs, uint32_t n_nodes, const lh_buf_extent* bufs, uint32_t n_bufs, char* msg, uint64_t cap) {
     return gc::graph_check(T, n_leafs, n_nodes, bufs, n_bufs, msg, cap);
+}
+
+int lh_graph_match(const lh_tensor* T, uint32_t n_leafs, uint32_t n_nodes, const lh_buf_extent* bufs, uint32_t n_bufs, lh_match_info* out) {
+    return gm::graph_match(T, n_leafs, n_nodes, bufs, n_bufs, out);
 }
 
 int lh_node_read(lh_ctx* ctx, uint32_t index, uint64_t off, float* dst, uint64_t n) {

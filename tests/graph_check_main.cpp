@@ -1,16 +1,19 @@
-// tests/graph_check_main.cpp — csrc/graph_check.h as a stand-alone program, so that the graph validator can run under host sanitizers
-// (tests/test_graph_check_cpu.py compiles it with -fsanitize=address,undefined and compares its verdicts with the library's).
+// tests/graph_check_main.cpp — csrc/graph_check.h and csrc/graph_match.h as a stand-alone program, so that the graph validator and the matcher of
+// the fused plan can run under host sanitizers (tests/test_graph_check_cpu.py compiles it with -fsanitize=address,undefined and compares its
+// verdicts with the library's).
 //
 // Input file (little endian), written by the test:
 //   u32 n_graphs; per graph: u32 n_leafs, n_nodes, n_bufs, n_vals; (n_leafs + n_nodes) records of 96 bytes = struct lh_tensor whose host field
 //   holds 1 + the index of the tensor's first host value (0: none); n_bufs x {u64 id, u64 nfloats, i32 dtype, i32 0}; n_vals x f32.
 //   u32 n_mutations; per mutation {u32 graph, u32 tensor, u32 field, u32 0, u64 value}: one field of one tensor of a COPY of the graph is set
-//   (fields: tests/graph_ops_ref.py F_*), the copy is checked, one line with the return code is printed.
+//   (fields: tests/graph_ops_ref.py F_*), the copy is checked and matched, one line with the return codes of lh_graph_check and lh_graph_match is
+//   printed.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
 #include "graph_check.h"
+#include "graph_match.h"
 
 struct GraphIn {
     uint32_t n_leafs = 0, n_nodes = 0;
@@ -96,7 +99,8 @@ int main(int argc, char** argv) {
         }
         char msg[256];
         const int rc = lh::gc::graph_check(t.data(), nl, nn, g.bufs.data(), (uint32_t)g.bufs.size(), msg, sizeof msg);
-        printf("%d\n", rc);
+        const int mrc = lh::gm::graph_match(t.data(), nl, nn, g.bufs.data(), (uint32_t)g.bufs.size(), nullptr);
+        printf("%d %d\n", rc, mrc);
     }
     fclose(f);
     return 0;

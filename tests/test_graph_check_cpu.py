@@ -6,8 +6,8 @@ addressing (tests/graph_ops_ref.py), without a device.
   mutant corpus   deterministic and exhaustive: one field of one tensor at a time.  SOUNDNESS: every mutant the model calls unsafe is refused.
                   CAP: at most 2 % of the mutants the model calls safe are refused, and at least a fifth of all mutants are safe.
   bounds          the a-priori bounds of RMSNorm and SoftMax hold for fp32 restatements in four summation orders and fail four wrong kernels.
-  sanitizers      tests/graph_check_main.cpp (graph_check.h behind its own main) built with -fsanitize=address,undefined runs the same corpora
-                  as a child process: no report, verdicts identical to the library's.
+  sanitizers      tests/graph_check_main.cpp (graph_check.h and graph_match.h behind its own main) built with -fsanitize=address,undefined runs the
+                  same corpora as a child process: no report, verdicts of lh_graph_check and of lh_graph_match identical to the library's.
 """
 import ctypes as C
 import os
@@ -34,6 +34,8 @@ def lib(built):
     hip = C.CDLL(pkg.LIBLLAMAHIP, mode=C.RTLD_GLOBAL)
     hip.lh_graph_check.restype = C.c_int
     hip.lh_graph_check.argtypes = [C.POINTER(R.LhTensor), C.c_uint32, C.c_uint32, C.POINTER(R.LhBufExtent), C.c_uint32, C.c_char_p, C.c_uint64]
+    hip.lh_graph_match.restype = C.c_int
+    hip.lh_graph_match.argtypes = [C.POINTER(R.LhTensor), C.c_uint32, C.c_uint32, C.POINTER(R.LhBufExtent), C.c_uint32, C.c_void_p]
     return hip
 
 
@@ -61,6 +63,12 @@ class HostStandIn:
 
     def __len__(self):
         return self.n
+
+
+def match_verdict(lib, g, packed=None, counts=None):
+    arr, ext, nb = packed or g.pack()
+    nl, nn = counts or g.abi_counts()
+    return lib.lh_graph_match(arr, nl, nn, ext, nb, None)
 
 
 def check(lib, g, n_leafs=None, n_nodes=None, packed=None):
@@ -449,15 +457,19 @@ def test_corpora_under_address_and_undefined_sanitizers(lib, mirror, corpus, ver
         if name.startswith("eval_small") or any(R.nelem(t) > BIG_LEAF for t in g.t[:g.n_leafs]):
             continue                                             # (the large ones add bytes, not paths)
         rc, _ = check(lib, g)
-        graphs.append(g); muts.append((len(graphs) - 1, 0, R.F_NONE, 0)); want.append(rc)
+        graphs.append(g); muts.append((len(graphs) - 1, 0, R.F_NONE, 0)); want.append((rc, match_verdict(lib, g)))
     for _, g, _, _ in cases.refused_cases():
         rc, _ = check(lib, g)
-        graphs.append(g); want.append(rc)
+        graphs.append(g); want.append((rc, match_verdict(lib, g)))
         muts.append((len(graphs) - 1, 0, R.F_COUNTS, (g.counts[0] << 32) | g.counts[1]) if g.counts else (len(graphs) - 1, 0, R.F_NONE, 0))
     for name, (g, ms, res) in verdicts.items():
         graphs.append(g)
         muts += [(len(graphs) - 1, i, f, v) for i, f, v in ms]
-        want += [rc for rc, _ in res]
+        arr, ext, nb = g.pack()
+        for mut, (rc, _) in zip(ms, res):
+            with Mutated(g, arr, mut) as m:
+                want.append((rc, match_verdict(lib, g, (arr, ext, nb), m.counts)))
+    assert sum(m == 1 for _, m in want) > 1000 and sum(m == 0 for _, m in want) > 1000    # the matcher's verdicts: both sorts, many
     path = str(tmp_path / "corpus.bin")
     with open(path, "wb") as fh:
         fh.write(struct.pack("<I", len(graphs)))
@@ -471,10 +483,10 @@ def test_corpora_under_address_and_undefined_sanitizers(lib, mirror, corpus, ver
         pytest.skip("the sanitizer runtime refuses to start here: " + run.stderr.strip().splitlines()[0])
     assert run.returncode == 0, f"exit {run.returncode}:\n{run.stderr[-3000:]}"
     assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr, run.stderr[-3000:]
-    got = [int(x) for x in run.stdout.split()]
+    got = [tuple(int(x) for x in ln.split()) for ln in run.stdout.splitlines()]
     assert len(got) == len(want)
     bad = [k for k in range(len(got)) if got[k] != want[k]]
-    assert not bad, f"{len(bad)} verdicts differ, first: mutation {muts[bad[0]]} stand-alone {got[bad[0]]} library {want[bad[0]]}"
+    assert not bad, f"{len(bad)} verdicts differ, first: mutation {muts[bad[0]]} stand-alone {got[bad[0]]} library {want[bad[0]]} (lh_graph_check, lh_graph_match)"
 
 
 # ---- bound self-checks -------------------------------------------------------------------------------------------------------------------
