@@ -168,6 +168,23 @@ int llamago_BatchDecodeLookup(llama_batch* b, const uint32_t* first_tokens, cons
                               float* logits_last, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap);
 int llamago_SpecAcceptPods(const uint32_t* arg, const uint32_t* tok, uint32_t n_pods, uint32_t n_rows, const uint32_t* k, const uint32_t* pos, const uint32_t* produced,
                            uint32_t n_steps, uint32_t ctx_size, uint32_t* a_out, uint32_t* pos_out, uint32_t* produced_out, uint32_t* pending_out, uint32_t* ids_out);
+/* The same on a batch behind llamago_BatchSetSampler (lh_batch_decode_sample_lookup, lh_sample_pod_rows, lh_spec_accept_sample_pods, lh_batch_sampler_read;
+ * the rule per pod and the contract are stated in llamahip.h): the generation loop of server.go:201-217 for every pod through verify passes whose pods x R
+ * rows are sampled in one launch (SampleTopPTopK, llama.go:455-707) - the ids, rings and draw counters of llamago_BatchDecode on the same batch.
+ * llamago_SamplePodRows / llamago_SpecAcceptSamplePods: that sampler launch / the accept step with the ring commit (appendToken, server.go:205) alone on host
+ * arrays, on the model context's device.  llamago_BatchSamplerRead: pod `pod`'s ring (llamago_BatchSamplerRingSize(b) entries - the ringSize of the last
+ * llamago_BatchSetSampler, 0 without a sampler; server.go:127-138), ids appended so far and next sampling call; each output optional. */
+int llamago_BatchDecodeSampleLookup(llama_batch* b, const uint32_t* first_tokens, const uint32_t* past, uint32_t n_steps, const lh_lookup_params* lp, uint32_t* out,
+                                    float* logits_last, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap);
+int llamago_SamplePodRows(const float* logits, uint32_t n_pods, uint32_t n_rows, uint32_t n_logits, const uint32_t* rings, uint32_t ring_size, const uint32_t* ring_pos,
+                          const uint64_t* draws, const uint32_t* tokens, const uint32_t* n_draft, uint32_t topK, float topP, float temp, float repeatPenalty,
+                          uint64_t seed, uint32_t* ids_out);
+int llamago_SpecAcceptSamplePods(const uint32_t* arg, const uint32_t* tok, uint32_t n_pods, uint32_t n_rows, const uint32_t* k, const uint32_t* pos,
+                                 const uint32_t* produced, uint32_t n_steps, uint32_t ctx_size, const uint32_t* rings, uint32_t ring_size, const uint32_t* ring_pos,
+                                 const uint64_t* draws, uint32_t* a_out, uint32_t* pos_out, uint32_t* produced_out, uint32_t* pending_out, uint32_t* ids_out,
+                                 uint32_t* rings_out, uint32_t* ring_pos_out, uint64_t* draws_out);
+uint32_t llamago_BatchSamplerRingSize(llama_batch* b);
+int llamago_BatchSamplerRead(llama_batch* b, uint32_t pod, uint32_t* ring_out, uint32_t* ring_pos_out, uint64_t* draw_out);
 /* lh_batch_decode: n_steps ticks of every pod from (first_tokens[i], past[i]) in one call; out [pods][n_steps], logits_last (optional) [pods][vocab]:
  * the logits of the last tick (llamago_BatchTick returns ids only). */
 int llamago_BatchDecode(llama_batch* b, const uint32_t* first_tokens, const uint32_t* past, uint32_t n_steps, uint32_t* out, float* logits_last);

@@ -422,7 +422,8 @@ int lh_batch_decode(lh_batch* b, const uint32_t* first_tokens, const uint32_t* p
  * histories; cache rows behind each position are stale and are overwritten by whatever runs next.
  * Refused before anything is enqueued, the batch left exactly as it was: the window condition, bad lookup parameters, a corpus id or first token >= vocab,
  * n_steps == 0, a null required argument (LH_EINVAL); a batch with a sampler set, a batch of layer-shard stages (LH_EUNSUPPORTED).
- * Out of scope: sampled batches, a context swap or shrinking passes at the window's end, segment attention for the pass, per-pod n_steps or corpora. */
+ * A batch with a sampler set takes lh_batch_decode_sample_lookup (below).
+ * Out of scope: a context swap or shrinking passes at the window's end, segment attention for the pass, per-pod n_steps or corpora. */
 int lh_batch_decode_lookup(lh_batch* b, const uint32_t* first_tokens, const uint32_t* past, uint32_t n_steps, const lh_lookup_params* lp,
                            uint32_t* out_tokens,        /* [rows][n_steps], as lh_batch_decode */
                            float* logits_last_host,     /* optional [rows][vocab] */
@@ -437,6 +438,56 @@ int lh_batch_decode_lookup(lh_batch* b, const uint32_t* first_tokens, const uint
 int lh_spec_accept_pods(lh_ctx* ctx, const uint32_t* arg, const uint32_t* tok, uint32_t n_pods, uint32_t n_rows, const uint32_t* k, const uint32_t* pos,
                         const uint32_t* produced, uint32_t n_steps, uint32_t ctx_size, uint32_t* a_out, uint32_t* pos_out, uint32_t* produced_out,
                         uint32_t* pending_out, uint32_t* ids_out);
+/* ---- the same for a SAMPLING batch: the loop a server with sampling on runs (server.go:201-217 per pod, TopK 40; the pods side by side, server.go:84-106).
+ * lh_batch_decode_sample_lookup is lh_batch_decode_lookup on a batch behind lh_batch_set_sampler, with two launches exchanged: ONE sampler launch over the
+ * P * R rows of the pass (k_sample_pod_rows, topK <= 1024; k_sample_small_pod_rows, topK <= 64) in place of the argmax, and the accept step commits every
+ * pod's ring and draw counter.  The rule per pod i is the rule of lh_llama_decode_sample_lookup on the pod's own sampler state: row r of pod i is
+ * SampleTopPTopK (llama.go:455-707) of logits row i * R + r as sampling call draw_i + r over pod i's ring as if tok[i * R + 1 .. i * R + r] had been appended
+ * behind its ring_pos ids; a = the leading j < k_i with arg[j] == tok[j + 1] (clipped as above); arg[0..a] are appended to pod i's ring in order
+ * (appendToken, server.go:205), ring_pos_i and draw_i move on by a + 1.  The uniforms are counter-based (seed, sampling call, rank), so this is an equality
+ * with the one-token ticks, no rejection sampling.  R (batch_spec_rows), the window condition past[i] + n_steps + R - 1 <= ctx, the host's look cadence, one
+ * captured graph per pass (re-captured also when the sampler variant, the ring or the state array changed), R = 1 = plain sampled ticks (the lh_batch_decode
+ * route), stats and trace: all as lh_batch_decode_lookup.
+ * Contract:
+ *  1. out_tokens = the ids of lh_batch_decode on the same sampling batch from the same state with the same arguments; so where P * R <= 8 (fp32) or <= 4
+ *     (block-int8) they are also each pod's solo lh_llama_decode_sample ids;
+ *  2. for any row count they are the sampler's ids on the pass's own logits (rows byte-equal to lh_batch_feed's with LLAMAHIP_FEED_ROW_ATTN=1);
+ *  3. afterwards the batch stands as lh_batch_decode leaves it: positions past + n_steps (host mirror included), each pod's last id pending in
+ *     lh_batch_tokens_dev, lh_batch_ids_dev and entry 0 of its output list, every pod's ring, ring_pos and draw equal to what the ticks would hold, the
+ *     evaluated tokens in the pods' histories.
+ * logits_last_host (optional) [rows][vocab] = the row each pod's LAST id was sampled from.
+ * Refused before anything is enqueued, batch and sampler state left exactly as they were: everything lh_batch_decode_lookup refuses; a batch without a
+ * sampler (LH_EINVAL, as lh_batch_feed_sample); a batch of layer-shard stages (LH_EUNSUPPORTED).
+ * Out of scope: a context swap or shrinking passes at the window's end, segment or shared-prefix attention for the pass, per-pod seeds, parameters, n_steps
+ * or corpora, layer shards and the pipeline. */
+int lh_batch_decode_sample_lookup(lh_batch* b, const uint32_t* first_tokens, const uint32_t* past, uint32_t n_steps, const lh_lookup_params* lp,
+                                  uint32_t* out_tokens,        /* [rows][n_steps], as lh_batch_decode */
+                                  float* logits_last_host,     /* optional [rows][vocab] */
+                                  lh_spec_stats* stats,        /* optional [rows] */
+                                  uint16_t* trace,             /* optional [rows][trace_cap] */
+                                  uint32_t trace_cap);
+/* The sampler launch of such a pass on its own (op-level twin of k_sample_pod_rows / k_sample_small_pod_rows, host in / host out like lh_sample_rows and
+ * lh_sample_pods): SampleTopPTopK (llama.go:455-707) for the rows of n_pods generation loops (server.go:201-217) at once.  logits_host [n_pods * n_rows]
+ * [n_logits] packed, rings_host [n_pods][ring_size] with ring_pos[i] ids appended so far, draws[i] = pod i's next sampling call, tokens_host [n_pods][n_rows]
+ * (entry 0 of a pod, its pending token, is ignored: it is in the ring already), n_draft[i] = pod i's draft length, one set of parameters.  ONE launch.
+ * ids_out[i * n_rows + r] = the id of row r of pod i for r <= n_draft[i]; the other entries are not written (the caller presets 0xFFFFFFFF).  Refusals as
+ * lh_sample_rows, with n_pods outside 1..64, n_rows outside 1..8 or n_pods * n_rows > 64 in place of the row count. */
+int lh_sample_pod_rows(lh_ctx* ctx, const float* logits_host, uint32_t n_pods, uint32_t n_rows, uint32_t n_logits, const uint32_t* rings_host,
+                       uint32_t ring_size, const uint32_t* ring_pos, const uint64_t* draws, const uint32_t* tokens_host, const uint32_t* n_draft,
+                       const lh_sample_params* sp, uint32_t* ids_out);
+/* lh_spec_accept_pods with the sampled commit (k_spec_accept_pods on the sampled route): additionally rings [n_pods][ring_size], ring_pos [n_pods] and
+ * draws [n_pods] in front of the pass; rings_out / ring_pos_out / draws_out (each optional) behind it - a pod that accepts a has arg[0..a] appended to its
+ * ring in order (appendToken, server.go:205, once per id of the loop server.go:201-217) and both counters moved on by a + 1; a finished pod commits nothing.
+ * ONE launch.  Refusals as lh_spec_accept_pods, and ring_size == 0 or a null ring argument (LH_EINVAL). */
+int lh_spec_accept_sample_pods(lh_ctx* ctx, const uint32_t* arg, const uint32_t* tok, uint32_t n_pods, uint32_t n_rows, const uint32_t* k, const uint32_t* pos,
+                               const uint32_t* produced, uint32_t n_steps, uint32_t ctx_size, const uint32_t* rings, uint32_t ring_size,
+                               const uint32_t* ring_pos, const uint64_t* draws, uint32_t* a_out, uint32_t* pos_out, uint32_t* produced_out,
+                               uint32_t* pending_out, uint32_t* ids_out, uint32_t* rings_out, uint32_t* ring_pos_out, uint64_t* draws_out);
+/* Pod `pod`'s sampler state of a sampling batch, after waiting for the stream: its lastNTokens ring (server.go:127-138; ring_out has room for
+ * lh_batch_sampler_ring_size(b) ids: the ring_size of the last lh_batch_set_sampler, 0 for a batch without a sampler), ring_pos = ids appended so far and draw = the index of its next sampling call (llama.go:658 seeds per call).  Each output is
+ * optional.  A batch without a sampler, a pod outside the batch: LH_EINVAL. */
+uint32_t lh_batch_sampler_ring_size(const lh_batch* b);
+int lh_batch_sampler_read(lh_batch* b, uint32_t pod, uint32_t* ring_out, uint32_t* ring_pos_out, uint64_t* draw_out);
 /* llama.Eval for any subset of the pods, packed into shared weight passes of <= 64 rows (whole-model batches, greedy).
  * Pod i evaluates tokens[i][0..n_tokens[i]) at positions past[i].. of ITS cache.
  * n_tokens[i] == 0: pod i is not fed (tokens[i], past[i] ignored).

@@ -29,6 +29,8 @@
 //   k_sample_rows / k_sample_small_rows: the same two bodies over the R rows of a verify pass in one launch, one workgroup per row, row r as
 //     sampling call draw + r over the ring as if the draft in front of it had been appended (ring_bitmap<true>); the speculative sampled loop
 //     (include/llamahip.h, lh_llama_decode_sample_lookup).
+//   k_sample_pod_rows / k_sample_small_pod_rows: the same over the P * R rows of a batch's verify pass, workgroup e = row e % R of pod e / R on that pod's state
+//     and ring (lh_batch_decode_sample_lookup).
 //   k_sample_pods / k_sample_small_pods: the single-row bodies over the pods of a batch in one launch, one workgroup per job {pod, logits row}, every pod on
 //     its own state, ring, step parameters and output list (the sampled tick of lh_batch and lh_batch_feed_sample; the workgroups run on separate CUs).
 //   k_feed_ring: the lastNTokens bookkeeping of a fed segment (server.go:127-138, 189-190) in front of that pod's sampling call.
@@ -45,6 +47,17 @@ struct SampleState {
 };
 
 constexpr uint32_t SAMPLE_MAX_K = 1024;
+
+// The loop's state in device memory: a captured pass is replayed for every position and every accepted count.
+struct SpecState {
+    uint32_t pos;        // position of the pending token (= tokens of the window in front of it)
+    uint32_t produced;   // ids in the output list
+    uint32_t n_steps;    // ids asked for: a pass that finds produced == n_steps does nothing
+    uint32_t k;          // draft length of the NEXT pass (its rows 1..k)
+    uint32_t last_a;     // accepted count of the last pass: its row last_a holds the logits behind the last evaluated token
+    uint32_t passes, drafted, accepted, empty;
+    uint32_t pad[7];
+};
 
 __host__ __device__ __forceinline__ uint64_t smp_mix64(uint64_t z) {
     z += 0x9E3779B97F4A7C15ull;
@@ -284,6 +297,18 @@ __global__ __launch_bounds__(1024) void k_sample_rows(const float* __restrict__ 
     const uint32_t row = blockIdx.x;
     if (n_draft && row > *n_draft) return;
     sample_body<EPT, true>(logits + (size_t)row * V, V, st, ring, nullptr, nullptr, arg + row, nullptr, nullptr, nullptr, 0, tok, row);
+}
+
+// k_sample_rows over the P * R rows of a batch's verify pass in ONE launch (include/llamahip.h, lh_sample_pod_rows; the loop of lh_batch_decode_sample_lookup):
+// workgroup e = row r = e % R of pod i = e / R.  It samples logits row e on pod i's state ss[i] and ring (ring + i * ring_cap) as sampling call ss[i].draw + r
+// over the ring as if pod i's tok[i * R + 1 .. i * R + r] had been appended; the id goes to arg[e].  Nothing else is written: k_spec_accept_pods commits.
+// A row behind its pod's draft (r > st[i].k) is filler the accept step never reads and returns at once, as does every row of a finished pod.
+template <int EPT>
+__global__ __launch_bounds__(1024) void k_sample_pod_rows(const float* __restrict__ logits, uint32_t V, SampleState* ss, uint32_t* __restrict__ ring, uint32_t ring_cap,
+                                                          const uint32_t* __restrict__ tok, const SpecState* __restrict__ st, uint32_t R, uint32_t* __restrict__ arg) {
+    const uint32_t e = blockIdx.x, i = e / R, r = e - i * R;
+    if (r > st[i].k || st[i].produced >= st[i].n_steps) return;
+    sample_body<EPT, true>(logits + (size_t)e * V, V, ss + i, ring + (size_t)i * ring_cap, nullptr, nullptr, arg + e, nullptr, nullptr, nullptr, 0, tok + (size_t)i * R, r);
 }
 
 // One job of a multi-pod launch: pod `pod` samples logits row `row` (a null table: job e = {e, e}, the tick of a batch).
@@ -583,6 +608,16 @@ __global__ __launch_bounds__(1024) void k_sample_small_rows(const float* __restr
     const uint32_t row = blockIdx.x;
     if (n_draft && row > *n_draft) return;
     sample_small_body<EPT, true>(logits + (size_t)row * V, V, st, ring, nullptr, nullptr, arg + row, nullptr, nullptr, nullptr, 0, tok, row);
+}
+
+// k_sample_pod_rows for topK <= 64 (a row that is not 16-byte aligned takes the body's 4-byte loads, as in k_sample_small_rows).
+template <int EPT>
+__global__ __launch_bounds__(1024) void k_sample_small_pod_rows(const float* __restrict__ logits, uint32_t V, SampleState* ss, uint32_t* __restrict__ ring, uint32_t ring_cap,
+                                                                const uint32_t* __restrict__ tok, const SpecState* __restrict__ st, uint32_t R, uint32_t* __restrict__ arg) {
+    const uint32_t e = blockIdx.x, i = e / R, r = e - i * R;
+    if (r > st[i].k || st[i].produced >= st[i].n_steps) return;
+    sample_small_body<EPT, true>(logits + (size_t)e * V, V, ss + i, ring + (size_t)i * ring_cap, nullptr, nullptr, arg + e, nullptr, nullptr, nullptr, 0, tok + (size_t)i * R,
+                                 r);
 }
 
 // k_sample_pods for topK <= 64.

@@ -13,16 +13,7 @@ constexpr uint32_t SPEC_UNKNOWN = 0xFFFFFFFFu;   // = Plan::HIST_UNKNOWN: a wind
 constexpr int SPEC_TH = 1024;
 constexpr uint32_t SPEC_ROWS_MAX = 8, SPEC_NGRAM_MAX = 8, SPEC_CORPUS_MAX = 65536;
 
-// The loop's state in device memory: a captured pass is replayed for every position and every accepted count.
-struct SpecState {
-    uint32_t pos;        // position of the pending token (= tokens of the window in front of it)
-    uint32_t produced;   // ids in the output list
-    uint32_t n_steps;    // ids asked for: a pass that finds produced == n_steps does nothing
-    uint32_t k;          // draft length of the NEXT pass (its rows 1..k)
-    uint32_t last_a;     // accepted count of the last pass: its row last_a holds the logits behind the last evaluated token
-    uint32_t passes, drafted, accepted, empty;
-    uint32_t pad[7];
-};
+// (SpecState, the loop's state in device memory, is defined in kernels_sample.h: the pods x rows sampler reads it.)
 struct SpecLookup {
     const uint32_t* corpus;   // device, may be nullptr
     uint32_t n_corpus, draft_max, ngram_max, ngram_min;
@@ -201,6 +192,9 @@ struct SpecPodsArgs {
     uint32_t* ids;            // [P] the same (the batch's array of produced ids), may be nullptr
     SpecPodSum* sum;          // [P]
     uint32_t R, ctx, vocab, out_cap, trace_cap;
+    SampleState* ss;          // [P] the sampled route (arg = the ids of k_sample_pod_rows / k_sample_small_pod_rows); nullptr: greedy
+    uint32_t* ring;           // [P][ring_cap] the pods' lastNTokens rings
+    uint32_t ring_cap;
 };
 struct SpecPodsSet { uint32_t pos[64]; uint32_t tok[64]; };
 
@@ -240,6 +234,8 @@ __global__ __launch_bounds__(SPEC_TH) void k_draft_lookup_pods(const SpecPodsArg
 // copies logits row a (the logits behind its last id) to last[i] and leaves its table rows and tokens where they are: as filler of the later passes they
 // re-evaluate the same tokens at the same positions, so no row ever stands past the window.  A finished pod changes nothing.  Every index written is
 // clamped to its buffer, as in k_spec_accept.
+// A.ss != nullptr: the sampled route (lh_batch_decode_sample_lookup) - arg[] are the ids of k_sample_pod_rows / k_sample_small_pod_rows, and a pod that
+// accepts a appends arg[0..a] to ITS ring in order, ring_pos and draw move on by a + 1 (k_spec_accept's commit per pod).  nullptr: the greedy route.
 __global__ __launch_bounds__(SPEC_TH) void k_spec_accept_pods(const SpecPodsArgs A, const SpecLookup lp, int lookup_next) {
     __shared__ int s_best;
     __shared__ uint32_t s_pos, s_done, s_fin, s_a;
@@ -261,6 +257,13 @@ __global__ __launch_bounds__(SPEC_TH) void k_spec_accept_pods(const SpecPodsArgs
             for (uint32_t j = 0; j <= a; ++j) {
                 if (produced + j < A.out_cap) A.out[(size_t)i * A.out_cap + produced + j] = arg[j];
                 if (win) win[p + 1 + j] = arg[j];   // win has ctx + 1 entries
+            }
+            if (A.ss) {   // the sampled commit of k_spec_accept, on the pod's own state and ring
+                SampleState* ss = A.ss + i;
+                uint32_t* ring = A.ring + (size_t)i * A.ring_cap;
+                const uint32_t rs = ss->ring_size, rp = ss->ring_pos;
+                if (rs) for (uint32_t j = 0; j <= a; ++j) ring[(rp + j) % rs] = arg[j];   // appendToken (server.go:205) per accepted id, in order
+                ss->ring_pos = rp + a + 1; ss->draw += a + 1;
             }
             const uint32_t s = st->passes;
             if (A.trace && s < A.trace_cap) A.trace[(size_t)i * A.trace_cap + s] = (uint16_t)((k << 8) | a);

@@ -149,6 +149,11 @@ int sample_launch(lh_ctx* ctx, const float* logits, uint32_t V, SampleState* st,
 // the rows of a verify pass in one launch (k_sample_rows / k_sample_small_rows): ids to arg[0..n_rows), nothing else written
 int sample_rows_launch(lh_ctx* ctx, const float* logits, uint32_t V, uint32_t n_rows, SampleState* st, uint32_t* ring, const uint32_t* tok, const uint32_t* n_draft,
                        uint32_t* arg, uint32_t topk_hint);
+// the n_pods * n_rows rows of a batch's verify pass in one launch (k_sample_pod_rows / k_sample_small_pod_rows): row r of pod i on ss[i] and ring i as call
+// draw_i + r, rows behind st[i].k and the rows of a finished pod left out; ids to arg[i * n_rows + r], nothing else written
+struct SpecState;
+int sample_pod_rows_launch(lh_ctx* ctx, const float* logits, uint32_t V, uint32_t n_pods, uint32_t n_rows, SampleState* ss, uint32_t* ring, uint32_t ring_cap,
+                           const uint32_t* tok, const SpecState* st, uint32_t* arg, uint32_t topk_hint);
 // the single-row sampler over n_jobs pods of a batch in one launch (k_sample_pods / k_sample_small_pods): job e = jobs[e] {pod, logits row}, or {e, e} without a table
 struct SampleJob;
 struct FeedRingSeg;

@@ -2239,6 +2239,7 @@ struct Batch {
     SampleState* ss_dev = nullptr; // [B]
     uint32_t* ring_dev = nullptr;  // [B][ring_cap]
     uint32_t ring_cap = 0, smp_topk = 0;
+    uint32_t ring_size = 0;        // of the last lh_batch_set_sampler (lh_batch_sampler_ring_size)
     bool sampling = false;
     // the captured tick
     hipGraph_t graph = nullptr;
@@ -3011,6 +3012,8 @@ static int spec_decode_lookup(Plan* p, uint32_t first_token, uint32_t past, uint
 // ---- lh_batch_decode_lookup: the same loop for the pods of a batch -------------------------------------------------------------------
 // A pass = the batched plan_eval of P * R rows on pod 0's plan (row i * R + r = row r of pod i, on pod i's cache: the table lh_batch_feed lays out for
 // P pods fed R tokens each, with the per-row attention kernels), k_batch_argmax over the P * R logits rows, k_spec_accept_pods.  One captured graph.
+// lh_batch_decode_sample_lookup (smp) exchanges two launches: k_sample_pod_rows / k_sample_small_pod_rows on the batch's sampler states and rings instead of
+// k_batch_argmax, and the accept step commits every pod's ring and draw counter (ss_dev / ring_dev).
 struct BatchSpec {
     SpecState* st = nullptr;           // [B]
     SpecPodSum* sum = nullptr;         // [B]
@@ -3031,6 +3034,11 @@ struct BatchSpec {
     SpecLookup cap_lp = {};
     uint16_t* cap_trace = nullptr;
     uint64_t cap_splitk_gen = 0, cap_scratch_gen = 0;
+    bool smp = false;                  // the running loop samples (lh_batch_decode_sample_lookup)
+    bool cap_smp = false, cap_small_k = false;   // the captured pass holds the sampler variant, the ring pointer and the state pointer
+    SampleState* cap_ss = nullptr;
+    uint32_t* cap_ring = nullptr;
+    uint32_t cap_ring_cap = 0;
     uint64_t warm = 0;                 // bit n - 1: a pass of n rows has run eagerly
 };
 static void batch_spec_drop_graph(BatchSpec* s) {
@@ -3096,6 +3104,7 @@ static SpecPodsArgs batch_spec_args(const Batch* b, uint32_t R) {
     a.arg = s->arg; a.st = s->st; a.rows = s->rows; a.tok = s->tok; a.win = s->win; a.out = b->out_dev; a.trace = s->trace;
     a.logits = b->pods[0]->logits; a.last = s->last; a.pend = b->tok_dev; a.ids = b->ids_dev; a.sum = s->sum;
     a.R = R; a.ctx = m.ctx; a.vocab = m.V; a.out_cap = b->out_cap; a.trace_cap = s->trace_cap;
+    if (s->smp) { a.ss = b->ss_dev; a.ring = b->ring_dev; a.ring_cap = b->ring_cap; }
     return a;
 }
 // the kernels of one pass, in stream order
@@ -3108,8 +3117,12 @@ static int batch_spec_enqueue_pass(Batch* b, uint32_t R, const SpecLookup& lp) {
     int rc;
     BatchCtx bc = {s->rows, s->tok, p0->attn_part ? s->part : nullptr};
     if ((rc = plan_eval(p0, nullptr, nullptr, nullptr, n, 0, false, &bc))) return rc;
-    LH_LAUNCH(k_batch_argmax, dim3(n), dim3(1024), 0, ctx->stream, (const float*)p0->logits, m.V, (BatchRow*)nullptr, (uint32_t*)nullptr, s->arg, (uint32_t*)nullptr, 0u,
-              (StepParams*)nullptr, 0);
+    if (s->smp) {
+        if ((rc = sample_pod_rows_launch(ctx, p0->logits, m.V, b->B, R, b->ss_dev, b->ring_dev, b->ring_cap, s->tok, s->st, s->arg, b->smp_topk))) return rc;
+    } else {
+        LH_LAUNCH(k_batch_argmax, dim3(n), dim3(1024), 0, ctx->stream, (const float*)p0->logits, m.V, (BatchRow*)nullptr, (uint32_t*)nullptr, s->arg, (uint32_t*)nullptr, 0u,
+                  (StepParams*)nullptr, 0);
+    }
     LH_LAUNCH(k_spec_accept_pods, dim3(b->B), dim3(SPEC_TH), 0, ctx->stream, batch_spec_args(b, R), lp, 1);
     LH_HIP(ctx, hipGetLastError());
     return 0;
@@ -3124,7 +3137,8 @@ static int batch_spec_pass(Batch* b, uint32_t R, const SpecLookup& lp) {
         return batch_spec_enqueue_pass(b, R, lp);
     }
     if (s->exec && (s->cap_R != R || memcmp(&s->cap_lp, &lp, sizeof lp) || s->cap_trace != s->trace || s->cap_trace_cap != s->trace_cap || s->cap_splitk_gen != ctx->splitk_gen ||
-                    s->cap_scratch_gen != b->scratch_gen()))
+                    s->cap_scratch_gen != b->scratch_gen() || s->cap_smp != s->smp ||
+                    (s->smp && (s->cap_small_k != (b->smp_topk <= 64) || s->cap_ss != b->ss_dev || s->cap_ring != b->ring_dev || s->cap_ring_cap != b->ring_cap))))
         batch_spec_drop_graph(s);
     if (!s->exec) {
         LH_HIP(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeRelaxed));
@@ -3134,14 +3148,16 @@ static int batch_spec_pass(Batch* b, uint32_t R, const SpecLookup& lp) {
         if (e != hipSuccess) LH_FAIL(ctx, LH_EHIP, "hipStreamEndCapture (batch speculative pass): %s", hipGetErrorString(e));
         LH_HIP(ctx, hipGraphInstantiate(&s->exec, s->graph, nullptr, nullptr, 0));
         s->cap_R = R; s->cap_lp = lp; s->cap_trace = s->trace; s->cap_trace_cap = s->trace_cap; s->cap_splitk_gen = ctx->splitk_gen; s->cap_scratch_gen = b->scratch_gen();
+        s->cap_smp = s->smp; s->cap_small_k = b->smp_topk <= 64; s->cap_ss = b->ss_dev; s->cap_ring = b->ring_dev; s->cap_ring_cap = b->ring_cap;
     }
     LH_HIP(ctx, hipGraphLaunch(s->exec, ctx->stream));
     return 0;
 }
 
-// The loop behind lh_batch_decode_lookup; the caller has checked every argument and R >= 2.
+// The loop behind lh_batch_decode_lookup and (smp) lh_batch_decode_sample_lookup; the caller has checked every argument and R >= 2.
 static int batch_decode_lookup(Batch* b, const uint32_t* first_tokens, const uint32_t* past, uint32_t n_steps, const lh_lookup_params* lpar, uint32_t R, uint32_t* out_tokens,
-                               float* logits_last_host, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap) {
+                               float* logits_last_host, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap, bool smp) {
+    const char* who = smp ? "lh_batch_decode_sample_lookup" : "lh_batch_decode_lookup";
     lh_ctx* ctx = b->ctx;
     Plan* p0 = b->pods[0];
     const ModelDesc& m = p0->md;
@@ -3154,6 +3170,7 @@ static int batch_decode_lookup(Batch* b, const uint32_t* first_tokens, const uin
     const size_t win_bytes = 4 * (size_t)B * W;
     if ((rc = ensure_staging(ctx, win_bytes + 4 * (size_t)n_corpus))) return rc;
     BatchSpec* s = b->spec;
+    s->smp = smp;
     // what the ticks so far did goes into the pods' histories (and waits for the stream: the staging buffer is free)
     if (b->pos_known) { if ((rc = batch_drain(b))) return rc; }
     else LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -3188,7 +3205,7 @@ static int batch_decode_lookup(Batch* b, const uint32_t* first_tokens, const uin
         LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
         uint32_t now = n_steps;
         for (uint32_t i = 0; i < B; ++i) now = std::min(now, hs[i].produced);
-        if (now < std::min(n_steps, low + q)) LH_FAIL(ctx, LH_EHIP, "lh_batch_decode_lookup: a pass produced no id for a pod");
+        if (now < std::min(n_steps, low + q)) LH_FAIL(ctx, LH_EHIP, "%s: a pass produced no id for a pod", who);
         low = now;
     }
     // ---- results, then the state lh_batch_feed leaves: every pod behind its last evaluated token, its last id pending
@@ -3207,7 +3224,7 @@ static int batch_decode_lookup(Batch* b, const uint32_t* first_tokens, const uin
     if ((rc = batch_set(b, nullptr, newpos.data(), 1))) return rc;
     LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (uint32_t i = 0; i < B; ++i) {
-        if (st[i].produced != n_steps || st[i].pos != newpos[i]) LH_FAIL(ctx, LH_EHIP, "lh_batch_decode_lookup: the accept step left pod %u in an inconsistent state", i);
+        if (st[i].produced != n_steps || st[i].pos != newpos[i]) LH_FAIL(ctx, LH_EHIP, "%s: the accept step left pod %u in an inconsistent state", who, i);
         const uint32_t* o = out.data() + (size_t)i * n_steps;
         for (uint32_t t = 0; t < n_steps; ++t) b->pods[i]->record(past[i] + t, t ? o[t - 1] : first_tokens[i]);
         memcpy(out_tokens + (size_t)i * n_steps, o, (size_t)n_steps * 4);
@@ -3728,6 +3745,7 @@ int lh_batch_set_sampler(lh_batch* h, const lh_sample_params* sp, uint32_t ring_
     }
     if ((sp->top_k <= 64) != (b->smp_topk <= 64)) batch_drop_graph(b);   // the captured tick holds the kernel variant
     b->smp_topk = sp->top_k;
+    b->ring_size = ring_size;
     // ring: ring_size zeros, then the ids seen so far (appendToken, server.go:129-138, 193-197)
     std::vector<uint32_t> ring((size_t)b->B * b->ring_cap, 0u);
     std::vector<SampleState> st(b->B);
@@ -3841,31 +3859,34 @@ int lh_batch_decode(lh_batch* h, const uint32_t* first_tokens, const uint32_t* p
     return LH_OK;
 }
 
-int lh_batch_decode_lookup(lh_batch* h, const uint32_t* first_tokens, const uint32_t* past, uint32_t n_steps, const lh_lookup_params* lp, uint32_t* out_tokens,
-                           float* logits_last_host, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap) {
+// lh_batch_decode_lookup and (smp) lh_batch_decode_sample_lookup: the checks, then the loop
+static int batch_decode_lookup_checked(lh_batch* h, const uint32_t* first_tokens, const uint32_t* past, uint32_t n_steps, const lh_lookup_params* lp, uint32_t* out_tokens,
+                                       float* logits_last_host, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap, bool smp) {
     if (!h) return LH_EINVAL;
+    const char* who = smp ? "lh_batch_decode_sample_lookup" : "lh_batch_decode_lookup";
     Batch* b = h->b;
     lh_ctx* ctx = b->ctx;
     const ModelDesc& m = b->pods[0]->md;
     LH_HIP(ctx, hipSetDevice(ctx->device));
     // ---- everything is checked before anything is enqueued or any host state moves
-    if (!first_tokens || !past || !out_tokens) LH_FAIL(ctx, LH_EINVAL, "lh_batch_decode_lookup: null argument");
-    if (!n_steps) LH_FAIL(ctx, LH_EINVAL, "lh_batch_decode_lookup: no ids asked for");
-    if (!m.first_stage() || !m.last_stage()) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_batch_decode_lookup needs whole-model pods (layers [%u, %u) of %u)", m.layer0, m.layer1, m.L);
-    if (b->sampling) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_batch_decode_lookup: the batch has a sampler set (greedy only; lh_batch_set_sampler(NULL) first)");
+    if (!first_tokens || !past || !out_tokens) LH_FAIL(ctx, LH_EINVAL, "%s: null argument", who);
+    if (!n_steps) LH_FAIL(ctx, LH_EINVAL, "%s: no ids asked for", who);
+    if (!m.first_stage() || !m.last_stage()) LH_FAIL(ctx, LH_EUNSUPPORTED, "%s needs whole-model pods (layers [%u, %u) of %u)", who, m.layer0, m.layer1, m.L);
+    if (!smp && b->sampling) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_batch_decode_lookup: the batch has a sampler set (greedy only; lh_batch_set_sampler(NULL) first)");
+    if (smp && !b->sampling) LH_FAIL(ctx, LH_EINVAL, "lh_batch_decode_sample_lookup: the batch has no sampler set (lh_batch_decode_lookup runs a greedy batch)");
     int rc;
     {   // draft_max is 1..7 for both weight types here: beyond the bit-identical rows the passes are batched Evals like a feed's
-        if (!lp) LH_FAIL(ctx, LH_EINVAL, "lh_batch_decode_lookup: no lookup parameters");
-        if (lp->draft_max < 1 || lp->draft_max > SPEC_ROWS_MAX - 1) LH_FAIL(ctx, LH_EINVAL, "lh_batch_decode_lookup: draft_max %u (1..%u)", lp->draft_max, SPEC_ROWS_MAX - 1);
+        if (!lp) LH_FAIL(ctx, LH_EINVAL, "%s: no lookup parameters", who);
+        if (lp->draft_max < 1 || lp->draft_max > SPEC_ROWS_MAX - 1) LH_FAIL(ctx, LH_EINVAL, "%s: draft_max %u (1..%u)", who, lp->draft_max, SPEC_ROWS_MAX - 1);
         lh_lookup_params one = *lp;
         one.draft_max = 1;
-        if ((rc = spec_check_params(ctx, m, &one, "lh_batch_decode_lookup"))) return rc;
+        if ((rc = spec_check_params(ctx, m, &one, who))) return rc;
     }
     const uint32_t R = batch_spec_rows(b, lp->draft_max);
     for (uint32_t i = 0; i < b->B; ++i) {
-        if (first_tokens[i] >= m.V) LH_FAIL(ctx, LH_EINVAL, "lh_batch_decode_lookup: token id %u of row %u outside the vocabulary of %u", first_tokens[i], i, m.V);
+        if (first_tokens[i] >= m.V) LH_FAIL(ctx, LH_EINVAL, "%s: token id %u of row %u outside the vocabulary of %u", who, first_tokens[i], i, m.V);
         if ((uint64_t)past[i] + n_steps + R - 1 > m.ctx)
-            LH_FAIL(ctx, LH_EINVAL, "lh_batch_decode_lookup: row %u: past %u + n_steps %u + %u rows per pass - 1 exceeds the context window of %u (the loop never leaves the window)",
+            LH_FAIL(ctx, LH_EINVAL, "%s: row %u: past %u + n_steps %u + %u rows per pass - 1 exceeds the context window of %u (the loop never leaves the window)", who,
                     i, past[i], n_steps, R, m.ctx);
     }
     if (R == 1) {   // no multi-row pass for this pod count on this plan's shapes: plain ticks, and the stats say so
@@ -3877,23 +3898,62 @@ int lh_batch_decode_lookup(lh_batch* h, const uint32_t* first_tokens, const uint
         return LH_OK;
     }
     for (uint32_t i = 0; i < b->B; ++i) share_written(b, i, past[i]);   // the passes write every pod's cache from past[i] on
-    return batch_decode_lookup(b, first_tokens, past, n_steps, lp, R, out_tokens, logits_last_host, stats, trace, trace_cap);
+    return batch_decode_lookup(b, first_tokens, past, n_steps, lp, R, out_tokens, logits_last_host, stats, trace, trace_cap, smp);
 }
 
-int lh_spec_accept_pods(lh_ctx* ctx, const uint32_t* arg, const uint32_t* tok, uint32_t n_pods, uint32_t n_rows, const uint32_t* k, const uint32_t* pos,
-                        const uint32_t* produced, uint32_t n_steps, uint32_t ctx_size, uint32_t* a_out, uint32_t* pos_out, uint32_t* produced_out, uint32_t* pending_out,
-                        uint32_t* ids_out) {
+int lh_batch_decode_lookup(lh_batch* h, const uint32_t* first_tokens, const uint32_t* past, uint32_t n_steps, const lh_lookup_params* lp, uint32_t* out_tokens,
+                           float* logits_last_host, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap) {
+    return batch_decode_lookup_checked(h, first_tokens, past, n_steps, lp, out_tokens, logits_last_host, stats, trace, trace_cap, false);
+}
+
+int lh_batch_decode_sample_lookup(lh_batch* h, const uint32_t* first_tokens, const uint32_t* past, uint32_t n_steps, const lh_lookup_params* lp, uint32_t* out_tokens,
+                                  float* logits_last_host, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap) {
+    return batch_decode_lookup_checked(h, first_tokens, past, n_steps, lp, out_tokens, logits_last_host, stats, trace, trace_cap, true);
+}
+
+uint32_t lh_batch_sampler_ring_size(const lh_batch* h) { return h && h->b->sampling ? h->b->ring_size : 0u; }
+
+int lh_batch_sampler_read(lh_batch* h, uint32_t pod, uint32_t* ring_out, uint32_t* ring_pos_out, uint64_t* draw_out) {
+    if (!h) return LH_EINVAL;
+    Batch* b = h->b;
+    lh_ctx* ctx = b->ctx;
+    LH_HIP(ctx, hipSetDevice(ctx->device));
+    if (!b->sampling) LH_FAIL(ctx, LH_EINVAL, "lh_batch_sampler_read: the batch has no sampler set");
+    if (pod >= b->B) LH_FAIL(ctx, LH_EINVAL, "lh_batch_sampler_read: pod %u outside the batch of %u", pod, b->B);
+    SampleState st;
+    LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    LH_HIP(ctx, hipMemcpy(&st, b->ss_dev + pod, sizeof st, hipMemcpyDeviceToHost));
+    if (ring_out) LH_HIP(ctx, hipMemcpy(ring_out, b->ring_dev + (size_t)pod * b->ring_cap, (size_t)st.ring_size * 4, hipMemcpyDeviceToHost));
+    if (ring_pos_out) *ring_pos_out = st.ring_pos;
+    if (draw_out) *draw_out = st.draw;
+    return LH_OK;
+}
+
+// lh_spec_accept_pods and (rings != nullptr) lh_spec_accept_sample_pods: one k_spec_accept_pods launch on host arrays
+static int spec_accept_pods_host(lh_ctx* ctx, const char* who, const uint32_t* arg, const uint32_t* tok, uint32_t n_pods, uint32_t n_rows, const uint32_t* k, const uint32_t* pos,
+                                 const uint32_t* produced, uint32_t n_steps, uint32_t ctx_size, const uint32_t* rings, uint32_t ring_size, const uint32_t* ring_pos,
+                                 const uint64_t* draws, uint32_t* a_out, uint32_t* pos_out, uint32_t* produced_out, uint32_t* pending_out, uint32_t* ids_out,
+                                 uint32_t* rings_out, uint32_t* ring_pos_out, uint64_t* draws_out) {
     if (!ctx) return LH_EINVAL;
-    if (!arg || !tok || !k || !pos || !produced || !a_out || !pos_out || !produced_out || !pending_out || !ids_out) LH_FAIL(ctx, LH_EINVAL, "lh_spec_accept_pods: null argument");
+    if (!arg || !tok || !k || !pos || !produced || !a_out || !pos_out || !produced_out || !pending_out || !ids_out) LH_FAIL(ctx, LH_EINVAL, "%s: null argument", who);
     const uint32_t P = n_pods, R = n_rows;
     if (P < 1 || P > BATCH_ROWS_MAX || R < 1 || R > SPEC_ROWS_MAX || P * R > BATCH_ROWS_MAX)
-        LH_FAIL(ctx, LH_EINVAL, "lh_spec_accept_pods: %u pods x %u rows (1..%u pods, 1..%u rows, at most %u rows in all)", P, R, BATCH_ROWS_MAX, SPEC_ROWS_MAX, BATCH_ROWS_MAX);
-    if (!ctx_size) LH_FAIL(ctx, LH_EINVAL, "lh_spec_accept_pods: an empty window");
+        LH_FAIL(ctx, LH_EINVAL, "%s: %u pods x %u rows (1..%u pods, 1..%u rows, at most %u rows in all)", who, P, R, BATCH_ROWS_MAX, SPEC_ROWS_MAX, BATCH_ROWS_MAX);
+    if (!ctx_size) LH_FAIL(ctx, LH_EINVAL, "%s: an empty window", who);
+    if (rings && !ring_size) LH_FAIL(ctx, LH_EINVAL, "%s: the lastNTokens ring needs at least one slot", who);
     LH_HIP(ctx, hipSetDevice(ctx->device));
-    // one allocation: arg | tok | pending | output lists [P][R] | states | summaries | row table
+    // one allocation: arg | tok | pending | output lists [P][R] | states | summaries | row table | sampler states | rings
     const size_t n = (size_t)P * R, o_tok = 4 * n, o_pend = o_tok + 4 * n, o_out = o_pend + 4 * (size_t)P, o_st = (o_out + 4 * n + 63) & ~(size_t)63,
-                 o_sum = o_st + sizeof(SpecState) * P, o_rows = o_sum + sizeof(SpecPodSum) * P, total = o_rows + sizeof(BatchRow) * n;
+                 o_sum = o_st + sizeof(SpecState) * P, o_rows = o_sum + sizeof(SpecPodSum) * P, o_ss = (o_rows + sizeof(BatchRow) * n + 63) & ~(size_t)63,
+                 o_ring = o_ss + (rings ? sizeof(SampleState) * P : 0), total = o_ring + (rings ? 4 * (size_t)P * ring_size : 0);
     std::vector<char> hb(total, 0);
+    if (rings) {
+        memcpy(hb.data() + o_ring, rings, 4 * (size_t)P * ring_size);
+        for (uint32_t i = 0; i < P; ++i) {   // only the ring and the two counters are read by the commit
+            SampleState* ss = (SampleState*)(hb.data() + o_ss) + i;
+            ss->ring_size = ring_size; ss->ring_pos = ring_pos[i]; ss->draw = draws[i];
+        }
+    }
     memcpy(hb.data(), arg, 4 * n);
     memcpy(hb.data() + o_tok, tok, 4 * n);
     std::vector<uint32_t> base(P);   // a pod's list holds only what this pass appends: entry `produced` of the loop's list is entry 0 here
@@ -3912,6 +3972,7 @@ int lh_spec_accept_pods(lh_ctx* ctx, const uint32_t* arg, const uint32_t* tok, u
         a.arg = (const uint32_t*)dev; a.tok = (uint32_t*)(dev + o_tok); a.pend = (uint32_t*)(dev + o_pend); a.out = (uint32_t*)(dev + o_out); a.st = (SpecState*)(dev + o_st);
         a.sum = (SpecPodSum*)(dev + o_sum); a.rows = (BatchRow*)(dev + o_rows);
         a.R = R; a.ctx = ctx_size; a.vocab = SPEC_UNKNOWN; a.out_cap = R;
+        if (rings) { a.ss = (SampleState*)(dev + o_ss); a.ring = (uint32_t*)(dev + o_ring); a.ring_cap = ring_size; }
         const SpecLookup none = {nullptr, 0, 0, 1, 1};
         LH_LAUNCH(k_spec_accept_pods, dim3(P), dim3(SPEC_TH), 0, ctx->stream, a, none, 0);
         e = hipGetLastError();
@@ -3919,8 +3980,14 @@ int lh_spec_accept_pods(lh_ctx* ctx, const uint32_t* arg, const uint32_t* tok, u
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     }
     hipFree(dev);
-    if (e != hipSuccess) LH_FAIL(ctx, LH_EHIP, "lh_spec_accept_pods: %s", hipGetErrorString(e));
+    if (e != hipSuccess) LH_FAIL(ctx, LH_EHIP, "%s: %s", who, hipGetErrorString(e));
+    if (rings && rings_out) memcpy(rings_out, hb.data() + o_ring, 4 * (size_t)P * ring_size);
     for (uint32_t i = 0; i < P; ++i) {
+        if (rings) {
+            const SampleState* ss = (const SampleState*)(hb.data() + o_ss) + i;
+            if (ring_pos_out) ring_pos_out[i] = ss->ring_pos;
+            if (draws_out) draws_out[i] = ss->draw;
+        }
         const SpecState* st = (const SpecState*)(hb.data() + o_st) + i;
         a_out[i] = st->last_a; pos_out[i] = st->pos; produced_out[i] = st->produced + base[i];
         pending_out[i] = ((const uint32_t*)(hb.data() + o_pend))[i];
@@ -3928,6 +3995,23 @@ int lh_spec_accept_pods(lh_ctx* ctx, const uint32_t* arg, const uint32_t* tok, u
         for (uint32_t j = 0; j < R; ++j) ids_out[(size_t)i * R + j] = j < appended ? ((const uint32_t*)(hb.data() + o_out))[(size_t)i * R + j] : SPEC_UNKNOWN;
     }
     return LH_OK;
+}
+
+int lh_spec_accept_pods(lh_ctx* ctx, const uint32_t* arg, const uint32_t* tok, uint32_t n_pods, uint32_t n_rows, const uint32_t* k, const uint32_t* pos,
+                        const uint32_t* produced, uint32_t n_steps, uint32_t ctx_size, uint32_t* a_out, uint32_t* pos_out, uint32_t* produced_out, uint32_t* pending_out,
+                        uint32_t* ids_out) {
+    return spec_accept_pods_host(ctx, "lh_spec_accept_pods", arg, tok, n_pods, n_rows, k, pos, produced, n_steps, ctx_size, nullptr, 0, nullptr, nullptr, a_out, pos_out,
+                                 produced_out, pending_out, ids_out, nullptr, nullptr, nullptr);
+}
+
+int lh_spec_accept_sample_pods(lh_ctx* ctx, const uint32_t* arg, const uint32_t* tok, uint32_t n_pods, uint32_t n_rows, const uint32_t* k, const uint32_t* pos,
+                               const uint32_t* produced, uint32_t n_steps, uint32_t ctx_size, const uint32_t* rings, uint32_t ring_size, const uint32_t* ring_pos,
+                               const uint64_t* draws, uint32_t* a_out, uint32_t* pos_out, uint32_t* produced_out, uint32_t* pending_out, uint32_t* ids_out,
+                               uint32_t* rings_out, uint32_t* ring_pos_out, uint64_t* draws_out) {
+    if (!ctx) return LH_EINVAL;
+    if (!rings || !ring_pos || !draws) LH_FAIL(ctx, LH_EINVAL, "lh_spec_accept_sample_pods: null argument");
+    return spec_accept_pods_host(ctx, "lh_spec_accept_sample_pods", arg, tok, n_pods, n_rows, k, pos, produced, n_steps, ctx_size, rings, ring_size, ring_pos, draws, a_out,
+                                 pos_out, produced_out, pending_out, ids_out, rings_out, ring_pos_out, draws_out);
 }
 
 int lh_batch_feed(lh_batch* h, const uint32_t* const* tokens, const uint32_t* n_tokens, const uint32_t* past, uint32_t* ids_host, float* logits_last_host,

@@ -46,6 +46,23 @@ int sample_rows_launch(lh_ctx* ctx, const float* logits, uint32_t V, uint32_t n_
     return 0;
 }
 
+int sample_pod_rows_launch(lh_ctx* ctx, const float* logits, uint32_t V, uint32_t n_pods, uint32_t n_rows, SampleState* ss, uint32_t* ring, uint32_t ring_cap,
+                           const uint32_t* tok, const SpecState* st, uint32_t* arg, uint32_t topk_hint) {
+    const bool small_k = topk_hint && topk_hint <= 64;
+    const uint32_t n = n_pods * n_rows;
+    LH_TRACE("%s/n%u", small_k ? "k_sample_small_pod_rows" : "k_sample_pod_rows", n);
+    if (small_k && V <= 32u * 1024u)
+        LH_LAUNCH(k_sample_small_pod_rows<32>, dim3(n), dim3(1024), 0, ctx->stream, logits, V, ss, ring, ring_cap, tok, st, n_rows, arg);
+    else if (small_k)
+        LH_LAUNCH(k_sample_small_pod_rows<64>, dim3(n), dim3(1024), 0, ctx->stream, logits, V, ss, ring, ring_cap, tok, st, n_rows, arg);
+    else if (V <= 32u * 1024u)
+        LH_LAUNCH(k_sample_pod_rows<32>, dim3(n), dim3(1024), 0, ctx->stream, logits, V, ss, ring, ring_cap, tok, st, n_rows, arg);
+    else
+        LH_LAUNCH(k_sample_pod_rows<64>, dim3(n), dim3(1024), 0, ctx->stream, logits, V, ss, ring, ring_cap, tok, st, n_rows, arg);
+    LH_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
 int sample_pods_launch(lh_ctx* ctx, const float* logits, uint32_t V, uint32_t n_jobs, const SampleJob* jobs, SampleState* ss, uint32_t* ring, uint32_t ring_cap,
                        StepParams* sp, uint32_t* out, uint32_t out_cap, uint32_t* ids, uint32_t topk_hint) {
     const bool small_k = topk_hint && topk_hint <= 64;
@@ -183,5 +200,55 @@ extern "C" int lh_sample_pods(lh_ctx* ctx, const float* logits_host, uint32_t n,
         ids_out[i] = ids[i];
         if (ring_pos_out) ring_pos_out[i] = st[i].ring_pos;
     }
+    return LH_OK;
+}
+
+extern "C" int lh_sample_pod_rows(lh_ctx* ctx, const float* logits_host, uint32_t n_pods, uint32_t n_rows, uint32_t n_logits, const uint32_t* rings_host,
+                                  uint32_t ring_size, const uint32_t* ring_pos, const uint64_t* draws, const uint32_t* tokens_host, const uint32_t* n_draft,
+                                  const lh_sample_params* sp, uint32_t* ids_out) {
+    if (!ctx) return LH_EINVAL;
+    if (!logits_host || !rings_host || !ring_pos || !draws || !tokens_host || !n_draft || !ids_out) LH_FAIL(ctx, LH_EINVAL, "lh_sample_pod_rows: null argument");
+    const uint32_t P = n_pods, R = n_rows;
+    if (P == 0 || P > 64 || R == 0 || R > 8 || P * R > 64)
+        LH_FAIL(ctx, LH_EINVAL, "lh_sample_pod_rows: %u pods x %u rows (1..64 pods, 1..8 rows, at most 64 rows in all)", P, R);
+    if (ring_size == 0) LH_FAIL(ctx, LH_EINVAL, "lh_sample_pod_rows: the lastNTokens ring needs at least one slot");
+    int rc;
+    if ((rc = sample_check(ctx, sp, n_logits))) return rc;
+    for (uint32_t i = 0; i < P; ++i)
+        for (uint32_t r = 1; r < R; ++r)
+            if (tokens_host[(size_t)i * R + r] >= n_logits)
+                LH_FAIL(ctx, LH_EINVAL, "lh_sample_pod_rows: pod %u: draft id %u at index %u outside the vocabulary of %u", i, tokens_host[(size_t)i * R + r], r, n_logits);
+    LH_HIP(ctx, hipSetDevice(ctx->device));
+    // one allocation: logits | rings | sampler states | pass states (k = n_draft, one id asked for, none produced) | tokens | ids
+    const size_t n = (size_t)P * R, b_lg = n * n_logits * 4, b_ring = (size_t)P * ring_size * 4;
+    const size_t o_ring = b_lg, o_st = (o_ring + b_ring + 63) & ~(size_t)63, o_ps = o_st + sizeof(SampleState) * 64, o_tok = o_ps + sizeof(SpecState) * 64, o_ids = o_tok + 4 * 64,
+                 total = o_ids + 4 * 64;
+    char* dev = nullptr;
+    LH_HIP(ctx, hipMalloc((void**)&dev, total));
+    SampleState st[64];
+    SpecState ps[64] = {};
+    for (uint32_t i = 0; i < P; ++i) {
+        st[i] = SampleState{sp->top_k, sp->top_p, sp->temp, sp->repeat_penalty, sp->seed, draws[i], ring_size, ring_pos[i]};
+        ps[i].n_steps = 1; ps[i].k = n_draft[i];
+    }
+    uint32_t ids[64];
+    hipError_t e = hipMemcpyAsync(dev, logits_host, b_lg, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dev + o_ring, rings_host, b_ring, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dev + o_st, st, sizeof(SampleState) * P, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dev + o_ps, ps, sizeof(SpecState) * P, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dev + o_tok, tokens_host, n * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(dev + o_ids, 0xFF, 4 * 64, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the host arrays are pageable memory
+    if (e == hipSuccess) {
+        rc = sample_pod_rows_launch(ctx, (const float*)dev, n_logits, P, R, (SampleState*)(dev + o_st), (uint32_t*)(dev + o_ring), ring_size, (const uint32_t*)(dev + o_tok),
+                                    (const SpecState*)(dev + o_ps), (uint32_t*)(dev + o_ids), sp->top_k);
+        if (rc) { (void)hipFree(dev); return rc; }
+        e = hipMemcpyAsync(ids, dev + o_ids, n * 4, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    }
+    (void)hipFree(dev);
+    if (e != hipSuccess) LH_FAIL(ctx, LH_EHIP, "lh_sample_pod_rows: %s", hipGetErrorString(e));
+    for (uint32_t i = 0; i < P; ++i)
+        for (uint32_t r = 0; r < R && r <= n_draft[i]; ++r) ids_out[(size_t)i * R + r] = ids[(size_t)i * R + r];   // the rows behind a draft stay the caller's
     return LH_OK;
 }

@@ -361,9 +361,21 @@ func (bt *BatchHIP) ShareInfo() (group, length []uint32) {
 // stream at once.  The loop never leaves the window: past[i] + nSteps + R - 1 <= CtxSize must hold (the caller takes the last positions with Tick).
 // Returns the ids per pod and the stats per pod; afterwards every pod's last id is pending, as behind Feed.  C++ twin: llamago_BatchDecodeLookup.
 func (bt *BatchHIP) DecodeLookup(firstTokens, past []uint32, nSteps, draftMax, ngramMax, ngramMin uint32, corpus []uint32) ([][]uint32, []SpecStatsHIP) {
+	return bt.decodeLookup("DecodeLookup", false, firstTokens, past, nSteps, draftMax, ngramMax, ngramMin, corpus)
+}
+
+// DecodeSampleLookup is DecodeLookup on a batch behind SetSampler (lh_batch_decode_sample_lookup): the generation loop of server.go:201-217 for every
+// pod, the pods x R rows of a pass sampled in ONE launch (SampleTopPTopK, llama.go:455-707) and committed per pod (appendToken, server.go:205).  The ids,
+// rings and draw counters are those of the sampled Ticks - an equality, the device sampler's uniforms being counter-based.  The window condition, the
+// return values and the state left behind are DecodeLookup's.  C++ twin: llamago_BatchDecodeSampleLookup.
+func (bt *BatchHIP) DecodeSampleLookup(firstTokens, past []uint32, nSteps, draftMax, ngramMax, ngramMin uint32, corpus []uint32) ([][]uint32, []SpecStatsHIP) {
+	return bt.decodeLookup("DecodeSampleLookup", true, firstTokens, past, nSteps, draftMax, ngramMax, ngramMin, corpus)
+}
+
+func (bt *BatchHIP) decodeLookup(who string, sample bool, firstTokens, past []uint32, nSteps, draftMax, ngramMax, ngramMin uint32, corpus []uint32) ([][]uint32, []SpecStatsHIP) {
 	n := len(bt.stages)
 	if len(firstTokens) != n || len(past) != n || nSteps == 0 {
-		fmt.Printf("\n[HALT] DecodeLookup: firstTokens and past need one entry per pod (%d), nSteps at least 1", n)
+		fmt.Printf("\n[HALT] %s: firstTokens and past need one entry per pod (%d), nSteps at least 1", who, n)
 		os.Exit(1)
 	}
 	flat := make([]uint32, n*int(nSteps))
@@ -378,8 +390,15 @@ func (bt *BatchHIP) DecodeLookup(firstTokens, past []uint32, nSteps, draftMax, n
 		}
 		lp.corpus, lp.n_corpus = &cc[0], C.uint32_t(m)
 	}
-	if rc := C.lh_batch_decode_lookup(bt.b, (*C.uint32_t)(unsafe.Pointer(&firstTokens[0])), (*C.uint32_t)(unsafe.Pointer(&past[0])), C.uint32_t(nSteps), &lp,
-		(*C.uint32_t)(unsafe.Pointer(&flat[0])), nil, (*C.lh_spec_stats)(unsafe.Pointer(&stats[0])), nil, 0); rc != 0 {
+	var rc C.int
+	if sample {
+		rc = C.lh_batch_decode_sample_lookup(bt.b, (*C.uint32_t)(unsafe.Pointer(&firstTokens[0])), (*C.uint32_t)(unsafe.Pointer(&past[0])), C.uint32_t(nSteps), &lp,
+			(*C.uint32_t)(unsafe.Pointer(&flat[0])), nil, (*C.lh_spec_stats)(unsafe.Pointer(&stats[0])), nil, 0)
+	} else {
+		rc = C.lh_batch_decode_lookup(bt.b, (*C.uint32_t)(unsafe.Pointer(&firstTokens[0])), (*C.uint32_t)(unsafe.Pointer(&past[0])), C.uint32_t(nSteps), &lp,
+			(*C.uint32_t)(unsafe.Pointer(&flat[0])), nil, (*C.lh_spec_stats)(unsafe.Pointer(&stats[0])), nil, 0)
+	}
+	if rc != 0 {
 		hipHalt(bt.ctx.hip.ctx)
 	}
 	out := make([][]uint32, n)
@@ -387,6 +406,23 @@ func (bt *BatchHIP) DecodeLookup(firstTokens, past []uint32, nSteps, draftMax, n
 		out[i] = flat[i*int(nSteps) : (i+1)*int(nSteps)]
 	}
 	return out, stats
+}
+
+// SamplerState returns pod `pod`'s lastNTokens ring (the ringSize entries of SetSampler; server.go:127-138), the ids appended to it so far and the
+// index of its next sampling call (lh_batch_sampler_read; waits for the stream).  C++ twin: llamago_BatchSamplerRead.
+func (bt *BatchHIP) SamplerState(pod uint32) (ring []uint32, ringPos uint32, draw uint64) {
+	n := uint32(C.lh_batch_sampler_ring_size(bt.b))
+	if n == 0 {
+		fmt.Printf("\n[HALT] SamplerState: the batch has no sampler set (SetSampler)")
+		os.Exit(1)
+	}
+	ring = make([]uint32, n)
+	var rp C.uint32_t
+	var dr C.uint64_t
+	if rc := C.lh_batch_sampler_read(bt.b, C.uint32_t(pod), (*C.uint32_t)(unsafe.Pointer(&ring[0])), &rp, &dr); rc != 0 {
+		hipHalt(bt.ctx.hip.ctx)
+	}
+	return ring, uint32(rp), uint64(dr)
 }
 
 func (bt *BatchHIP) ids() []uint32 {

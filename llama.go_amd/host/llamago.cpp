@@ -1490,6 +1490,39 @@ int llamago_SpecAcceptPods(const uint32_t* arg, const uint32_t* tok, uint32_t n_
     if (lh_spec_accept_pods(h, arg, tok, n_pods, n_rows, k, pos, produced, n_steps, ctx_size, a_out, pos_out, produced_out, pending_out, ids_out)) return halt_rc(lh_last_error(h));
     return 0;
 }
+// the same on a sampling batch (lh_batch_decode_sample_lookup), its sampler launch and its accept step alone, and a pod's sampler state
+int llamago_BatchDecodeSampleLookup(llama_batch* p, const uint32_t* first_tokens, const uint32_t* past, uint32_t n_steps, const lh_lookup_params* lp, uint32_t* out,
+                                    float* logits_last, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap) {
+    if (!p) return halt_rc("llamago_BatchDecodeSampleLookup: bad arguments");
+    if (lh_batch_decode_sample_lookup(p->b, first_tokens, past, n_steps, lp, out, logits_last, stats, trace, trace_cap)) return halt_rc(lh_last_error(p->mlctx->hip));
+    return 0;
+}
+int llamago_SamplePodRows(const float* logits, uint32_t n_pods, uint32_t n_rows, uint32_t n_logits, const uint32_t* rings, uint32_t ring_size, const uint32_t* ring_pos,
+                          const uint64_t* draws, const uint32_t* tokens, const uint32_t* n_draft, uint32_t topK, float topP, float temp, float repeatPenalty,
+                          uint64_t seed, uint32_t* ids_out) {
+    lh_ctx* h = model_ctx();
+    if (!h) return 1;
+    const lh_sample_params sp = {topK, topP, temp, repeatPenalty, seed};
+    if (lh_sample_pod_rows(h, logits, n_pods, n_rows, n_logits, rings, ring_size, ring_pos, draws, tokens, n_draft, &sp, ids_out)) return halt_rc(lh_last_error(h));
+    return 0;
+}
+int llamago_SpecAcceptSamplePods(const uint32_t* arg, const uint32_t* tok, uint32_t n_pods, uint32_t n_rows, const uint32_t* k, const uint32_t* pos,
+                                 const uint32_t* produced, uint32_t n_steps, uint32_t ctx_size, const uint32_t* rings, uint32_t ring_size, const uint32_t* ring_pos,
+                                 const uint64_t* draws, uint32_t* a_out, uint32_t* pos_out, uint32_t* produced_out, uint32_t* pending_out, uint32_t* ids_out,
+                                 uint32_t* rings_out, uint32_t* ring_pos_out, uint64_t* draws_out) {
+    lh_ctx* h = model_ctx();
+    if (!h) return 1;
+    if (lh_spec_accept_sample_pods(h, arg, tok, n_pods, n_rows, k, pos, produced, n_steps, ctx_size, rings, ring_size, ring_pos, draws, a_out, pos_out, produced_out,
+                                   pending_out, ids_out, rings_out, ring_pos_out, draws_out))
+        return halt_rc(lh_last_error(h));
+    return 0;
+}
+uint32_t llamago_BatchSamplerRingSize(llama_batch* p) { return p ? lh_batch_sampler_ring_size(p->b) : 0u; }
+int llamago_BatchSamplerRead(llama_batch* p, uint32_t pod, uint32_t* ring_out, uint32_t* ring_pos_out, uint64_t* draw_out) {
+    if (!p) return halt_rc("llamago_BatchSamplerRead: bad arguments");
+    if (lh_batch_sampler_read(p->b, pod, ring_out, ring_pos_out, draw_out)) return halt_rc(lh_last_error(p->mlctx->hip));
+    return 0;
+}
 // lh_batch_decode: n_steps ticks of every pod from (first_tokens[i], past[i]); out [pods][n_steps], logits_last (optional) [pods][vocab] of the last tick
 int llamago_BatchDecode(llama_batch* p, const uint32_t* first_tokens, const uint32_t* past, uint32_t n_steps, uint32_t* out, float* logits_last) {
     if (!p || !first_tokens || !past || !n_steps) return halt_rc("llamago_BatchDecode: bad arguments");

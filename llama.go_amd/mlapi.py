@@ -628,6 +628,60 @@ def SamplePods(ml, logits, rings, ring_pos, draws, topK=40, topP=0.95, temp=0.8,
     return out[:n], rout[:n, :rs], pout[:n]
 
 
+def sample_pod_rows(ml, logits, rings, ring_pos, draws, tokens, n_draft, topK=40, topP=0.95, temp=0.8, repeatPenalty=1.10, seed=0):
+    """llamago_SamplePodRows: the pods x R rows of a batch's verify pass sampled in one launch (lh_sample_pod_rows; k_sample_pod_rows /
+    k_sample_small_pod_rows).  logits [P * R][V]; rings [P][ring_size] with ring_pos[i] ids appended so far; draws[i] = pod i's next sampling call; tokens
+    [P][R] = per pod the pending token (ignored) and the draft; n_draft[i] = pod i's draft length.  Row r of pod i is sampling call draws[i] + r over ring i
+    as if tokens[i][1..r] had been appended.  -> uint32 array [P][R], 0xFFFFFFFF in the rows behind a pod's draft."""
+    tk = np.ascontiguousarray(tokens, dtype=np.uint32)
+    P, R = (tk.shape if tk.ndim == 2 else (0, 0))
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    V = lg.shape[-1] if lg.ndim >= 1 and lg.size else 0
+    rg = np.ascontiguousarray(rings, dtype=np.uint32)
+    rs = rg.size // P if P else 0
+    assert lg.size == P * R * V and len(ring_pos) == len(draws) == len(n_draft) == P, (lg.shape, tk.shape)
+    f = ml.lib.llamago_SamplePodRows
+    f.restype = C.c_int
+    f.argtypes = [c_f32p, c_u32, c_u32, c_u32, c_u32p, c_u32, c_u32p, C.POINTER(c_u64), c_u32p, c_u32p, c_u32, C.c_float, C.c_float, C.c_float, c_u64, c_u32p]
+    m = max(P, 1)
+    rp, nd = ((c_u32 * m)(*[int(x) for x in v]) for v in (ring_pos, n_draft))
+    dr = (c_u64 * m)(*[int(x) for x in draws])
+    out = np.full(max(P * R, 64), 0xFFFFFFFF, dtype=np.uint32)
+    if f(lg.ctypes.data_as(c_f32p), P, R, V, rg.ctypes.data_as(c_u32p), rs, rp, dr, tk.ctypes.data_as(c_u32p), nd, int(topK), topP, temp, repeatPenalty, int(seed),
+         out.ctypes.data_as(c_u32p)):
+        raise MLError(f"llamago_SamplePodRows: {ml.last_error()}")
+    return out[:P * R].reshape(P, R)
+
+
+def spec_accept_sample_pods(ml, arg, tok, k, pos, produced, n_steps, ctx, rings, ring_pos, draws):
+    """llamago_SpecAcceptSamplePods: spec_accept_pods with the sampled commit (lh_spec_accept_sample_pods; k_spec_accept_pods on the sampled route).  rings
+    [pods][ring_size], ring_pos / draws [pods] = the pods' sampler state in front of the pass.
+    -> (a, pos, produced, pending, the ids appended per pod, rings [pods][ring_size], ring_pos [pods], draws [pods])."""
+    arg = np.ascontiguousarray(arg, dtype=np.uint32)
+    tok = np.ascontiguousarray(tok, dtype=np.uint32)
+    P, R = (arg.shape if arg.ndim == 2 else (0, 0))
+    rg = np.ascontiguousarray(rings, dtype=np.uint32)
+    rs = rg.size // P if P else 0
+    assert tok.shape == arg.shape and len(k) == len(pos) == len(produced) == len(ring_pos) == len(draws) == P
+    f = ml.lib.llamago_SpecAcceptSamplePods
+    f.restype = C.c_int
+    f.argtypes = [c_u32p, c_u32p, c_u32, c_u32, c_u32p, c_u32p, c_u32p, c_u32, c_u32, c_u32p, c_u32, c_u32p, C.POINTER(c_u64), c_u32p, c_u32p, c_u32p, c_u32p, c_u32p,
+                  c_u32p, c_u32p, C.POINTER(c_u64)]
+    m = max(P, 1)
+    kk, pp, pr, rp = ((c_u32 * m)(*[int(x) for x in v]) for v in (k, pos, produced, ring_pos))
+    dr = (c_u64 * m)(*[int(x) for x in draws])
+    a, npos, nprod, pend, rpo = ((c_u32 * m)() for _ in range(5))
+    dro = (c_u64 * m)()
+    ids = (c_u32 * max(P * R, 1))()
+    rout = np.zeros((m, max(rs, 1)), dtype=np.uint32)
+    if f(arg.ctypes.data_as(c_u32p), tok.ctypes.data_as(c_u32p), P, R, kk, pp, pr, int(n_steps), int(ctx), rg.ctypes.data_as(c_u32p), rs, rp, dr, a, npos, nprod, pend,
+         ids, rout.ctypes.data_as(c_u32p), rpo, dro):
+        raise MLError(f"llamago_SpecAcceptSamplePods: {ml.last_error()}")
+    appended = [[int(t) for t in ids[i * R:i * R + (nprod[i] - int(produced[i]))]] for i in range(P)]
+    return ([int(x) for x in a[:P]], [int(x) for x in npos[:P]], [int(x) for x in nprod[:P]], [int(x) for x in pend[:P]], appended,
+            rout.reshape(-1)[:P * rs].reshape(P, rs), [int(x) for x in rpo[:P]], [int(x) for x in dro[:P]])
+
+
 FEED_NEW, FEED_PENDING = 1, 2   # include/llamahip.h: LH_FEED_NEW, LH_FEED_PENDING
 
 
@@ -930,18 +984,40 @@ class Batch:
         """llamago_BatchDecodeLookup: n_steps greedy ids per pod from (first_tokens[i], past[i]) through lookup-drafted verify passes of pods x R rows
         (lh_batch_decode_lookup).  -> (ids per pod, [pods][vocab] logits behind each pod's last id or None, per pod a stats dict(passes, rows, drafted,
         accepted, empty), per pod the trace list of (k, a) per pass)."""
+        return self._decode_lookup(self.ml.lib.llamago_BatchDecodeLookup, "llamago_BatchDecodeLookup", first_tokens, past, n_steps, draft_max, ngram_max, ngram_min,
+                                   corpus, want_logits)
+
+    def DecodeSampleLookup(self, first_tokens, past, n_steps, draft_max, ngram_max=3, ngram_min=1, corpus=None, want_logits=False):
+        """llamago_BatchDecodeSampleLookup: DecodeLookup on a batch behind SetSampler (lh_batch_decode_sample_lookup) - the ids, rings and draw counters of
+        Decode on the same batch, through verify passes whose pods x R rows are sampled in one launch.  Returns as DecodeLookup; the logits are the rows
+        each pod's last id was sampled from."""
+        return self._decode_lookup(self.ml.lib.llamago_BatchDecodeSampleLookup, "llamago_BatchDecodeSampleLookup", first_tokens, past, n_steps, draft_max, ngram_max,
+                                   ngram_min, corpus, want_logits)
+
+    def SamplerState(self, pod):
+        """llamago_BatchSamplerRead (lh_batch_sampler_read): pod `pod`'s sampler state -> (ring as a list of ring_size ids, ring_pos, draw)."""
+        f = self.ml.lib.llamago_BatchSamplerRead
+        f.restype, f.argtypes = C.c_int, [VP, c_u32, c_u32p, c_u32p, C.POINTER(c_u64)]
+        g = self.ml.lib.llamago_BatchSamplerRingSize
+        g.restype, g.argtypes = c_u32, [VP]
+        n = int(g(self.h))                     # 0: no sampler set - the read below says so
+        ring, rp, dr = (c_u32 * max(n, 1))(), c_u32(0), c_u64(0)
+        if f(self.h, int(pod), ring, C.byref(rp), C.byref(dr)):
+            raise MLError(f"llamago_BatchSamplerRead: {self.ml.last_error()}")
+        return [int(t) for t in ring[:n]], int(rp.value), int(dr.value)
+
+    def _decode_lookup(self, fn, name, first_tokens, past, n_steps, draft_max, ngram_max, ngram_min, corpus, want_logits):
         assert len(first_tokens) == self.pods and len(past) == self.pods
-        L = self.ml.lib
-        L.llamago_BatchDecodeLookup.restype = C.c_int
-        L.llamago_BatchDecodeLookup.argtypes = [VP, c_u32p, c_u32p, c_u32, C.POINTER(LookupParams), c_u32p, c_f32p, C.POINTER(SpecStats), C.POINTER(C.c_uint16), c_u32]
+        fn.restype = C.c_int
+        fn.argtypes = [VP, c_u32p, c_u32p, c_u32, C.POINTER(LookupParams), c_u32p, c_f32p, C.POINTER(SpecStats), C.POINTER(C.c_uint16), c_u32]
         lp, _keep = lookup_params(draft_max, ngram_max, ngram_min, corpus)
         n = max(int(n_steps), 1)
         tk = (c_u32 * self.pods)(*[int(t) for t in first_tokens])
         ps = (c_u32 * self.pods)(*[int(x) for x in past])
         out, st, tr = (c_u32 * (self.pods * n))(), (SpecStats * self.pods)(), (C.c_uint16 * (self.pods * n))()
         lg = np.empty((self.pods, self.model.hp.vocabSize), dtype=np.float32) if want_logits else None
-        if L.llamago_BatchDecodeLookup(self.h, tk, ps, int(n_steps), C.byref(lp), out, lg.ctypes.data_as(c_f32p) if want_logits else None, st, tr, n):
-            raise MLError(f"llamago_BatchDecodeLookup: {self.ml.last_error()}")
+        if fn(self.h, tk, ps, int(n_steps), C.byref(lp), out, lg.ctypes.data_as(c_f32p) if want_logits else None, st, tr, n):
+            raise MLError(f"{name}: {self.ml.last_error()}")
         ids = [[int(t) for t in out[i * n:i * n + n_steps]] for i in range(self.pods)]
         stats = [dict(passes=int(s.passes), rows=int(s.rows), drafted=int(s.drafted), accepted=int(s.accepted), empty=int(s.empty)) for s in st]
         traces = [[(int(v) >> 8, int(v) & 0xFF) for v in tr[i * n:i * n + min(st[i].passes, n)]] for i in range(self.pods)]

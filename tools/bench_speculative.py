@@ -13,12 +13,22 @@ rates here are those of a replayed or a random text, never a model result.
           per pod, draft_max 1 / 3 / 7 (R lowered to what P pods leave room for): a pass of P * R rows against a tick of P rows of lh_batch_decode, same
           process, alternating; aggregate tokens/s with the replay corpus (acceptance 1 by construction: a CEILING, not a model result), without a
           corpus, and of the plain ticks; the break-even mean of accepted ids per pod and pass
-usage: python tools/bench_speculative.py [pass golden] [--sample] [--pods P] [--layers 32] [--reps 5] [--int8] [--out profiles/speculative.txt]"""
+  --pods P --sample  the pods of a SAMPLING batch (lh_batch_decode_sample_lookup; results: profiles/batch_sample_lookup.txt): the same P pods, ctx 256, 96
+          sampled ids per pod (topK 40, topP 0.95, temp 0.8, penalty 1.1), draft_max 1 / 3 / 7, every start a SetSampler + FeedSample(NEW + prompt) that is
+          timed on its own and taken off: a sampled pass of P * R rows against a plain sampled tick of P pods of lh_batch_decode, same process,
+          alternating; the sampler launch over P * R rows (lh_sample_pod_rows) against the tick's launch over P rows (lh_sample_pods), both as host twins
+          whose wall time INCLUDES the upload of their logits; the loop with the replay corpus (the corpus is the run itself: acceptance 1 by
+          construction, a CEILING, never a model result) and with no corpus; the break-even mean of accepted ids per pod and pass.
+          The KERNEL time of the sampler launches is not a host figure: run this part under a kernel trace, one row count per run, the layer count being
+          of no matter to the sampler -
+            rocprofv3 --kernel-trace --stats -d DIR -- python tools/bench_speculative.py --pods P --sample --draft-max K --layers 2 --reps 2
+          - and read k_sample_small_pod_rows (P * R workgroups, the passes) against k_sample_small_pods (P workgroups, the ticks) in the kernel statistics
+usage: python tools/bench_speculative.py [pass golden] [--sample] [--pods P] [--draft-max K] [--layers 32] [--reps 5] [--int8] [--out profiles/speculative.txt]"""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
-from llama_go_amd.mlapi import PROMPT, SHAPES, Batch, decode_greedy_resident, load_product, make_hparams
+from llama_go_amd.mlapi import FEED_NEW, PROMPT, SHAPES, Batch, SamplePods, decode_greedy_resident, load_product, make_hparams, sample_pod_rows
 
 ap = argparse.ArgumentParser()
 ap.add_argument("parts", nargs="*", default=["pass", "golden"])
@@ -27,6 +37,7 @@ ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--int8", action="store_true", help="block-int8 weights too")
 ap.add_argument("--sample", action="store_true", help="the sampled route (SampleDecodeLookup against SampleDecode) instead of the greedy parts")
 ap.add_argument("--pods", type=int, default=0, help="the pods of a batch (Batch.DecodeLookup against the ticks of lh_batch_decode) instead of the solo parts")
+ap.add_argument("--draft-max", type=int, default=0, help="--pods P --sample: this draft_max only (default: 1, 3 and 7)")
 ap.add_argument("--out", default=None, help="append the result lines to this file")
 args = ap.parse_args()
 prod = load_product()
@@ -59,6 +70,81 @@ def prompt_state(m, ctx, prompt):
     c = m.NewContext(ctx, 1)
     return c, int(np.argmax(c.Eval(prompt, 0)))
 
+
+if args.sample and args.pods:
+    args.parts = []
+    P, ctx, n = args.pods, 256, 96
+    SMP = dict(topK=40, topP=0.95, temp=0.8, repeatPenalty=1.1, seed=1234)
+    prompts = [[PROMPT[0]] + [(t + 17 * i) % 32000 for t in PROMPT[1:]] for i in range(P)]
+    past = [len(p) for p in prompts]
+    for int8 in ([False, True] if args.int8 else [False]):
+        m = model(ctx, int8)
+        b = Batch(m, ctx, P)
+
+        def head():   # what every leg starts with: a new job on every pod, its first id pending
+            b.SetSampler(ringSize=ctx, **SMP)
+            return b.FeedSample(prompts, [0] * P, [FEED_NEW] * P)
+        first = head()
+        run = b.Decode(first, past, n)
+        replay = [t for p, f, gi in zip(prompts, first, run) for t in list(p) + [f] + gi]
+        for K in ((args.draft_max,) if args.draft_max else (1, 3, 7)):
+            res = {}
+
+            def loop(corpus):
+                ids, _, st, _ = b.DecodeSampleLookup(head(), past, n, K, 3, 1, corpus)
+                res.update(rows=st[0]["rows"], passes=max(s["passes"] for s in st), accepted=sum(s["accepted"] for s in st), pod_passes=sum(s["passes"] for s in st),
+                           same_ids=ids == run)
+
+            def ticks():
+                b.Decode(head(), past, n)
+            ts = {"head": [], "replay": [], "ticks": [], "no_corpus": []}
+            legs = (("head", head), ("replay", lambda: loop(replay)), ("ticks", ticks), ("no_corpus", lambda: loop(None)))
+            for _, fn in legs:
+                fn()
+            shape = {}
+            for _ in range(args.reps):
+                for name, fn in legs:
+                    t0 = time.perf_counter(); fn(); ts[name].append((time.perf_counter() - t0) * 1e3)
+                    if name in ("replay", "no_corpus"):
+                        shape[name] = dict(res)
+            md = {k: sorted(v)[len(v) // 2] for k, v in ts.items()}
+            R = shape["replay"]["rows"]
+            if R == 1:
+                emit(dict(part="pods_sample", int8=int8, layers=args.layers, pods=P, draft_max=K, rows=1, note="no room for a second row: plain sampled ticks"))
+                continue
+            tick_ms = (md["ticks"] - md["head"]) / n
+            out = dict(part="pods_sample", int8=int8, layers=args.layers, pods=P, draft_max=K, rows=R, pass_rows=P * R, ids_per_pod=n, head_ms=round(md["head"], 3),
+                       tick_ms=round(tick_ms, 3), ticks_tok_s=round(P * n / (md["ticks"] - md["head"]) * 1e3, 1))
+            for name in ("replay", "no_corpus"):
+                ms = md[name] - md["head"]
+                out.update({f"{name}_passes": shape[name]["passes"], f"{name}_accepted_per_pod_pass": round(shape[name]["accepted"] / shape[name]["pod_passes"], 3),
+                            f"{name}_pass_ms": round(ms / shape[name]["passes"], 3), f"{name}_tok_s": round(P * n / ms * 1e3, 1),
+                            f"{name}_ids_equal_ticks": shape[name]["same_ids"]})
+            out["replay_is"] = "acceptance-1 ceiling (the corpus is the run itself), not a model result"
+            out["pass_over_tick"] = round(out["no_corpus_pass_ms"] / tick_ms, 3)
+            # the route wins when ids per pod and pass = 1 + mean accepted > pass time / tick time
+            out["break_even_accepted_per_pod_pass"] = round(out["no_corpus_pass_ms"] / tick_ms - 1, 3)
+            # the sampler launches alone, as host twins on random logits (their wall time includes the upload of P * R resp. P rows of 32000 floats)
+            rng = np.random.default_rng(K)
+            lg = (rng.standard_normal((P * R, 32000)) * 4).astype(np.float32)
+            rings, rpos, draws = np.zeros((P, ctx), np.uint32), [0] * P, list(range(P))
+            toks = rng.integers(0, 32000, (P, R)).astype(np.uint32)
+            lg_ticks = np.ascontiguousarray(lg[::R])
+            tw = {"pod_rows": [], "pods": []}
+            twins = (("pod_rows", lambda: sample_pod_rows(prod, lg, rings, rpos, draws, toks, [R - 1] * P, **SMP)),
+                     ("pods", lambda: SamplePods(prod, lg_ticks, rings, rpos, draws, **SMP)))
+            for _, fn in twins:
+                fn()
+            for _ in range(args.reps):
+                for name, fn in twins:
+                    t0 = time.perf_counter(); fn(); tw[name].append((time.perf_counter() - t0) * 1e3)
+            out["sampler_twin_pod_rows_ms"] = round(sorted(tw["pod_rows"])[len(tw["pod_rows"]) // 2], 3)
+            out["sampler_twin_pods_ms"] = round(sorted(tw["pods"])[len(tw["pods"]) // 2], 3)
+            out["sampler_twins_include"] = "the upload of their logits rows"
+            emit(out)
+        b.free()
+        m.free()
+    args.sample, args.pods = False, 0
 
 if args.sample:
     args.parts = []
