@@ -3,6 +3,7 @@
 #include "common.h"
 #include "kernels_common.h"
 #include "attn_worklist.h"
+#include "graph_cache.h"
 
 namespace lh {
 
@@ -44,7 +45,7 @@ struct Plan {
     ModelDesc md;
     // scratch, sized for n_cap rows
     uint32_t n_cap = 0;
-    uint64_t scratch_gen = 0;                 // counts re-allocations of the scratch below (graphs captured elsewhere - lh_batch - compare it)
+    uint64_t scratch_gen = 0;                 // counts re-allocations of the scratch below (every captured graph that runs on this plan compares it)
     float *xa = nullptr, *xb = nullptr, *h = nullptr, *qraw = nullptr, *kraw = nullptr, *vraw = nullptr, *q = nullptr, *attn = nullptr;
     float *a1 = nullptr, *a3 = nullptr, *g = nullptr, *logits = nullptr;
     uint16_t* s3 = nullptr;                   // block-int8 plans: the activations of the int8 matmuls as three bf16 planes each (kernels_stream_q8b.h):
@@ -69,6 +70,7 @@ struct Plan {
     StepParams* sp_host = nullptr;   // pinned
     uint32_t* out_tokens_dev = nullptr;
     uint32_t out_cap = 0;
+    uint64_t out_gen = 0;            // counts re-allocations of out_tokens_dev (the slots that advance hold its address)
     uint32_t* argmax_dev = nullptr;
     // captured decode graphs: one Eval(N=1) (embed .. logits); the same + argmax + advance (resident greedy loop) as 1 step and as
     // GRAPH_MULTI consecutive steps per launch; the same + device sampler + advance (resident sampling loop), 1 and GRAPH_MULTI steps.
@@ -76,12 +78,12 @@ struct Plan {
     // with one launch per token) and shave the launch gap between tokens.
     enum { G_STEP = 0, G_ADV1, G_ADVN, G_SMP1, G_SMPN, G_COUNT };
     static constexpr uint32_t GRAPH_MULTI = 8;
-    hipGraph_t graph[G_COUNT] = {};
-    hipGraphExec_t exec[G_COUNT] = {};
+    CapturedGraph<DecodeKey> graphs[G_COUNT];
     struct SampleState* ss_dev = nullptr;     // sampler parameters + counters (read by the captured sampler kernel)
     uint32_t* ring_dev = nullptr;             // lastNTokens ring
     uint32_t ring_cap = 0;
     uint32_t smp_topk = 0;                    // topK the sampler launches (and the captured graph) were chosen for
+    uint64_t smp_gen = 0;                     // counts what the captured sampled steps hold and decode_sample changes: the kernel variant (topK <= 64 or not), the ring's address
     char* score_dev = nullptr;                // lh_llama_score: [score_cap] lh_row_score, then [score_cap] target ids
     uint32_t score_cap = 0;
     struct Spec* spec = nullptr;              // lookup-draft speculative decoding (lh_llama_verify, lh_llama_decode_lookup): device state + the captured pass

@@ -96,21 +96,25 @@ static int set_lds_once(lh_ctx* ctx, KernT kern, size_t lds, bool* flags) {
 // Callers fall back ONLY on ST_NA; every other non-zero value is a real failure and is returned as it is.
 static constexpr int ST_NA = 1;
 
-// Grow-only device scratch of floats: waits for the stream (the old buffer may be in use), frees, allocates.  gen, where given, counts the re-allocations:
-// a captured graph that holds the old address compares it and is captured anew.  Where a launch can be part of a stream capture the call stands in
-// front of its prepare-only return, so that the prepare pass before the capture has sized the buffer (hipMalloc is not allowed under a capture).
-static int grow_floats(lh_ctx* ctx, float** buf, uint64_t* cap, uint64_t need, uint64_t* gen = nullptr) {
+// Grow-only device buffer of *cap elements of elem_bytes each (at least floor of them once it exists): waits for the stream (the old buffer may be in
+// use), frees, allocates.  gen, where given, counts the re-allocations: a captured graph that holds the old address has it in its key and is captured
+// anew (graph_cache.h).  Where a launch can be part of a stream capture the call stands in front of its prepare-only return, so that the prepare pass
+// before the capture has sized the buffer (hipMalloc is not allowed under a capture).
+template <typename T, typename Cap>
+static int grow(lh_ctx* ctx, T** buf, Cap* cap, uint64_t need, size_t elem_bytes = sizeof(T), uint64_t floor = 0, uint64_t* gen = nullptr) {
     if (need <= *cap) return 0;
+    need = std::max(need, floor);
     LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (*buf) LH_HIP(ctx, hipFree(*buf));
     *buf = nullptr; *cap = 0;
     if (gen) ++*gen;
-    LH_HIP(ctx, hipMalloc((void**)buf, need * 4));
-    *cap = need;
+    LH_HIP(ctx, hipMalloc((void**)buf, need * elem_bytes));
+    *cap = (Cap)need;
     return 0;
 }
-// the context's split-K partial products (lh_ctx::splitk; lh_batch and the verify pass compare splitk_gen)
-static int ensure_splitk(lh_ctx* ctx, uint64_t need_floats) { return grow_floats(ctx, &ctx->splitk, &ctx->splitk_floats, need_floats, &ctx->splitk_gen); }
+static int grow_floats(lh_ctx* ctx, float** buf, uint64_t* cap, uint64_t need) { return grow(ctx, buf, cap, need); }
+// the context's split-K partial products (lh_ctx::splitk; every graph whose launches may read them has splitk_gen in its key)
+static int ensure_splitk(lh_ctx* ctx, uint64_t need_floats) { return grow(ctx, &ctx->splitk, &ctx->splitk_floats, need_floats, 4, 0, &ctx->splitk_gen); }
 
 template <int KI, int U, int PRO, int EPI, int MAP, int THR = TH>
 static int launch_gemv(lh_ctx* ctx, const GemvArgs& a, const char* name, uint64_t bytes) {
@@ -1286,15 +1290,6 @@ static int launch_attention_rows(Plan* p, const AttnArgs& a, const BatchCtx* bc)
 }
 
 // ---------------------------------------------------------------------------------------------------
-static void drop_graphs(Plan* p, uint32_t mask) {
-    for (int i = 0; i < Plan::G_COUNT; ++i) {
-        if (!(mask & (1u << i))) continue;
-        if (p->exec[i]) { hipGraphExecDestroy(p->exec[i]); p->exec[i] = nullptr; }
-        if (p->graph[i]) { hipGraphDestroy(p->graph[i]); p->graph[i] = nullptr; }
-    }
-}
-static constexpr uint32_t GM_ADV = (1u << Plan::G_ADV1) | (1u << Plan::G_ADVN), GM_SMP = (1u << Plan::G_SMP1) | (1u << Plan::G_SMPN);
-
 static void spec_free(Plan* p);
 int plan_ensure_rows(Plan* p, uint32_t n) {
     if (n <= p->n_cap) return 0;
@@ -1323,8 +1318,6 @@ int plan_ensure_rows(Plan* p, uint32_t n) {
     LH_HIP(ctx, hipMalloc((void**)&p->tokens_dev, (size_t)n * 4));
     p->n_cap = n;
     p->scratch_gen++;
-    // captured graphs hold the old scratch addresses
-    drop_graphs(p, ~0u);
     return 0;
 }
 
@@ -1360,7 +1353,7 @@ void plan_destroy(Plan* p) {
     if (!p) return;
     hipSetDevice(p->ctx->device);
     hipStreamSynchronize(p->ctx->stream);
-    drop_graphs(p, ~0u);
+    for (auto& g : p->graphs) g.drop();
     if (p->ss_dev) hipFree(p->ss_dev);
     if (p->ring_dev) hipFree(p->ring_dev);
     float* bufs[] = {p->xa, p->xb, p->h, p->qraw, p->kraw, p->vraw, p->q, p->attn, p->a1, p->a3, p->g, p->logits, p->scores, p->vt, p->part, p->fa_part, p->emb};
@@ -1476,41 +1469,26 @@ static int enqueue_decode(Plan* p, const StepParams* sp, const float* x_in, floa
     return 0;
 }
 
-static int ensure_out_tokens(Plan* p, uint32_t n) {
-    if (n <= p->out_cap) return 0;
-    lh_ctx* ctx = p->ctx;
-    LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (p->out_tokens_dev) LH_HIP(ctx, hipFree(p->out_tokens_dev));
-    p->out_tokens_dev = nullptr;
-    const uint32_t cap = std::max(n, 4096u);
-    LH_HIP(ctx, hipMalloc((void**)&p->out_tokens_dev, (size_t)cap * 4));
-    p->out_cap = cap;
-    // graphs captured the old pointer
-    drop_graphs(p, GM_ADV | GM_SMP);
-    return 0;
-}
+static int ensure_out_tokens(Plan* p, uint32_t n) { return grow(p->ctx, &p->out_tokens_dev, &p->out_cap, n, 4, 4096, &p->out_gen); }
 
-// slot: Plan::G_*; the multi-step slots capture GRAPH_MULTI consecutive steps (the step parameters advance in device memory)
+// slot: Plan::G_*; the multi-step slots capture GRAPH_MULTI consecutive steps (the step parameters advance in device memory).  The slots never run
+// eagerly: a prepare-only pass in front of the capture sets the kernel attributes and sizes the buffers.
 static int ensure_decode_graph(Plan* p, int slot) {
-    lh_ctx* ctx = p->ctx;
-    if (p->exec[slot]) return 0;
     const int adv = slot == Plan::G_STEP ? 0 : (slot == Plan::G_ADV1 || slot == Plan::G_ADVN) ? 1 : 2;
     const uint32_t reps = (slot == Plan::G_ADVN || slot == Plan::G_SMPN) ? Plan::GRAPH_MULTI : 1;
-    if (adv) { int rc = ensure_out_tokens(p, 1); if (rc) return rc; }
+    int rc;
+    if (adv && (rc = ensure_out_tokens(p, 1))) return rc;
+    const DecodeKey key = {p->scratch_gen, adv ? p->out_gen : 0, adv == 2 ? p->smp_gen : 0};
+    if (p->graphs[slot].current(key)) return 0;
     g_prepare_only = true;
-    int rc = enqueue_decode(p, p->sp_dev, nullptr, nullptr, adv, nullptr);
+    rc = enqueue_decode(p, p->sp_dev, nullptr, nullptr, adv, nullptr);
     g_prepare_only = false;
     if (rc) return rc;
-    // Relaxed: other pods' threads keep allocating / copying while this one captures (server.go:88-101 runs pods concurrently).  The
-    // captured stream is non-blocking and nothing inside the capture touches the legacy stream; in the stricter modes a
-    // synchronous hipMemcpy of ANOTHER thread invalidated this capture (tests/test_gpu_llama.py::test_concurrent_pods_share_one_model).
-    LH_HIP(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeRelaxed));
-    for (uint32_t r = 0; r < reps && !rc; ++r) rc = enqueue_decode(p, p->sp_dev, nullptr, nullptr, adv, nullptr);
-    hipError_t e = hipStreamEndCapture(ctx->stream, &p->graph[slot]);
-    if (rc) return rc;
-    if (e != hipSuccess) LH_FAIL(ctx, LH_EHIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-    LH_HIP(ctx, hipGraphInstantiate(&p->exec[slot], p->graph[slot], nullptr, nullptr, 0));
-    return 0;
+    return p->graphs[slot].capture(p->ctx, key, "", [&] {
+        int r = 0;
+        for (uint32_t i = 0; i < reps && !r; ++i) r = enqueue_decode(p, p->sp_dev, nullptr, nullptr, adv, nullptr);
+        return r;
+    });
 }
 // n_steps resident steps as graph launches: as many GRAPH_MULTI-step launches as fit, single steps for the rest
 static int launch_resident_steps(Plan* p, uint32_t n_steps, int slot1, int slotn) {
@@ -1521,11 +1499,11 @@ static int launch_resident_steps(Plan* p, uint32_t n_steps, int slot1, int slotn
     // capture + instantiation of the multi-step graph too, not the first long run after it
     if ((rc = ensure_decode_graph(p, slotn))) return rc;
     if (n_steps >= Plan::GRAPH_MULTI) {
-        for (; s + Plan::GRAPH_MULTI <= n_steps; s += Plan::GRAPH_MULTI) LH_HIP(ctx, hipGraphLaunch(p->exec[slotn], ctx->stream));
+        for (; s + Plan::GRAPH_MULTI <= n_steps; s += Plan::GRAPH_MULTI) if ((rc = p->graphs[slotn].launch(ctx))) return rc;
     }
     if (s < n_steps) {
         if ((rc = ensure_decode_graph(p, slot1))) return rc;
-        for (; s < n_steps; ++s) LH_HIP(ctx, hipGraphLaunch(p->exec[slot1], ctx->stream));
+        for (; s < n_steps; ++s) if ((rc = p->graphs[slot1].launch(ctx))) return rc;
     }
     return 0;
 }
@@ -1541,13 +1519,7 @@ int plan_embeddings(Plan* p, uint32_t n, float** out) {
     lh_ctx* ctx = p->ctx;
     const ModelDesc& m = p->md;
     if (!m.last_stage() || n == 0 || n > p->n_cap) LH_FAIL(ctx, LH_EINVAL, "embeddings: the last Eval of this plan had no %u final rows", n);
-    if (n > p->emb_cap) {
-        LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (p->emb) LH_HIP(ctx, hipFree(p->emb));
-        p->emb = nullptr; p->emb_cap = 0;
-        LH_HIP(ctx, hipMalloc((void**)&p->emb, (size_t)n * m.d * 4));
-        p->emb_cap = n;
-    }
+    if (const int rc = grow(ctx, &p->emb, &p->emb_cap, n, (size_t)m.d * 4)) return rc;
     // every route of plan_eval leaves the residual rows behind the last layer in p->xa; RMSNorm (ml.go:1753-1812) then Mul by the norm weight
     // (ml.go:1877-1914): k_rmsnorm_rows' arithmetic (fp32 squares, f64 sum, one fp32 scale, two roundings per element)
     LH_LAUNCH(k_rmsnorm_rows, dim3(n), dim3(256), 0, ctx->stream, (const float*)p->xa, m.norm, p->emb, m.d);
@@ -1635,8 +1607,7 @@ int plan_decode_step(Plan* p, uint32_t token, uint32_t past) {
     if (p->use_graph) {
         if ((rc = ensure_decode_graph(p, Plan::G_STEP))) return rc;
         if ((rc = upload_step_params(p, 0, token, past, 0))) return rc;
-        LH_HIP(ctx, hipGraphLaunch(p->exec[Plan::G_STEP], ctx->stream));
-        return 0;
+        return p->graphs[Plan::G_STEP].launch(ctx);
     }
     if ((rc = upload_step_params(p, 0, token, past, 0))) return rc;
     return enqueue_decode(p, p->sp_dev, nullptr, nullptr, false, nullptr);
@@ -2241,16 +2212,17 @@ struct Batch {
     uint32_t ring_cap = 0, smp_topk = 0;
     uint32_t ring_size = 0;        // of the last lh_batch_set_sampler (lh_batch_sampler_ring_size)
     bool sampling = false;
-    // the captured tick
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    const float* cap_x_in = nullptr;
-    float* cap_x_out = nullptr;
-    uint64_t cap_splitk_gen = 0, cap_scratch_gen = 0;
+    uint64_t smp_gen = 0;          // counts what the captured tick holds and lh_batch_set_sampler changes: the ring's address, the kernel variant (topK <= 64 or not)
+    // the captured tick (warm bit 0) and everything it holds by value
+    struct TickKey {
+        const float* x_in;
+        float* x_out;
+        uint64_t splitk_gen, scratch_gen, smp_gen;
+        uint32_t sampling, per_pod, shared, share_qb;   // (share_qb: 0 unless shared)
+    };
+    CapturedGraph<TickKey> tick;
     uint64_t scratch_gen() const { uint64_t g = 0; for (const Plan* p : pods) g += p->scratch_gen; return g; }   // grows when any pod's scratch moved
-    bool cap_sampling = false;
-    bool per_pod = false, cap_per_pod = false;   // LLAMAHIP_SAMPLE_PER_POD=1: one sampler launch per row (read where the tick is captured)
-    bool warm = false;
+    bool per_pod = false;          // LLAMAHIP_SAMPLE_PER_POD=1: one sampler launch per row (read where the tick is enqueued)
     // host mirror of the rows' positions (rows_dev[i].pos): the tick kernels advance them in device memory with no bound of their own, so
     // the window check of every other Eval entry point (plan_eval: past + n <= ctx) is made here before a tick is enqueued
     std::vector<uint32_t> pos;
@@ -2277,8 +2249,8 @@ struct Batch {
     ShareTable* share_dev = nullptr;
     ShareTable share_sent;         // (set to "no block" where share_dev is allocated)
     uint32_t share_sent_blocks = 0;
-    bool shared = false, cap_shared = false;   // the tick takes k_attention_split_shared (some block in the table, LLAMAHIP_SHARE_ROW_ATTN unset)
-    uint32_t share_qb = 0, cap_share_qb = 0;
+    bool shared = false;           // the tick takes k_attention_split_shared (some block in the table, LLAMAHIP_SHARE_ROW_ATTN unset)
+    uint32_t share_qb = 0;
     float* logits() const { return batched || B == 1 ? pods[0]->logits : logits_own; }
 };
 
@@ -2311,11 +2283,6 @@ static void share_info(Batch* b, uint32_t* group, uint32_t* len) {
         if (b->sh_gid[i] != Batch::SH_NONE) for (uint32_t j = 0; j < i; ++j) if (b->sh_gid[j] == b->sh_gid[i]) { lo = j; break; }
         group[i] = lo; len[i] = b->sh_len[i];
     }
-}
-
-static void batch_drop_graph(Batch* b) {
-    if (b->exec) { hipGraphExecDestroy(b->exec); b->exec = nullptr; }
-    if (b->graph) { hipGraphDestroy(b->graph); b->graph = nullptr; }
 }
 
 // the kernels of one tick, in stream order
@@ -2391,25 +2358,8 @@ static int batch_tick_unchecked(Batch* b, const float* x_in, float* x_out) {
     const char* pp = getenv("LLAMAHIP_SAMPLE_PER_POD");
     b->per_pod = pp && pp[0] == '1';
     if ((rc = share_prepare(b))) return rc;   // the block table of the pods that share a prefix, re-sent when it changed (outside the captured graph)
-    if (!p0->use_graph || !b->warm) {
-        b->warm = true;
-        return batch_enqueue_tick(b, x_in, x_out);
-    }
-    if (b->exec && (b->cap_x_in != x_in || b->cap_x_out != x_out || b->cap_splitk_gen != ctx->splitk_gen || b->cap_scratch_gen != b->scratch_gen() || b->cap_sampling != b->sampling ||
-                    b->cap_per_pod != b->per_pod || b->cap_shared != b->shared || (b->shared && b->cap_share_qb != b->share_qb)))
-        batch_drop_graph(b);
-    if (!b->exec) {
-        LH_HIP(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeRelaxed));
-        rc = batch_enqueue_tick(b, x_in, x_out);
-        hipError_t e = hipStreamEndCapture(ctx->stream, &b->graph);
-        if (rc) { if (b->graph) { hipGraphDestroy(b->graph); b->graph = nullptr; } return rc; }
-        if (e != hipSuccess) LH_FAIL(ctx, LH_EHIP, "hipStreamEndCapture (batch tick): %s", hipGetErrorString(e));
-        LH_HIP(ctx, hipGraphInstantiate(&b->exec, b->graph, nullptr, nullptr, 0));
-        b->cap_x_in = x_in; b->cap_x_out = x_out; b->cap_splitk_gen = ctx->splitk_gen; b->cap_scratch_gen = b->scratch_gen(); b->cap_sampling = b->sampling;
-        b->cap_per_pod = b->per_pod; b->cap_shared = b->shared; b->cap_share_qb = b->share_qb;
-    }
-    LH_HIP(ctx, hipGraphLaunch(b->exec, ctx->stream));
-    return 0;
+    const Batch::TickKey key = {x_in, x_out, ctx->splitk_gen, b->scratch_gen(), b->smp_gen, b->sampling, b->per_pod, b->shared, b->shared ? b->share_qb : 0};
+    return b->tick.run(ctx, p0->use_graph, 0, key, " (batch tick)", [&] { return batch_enqueue_tick(b, x_in, x_out); });
 }
 
 static void batch_spec_free(Batch* b);
@@ -2417,7 +2367,7 @@ static void batch_free(Batch* b) {
     if (!b) return;
     hipSetDevice(b->ctx->device);
     hipStreamSynchronize(b->ctx->stream);
-    batch_drop_graph(b);
+    b->tick.drop();
     batch_spec_free(b);
     void* bufs[] = {b->rows_dev, b->tok_dev, b->ids_dev, b->out_dev, b->sp_dev, b->logits_own, b->attn_part, b->ss_dev, b->ring_dev, b->feed_dev, b->feed_part, b->share_dev};
     for (void* q : bufs) if (q) hipFree(q);
@@ -2514,7 +2464,7 @@ static uint32_t env_u32(const char* name, uint32_t dflt) {
 // ---- prefix sharing: the tick's block table ---------------------------------------------------------------------------------------------------------
 // Before a tick is enqueued the batch derives the table from the pods' group state (share_schedule.h: a pure function, B <= 64 rows), compares it with
 // the table last sent and re-sends it on change (k_share_set, the table as kernel arguments, in stream order in front of the tick: the captured graph
-// reads it from a fixed address, so a changed table needs no new capture).  Only "no block" <-> "some block" changes the tick's launches (cap_shared).
+// reads it from a fixed address, so a changed table needs no new capture).  Only "no block" <-> "some block" changes the tick's launches (TickKey::shared).
 // Switches, read per tick: LLAMAHIP_SHARE_ROW_ATTN=1 (the per-row kernels: the A/B switch and the tests' reference), LLAMAHIP_SHARE_QB, LLAMAHIP_SHARE_MIN.
 static constexpr uint32_t SHARE_QB = 4;    // rows per block (LLAMAHIP_SHARE_QB: 2, 4, 8).  Measured (profiles/shared_prefix.txt, 7B fp32, ctx 2048): 4 beats 8 in every case - 64 pods
                                            // behind 1920 shared keys 18.15 ms per tick at 4 (two workgroups per CU), 20.71 at 8 (one), 29.19 on the per-row kernels
@@ -2624,13 +2574,7 @@ static int batch_feed(Batch* b, const uint32_t* const* tokens, const uint32_t* n
     if (pass_bytes && (rc = plan_ensure_rows(p0, FEED_PASS_ROWS))) return rc;   // (the captured tick re-captures on scratch_gen)
     if (bytes) {
         if ((rc = ensure_staging(ctx, bytes))) return rc;
-        if (bytes > b->feed_cap) {
-            LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (b->feed_dev) LH_HIP(ctx, hipFree(b->feed_dev));
-            b->feed_dev = nullptr; b->feed_cap = 0;
-            LH_HIP(ctx, hipMalloc((void**)&b->feed_dev, bytes));
-            b->feed_cap = bytes;
-        }
+        if ((rc = grow(ctx, &b->feed_dev, &b->feed_cap, bytes))) return rc;
         if (pass_bytes && p0->attn_part && !b->feed_part)
             LH_HIP(ctx, hipMalloc((void**)&b->feed_part, 4 * (size_t)FEED_PASS_ROWS * m.H * ((m.ctx + ATT_TC - 1) / ATT_TC) * (m.hd + 2)));
     }
@@ -2778,26 +2722,22 @@ struct Spec {
     uint32_t trace_cap = 0;
     float* part = nullptr;             // split-T attention partials for SPEC_ROWS_MAX rows (plans with ctx > 256)
     bool smp = false;                  // the passes sample (set by the entry points before they enqueue a pass)
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    // what the captured pass holds by value
-    uint32_t cap_R = 0, cap_trace_cap = 0;
-    SpecLookup cap_lp = {};
-    uint32_t* cap_out = nullptr;
-    uint16_t* cap_trace = nullptr;
-    uint64_t cap_splitk_gen = 0, cap_scratch_gen = 0;
-    bool cap_smp = false, cap_smp_small = false;   // sampled route: the kernel variant (topK <= 64 or not) and the ring pointer
-    uint32_t* cap_ring = nullptr;
-    uint32_t warm = 0;                 // bit R: a pass of R rows has run eagerly (it sets kernel attributes a capture must not)
+    // the captured pass (warm bit R: a pass of R rows) and what it holds by value
+    struct Key {
+        uint32_t R, trace_cap;
+        SpecLookup lp;
+        uint32_t* out;
+        uint16_t* trace;
+        uint64_t splitk_gen, scratch_gen;
+        uint32_t smp, smp_small;       // sampled route: the kernel variant (topK <= 64 or not) and the ring pointer
+        uint32_t* ring;
+    };
+    CapturedGraph<Key> pass;
 };
-static void spec_drop_graph(Spec* s) {
-    if (s->exec) { hipGraphExecDestroy(s->exec); s->exec = nullptr; }
-    if (s->graph) { hipGraphDestroy(s->graph); s->graph = nullptr; }
-}
 static void spec_free(Plan* p) {
     Spec* s = p->spec;
     if (!s) return;
-    spec_drop_graph(s);
+    s->pass.drop();
     void* bufs[] = {s->st, s->sp, s->rows, s->tok, s->arg, s->win, s->corpus, s->trace, s->part};
     for (void* q : bufs) if (q) hipFree(q);
     delete s;
@@ -2818,22 +2758,9 @@ static int spec_ensure(Plan* p, uint32_t n_corpus, uint32_t n_trace) {
         LH_HIP(ctx, hipMalloc((void**)&s->win, 4 * ((size_t)m.ctx + 1)));
         if (p->attn_part) LH_HIP(ctx, hipMalloc((void**)&s->part, 4 * (size_t)SPEC_ROWS_MAX * m.H * ((m.ctx + ATT_TC - 1) / ATT_TC) * (m.hd + 2)));
     }
-    if (n_corpus > s->corpus_cap) {
-        LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (s->corpus) LH_HIP(ctx, hipFree(s->corpus));
-        s->corpus = nullptr; s->corpus_cap = 0;
-        LH_HIP(ctx, hipMalloc((void**)&s->corpus, 4 * (size_t)n_corpus));
-        s->corpus_cap = n_corpus;
-    }
-    if (n_trace > s->trace_cap) {
-        LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (s->trace) LH_HIP(ctx, hipFree(s->trace));
-        s->trace = nullptr; s->trace_cap = 0;
-        const uint32_t cap = std::max(n_trace, 4096u);
-        LH_HIP(ctx, hipMalloc((void**)&s->trace, 2 * (size_t)cap));
-        s->trace_cap = cap;
-    }
-    return 0;
+    int rc;
+    if ((rc = grow(ctx, &s->corpus, &s->corpus_cap, n_corpus))) return rc;
+    return grow(ctx, &s->trace, &s->trace_cap, n_trace, 2, 4096);
 }
 // the largest row count <= want a pass can take: 1 (the decode step) or a count of the bit-identical rows path
 static uint32_t spec_pass_rows(const Plan* p, uint32_t want) {
@@ -2870,29 +2797,8 @@ static int spec_enqueue_pass(Plan* p, uint32_t n, uint32_t n_table, const SpecLo
 static int spec_pass(Plan* p, uint32_t R, const SpecLookup& lp) {
     lh_ctx* ctx = p->ctx;
     Spec* s = p->spec;
-    if (!p->use_graph || !(s->warm & (1u << R))) {
-        s->warm |= 1u << R;
-        return spec_enqueue_pass(p, R, R, lp, 1);
-    }
-    const bool smp_small = s->smp && p->smp_topk <= 64;
-    uint32_t* const ring = s->smp ? p->ring_dev : nullptr;
-    if (s->exec && (s->cap_R != R || memcmp(&s->cap_lp, &lp, sizeof lp) || s->cap_out != spec_out(p) || s->cap_trace != s->trace || s->cap_trace_cap != s->trace_cap ||
-                    s->cap_splitk_gen != ctx->splitk_gen || s->cap_scratch_gen != p->scratch_gen || s->cap_smp != s->smp || s->cap_smp_small != smp_small ||
-                    s->cap_ring != ring))
-        spec_drop_graph(s);
-    if (!s->exec) {
-        LH_HIP(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeRelaxed));
-        const int rc = spec_enqueue_pass(p, R, R, lp, 1);
-        hipError_t e = hipStreamEndCapture(ctx->stream, &s->graph);
-        if (rc) { if (s->graph) { hipGraphDestroy(s->graph); s->graph = nullptr; } return rc; }
-        if (e != hipSuccess) LH_FAIL(ctx, LH_EHIP, "hipStreamEndCapture (speculative pass): %s", hipGetErrorString(e));
-        LH_HIP(ctx, hipGraphInstantiate(&s->exec, s->graph, nullptr, nullptr, 0));
-        s->cap_R = R; s->cap_lp = lp; s->cap_out = spec_out(p); s->cap_trace = s->trace; s->cap_trace_cap = s->trace_cap;
-        s->cap_splitk_gen = ctx->splitk_gen; s->cap_scratch_gen = p->scratch_gen;
-        s->cap_smp = s->smp; s->cap_smp_small = smp_small; s->cap_ring = ring;
-    }
-    LH_HIP(ctx, hipGraphLaunch(s->exec, ctx->stream));
-    return 0;
+    const Spec::Key key = {R, s->trace_cap, lp, spec_out(p), s->trace, ctx->splitk_gen, p->scratch_gen, s->smp, s->smp && p->smp_topk <= 64, s->smp ? p->ring_dev : nullptr};
+    return s->pass.run(ctx, p->use_graph, R, key, " (speculative pass)", [&] { return spec_enqueue_pass(p, R, R, lp, 1); });
 }
 static int spec_set(Plan* p, uint32_t pos, uint32_t produced, uint32_t n_steps, const SpecToks& toks, uint32_t k, uint32_t n_rows, int reset) {
     lh_ctx* ctx = p->ctx;
@@ -3027,28 +2933,24 @@ struct BatchSpec {
     uint32_t corpus_cap = 0;
     uint16_t* trace = nullptr;         // [B][trace_cap]
     uint32_t trace_cap = 0;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    // what the captured pass holds by value
-    uint32_t cap_R = 0, cap_trace_cap = 0;
-    SpecLookup cap_lp = {};
-    uint16_t* cap_trace = nullptr;
-    uint64_t cap_splitk_gen = 0, cap_scratch_gen = 0;
     bool smp = false;                  // the running loop samples (lh_batch_decode_sample_lookup)
-    bool cap_smp = false, cap_small_k = false;   // the captured pass holds the sampler variant, the ring pointer and the state pointer
-    SampleState* cap_ss = nullptr;
-    uint32_t* cap_ring = nullptr;
-    uint32_t cap_ring_cap = 0;
-    uint64_t warm = 0;                 // bit n - 1: a pass of n rows has run eagerly
+    // the captured pass (warm bit n - 1: a pass of n rows) and what it holds by value
+    struct Key {
+        uint32_t R, trace_cap;
+        SpecLookup lp;
+        uint16_t* trace;
+        uint64_t splitk_gen, scratch_gen;
+        uint32_t smp, small_k;         // a sampled pass also holds the sampler variant, the state pointer, the ring pointer and its stride (zeros in a greedy one)
+        SampleState* ss;
+        uint32_t* ring;
+        uint64_t ring_cap;
+    };
+    CapturedGraph<Key> pass;
 };
-static void batch_spec_drop_graph(BatchSpec* s) {
-    if (s->exec) { hipGraphExecDestroy(s->exec); s->exec = nullptr; }
-    if (s->graph) { hipGraphDestroy(s->graph); s->graph = nullptr; }
-}
 static void batch_spec_free(Batch* b) {
     BatchSpec* s = b->spec;
     if (!s) return;
-    batch_spec_drop_graph(s);
+    s->pass.drop();
     void* bufs[] = {s->st, s->sum, s->rows, s->tok, s->arg, s->win, s->last, s->part, s->corpus, s->trace};
     for (void* q : bufs) if (q) hipFree(q);
     delete s;
@@ -3072,22 +2974,9 @@ static int batch_spec_ensure(Batch* b, uint32_t n_corpus, uint32_t n_trace) {
         LH_HIP(ctx, hipMalloc((void**)&s->last, 4 * (size_t)B * m.V));
         if (p0->attn_part) LH_HIP(ctx, hipMalloc((void**)&s->part, 4 * (size_t)BATCH_ROWS_MAX * m.H * ((m.ctx + ATT_TC - 1) / ATT_TC) * (m.hd + 2)));
     }
-    if (n_corpus > s->corpus_cap) {
-        LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (s->corpus) LH_HIP(ctx, hipFree(s->corpus));
-        s->corpus = nullptr; s->corpus_cap = 0;
-        LH_HIP(ctx, hipMalloc((void**)&s->corpus, 4 * (size_t)n_corpus));
-        s->corpus_cap = n_corpus;
-    }
-    if (n_trace > s->trace_cap) {
-        LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (s->trace) LH_HIP(ctx, hipFree(s->trace));
-        s->trace = nullptr; s->trace_cap = 0;
-        const uint32_t cap = std::max(n_trace, 256u);
-        LH_HIP(ctx, hipMalloc((void**)&s->trace, 2 * (size_t)B * cap));
-        s->trace_cap = cap;
-    }
-    return 0;
+    int rc;
+    if ((rc = grow(ctx, &s->corpus, &s->corpus_cap, n_corpus))) return rc;
+    return grow(ctx, &s->trace, &s->trace_cap, n_trace, 2 * (size_t)B, 256);   // (an element = one pass of every pod)
 }
 // rows per pod and pass: draft_max + 1, lowered to the largest R whose P * R rows share one weight pass on this plan; 1 = plain ticks.
 // (A batch of one pod is never `batched` - one row needs no table - but its R rows are a batched Eval like any other.)
@@ -3131,27 +3020,9 @@ static int batch_spec_enqueue_pass(Batch* b, uint32_t R, const SpecLookup& lp) {
 static int batch_spec_pass(Batch* b, uint32_t R, const SpecLookup& lp) {
     lh_ctx* ctx = b->ctx;
     BatchSpec* s = b->spec;
-    const uint64_t bit = 1ull << (b->B * R - 1);
-    if (!b->pods[0]->use_graph || !(s->warm & bit)) {
-        s->warm |= bit;
-        return batch_spec_enqueue_pass(b, R, lp);
-    }
-    if (s->exec && (s->cap_R != R || memcmp(&s->cap_lp, &lp, sizeof lp) || s->cap_trace != s->trace || s->cap_trace_cap != s->trace_cap || s->cap_splitk_gen != ctx->splitk_gen ||
-                    s->cap_scratch_gen != b->scratch_gen() || s->cap_smp != s->smp ||
-                    (s->smp && (s->cap_small_k != (b->smp_topk <= 64) || s->cap_ss != b->ss_dev || s->cap_ring != b->ring_dev || s->cap_ring_cap != b->ring_cap))))
-        batch_spec_drop_graph(s);
-    if (!s->exec) {
-        LH_HIP(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeRelaxed));
-        const int rc = batch_spec_enqueue_pass(b, R, lp);
-        hipError_t e = hipStreamEndCapture(ctx->stream, &s->graph);
-        if (rc) { if (s->graph) { hipGraphDestroy(s->graph); s->graph = nullptr; } return rc; }
-        if (e != hipSuccess) LH_FAIL(ctx, LH_EHIP, "hipStreamEndCapture (batch speculative pass): %s", hipGetErrorString(e));
-        LH_HIP(ctx, hipGraphInstantiate(&s->exec, s->graph, nullptr, nullptr, 0));
-        s->cap_R = R; s->cap_lp = lp; s->cap_trace = s->trace; s->cap_trace_cap = s->trace_cap; s->cap_splitk_gen = ctx->splitk_gen; s->cap_scratch_gen = b->scratch_gen();
-        s->cap_smp = s->smp; s->cap_small_k = b->smp_topk <= 64; s->cap_ss = b->ss_dev; s->cap_ring = b->ring_dev; s->cap_ring_cap = b->ring_cap;
-    }
-    LH_HIP(ctx, hipGraphLaunch(s->exec, ctx->stream));
-    return 0;
+    BatchSpec::Key key = {R, s->trace_cap, lp, s->trace, ctx->splitk_gen, b->scratch_gen(), s->smp, 0, nullptr, nullptr, 0};
+    if (s->smp) { key.small_k = b->smp_topk <= 64; key.ss = b->ss_dev; key.ring = b->ring_dev; key.ring_cap = b->ring_cap; }
+    return s->pass.run(ctx, b->pods[0]->use_graph, b->B * R - 1, key, " (batch speculative pass)", [&] { return batch_spec_enqueue_pass(b, R, lp); });
 }
 
 // The loop behind lh_batch_decode_lookup and (smp) lh_batch_decode_sample_lookup; the caller has checked every argument and R >= 2.
@@ -3524,17 +3395,9 @@ static int decode_sample(lh_llama* m, const char* who, const uint32_t* prompt, u
     if ((rc = sample_check(ctx, sp, md.V))) return rc;
     if ((rc = ensure_out_tokens(p, n_predict))) return rc;
     if (!p->ss_dev) LH_HIP(ctx, hipMalloc((void**)&p->ss_dev, sizeof(SampleState)));
-    if ((sp->top_k <= 64) != (p->smp_topk <= 64)) drop_graphs(p, GM_SMP);  // the captured graphs hold the kernel variant
+    if ((sp->top_k <= 64) != (p->smp_topk <= 64)) p->smp_gen++;  // the captured sampled steps hold the kernel variant
     p->smp_topk = sp->top_k;
-    if (ring_size > p->ring_cap) {  // the captured sampler holds the ring pointer
-        LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (p->ring_dev) LH_HIP(ctx, hipFree(p->ring_dev));
-        p->ring_dev = nullptr;
-        p->ring_cap = 0;
-        LH_HIP(ctx, hipMalloc((void**)&p->ring_dev, (size_t)ring_size * 4));
-        p->ring_cap = ring_size;
-        drop_graphs(p, GM_SMP);
-    }
+    if ((rc = grow(ctx, &p->ring_dev, &p->ring_cap, ring_size, 4, 0, &p->smp_gen))) return rc;  // ... and the ring pointer
     // ring: ring_size zeros, then the prompt ids (appendToken, server.go:129-138, 193-197): what remains is the last ring_size of them
     {
         std::vector<uint32_t> ring(ring_size, 0u);
@@ -3736,14 +3599,8 @@ int lh_batch_set_sampler(lh_batch* h, const lh_sample_params* sp, uint32_t ring_
     if (ring_size == 0) LH_FAIL(ctx, LH_EINVAL, "lh_batch_set_sampler: the lastNTokens ring needs at least one slot (the reference uses CtxSize, server.go:127)");
     LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (!b->ss_dev) LH_HIP(ctx, hipMalloc((void**)&b->ss_dev, sizeof(SampleState) * b->B));
-    if (ring_size > b->ring_cap) {
-        if (b->ring_dev) LH_HIP(ctx, hipFree(b->ring_dev));
-        b->ring_dev = nullptr; b->ring_cap = 0;
-        LH_HIP(ctx, hipMalloc((void**)&b->ring_dev, (size_t)b->B * ring_size * 4));
-        b->ring_cap = ring_size;
-        batch_drop_graph(b);
-    }
-    if ((sp->top_k <= 64) != (b->smp_topk <= 64)) batch_drop_graph(b);   // the captured tick holds the kernel variant
+    if ((rc = grow(ctx, &b->ring_dev, &b->ring_cap, ring_size, (size_t)b->B * 4, 0, &b->smp_gen))) return rc;   // (an element = one slot of every pod's ring)
+    if ((sp->top_k <= 64) != (b->smp_topk <= 64)) b->smp_gen++;   // the captured tick holds the kernel variant
     b->smp_topk = sp->top_k;
     b->ring_size = ring_size;
     // ring: ring_size zeros, then the ids seen so far (appendToken, server.go:129-138, 193-197)

@@ -1,7 +1,7 @@
 """The trigger table and the scripts of the session tests (tests/session_ref.py runs them; no GPU needed to import).
 
 TRIGGERS lists every place in csrc/plan.hip, score.hip, abi.hip and comm.hip that re-allocates something or drops / re-keys a captured graph (found by
-reading every `hipFree(`, `drop_graphs`, `*_drop_graph` and `cap_*` of those files).  Each row says what a captured graph must do behind it:
+reading every call of the grow helper `grow(`, every `hipFree(`, every generation counter `*_gen` and every key struct of a CapturedGraph in those files).  Each row says what a captured graph must do behind it:
   recapture   the graph holds what moved: the next graph-run step must record launches again (CAPTURE), the one after it none (REPLAY)
   keep        nothing a graph holds moved: the next graph-run step must still REPLAY
 and names the scripts whose steps fire it (Step.fires; "name>Call" where the graph that must notice belongs to another call than the next one: a lookup
@@ -21,13 +21,13 @@ RECAPTURE, KEEP = "recapture", "keep"
 # name -> (where, what fires it, what a captured graph must do behind it, scripts that fire it or the reason none does)
 TRIGGERS = {
     "plan_ensure_rows": ("plan.hip plan_ensure_rows", "an Eval / Score / Verify / feed pass of more rows than the plan's scratch holds: every scratch buffer, the "
-                         "s3 planes and tokens_dev move, scratch_gen grows, drop_graphs(~0)", RECAPTURE,
+                         "s3 planes and tokens_dev move, scratch_gen grows (in every key: DecodeKey, TickKey, Spec::Key, BatchSpec::Key)", RECAPTURE,
                          ("solo.growing_prompts", "solo.resident_around_detours", "solo.speculation_interleaved", "batch.ticks_around_feeds", "batch.lookup_among_ticks")),
-    "ensure_out_tokens": ("plan.hip ensure_out_tokens", "a resident run of more than 4096 ids: out_tokens_dev moves, only GM_ADV | GM_SMP are dropped", RECAPTURE,
+    "ensure_out_tokens": ("plan.hip ensure_out_tokens", "a resident run of more than 4096 ids: out_tokens_dev moves, out_gen grows (DecodeKey of the ADV and SMP slots only)", RECAPTURE,
                           ("solo.more_than_4096_ids",)),
-    "solo_sampler_variant": ("plan.hip decode_sample", "topK crosses 64: the captured sampled step holds the kernel variant, GM_SMP dropped", RECAPTURE,
+    "solo_sampler_variant": ("plan.hip decode_sample", "topK crosses 64: the captured sampled step holds the kernel variant, smp_gen grows (DecodeKey of the SMP slots)", RECAPTURE,
                              ("solo.sampler_reconfiguration",)),
-    "solo_ring_growth": ("plan.hip decode_sample", "a ring larger than ring_cap: ring_dev moves, GM_SMP dropped; the sampled verify pass compares cap_ring", RECAPTURE,
+    "solo_ring_growth": ("plan.hip decode_sample", "a ring larger than ring_cap: ring_dev moves, smp_gen grows (DecodeKey of the SMP slots); the sampled verify pass compares Spec::Key::ring", RECAPTURE,
                          ("solo.sampler_reconfiguration",)),
     "solo_ring_smaller": ("plan.hip decode_sample", "a ring smaller than ring_cap: ring_dev stays, the ring is re-initialised in place", KEEP,
                           ("solo.sampler_reconfiguration",)),
@@ -40,7 +40,7 @@ TRIGGERS = {
                     ("solo.resident_around_detours",)),
     "eval_cache": ("host/llamago.cpp llama_Eval (llamago_KeepDecodeGraph)", "the host mirror keeps the one-token ml graph between Evals and moves its position: an n-row "
                    "Eval between two one-token Evals must not leave the kept graph on the old scratch", RECAPTURE, ("solo.growing_prompts",)),
-    "ensure_splitk": ("plan.hip ensure_splitk (grow_floats)", "a split-K launch of more partial products than the context's buffer holds: splitk moves, splitk_gen "
+    "ensure_splitk": ("plan.hip ensure_splitk (grow)", "a split-K launch of more partial products than the context's buffer holds: splitk moves, splitk_gen "
                       "grows (the batch tick and both verify passes compare it; solo decode graphs hold no split-K buffer)", RECAPTURE,
                       ("solo.growing_prompts", "batch.ticks_around_feeds")),
     "ensure_xs3": ("plan.hip ensure_xs3", "block-int8, a prompt from 89 rows on: the context's bf16 planes move, splitk_gen grows", RECAPTURE,
@@ -52,37 +52,37 @@ TRIGGERS = {
                           "allocated for the plans that hold its address", KEEP, ("solo.longer_window_appears",)),
     "other_object_freed": ("plan.hip plan_destroy / batch_free", "another context or batch of the same model is created, used and freed: its buffers return to the "
                            "allocator while the long-lived object's graphs stay valid", KEEP, ("solo.longer_window_appears", "batch.batches_come_and_go")),
-    "spec_key_R": ("plan.hip spec_pass (cap_R, warm)", "lookup passes of another row count: the first one runs eagerly, the graph is re-captured", RECAPTURE,
+    "spec_key_R": ("plan.hip spec_pass (Spec::Key::R, warm bit R)", "lookup passes of another row count: the first one runs eagerly, the graph is re-captured", RECAPTURE,
                    ("solo.speculation_interleaved",)),
-    "spec_key_lookup": ("plan.hip spec_pass (cap_lp) / spec_ensure corpus", "another n-gram range or a corpus: the accept kernel holds them by value, the corpus buffer moves",
+    "spec_key_lookup": ("plan.hip spec_pass (Spec::Key::lp) / spec_ensure corpus", "another n-gram range or a corpus: the accept kernel holds them by value, the corpus buffer moves",
                         RECAPTURE, ("solo.speculation_interleaved",)),
-    "spec_key_sampled": ("plan.hip spec_pass (cap_smp, cap_smp_small, cap_ring, cap_out)", "greedy passes after sampled ones and back: other launches, other output offset",
+    "spec_key_sampled": ("plan.hip spec_pass (Spec::Key::smp, smp_small, ring, out)", "greedy passes after sampled ones and back: other launches, other output offset",
                          RECAPTURE, ("solo.speculation_interleaved",)),
-    "spec_trace_growth": ("plan.hip spec_ensure / batch_spec_ensure (trace)", "a lookup run of more passes than the trace buffer holds (4096): the buffer moves, cap_trace "
+    "spec_trace_growth": ("plan.hip spec_ensure / batch_spec_ensure (trace)", "a lookup run of more passes than the trace buffer holds (4096): the buffer moves, the keys' trace "
                           "differs", RECAPTURE, "not covered: needs a lookup run of more than 4096 ids per call, which no script's window allows in a few seconds"),
-    "batch_scratch_gen": ("plan.hip batch_tick_unchecked (cap_scratch_gen)", "a feed grows pod 0's scratch to FEED_PASS_ROWS, or a pod's own Eval (a feed of "
+    "batch_scratch_gen": ("plan.hip batch_tick_unchecked (TickKey::scratch_gen)", "a feed grows pod 0's scratch to FEED_PASS_ROWS, or a pod's own Eval (a feed of "
                           "LLAMAHIP_FEED_SOLO_MIN rows and more) grows that pod's: the sum of the pods' scratch_gen moves", RECAPTURE,
                           ("batch.ticks_around_feeds", "batch.lookup_among_ticks")),
     "feed_dev": ("plan.hip batch_feed (feed_dev, feed_part)", "a feed whose tables need more bytes than feed_dev holds; only the feed's own eager passes read it", KEEP,
                  ("batch.ticks_around_feeds",)),
-    "batch_sampling": ("plan.hip batch_tick_unchecked (cap_sampling)", "lh_batch_set_sampler on or off: the tick ends in another kernel", RECAPTURE,
+    "batch_sampling": ("plan.hip batch_tick_unchecked (TickKey::sampling)", "lh_batch_set_sampler on or off: the tick ends in another kernel", RECAPTURE,
                        ("batch.sampler_on_off_on", "batch.lookup_among_ticks")),
-    "batch_ring_growth": ("plan.hip lh_batch_set_sampler", "a ring larger than ring_cap: ring_dev moves, batch_drop_graph", RECAPTURE, ("batch.sampler_on_off_on",)),
-    "batch_sampler_variant": ("plan.hip lh_batch_set_sampler", "topK crosses 64: batch_drop_graph", RECAPTURE, ("batch.sampler_on_off_on",)),
+    "batch_ring_growth": ("plan.hip lh_batch_set_sampler", "a ring larger than ring_cap: ring_dev moves, Batch::smp_gen grows (TickKey::smp_gen)", RECAPTURE, ("batch.sampler_on_off_on",)),
+    "batch_sampler_variant": ("plan.hip lh_batch_set_sampler", "topK crosses 64: Batch::smp_gen grows (TickKey::smp_gen)", RECAPTURE, ("batch.sampler_on_off_on",)),
     "batch_ring_smaller": ("plan.hip lh_batch_set_sampler", "a ring smaller than ring_cap, same variant: every ring re-initialised in place with the new size", KEEP,
                            ("batch.sampler_on_off_on",)),
-    "env_sample_per_pod": ("plan.hip batch_tick_unchecked (cap_per_pod)", "LLAMAHIP_SAMPLE_PER_POD changes between two ticks", RECAPTURE, ("batch.sampler_on_off_on",)),
-    "batch_shared": ("plan.hip batch_tick_unchecked (cap_shared)", "the block table goes from no block to some block (a fork) or back (LLAMAHIP_SHARE_ROW_ATTN)", RECAPTURE,
+    "env_sample_per_pod": ("plan.hip batch_tick_unchecked (TickKey::per_pod)", "LLAMAHIP_SAMPLE_PER_POD changes between two ticks", RECAPTURE, ("batch.sampler_on_off_on",)),
+    "batch_shared": ("plan.hip batch_tick_unchecked (TickKey::shared)", "the block table goes from no block to some block (a fork) or back (LLAMAHIP_SHARE_ROW_ATTN)", RECAPTURE,
                      ("batch.fork_and_unfork",)),
     "share_table": ("plan.hip share_prepare (share_sent)", "a member leaves its group or a group re-forms: the table is re-sent in front of the tick, the captured tick "
                     "reads it from a fixed address", KEEP, ("batch.fork_and_unfork",)),
-    "env_share_qb": ("plan.hip batch_tick_unchecked (cap_share_qb)", "LLAMAHIP_SHARE_QB changes between two shared ticks", RECAPTURE, ("batch.fork_and_unfork",)),
+    "env_share_qb": ("plan.hip batch_tick_unchecked (TickKey::share_qb)", "LLAMAHIP_SHARE_QB changes between two shared ticks", RECAPTURE, ("batch.fork_and_unfork",)),
     "env_feed_row_attn": ("plan.hip batch_feed", "LLAMAHIP_FEED_ROW_ATTN=1 for one feed: the per-row kernels, the same bytes; feeds are never captured", KEEP,
                           ("batch.ticks_around_feeds",)),
-    "batch_spec_key_R": ("plan.hip batch_spec_pass (cap_R, warm)", "lookup passes of another pods x R", RECAPTURE, ("batch.lookup_among_ticks",)),
-    "batch_spec_key_sampled": ("plan.hip batch_spec_pass (cap_smp, cap_small_k, cap_ss, cap_ring, cap_ring_cap)", "sampled passes after greedy ones and back", RECAPTURE,
+    "batch_spec_key_R": ("plan.hip batch_spec_pass (BatchSpec::Key::R, warm bit pods x R - 1)", "lookup passes of another pods x R", RECAPTURE, ("batch.lookup_among_ticks",)),
+    "batch_spec_key_sampled": ("plan.hip batch_spec_pass (BatchSpec::Key::smp, small_k, ss, ring, ring_cap)", "sampled passes after greedy ones and back", RECAPTURE,
                                ("batch.lookup_among_ticks",)),
-    "batch_x_in_out": ("plan.hip batch_tick_unchecked (cap_x_in, cap_x_out)", "a layer shard's tick gets another residual buffer", RECAPTURE,
+    "batch_x_in_out": ("plan.hip batch_tick_unchecked (TickKey::x_in, x_out)", "a layer shard's tick gets another residual buffer", RECAPTURE,
                        "not covered: needs ranks (only lh_pipeline_* hands a tick residual buffers)"),
     "pipeline_rows_cap": ("comm.hip lh_pipeline (rows_cap)", "the grouped re-allocation of a pipeline's row buffers", RECAPTURE, "not covered: needs ranks"),
     "arena": ("abi.hip ensure_arena", "the node path's tensor arena grows; the node path captures nothing", KEEP,
