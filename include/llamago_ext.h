@@ -58,6 +58,20 @@ int llamago_SetModelTensor(llama_model* m, const char* name, const float* data, 
  * (declared with the batch below). */
 int llamago_CacheRead(llama_context* c, int which, uint64_t off_floats, float* dst, uint64_t n);
 int llamago_CacheWrite(llama_context* c, int which, uint64_t off_floats, const float* src, uint64_t n);
+/* f16 weight matrices kept f16 in HBM (ML_TYPE_F16 = dtype 1 of llamahip.h; norm vectors and tok_embeddings stay f32).  Every Eval route of such a model
+ * produces the bytes an f32 model holding the same values produces: one row and 2..8 rows on f16 forms of the decode stream kernels, every other row
+ * count on the f32 kernels behind an exact widening pass.
+ * llamago_LoadModelKeepF16: llama_LoadModel, except that a file whose weight matrices (seven per layer + output) are ALL f16 keeps them as halves
+ *   (lh_tensor_register dtype 1, no f32 copy); any other file loads exactly as llama_LoadModel loads it.
+ * llamago_NarrowModelF16 / llamago_WidenModelF16 (llamago_QuantizeModelQ8's shape; for synthetic models and the tests' f32 twin): the matrices through
+ *   lh_buf_narrow_f16 (round to nearest even; *n_changed, optional, = elements whose value changed) / back through lh_buf_widen_f16 (exact), the old
+ *   copies released.  Refused (non-zero, ml_LastError) while contexts, batches or pipelines of the model are alive, and on a block-int8 model.
+ * llamago_ModelWeightType: 0 (f32) / 1 (f16) / 7 (block-int8).
+ * On an f16 model llamago_SetModelTensor (of a matrix), llamago_QuantizeModelQ8 and llama_SaveModel refuse with a message that says so. */
+llama_model* llamago_LoadModelKeepF16(const char* fileName, uint32_t ctxSize);
+int llamago_NarrowModelF16(llama_model* m, uint64_t* n_changed);
+int llamago_WidenModelF16(llama_model* m);
+int llamago_ModelWeightType(const llama_model* m);
 
 /* ---- [product] harness helper of the kept decode graph (no GPU needed) -------------------------------------------------- */
 /* The array llama_Eval hands to lh_graph_compute for N tokens (ids 1..N) at pastQuery, as numbers: per tensor 16 int64 = op, dtype, flags, ne[4],

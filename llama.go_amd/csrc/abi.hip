@@ -288,8 +288,27 @@ void* lh_ctx_stream(lh_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 int lh_tensor_register(lh_ctx* ctx, uint64_t key, int dtype, const uint32_t ne[4], int persistent, const void* host, lh_buf* out) {
     if (!ctx || !ne || !out) LH_FAIL(ctx, LH_EINVAL, "lh_tensor_register: NULL argument");
     (void)persistent;
-    if (dtype != 0 && dtype != 7) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_tensor_register: dtype %d not supported (f32 and block-int8 only; the reference loader accepts f32/f16, llama.go:956-959)", dtype);
+    if (dtype != 0 && dtype != 1 && dtype != 7) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_tensor_register: dtype %d not supported (f32, f16 and block-int8 only; the reference loader accepts f32/f16, llama.go:956-959)", dtype);
     LH_HIP(ctx, hipSetDevice(ctx->device));
+    if (dtype == 1) {   // f16 weight matrix: the halves as they are, 2 bytes per element
+        if (ne[2] != 1 || ne[3] != 1 || !ne[0] || !ne[1]) LH_FAIL(ctx, LH_ESHAPE, "lh_tensor_register: f16 needs a 2-D matrix");
+        auto b = std::make_unique<Buffer>();
+        b->nfloats = (uint64_t)ne[0] * ne[1]; b->dtype = 1; b->rows = ne[1]; b->cols = ne[0]; b->key = key; b->device = ctx->device;
+        b->bytes = b->nfloats * 2;
+        b->unchecked = true;   // (no fp32 values for the bf16 split's range check; no node-path MulMat takes the buffer anyway)
+        hipError_t e = hipMalloc((void**)&b->dev, b->bytes);
+        if (e != hipSuccess) LH_FAIL(ctx, LH_ENOMEM, "lh_tensor_register: hipMalloc(%llu bytes): %s", (unsigned long long)b->bytes, hipGetErrorString(e));
+        e = host ? hipMemcpyAsync(b->dev, host, b->bytes, hipMemcpyHostToDevice, ctx->stream) : hipMemsetAsync(b->dev, 0, b->bytes, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) { hipFree(b->dev); LH_FAIL(ctx, LH_EHIP, "lh_tensor_register: f16 upload: %s", hipGetErrorString(e)); }
+        std::lock_guard<std::mutex> lk(ctx->ds->mu);
+        lh_buf id = ctx->ds->next_id++;
+        if (key) ctx->ds->by_key[key] = id;
+        ctx->ds->bufs[id] = std::move(b);
+        ctx->ds->bufs_gen.fetch_add(1, std::memory_order_release);
+        *out = id;
+        return LH_OK;
+    }
     if (dtype == 7) {
         if (ne[0] % 32 || ne[2] != 1 || ne[3] != 1 || !host) LH_FAIL(ctx, LH_ESHAPE, "lh_tensor_register: block-int8 needs a 2-D matrix with columns %% 32 == 0 and host blocks");
         const uint64_t nblocks = (uint64_t)ne[0] * ne[1] / 32;
@@ -374,6 +393,7 @@ int lh_buf_read(lh_ctx* ctx, lh_buf buf, uint64_t off, float* dst, uint64_t n) {
     if (rc) return rc;
     if (!dst) LH_FAIL(ctx, LH_EINVAL, "lh_buf_read: dst is NULL");
     if (b->dtype == 7) return lh_buf_read_q8(ctx, buf, off, dst, n);
+    if (b->dtype != 0) LH_FAIL(ctx, LH_EINVAL, "lh_buf_read: an f16 buffer holds no floats (lh_buf_widen_f16 makes an fp32 copy)");
     LH_HIP(ctx, hipSetDevice(ctx->device));
     LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     LH_HIP(ctx, hipMemcpyAsync(dst, b->dev + off, n * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -385,6 +405,7 @@ int lh_buf_fill_synth(lh_ctx* ctx, lh_buf buf, uint64_t off, uint64_t n, uint64_
     Buffer* b;
     int rc = get_buf(ctx, buf, off, n, &b, "lh_buf_fill_synth");
     if (rc) return rc;
+    if (b->dtype == 1) LH_FAIL(ctx, LH_EINVAL, "lh_buf_fill_synth: not an f32 buffer (f16: fill an f32 buffer, then lh_buf_narrow_f16)");
     LH_HIP(ctx, hipSetDevice(ctx->device));
     const uint64_t key = mix64(seed ^ ((uint64_t)tensor_id * 0xD6E8FEB86659FD93ull));
     uint64_t blocks = (n + 255) / 256;
@@ -400,6 +421,7 @@ int lh_buf_quantize_q8(lh_ctx* ctx, lh_buf src, uint32_t rows, uint32_t cols, lh
     if (!out) return LH_EINVAL;
     int rc = get_buf(ctx, src, 0, (uint64_t)rows * cols, &sb, "lh_buf_quantize_q8");
     if (rc) return rc;
+    if (sb->dtype == 1) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_buf_quantize_q8: the source is f16 (quantise before narrowing)");
     if (sb->dtype != 0 || cols % 32) LH_FAIL(ctx, LH_ESHAPE, "lh_buf_quantize_q8: needs an f32 matrix with columns %% 32 == 0");
     LH_HIP(ctx, hipSetDevice(ctx->device));
     const uint64_t n = (uint64_t)rows * cols, nblocks = n / 32;
@@ -419,6 +441,56 @@ int lh_buf_quantize_q8(lh_ctx* ctx, lh_buf src, uint32_t rows, uint32_t cols, lh
     ctx->ds->bufs_gen.fetch_add(1, std::memory_order_release);
     *out = id;
     return LH_OK;
+}
+
+static int add_buffer(lh_ctx* ctx, std::unique_ptr<Buffer> b, lh_buf* out) {
+    std::lock_guard<std::mutex> lk(ctx->ds->mu);
+    lh_buf id = ctx->ds->next_id++;
+    ctx->ds->bufs[id] = std::move(b);
+    ctx->ds->bufs_gen.fetch_add(1, std::memory_order_release);
+    *out = id;
+    return LH_OK;
+}
+
+int lh_buf_narrow_f16(lh_ctx* ctx, lh_buf src, uint32_t rows, uint32_t cols, lh_buf* out, uint64_t* n_changed) {
+    Buffer* sb;
+    if (!out || !rows || !cols) return LH_EINVAL;
+    int rc = get_buf(ctx, src, 0, (uint64_t)rows * cols, &sb, "lh_buf_narrow_f16");
+    if (rc) return rc;
+    if (sb->dtype != 0) LH_FAIL(ctx, LH_EINVAL, "lh_buf_narrow_f16: the source must be an f32 buffer");
+    LH_HIP(ctx, hipSetDevice(ctx->device));
+    const uint64_t n = (uint64_t)rows * cols;
+    auto b = std::make_unique<Buffer>();
+    b->nfloats = n; b->dtype = 1; b->rows = rows; b->cols = cols; b->device = ctx->device; b->bytes = n * 2;
+    b->unchecked = true;
+    unsigned long long* cnt = nullptr;
+    unsigned long long h = 0;
+    LH_HIP(ctx, hipMalloc((void**)&b->dev, b->bytes));
+    hipError_t e = hipMalloc((void**)&cnt, sizeof *cnt);
+    if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, sizeof *cnt, ctx->stream);
+    if (e == hipSuccess && (rc = narrow_f16_launch(ctx, sb->dev, b->dev, n, cnt))) e = hipErrorUnknown;
+    if (e == hipSuccess) e = hipMemcpyAsync(&h, cnt, sizeof h, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (cnt) hipFree(cnt);
+    if (e != hipSuccess) { hipFree(b->dev); if (rc) return rc; LH_FAIL(ctx, LH_EHIP, "lh_buf_narrow_f16: %s", hipGetErrorString(e)); }
+    if (n_changed) *n_changed = h;
+    return add_buffer(ctx, std::move(b), out);
+}
+
+int lh_buf_widen_f16(lh_ctx* ctx, lh_buf src, lh_buf* out) {
+    if (!ctx || !out) return LH_EINVAL;
+    Buffer* sb = find_buffer(ctx->ds, src);
+    if (!sb) LH_FAIL(ctx, LH_EINVAL, "lh_buf_widen_f16: unknown buffer %llu", (unsigned long long)src);
+    if (sb->dtype != 1) LH_FAIL(ctx, LH_EINVAL, "lh_buf_widen_f16: the source must be an f16 buffer");
+    LH_HIP(ctx, hipSetDevice(ctx->device));
+    auto b = std::make_unique<Buffer>();
+    b->nfloats = sb->nfloats; b->dtype = 0; b->device = ctx->device; b->bytes = sb->nfloats * 4;
+    b->unchecked = true;   // (values the host never saw: as after lh_buf_fill_synth)
+    LH_HIP(ctx, hipMalloc((void**)&b->dev, b->bytes));
+    int rc = widen_f16_launch(ctx, sb->dev, b->dev, sb->nfloats);
+    hipError_t e = rc ? hipErrorUnknown : hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { hipFree(b->dev); if (rc) return rc; LH_FAIL(ctx, LH_EHIP, "lh_buf_widen_f16: %s", hipGetErrorString(e)); }
+    return add_buffer(ctx, std::move(b), out);
 }
 
 int lh_buf_read_q8(lh_ctx* ctx, lh_buf buf, uint64_t off, float* dst, uint64_t n) {

@@ -60,9 +60,9 @@ void route_trace(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 // A persistent device buffer (weights / KV cache), shared by every context of the device.
 struct Buffer {
     float* dev = nullptr;
-    uint64_t nfloats = 0;  // f32 elements (for block-int8: logical elements)
+    uint64_t nfloats = 0;  // f32 elements (for block-int8 and f16: logical elements)
     uint64_t bytes = 0;
-    int dtype = 0;              // ml.DType: 0 = f32, 7 = block-int8 (planes: int8 quants at dev, fp32 scales at `scales`)
+    int dtype = 0;              // ml.DType: 0 = f32, 1 = f16 (halves at dev, 2 bytes per element), 7 = block-int8 (planes: int8 quants at dev, fp32 scales at `scales`)
     float* scales = nullptr;    // block-int8: [rows][cols/32]
     uint32_t rows = 0, cols = 0;
     uint64_t key = 0;
@@ -155,6 +155,9 @@ struct lh_ctx {
     // the activation rows of a long-prompt GEMM as three bf16 planes (k_gemm_b9); grows, never shrinks
     uint16_t* xs3 = nullptr;
     uint64_t xs3_elems = 0;
+    // fp32 images of f16 weight matrices for the routes without f16 kernels (Plan::md_wide): one allocation per size asked for at plan_create,
+    // shared by the context's plans of that size, freed with the context - an address handed out never moves
+    std::vector<std::pair<uint64_t, float*>> wide;   // (size and kind, address)
     // lh_ctx_time_computes: events around each lh_graph_compute + host time inside it
     bool tc_on = false, tc_end = false;
     hipEvent_t tc_ev0 = nullptr, tc_ev1 = nullptr;
@@ -167,4 +170,8 @@ int ensure_arena(lh_ctx* ctx, uint64_t bytes);
 int ensure_staging(lh_ctx* ctx, uint64_t bytes);
 int ensure_rope_table(lh_ctx* ctx, uint32_t positions, uint32_t dims, const double2** table);
 inline int select_device(lh_ctx* ctx) { return hipSetDevice(ctx->device) == hipSuccess ? 0 : LH_EHIP; }
+// plan.hip (kernels_f16.h), enqueued on the context's stream: n halves -> floats, exact (k_widen_f16); n floats -> halves, round to nearest even,
+// *changed_dev += the elements whose value changed (k_narrow_f16)
+int widen_f16_launch(lh_ctx* ctx, const void* src_f16, float* dst, uint64_t n);
+int narrow_f16_launch(lh_ctx* ctx, const float* src, void* dst_f16, uint64_t n, unsigned long long* changed_dev);
 }  // namespace lh

@@ -13,6 +13,7 @@
 #include "kernels_stream_b9.h"
 #include "kernels_gemm_b9.h"
 #include "kernels_rows.h"
+#include "kernels_f16.h"
 #include "kernels_attn_seg.h"
 #include "kernels_attn_share.h"
 #include "kernels_spec.h"
@@ -116,6 +117,33 @@ static int grow_floats(lh_ctx* ctx, float** buf, uint64_t* cap, uint64_t need) {
 // the context's split-K partial products (lh_ctx::splitk; every graph whose launches may read them has splitk_gen in its key)
 static int ensure_splitk(lh_ctx* ctx, uint64_t need_floats) { return grow(ctx, &ctx->splitk, &ctx->splitk_floats, need_floats, 4, 0, &ctx->splitk_gen); }
 
+// ---- f16 <-> f32 (kernels_f16.h) ----
+static inline dim3 cvt_grid(uint64_t n) { return dim3((unsigned)std::min<uint64_t>(std::max<uint64_t>((n / 4 + 255) / 256, 1), 16384)); }
+int widen_f16_launch(lh_ctx* ctx, const void* src_f16, float* dst, uint64_t n) {
+    if (g_prepare_only || g_only) return 0;
+    TraceScope ts_(ctx->stream, "widen_f16");
+    LH_TRACE("k_widen_f16");
+    LH_LAUNCH(k_widen_f16, cvt_grid(n), dim3(256), 0, ctx->stream, (const _Float16*)src_f16, dst, n);
+    LH_HIP(ctx, hipGetLastError());
+    return 0;
+}
+int narrow_f16_launch(lh_ctx* ctx, const float* src, void* dst_f16, uint64_t n, unsigned long long* changed_dev) {
+    LH_LAUNCH(k_narrow_f16, cvt_grid(n), dim3(256), 0, ctx->stream, src, (_Float16*)dst_f16, n, changed_dev);
+    LH_HIP(ctx, hipGetLastError());
+    return 0;
+}
+// an fp32 image of nfloats elements that lives as long as the context and never moves (lh_ctx::wide); kind 0 = a layer's matrices, 1 = the output
+// matrix (a layer image and an output image of the same size stay two allocations: a route reads both)
+static int wide_image(lh_ctx* ctx, uint64_t nfloats, int kind, float** out) {
+    const uint64_t key = (nfloats << 1) | (uint64_t)kind;
+    for (const auto& w : ctx->wide) if (w.first == key) { *out = w.second; return 0; }
+    float* dev = nullptr;
+    if (hipMalloc((void**)&dev, nfloats * 4) != hipSuccess) LH_FAIL(ctx, LH_ENOMEM, "plan: no memory for the fp32 image of f16 weights (%llu floats)", (unsigned long long)nfloats);
+    ctx->wide.emplace_back(key, dev);
+    *out = dev;
+    return 0;
+}
+
 template <int KI, int U, int PRO, int EPI, int MAP, int THR = TH>
 static int launch_gemv(lh_ctx* ctx, const GemvArgs& a, const char* name, uint64_t bytes) {
     static bool flags[16] = {};
@@ -176,7 +204,11 @@ template <int PRO, int EPI, int MAP>
 static int gemv_f32(lh_ctx* ctx, const GemvArgs& a, const char* name);
 
 template <int PRO, int EPI, int MAP>
+static int gemv_f16(lh_ctx* ctx, const GemvArgs& a, const char* name);
+
+template <int PRO, int EPI, int MAP>
 static int gemv(lh_ctx* ctx, const GemvArgs& a, const char* name, int wtype = 0) {
+    if (wtype == 1) return gemv_f16<PRO, EPI, MAP>(ctx, a, name);
     return wtype == 7 ? gemv_q8<PRO, EPI, MAP>(ctx, a, name) : gemv_f32<PRO, EPI, MAP>(ctx, a, name);
 }
 
@@ -223,6 +255,67 @@ static int gemv_f32(lh_ctx* ctx, const GemvArgs& a, const char* name) {
         // (six float4 of x, gamma and two rows each do not fit the 128 registers of a 1024-thread workgroup next to the norm: 20 B of scratch)
         case 6: return launch_gemv<6, (PRO == PRO_RMSNORM ? 1 : 2), PRO, EPI, MAP>(ctx, a, name, bytes);
         default: LH_FAIL(ctx, LH_EUNSUPPORTED, "gemv %s: K=%u exceeds the supported 24576 columns", name, a.K);
+    }
+}
+
+// ---- f16 weight matrices (kernels_f16.h): the workgroup size and float4-per-thread count gemv_f32 picks for the shape - they fix the lane -> column
+// map and the cross-wave order, hence the bits - and twice its rows in flight: a row of halves is half the bytes, and U is not part of the sums.
+template <int KI, int U, int PRO, int EPI, int MAP, int THR = TH>
+static int launch_gemv_h(lh_ctx* ctx, const GemvArgs& a, const char* name, uint64_t bytes) {
+    static bool flags[16] = {};
+    int rc = set_lds_once(ctx, k_gemv_sa_h<KI, U, THR, PRO, EPI, MAP>, FAT_LDS, flags);
+    if (rc) return rc;
+    if (skip_launch(name)) return 0;
+    ProfScope ps(ctx->stream, name, bytes);
+    GemvArgs b = a;
+    b.wg_q = (a.M / 2) / (uint32_t)ctx->ds->num_cu; b.wg_r = (a.M / 2) % (uint32_t)ctx->ds->num_cu;   // wg_row_block
+    LH_TRACE("k_gemv_sa_h<%d,%d,%d>", KI, U, THR);
+    LH_LAUNCH((k_gemv_sa_h<KI, U, THR, PRO, EPI, MAP>), dim3(ctx->ds->num_cu), dim3(THR), FAT_LDS, ctx->stream, b);
+    LH_HIP(ctx, hipGetLastError());
+    return 0;
+}
+// LLAMAHIP_F16_U = 2 / 4 / 8: rows in flight of the K = 4096 launches (the sweep of tools/bench_f16.py); anything else: the shipped choice
+static int f16_u_override() {
+    static const int v = getenv("LLAMAHIP_F16_U") ? atoi(getenv("LLAMAHIP_F16_U")) : 0;
+    return v;
+}
+template <int PRO, int EPI, int MAP>
+static int gemv_f16(lh_ctx* ctx, const GemvArgs& a, const char* name) {
+    if (a.K % 4 || ((EPI == EPI_QKV_ROPE || EPI == EPI_SILU_MUL) && a.M % 2))
+        LH_FAIL(ctx, LH_ESHAPE, "gemv (f16 weights) %s: K=%u must be a multiple of 4%s", name, a.K, a.M % 2 ? " and the row count even" : "");
+    const uint32_t K4 = a.K / 4;
+    const uint64_t bytes = (uint64_t)a.M * a.K * 2;
+    const uint32_t rows_wg = a.M / (uint32_t)ctx->ds->num_cu + 4;
+    if (K4 <= 4 * 256 && rows_wg <= 256) {
+        switch ((K4 + 255) / 256) {
+            case 1: return launch_gemv_h<1, 8, PRO, EPI, MAP, 256>(ctx, a, name, bytes);
+            case 2: return launch_gemv_h<2, 8, PRO, EPI, MAP, 256>(ctx, a, name, bytes);
+            case 3: return launch_gemv_h<3, 4, PRO, EPI, MAP, 256>(ctx, a, name, bytes);
+            default:
+                if (f16_u_override() == 2) return launch_gemv_h<4, 2, PRO, EPI, MAP, 256>(ctx, a, name, bytes);
+                if (f16_u_override() == 8) return launch_gemv_h<4, 8, PRO, EPI, MAP, 256>(ctx, a, name, bytes);
+                return launch_gemv_h<4, 4, PRO, EPI, MAP, 256>(ctx, a, name, bytes);
+        }
+    }
+    if (K4 <= 6 * 512 && rows_wg <= 512) {
+        switch ((K4 + 511) / 512) {
+            case 1: return launch_gemv_h<1, 4, PRO, EPI, MAP, 512>(ctx, a, name, bytes);
+            case 2: return launch_gemv_h<2, 4, PRO, EPI, MAP, 512>(ctx, a, name, bytes);
+            case 3: return launch_gemv_h<3, 4, PRO, EPI, MAP, 512>(ctx, a, name, bytes);
+            case 4: return launch_gemv_h<4, 2, PRO, EPI, MAP, 512>(ctx, a, name, bytes);
+            case 5: return launch_gemv_h<5, 2, PRO, EPI, MAP, 512>(ctx, a, name, bytes);
+            default: return launch_gemv_h<6, 2, PRO, EPI, MAP, 512>(ctx, a, name, bytes);
+        }
+    }
+    if (rows_wg > (uint32_t)TH) LH_FAIL(ctx, LH_EUNSUPPORTED, "gemv (f16 weights) %s: M=%u exceeds %d rows per workgroup", name, a.M, TH - 4);
+    switch ((K4 + TH - 1) / TH) {
+        case 1: return launch_gemv_h<1, 4, PRO, EPI, MAP>(ctx, a, name, bytes);
+        case 2: return launch_gemv_h<2, 4, PRO, EPI, MAP>(ctx, a, name, bytes);
+        case 3: return launch_gemv_h<3, 2, PRO, EPI, MAP>(ctx, a, name, bytes);
+        case 4: return launch_gemv_h<4, 4, PRO, EPI, MAP>(ctx, a, name, bytes);
+        case 5: return launch_gemv_h<5, 4, PRO, EPI, MAP>(ctx, a, name, bytes);
+        case 6: return launch_gemv_h<6, 2, PRO, EPI, MAP>(ctx, a, name, bytes);   // (halved weight slots: two rows fit next to the norm where fp32 has one)
+        default: LH_FAIL(ctx, LH_EUNSUPPORTED, "gemv (f16 weights) %s: K=%u exceeds the supported 24576 columns", name, a.K);
     }
 }
 
@@ -306,13 +399,59 @@ static int gemv_q8_rows_nc(lh_ctx* ctx, const GemvRowsArgs& a, const char* name)
     if (a.K / 16 <= 256) return launch_gemv_q8_rows<1, U, NC, PRO, EPI, MAP>(ctx, a, name, bytes);
     return launch_gemv_q8_rows<3, (NC <= 2 ? 2 : 1), NC, PRO, EPI, MAP>(ctx, a, name, bytes);
 }
+// f16 twin (k_gemv_rows_h): gemv_rows_nc's shapes and limits (the activation registers are the same), twice its weight rows in flight
+template <int KI, int U, int THR, int NC, int PRO, int EPI, int MAP>
+static int launch_gemv_rows_h(lh_ctx* ctx, const GemvRowsArgs& a, const char* name, uint64_t bytes) {
+    static bool flags[16] = {};
+    int rc = set_lds_once(ctx, k_gemv_rows_h<KI, U, THR, NC, PRO, EPI, MAP>, FAT_LDS, flags);
+    if (rc) return rc;
+    if (g_prepare_only) return 0;
+    ProfScope ps(ctx->stream, name, bytes);
+    GemvRowsArgs b = a;
+    b.wg_q = (a.M / 2) / (uint32_t)ctx->ds->num_cu; b.wg_r = (a.M / 2) % (uint32_t)ctx->ds->num_cu;   // wg_row_block
+    LH_TRACE("k_gemv_rows_h<%d,%d,%d,%d>", KI, U, THR, NC);
+    LH_LAUNCH((k_gemv_rows_h<KI, U, THR, NC, PRO, EPI, MAP>), dim3(ctx->ds->num_cu), dim3(THR), FAT_LDS, ctx->stream, b);
+    LH_HIP(ctx, hipGetLastError());
+    return 0;
+}
+template <int NC, int PRO, int EPI, int MAP>
+static int gemv_rows_h_nc(lh_ctx* ctx, const GemvRowsArgs& a, const char* name) {
+    if (!gemv_rows_shape_ok(ctx, a.M, a.K, NC, PRO == PRO_RMSNORM)) LH_FAIL(ctx, LH_ESHAPE, "gemv_rows (f16 weights) %s: %u x %u has no %d-row instantiation", name, a.M, a.K, NC);
+    const uint32_t K4 = a.K / 4, rows_wg = a.M / (uint32_t)ctx->ds->num_cu + 4;
+    const uint64_t bytes = (uint64_t)a.M * a.K * 2;
+    // (eight activation rows keep k_gemv_rows' own count: more weight rows in flight measured slower there - profiles/r04_rows_kernel_u.txt - and their
+    // row bases no longer fit the scalar registers)
+    if (K4 <= 4 * 256 && rows_wg <= 256) {
+        switch ((K4 + 255) / 256) {
+            case 1: return launch_gemv_rows_h<1, (NC > 4 ? 4 : 8), 256, NC, PRO, EPI, MAP>(ctx, a, name, bytes);
+            case 2: return launch_gemv_rows_h<2, (NC > 4 ? 4 : 8), 256, NC, PRO, EPI, MAP>(ctx, a, name, bytes);
+            case 3: return launch_gemv_rows_h<3, (NC > 4 ? 2 : 4), 256, NC, PRO, EPI, MAP>(ctx, a, name, bytes);
+            default: return launch_gemv_rows_h<4, (NC > 4 ? 2 : 4), 256, NC, PRO, EPI, MAP>(ctx, a, name, bytes);
+        }
+    }
+    if constexpr (NC > 4 && PRO == PRO_RMSNORM) return LH_ESHAPE;   // (refused above)
+    else {
+    switch ((K4 + 511) / 512) {
+        case 1: return launch_gemv_rows_h<1, (NC > 4 ? 2 : 4), 512, NC, PRO, EPI, MAP>(ctx, a, name, bytes);
+        case 2: return launch_gemv_rows_h<2, (NC > 4 ? 2 : 4), 512, NC, PRO, EPI, MAP>(ctx, a, name, bytes);
+        case 3: return launch_gemv_rows_h<3, (NC > 4 ? 2 : 4), 512, NC, PRO, EPI, MAP>(ctx, a, name, bytes);
+        case 4: return launch_gemv_rows_h<4, (NC > 4 ? 1 : 2), 512, NC, PRO, EPI, MAP>(ctx, a, name, bytes);
+        case 5: return launch_gemv_rows_h<5, (NC > 4 ? 1 : 2), 512, NC, PRO, EPI, MAP>(ctx, a, name, bytes);
+        default: return launch_gemv_rows_h<6, (NC > 4 ? 1 : 2), 512, NC, PRO, EPI, MAP>(ctx, a, name, bytes);
+    }
+    }
+}
 template <int PRO, int EPI, int MAP>
 static int gemv_rows(lh_ctx* ctx, const GemvRowsArgs& a, const char* name, int wtype = 0) {
+    if (wtype == 1) {
+        if (a.n > 4) return gemv_rows_h_nc<8, PRO, EPI, MAP>(ctx, a, name);
+        return a.n <= 2 ? gemv_rows_h_nc<2, PRO, EPI, MAP>(ctx, a, name) : gemv_rows_h_nc<4, PRO, EPI, MAP>(ctx, a, name);
+    }
     if (wtype == 7) return a.n <= 2 ? gemv_q8_rows_nc<2, PRO, EPI, MAP>(ctx, a, name) : gemv_q8_rows_nc<4, PRO, EPI, MAP>(ctx, a, name);
     if (a.n > 4) return gemv_rows_nc<8, PRO, EPI, MAP>(ctx, a, name);
     return a.n <= 2 ? gemv_rows_nc<2, PRO, EPI, MAP>(ctx, a, name) : gemv_rows_nc<4, PRO, EPI, MAP>(ctx, a, name);
 }
-// rows the decode stream carries: fp32 up to 8 (round 4; 32 FMAs per 16-byte load = a sixth of a CU's vector rate at the stream's pace),
+// rows the decode stream carries: fp32 and f16 up to 8 (round 4; 32 FMAs per 16-byte load = a sixth of a CU's vector rate at the stream's pace),
 // block-int8 up to 4 (its 16 converts + 16 NC FMAs per load saturate the vector ALU from there on)
 static constexpr uint32_t GEMV_ROWS_MAX_F32 = 8, GEMV_ROWS_MAX_Q8 = 4;
 static uint32_t gemv_rows_max(int wtype) { return wtype == 7 ? GEMV_ROWS_MAX_Q8 : GEMV_ROWS_MAX_F32; }
@@ -320,7 +459,8 @@ static uint32_t gemv_rows_max(int wtype) { return wtype == 7 ? GEMV_ROWS_MAX_Q8 
 static bool rows_path_ok(lh_ctx* ctx, const ModelDesc& m, uint32_t n) {
     if (n > gemv_rows_max(m.wtype)) return false;
     const uint32_t nc = n <= 2 ? 2 : (n <= 4 ? 4 : 8);
-    auto ok = [&](uint32_t M, uint32_t K, bool norm) { return m.wtype == 7 ? gemv_q8_rows_shape_ok(ctx, M, K) : (m.wtype == 0 && gemv_rows_shape_ok(ctx, M, K, nc, norm)); };
+    // (f16: the fp32 predicate - k_gemv_rows_h keeps k_gemv_rows' activation registers and takes no more for its weight slots)
+    auto ok = [&](uint32_t M, uint32_t K, bool norm) { return m.wtype == 7 ? gemv_q8_rows_shape_ok(ctx, M, K) : ((m.wtype == 0 || m.wtype == 1) && gemv_rows_shape_ok(ctx, M, K, nc, norm)); };
     return m.hd % 2 == 0 && m.d % 4 == 0 && ok(3 * m.d, m.d, true) && ok(m.d, m.d, false) && ok(2 * m.F, m.d, true) && ok(m.d, m.F, false) && (!m.last_stage() || ok(m.V, m.d, true));
 }
 
@@ -1308,7 +1448,7 @@ int plan_ensure_rows(Plan* p, uint32_t n) {
     if (n > 1) { rc |= re(&p->qraw, nd); rc |= re(&p->kraw, nd); rc |= re(&p->vraw, nd); rc |= re(&p->a1, nf); rc |= re(&p->a3, nf); }
     if (m.last_stage()) rc |= re(&p->logits, (size_t)n * m.V);
     if (rc) return LH_EHIP;
-    if (n > 1 && (m.wtype == 7 || m.wtype == 0)) {   // the activations as planes: every row of a block-int8 plan, up to k_stream_b9's 64 rows of an fp32 one
+    if (n > 1 && (m.wtype == 7 || m.wtype == 0 || m.wtype == 1)) {   // the activations as planes: every row of a block-int8 plan, up to k_stream_b9's 64 rows of an fp32 one (f16: the fp32 schedule)
         if (p->s3) LH_HIP(ctx, hipFree(p->s3));
         p->s3 = nullptr;
         p->s3_rows = m.wtype == 7 ? n : std::min<uint32_t>(n, B9S_MAX_ROWS);
@@ -1338,7 +1478,19 @@ int plan_create(lh_ctx* ctx, const ModelDesc& md, Plan** out) {
     if (e != hipSuccess) { set_error(ctx, "plan_create: %s", hipGetErrorString(e)); plan_destroy(p); return LH_ENOMEM; }
     rc = plan_ensure_rows(p, 1);
     if (rc) { plan_destroy(p); return rc; }
-    p->hist = md.kv_hist ? md.kv_hist : std::make_shared<std::vector<uint32_t>>();
+    if (md.wtype == 1) {   // the fp32 images of the widened routes (Plan::md_wide): sized here, once
+        const uint64_t d = md.d, F = md.F;
+        if ((rc = wide_image(ctx, 4 * d * d + 3 * d * F, 0, &p->wide_layer)) || (md.last_stage() && (rc = wide_image(ctx, (uint64_t)md.V * d, 1, &p->wide_out)))) { plan_destroy(p); return rc; }
+        p->md_wide = md;
+        p->md_wide.wtype = 0;
+        p->md_wide.output = p->wide_out;
+        float* w = p->wide_layer;
+        for (uint32_t il = md.layer0; il < md.layer1; ++il) {
+            LayerW& L = p->md_wide.layers[il];
+            L.wq = w; L.wk = w + d * d; L.wv = w + 2 * d * d; L.wo = w + 3 * d * d; L.w1 = w + 4 * d * d; L.w3 = w + 4 * d * d + d * F; L.w2 = w + 4 * d * d + 2 * d * F;
+        }
+    }
+    p->hist =md.kv_hist ? md.kv_hist : std::make_shared<std::vector<uint32_t>>();
     if (p->hist->size() < md.ctx) p->hist->resize(md.ctx, Plan::HIST_UNKNOWN);
     if (md.ctx > 256 && md.hd == 128) {   // long contexts: decode attention split over the keys (k_attention_split)
         const size_t nch = (md.ctx + ATT_TC - 1) / ATT_TC;
@@ -1650,6 +1802,8 @@ static bool q8_stream_ok(lh_ctx* ctx, const ModelDesc& m, uint32_t n, uint32_t n
 //   Skinny   fp32, 2..8 rows of one stream where k_stream_* is not built for the shape: k_skinny
 //   Planes   the activations as three bf16 planes: block-int8 on k_stream_q8b (3..64 rows of a batch, 3..88 of a prompt), fp32 at 49..64 rows on k_stream_b9
 //   Prefill  everything else: the fp32 stream kernels and tile GEMMs, the dequantising GEMM, the column kernels
+// f16 weights (wtype 1): Step and Rows on the f16 forms of their kernels (kernels_f16.h); for every other row count the route eval_route picks for a wtype-0
+// model of the same shapes, run on that model's kernels over an fp32 image of the matrices (sched_md, route_layer below).
 // Rows of different streams (BatchCtx) take ONE weight pass only on a route whose position-dependent kernels all read the row table: Rows and Planes,
 // and Prefill with fp32 weights (k_stream_mm2's RoPE epilogue, k_rope_store, k_attention, k_attention_split).  Step, Q8Steps and Skinny do not read it, nor
 // do Prefill's tile GEMM RoPE epilogue above 64 rows and its prompt attention kernels, which the at most BATCH_ROWS_MAX rows of a batch never take
@@ -1669,8 +1823,9 @@ static EvalRoute eval_route(lh_ctx* ctx, const ModelDesc& m, uint32_t n, bool ba
 }
 // Prefill's grouped MFMA launches: from 9 rows (tile GEMM), fp32 weights from 2 rows on the streaming MFMA kernel
 static bool prefill_mfma(const ModelDesc& m, uint32_t n) { return (n >= MFMA_MIN_ROWS || (n >= 2 && m.wtype == 0)) && m.d % GBK == 0 && m.F % GBK == 0; }
+static const ModelDesc& sched_md(const Plan* p);
 bool plan_batch_rows_ok(const Plan* p, uint32_t n) {
-    const ModelDesc& m = p->md;
+    const ModelDesc& m = sched_md(p);
     if (n < 2 || n > BATCH_ROWS_MAX) return false;
     const EvalRoute route = eval_route(p->ctx, m, n, true);
     if (route == EvalRoute::Rows) return true;   // two to eight (block-int8: four) rows ride the decode stream itself
@@ -1689,6 +1844,30 @@ struct EvalCall {   // the arguments of one plan_eval
     const BatchCtx* bc;
 };
 static float attn_scale(const ModelDesc& m) { return (float)(1.0 / sqrt((double)m.d / (double)m.H)); }
+// What a route's schedule is chosen for and runs on: the plan's model - or, for an f16 model, its fp32 shadow (Plan::md_wide), so that eval_route picks
+// what it picks for a wtype-0 model of the same shapes.  Step and Rows, which the same predicates admit for both, run on the model itself (sched_md is
+// not asked there); Skinny, Planes and Prefill open with it and see an fp32 model.
+static const ModelDesc& sched_md(const Plan* p) { return p->md.wtype == 1 ? p->md_wide : p->md; }
+// The matrices of layer il for a route that works on m (sched_md): the model's own, or the fp32 image after enqueuing its widening - one exact pass
+// (k_widen_f16) per matrix in front of the layer's launches; the stream orders it behind the launches of the layer before, which read the same image.
+static const LayerW& route_layer(Plan* p, const ModelDesc& m, uint32_t il) {
+    if (&m != &p->md_wide) return m.layers[il];
+    const LayerW& S = p->md.layers[il];
+    const LayerW& W = m.layers[il];
+    const uint64_t dd = (uint64_t)m.d * m.d, dF = (uint64_t)m.d * m.F;
+    const float* src[7] = {S.wq, S.wk, S.wv, S.wo, S.w1, S.w3, S.w2};
+    const float* dst[7] = {W.wq, W.wk, W.wv, W.wo, W.w1, W.w3, W.w2};
+    for (int k = 0; k < 7; ++k) widen_f16_launch(p->ctx, src[k], (float*)dst[k], k < 4 ? dd : dF);   // (a launch error surfaces at the layer's hipGetLastError)
+    return W;
+}
+// the output matrix for a route's lm_head of more than one row (or over planes): as above
+static const float* route_output(Plan* p, const ModelDesc& m) {
+    if (&m == &p->md_wide) widen_f16_launch(p->ctx, p->md.output, p->wide_out, (uint64_t)m.V * m.d);
+    return m.output;
+}
+// the output matrix for ONE logits row on the decode stream: an f16 model's halves as they are (k_gemv_sa_h computes the bits k_gemv_sa would over the image)
+struct HeadRow { const float* w; int wtype; };
+static HeadRow head_row(const Plan* p, const ModelDesc& m) { return &m == &p->md_wide ? HeadRow{p->md.output, 1} : HeadRow{m.output, m.wtype}; }
 // The logits rows of the last stage, first row and count: all n as the reference evaluates them (llama.go:372-384), or the last one alone, which is all
 // llama.Eval reads (llama.go:394-401), for callers that say so (LH_GRAPH_LAST_ROW_LOGITS, the lh_llama_* entry points) - in its usual place.
 struct LogitsRows { uint32_t r0, nr; };
@@ -1832,14 +2011,14 @@ static int eval_q8_steps(Plan* p, const EvalCall& c) {
 // short prompt: 4 fused weight passes per layer + the per-query attention kernel (like the decode step, n rows wide)
 static int eval_skinny(Plan* p, const EvalCall& c, const float* x) {
     lh_ctx* ctx = p->ctx;
-    const ModelDesc& m = p->md;
+    const ModelDesc& m = sched_md(p);
     const uint32_t n = c.n, past = c.past;
     float* x_out_dev = c.x_out_dev;
     int rc;
     const float scale = attn_scale(m);
     const uint32_t d = m.d, F = m.F;
     for (uint32_t il = m.layer0; il < m.layer1; ++il) {
-        const LayerW& L = m.layers[il];
+        const LayerW& L = route_layer(p, m, il);
         const size_t slot = (size_t)(il - m.cache_layer0) * m.ctx * d;
         {   // RMSNorm*gamma -> wq|wk|wv -> RoPE(Q, new K rows) -> K,V appended   (llama.go:255-297)
             SkinnyArgs a = {};
@@ -1871,11 +2050,12 @@ static int eval_skinny(Plan* p, const EvalCall& c, const float* x) {
         const auto [r0, nr] = logits_rows(c);
         if (nr == 1) {
             GemvArgs a = {};
-            a.w[0] = m.output; a.M = m.V; a.K = d; a.x = x + (size_t)r0 * d; a.gamma = m.norm; a.y = p->logits + (size_t)r0 * m.V;
-            if ((rc = gemv<PRO_RMSNORM, EPI_STORE, MAP_SINGLE>(ctx, a, "gemv_lmhead", 0))) return rc;
+            const HeadRow hw = head_row(p, m);
+            a.w[0] = hw.w; a.M = m.V; a.K = d; a.x = x + (size_t)r0 * d; a.gamma = m.norm; a.y = p->logits + (size_t)r0 * m.V;
+            if ((rc = gemv<PRO_RMSNORM, EPI_STORE, MAP_SINGLE>(ctx, a, "gemv_lmhead", hw.wtype))) return rc;
         } else {
             SkinnyArgs a = {};
-            a.w[0] = m.output; a.M = m.V; a.K = d; a.x = x; a.ldx = d; a.n = n; a.gamma = m.norm; a.y = p->logits; a.ldy = m.V;
+            a.w[0] = route_output(p, m); a.M = m.V; a.K = d; a.x = x; a.ldx = d; a.n = n; a.gamma = m.norm; a.y = p->logits; a.ldy = m.V;
             if ((rc = launch_skinny<PRO_RMSNORM, EPI_STORE, MAP_SINGLE>(p, a, "skinny_lmhead"))) return rc;
         }
     }
@@ -1892,7 +2072,7 @@ static int eval_skinny(Plan* p, const EvalCall& c, const float* x) {
 // hands an fp32 Eval to Prefill).
 static int eval_planes(Plan* p, const EvalCall& c, const float* x) {
     lh_ctx* ctx = p->ctx;
-    const ModelDesc& m = p->md;
+    const ModelDesc& m = sched_md(p);
     const uint32_t n = c.n, past = c.past;
     const BatchRow* rows = c.bc ? c.bc->rows : nullptr;
     float* x_out_dev = c.x_out_dev;
@@ -1908,7 +2088,7 @@ static int eval_planes(Plan* p, const EvalCall& c, const float* x) {
 #define PLANES_TRY(expr, what) do { if ((rc = (expr))) { if (rc == ST_NA) LH_FAIL(ctx, LH_ESHAPE, "Eval of %u rows over activation planes: no launch for %s (embd %u, ff %u, weight type %u)", n, what, d, F, m.wtype); return rc; } } while (0)
     bool h_ready = false;
     for (uint32_t il = m.layer0; il < m.layer1; ++il) {
-        const LayerW& L = m.layers[il];
+        const LayerW& L = route_layer(p, m, il);
         const size_t slot = (size_t)(il - m.cache_layer0) * m.ctx * d;
         if (!h_ready) { TraceScope ts_(ctx->stream, "rmsnorm_rows_s3"); if (!g_prepare_only) LH_LAUNCH(k_rmsnorm_rows_s3, dim3(n), dim3(256), 0, ctx->stream, x, L.attn_norm, (float*)nullptr, hs, pd, d); }
         {   // wq|wk|wv -> RoPE(Q, new K rows) -> K, V appended   (llama.go:263-297)
@@ -1952,7 +2132,7 @@ static int eval_planes(Plan* p, const EvalCall& c, const float* x) {
     }
     if (m.last_stage()) {   // lm_head on the rows the caller reads (llama.go:374-384, 394-401); hs / p->h hold RMSNorm * norm of every row
         const auto [r0, nr] = logits_rows(c);
-        const float* wv = m.output; const float* sv = m.s_output; float* yv = p->logits + (size_t)r0 * m.V;
+        const float* wv = route_output(p, m); const float* sv = m.s_output; float* yv = p->logits + (size_t)r0 * m.V;   // (m.output below: the same address)
         for (uint32_t b0 = 0; b0 < nr; b0 += STREAM_ROWS_Q8) {
             float* yb = yv + (size_t)b0 * m.V;
             const uint32_t nb = std::min(STREAM_ROWS_Q8, nr - b0);
@@ -1985,7 +2165,7 @@ static int eval_planes(Plan* p, const EvalCall& c, const float* x) {
 // the dequantising GEMM of block-int8 weights, the column kernels for what neither takes
 static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
     lh_ctx* ctx = p->ctx;
-    const ModelDesc& m = p->md;
+    const ModelDesc& m = sched_md(p);
     const uint32_t n = c.n, past = c.past, d = m.d, F = m.F;
     const BatchCtx* bc = c.bc;
     const BatchRow* rows = bc ? bc->rows : nullptr;
@@ -2000,7 +2180,7 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
     const uint32_t sb = two_pass ? (n + 1) / 2 : n;   // rows per pass of the stream kernels
     bool h_ready = false;   // p->h already holds this layer's RMSNorm * attn_norm rows (written by the previous layer's w2 reduce pass)
     for (uint32_t il = m.layer0; il < m.layer1; ++il) {
-        const LayerW& L = m.layers[il];
+        const LayerW& L = route_layer(p, m, il);
         const size_t slot = (size_t)(il - m.cache_layer0) * m.ctx * d;
         const bool mfma = prefill_mfma(m, n);
         const bool q8 = m.wtype == 7;
@@ -2134,9 +2314,10 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
             }
         } else if (nr == 1) {   // the one row llama.Eval reads: the decode weight stream (76 us on 7B; the column kernel took 122)
             GemvArgs ga = {};
-            ga.w[0] = m.output; ga.M = m.V; ga.K = d; ga.x = p->h + (size_t)r0 * d; ga.y = p->logits + (size_t)r0 * m.V;
-            if ((rc = gemv<PRO_PLAIN, EPI_STORE, MAP_SINGLE>(ctx, ga, "gemv_lmhead_row", 0))) return rc;
-        } else if ((rc = gemm_small_n(ctx, m.output, p->h + (size_t)r0 * d, p->logits + (size_t)r0 * m.V, nullptr, m.V, d, nr, d, m.V, "gemm_lmhead"))) return rc;
+            const HeadRow hw = head_row(p, m);
+            ga.w[0] = hw.w; ga.M = m.V; ga.K = d; ga.x = p->h + (size_t)r0 * d; ga.y = p->logits + (size_t)r0 * m.V;
+            if ((rc = gemv<PRO_PLAIN, EPI_STORE, MAP_SINGLE>(ctx, ga, "gemv_lmhead_row", hw.wtype))) return rc;
+        } else if ((rc = gemm_small_n(ctx, route_output(p, m), p->h + (size_t)r0 * d, p->logits + (size_t)r0 * m.V, nullptr, m.V, d, nr, d, m.V, "gemm_lmhead"))) return rc;
     }
     LH_HIP(ctx, hipGetLastError());
     return 0;
@@ -2163,7 +2344,7 @@ int plan_eval(Plan* p, const uint32_t* tokens_host, const float* x_in_dev, float
     int rc;
     if (!bc && (rc = plan_ensure_rows(p, n))) return rc;
     const EvalCall c = {tokens_host, x_in_dev, x_out_dev, n, past, last_row_only, bc};
-    const EvalRoute route = eval_route(ctx, m, n, bc != nullptr);
+    const EvalRoute route = eval_route(ctx, sched_md(p), n, bc != nullptr);
     const float* x = nullptr;   // the rows the first layer reads
     if (route != EvalRoute::Step && route != EvalRoute::Q8Steps && (rc = eval_input(p, c, route, &x))) return rc;   // (the single steps embed their own token)
     switch (route) {
@@ -3125,6 +3306,7 @@ void lh_ctx_destroy(lh_ctx* ctx) {
     if (ctx->arena) hipFree(ctx->arena);
     if (ctx->splitk) hipFree(ctx->splitk);
     if (ctx->xs3) hipFree(ctx->xs3);
+    for (auto& w : ctx->wide) hipFree(w.second);
     if (ctx->tc_ev0) { hipEventDestroy(ctx->tc_ev0); hipEventDestroy(ctx->tc_ev1); }
     if (ctx->staging) hipHostFree(ctx->staging);
     if (ctx->out_pinned) hipHostFree(ctx->out_pinned);
@@ -3170,7 +3352,7 @@ int lh_llama_create(lh_ctx* ctx, const lh_llama_desc* desc, lh_llama** out) {
     if (!ctx || !desc || !out) LH_FAIL(ctx, LH_EINVAL, "lh_llama_create: NULL argument");
     *out = nullptr;
     LH_HIP(ctx, hipSetDevice(ctx->device));
-    if (desc->weight_dtype != 0 && desc->weight_dtype != 7) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_llama_create: weight dtype %d not supported", desc->weight_dtype);
+    if (desc->weight_dtype != 0 && desc->weight_dtype != 1 && desc->weight_dtype != 7) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_llama_create: weight dtype %d not supported", desc->weight_dtype);
     ModelDesc md;
     md.V = desc->vocab; md.d = desc->embd; md.H = desc->heads; md.L = desc->layers; md.F = desc->ff; md.ctx = desc->ctx;
     if (!md.H || !md.d || md.d % md.H) LH_FAIL(ctx, LH_ESHAPE, "lh_llama_create: bad embd/heads");
@@ -3191,6 +3373,7 @@ int lh_llama_create(lh_ctx* ctx, const lh_llama_desc* desc, lh_llama** out) {
     auto needw = [&](lh_buf b, uint64_t rows, uint64_t cols, const char* what, const float** dst, const float** sc) -> int {
         Buffer* bf = find_buffer(ctx->ds, b);
         if (!bf) LH_FAIL(ctx, LH_EINVAL, "lh_llama_create: %s is not a registered buffer", what);
+        if (md.wtype == 1 && bf->dtype != 1) LH_FAIL(ctx, LH_EINVAL, "lh_llama_create: weight_dtype 1 (f16) but %s is a dtype-%d buffer: every matrix of an f16 model must be f16", what, bf->dtype);
         if (bf->nfloats < rows * cols || bf->dtype != md.wtype) LH_FAIL(ctx, LH_ESHAPE, "lh_llama_create: %s has the wrong size or dtype", what);
         if (md.wtype == 7 && (bf->rows != rows || bf->cols != cols)) LH_FAIL(ctx, LH_ESHAPE, "lh_llama_create: %s block-int8 shape mismatch", what);
         *dst = bf->dev;

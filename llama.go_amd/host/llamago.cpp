@@ -381,7 +381,7 @@ struct llama_layer { ml_tensor *attentionNorm, *wq, *wk, *wv, *wo, *ffn_norm, *w
 struct llama_model {  // llama.go:181-193
     llama_hparams hp;
     uint32_t ffSize;
-    int wtype = ML_TYPE_F32;  // dtype of the weight matrices (ML_TYPE_Q8_0 after llamago_QuantizeModelQ8)
+    int wtype = ML_TYPE_F32;  // dtype of the weight matrices (ML_TYPE_Q8_0 after llamago_QuantizeModelQ8; ML_TYPE_F16 after llamago_NarrowModelF16 / llamago_LoadModelKeepF16)
     ml_tensor *tokEmbeddings = nullptr, *norm = nullptr, *output = nullptr;
     std::vector<llama_layer> layers;
     uint32_t layer0, layer1;
@@ -415,17 +415,18 @@ static void eval_cache_free(struct eval_cache* c);
 static uint32_t ff_size(uint32_t embd, uint32_t mult) { return ((2 * (4 * embd) / 3 + mult - 1) / mult) * mult; }  // llama.go:761
 
 // persistent device tensor without a host copy
-static ml_tensor* new_weight(uint32_t dims, uint32_t ne0, uint32_t ne1) {
+// (reg = false: no device buffer yet - llamago_LoadModelKeepF16 registers a matrix's halves when it reads them)
+static ml_tensor* new_weight(uint32_t dims, uint32_t ne0, uint32_t ne1, bool reg = true) {
     lh_ctx* h = model_ctx();
     if (!h) return nullptr;
     ml_tensor* t = new_leaf(ML_TYPE_F32, dims, ne0, ne1, 1, /*alloc_host=*/false);
     t->persistent = true;
     const uint32_t ne[4] = {ne0, ne1, 1, 1};
-    if (lh_tensor_register(h, 0, 0, ne, 1, nullptr, &t->buf)) { g_err = lh_last_error(h); delete t; return nullptr; }
+    if (reg && lh_tensor_register(h, 0, 0, ne, 1, nullptr, &t->buf)) { g_err = lh_last_error(h); delete t; return nullptr; }
     return t;
 }
 
-static llama_model* alloc_model(const llama_hparams* hp, uint32_t layer0, uint32_t layer1) {  // llama.go:819-863
+static llama_model* alloc_model(const llama_hparams* hp, uint32_t layer0, uint32_t layer1, bool mats = true) {  // llama.go:819-863; mats = false: matrices without a device buffer yet
     llama_model* m = new llama_model();
     m->hp = *hp;
     m->ffSize = ff_size(hp->embdSize, hp->multSize);
@@ -436,20 +437,20 @@ static llama_model* alloc_model(const llama_hparams* hp, uint32_t layer0, uint32
     if (layer0 == 0) ok &= (m->tokEmbeddings = new_weight(2, d, V)) != nullptr;
     if (layer1 == hp->layersCount) {
         ok &= (m->norm = new_weight(1, d, 1)) != nullptr;
-        ok &= (m->output = new_weight(2, d, V)) != nullptr;
+        ok &= (m->output = new_weight(2, d, V, mats)) != nullptr;
     }
     m->layers.assign(hp->layersCount, llama_layer{});
     for (uint32_t i = layer0; i < layer1 && ok; i++) {
         llama_layer& l = m->layers[i];
         ok &= (l.attentionNorm = new_weight(1, d, 1)) != nullptr;
-        ok &= (l.wq = new_weight(2, d, d)) != nullptr;
-        ok &= (l.wk = new_weight(2, d, d)) != nullptr;
-        ok &= (l.wv = new_weight(2, d, d)) != nullptr;
-        ok &= (l.wo = new_weight(2, d, d)) != nullptr;
+        ok &= (l.wq = new_weight(2, d, d, mats)) != nullptr;
+        ok &= (l.wk = new_weight(2, d, d, mats)) != nullptr;
+        ok &= (l.wv = new_weight(2, d, d, mats)) != nullptr;
+        ok &= (l.wo = new_weight(2, d, d, mats)) != nullptr;
         ok &= (l.ffn_norm = new_weight(1, d, 1)) != nullptr;
-        ok &= (l.w1 = new_weight(2, d, F)) != nullptr;
-        ok &= (l.w2 = new_weight(2, F, d)) != nullptr;
-        ok &= (l.w3 = new_weight(2, d, F)) != nullptr;
+        ok &= (l.w1 = new_weight(2, d, F, mats)) != nullptr;
+        ok &= (l.w2 = new_weight(2, F, d, mats)) != nullptr;
+        ok &= (l.w3 = new_weight(2, d, F, mats)) != nullptr;
     }
     if (!ok) { llama_FreeModel(m); return nullptr; }
     return m;
@@ -572,7 +573,22 @@ static uint16_t f32_to_f16(float f) {
 static uint32_t rd_u32(FILE* f) { unsigned char b[4]; if (fread(b, 1, 4, f) != 4) return 0; return (uint32_t)b[3] << 24 | (uint32_t)b[2] << 16 | (uint32_t)b[1] << 8 | b[0]; }
 static const uint32_t LLAMA_FILE_MAGIC = 0x67676a74u;
 
-llama_model* llama_LoadModel(const char* fileName, uint32_t ctxSize) {
+static bool is_matrix_name(const char* name) {   // the seven matrices of a layer and `output`: what an f16 model keeps as halves
+    if (!strcmp(name, "output.weight")) return true;
+    const char* dot = strstr(name, "layers.") == name ? strchr(name + 7, '.') : nullptr;
+    if (!dot) return false;
+    static const char* mats[7] = {"attention.wq.weight", "attention.wk.weight", "attention.wv.weight", "attention.wo.weight",
+                                  "feed_forward.w1.weight", "feed_forward.w2.weight", "feed_forward.w3.weight"};
+    for (const char* mn : mats) if (!strcmp(dot + 1, mn)) return true;
+    return false;
+}
+static llama_model* load_model(const char* fileName, uint32_t ctxSize, bool keep_f16);
+llama_model* llama_LoadModel(const char* fileName, uint32_t ctxSize) { return load_model(fileName, ctxSize, false); }
+llama_model* llamago_LoadModelKeepF16(const char* fileName, uint32_t ctxSize) { return load_model(fileName, ctxSize, true); }
+int llamago_ModelWeightType(const llama_model* m) { return m ? m->wtype : -1; }
+// keep_f16: when EVERY weight matrix of the file is f16, the halves go to HBM as they are (dtype 1; norm vectors and tok_embeddings f32 as ever);
+// any other file loads exactly as without the flag
+static llama_model* load_model(const char* fileName, uint32_t ctxSize, bool keep_f16) {
     FILE* f = fopen(fileName, "rb");
     if (!f) return (llama_model*)halt("[ERROR] cannot open model file");
     if (rd_u32(f) != LLAMA_FILE_MAGIC) { fclose(f); return (llama_model*)halt("[ERROR] Invalid model file! Wrong MAGIC in header"); }  // llama.go:722-732
@@ -584,7 +600,28 @@ llama_model* llama_LoadModel(const char* fileName, uint32_t ctxSize) {
     hp.layersCount = rd_u32(f); hp.rotCount = rd_u32(f); hp.f16 = rd_u32(f);  // llama.go:743-749
     if (!hp.vocabSize || !hp.embdSize || !hp.headsCount || !hp.layersCount || !hp.multSize) { fclose(f); return (llama_model*)halt("[ERROR] Invalid model file! Bad hyper-parameters"); }
     for (uint32_t i = 0; i < hp.vocabSize; i++) { const uint32_t len = rd_u32(f); fseek(f, (long)len + 4, SEEK_CUR); }  // vocab llama.go:799-811 (not on the hot path)
-    llama_model* m = alloc_model(&hp, 0, 0);
+    if (keep_f16) {   // a first pass over the tensor headers: are all 7 * layers + 1 matrices there, and f16?
+        const long data0 = ftell(f);
+        const uint32_t d = hp.embdSize, F = ff_size(hp.embdSize, hp.multSize), V = hp.vocabSize;
+        uint64_t mats = 0;
+        for (;;) {
+            const uint32_t dims = rd_u32(f);
+            if (dims < 1 || dims > 2) break;
+            const uint32_t nameLen = rd_u32(f), dtype = rd_u32(f);
+            uint64_t n = 1;
+            for (uint32_t i = 0; i < dims; i++) n *= rd_u32(f);
+            char name[256];
+            if (nameLen >= sizeof name || fread(name, 1, nameLen, f) != nameLen) { keep_f16 = false; break; }
+            name[nameLen] = 0;
+            if (is_matrix_name(name)) { if (dtype != ML_TYPE_F16) { keep_f16 = false; break; } mats++; }
+            if (n > (uint64_t)std::max(V, F) * d || (dtype != ML_TYPE_F16 && dtype != ML_TYPE_F32)) { keep_f16 = false; break; }   // (the load below reports what is wrong)
+            const long off = (ftell(f) + 31) & ~31L;
+            if (fseek(f, off + (long)(n * (dtype == ML_TYPE_F16 ? 2 : 4)), SEEK_SET)) { keep_f16 = false; break; }
+        }
+        if (mats != 7ull * hp.layersCount + 1) keep_f16 = false;
+        fseek(f, data0, SEEK_SET);
+    }
+    llama_model* m = alloc_model(&hp, 0, 0, !keep_f16);
     if (!m) { fclose(f); return nullptr; }
     lh_ctx* h = model_ctx();
     std::vector<float> bounce;
@@ -605,6 +642,14 @@ llama_model* llama_LoadModel(const char* fileName, uint32_t ctxSize) {
         off = (off + 31) & ~31L;  // 32-byte alignment llama.go:926-933
         fseek(f, off, SEEK_SET);
         const uint64_t n = nelements(t);
+        if (keep_f16 && is_matrix_name(name)) {   // the halves as they are: no fp32 bounce, no fp32 copy in HBM
+            half.resize(n);
+            if (t->buf || dtype != ML_TYPE_F16 || fread(half.data(), 2, n, f) != n) { fclose(f); llama_FreeModel(m); return (llama_model*)halt("[ERROR] Failed to read FP16 tensor from model!"); }
+            const uint32_t ne4[4] = {t->ne[0], t->ne[1], 1, 1};
+            if (lh_tensor_register(h, 0, ML_TYPE_F16, ne4, 1, half.data(), &t->buf)) { g_err = lh_last_error(h); fclose(f); llama_FreeModel(m); return nullptr; }
+            t->type = ML_TYPE_F16;
+            continue;
+        }
         bounce.resize(n);
         if (dtype == ML_TYPE_F16) {  // widened to f32 at load, llama.go:938-941
             half.resize(n);
@@ -616,6 +661,7 @@ llama_model* llama_LoadModel(const char* fileName, uint32_t ctxSize) {
         if (lh_buf_upload(h, t->buf, 0, bounce.data(), n)) { g_err = lh_last_error(h); fclose(f); llama_FreeModel(m); return nullptr; }
     }
     fclose(f);
+    if (keep_f16) m->wtype = ML_TYPE_F16;
     return m;
 }
 
@@ -638,6 +684,7 @@ static int wr_tensor(FILE* f, const char* name, ml_tensor* t, int ftype) {  // s
 int llama_SaveModel(const llama_model* mc, const char* fileName, int ftype) {
     llama_model* m = (llama_model*)mc;
     if (m->layer0 != 0 || m->layer1 != m->hp.layersCount) return halt_rc("llama_SaveModel: partial (layer-sharded) model");
+    if (m->wtype == ML_TYPE_F16) return halt_rc("llama_SaveModel: the model's matrices are f16 in HBM; saving f16 models is not supported (llamago_WidenModelF16 first)");
     FILE* f = fopen(fileName, "wb");
     if (!f) return halt_rc("llama_SaveModel: cannot open file");
     wr_u32(f, LLAMA_FILE_MAGIC); wr_u32(f, 1);
@@ -1654,6 +1701,7 @@ int llamago_PipelineSync(llama_pipeline* p) { return lh_ctx_sync(p->mlctx->hip) 
 // (norm vectors and the embedding table, which is only gathered from, stay f32) and release the f32 copies.
 int llamago_QuantizeModelQ8(llama_model* m) {
     if (m->wtype == ML_TYPE_Q8_0) return 0;
+    if (m->wtype == ML_TYPE_F16) return halt_rc("llamago_QuantizeModelQ8: the model's matrices are f16 (quantise before narrowing)");
     { std::lock_guard<std::mutex> lk(m->mu);
       if (m->users > 0) return halt_rc("llamago_QuantizeModelQ8: contexts of this model are alive (their plans address the f32 weights); quantise before creating contexts"); }
     lh_ctx* h = model_ctx();
@@ -1675,6 +1723,41 @@ int llamago_QuantizeModelQ8(llama_model* m) {
     if (!rc) m->wtype = ML_TYPE_Q8_0;
     return rc;
 }
+// f16 matrices (ML_TYPE_F16, dtype 1 of the C-ABI): llamago_QuantizeModelQ8's shape.  Narrow: every weight MATRIX through lh_buf_narrow_f16 (round to
+// nearest even) and the f32 copies released; *n_changed = the elements whose value changed.  Widen: the inverse through lh_buf_widen_f16 - the model is
+// f32 again and holds the narrowed values (the tests' way to an fp32 twin without a file).
+static int convert_matrices(llama_model* m, const char* who, int from, int to, uint64_t* n_changed) {
+    char msg[256];
+    if (!m) { snprintf(msg, sizeof msg, "%s: null argument", who); return halt_rc(msg); }
+    if (m->wtype == to) { if (n_changed) *n_changed = 0; return 0; }
+    if (m->wtype != from) { snprintf(msg, sizeof msg, "%s: the model's matrices are dtype %d, not %s", who, m->wtype, from == ML_TYPE_F32 ? "f32" : "f16"); return halt_rc(msg); }
+    { std::lock_guard<std::mutex> lk(m->mu);
+      if (m->users > 0) { snprintf(msg, sizeof msg, "%s: contexts of this model are alive (their plans address the weights); convert before creating contexts", who); return halt_rc(msg); } }
+    lh_ctx* h = model_ctx();
+    if (!h) return 1;
+    uint64_t total = 0;
+    auto cv = [&](ml_tensor* t) -> int {
+        if (!t) return 0;
+        lh_buf nb = 0;
+        uint64_t ch = 0;
+        if (to == ML_TYPE_F16 ? lh_buf_narrow_f16(h, t->buf, t->ne[1], t->ne[0], &nb, &ch) : lh_buf_widen_f16(h, t->buf, &nb)) return halt_rc(lh_last_error(h));
+        lh_buf_free(h, t->buf);
+        t->buf = nb;
+        t->type = to;
+        total += ch;
+        return 0;
+    };
+    int rc = cv(m->output);
+    for (uint32_t i = m->layer0; i < m->layer1 && !rc; i++) {
+        llama_layer& l = m->layers[i];
+        rc |= cv(l.wq); rc |= cv(l.wk); rc |= cv(l.wv); rc |= cv(l.wo); rc |= cv(l.w1); rc |= cv(l.w2); rc |= cv(l.w3);
+    }
+    if (!rc) m->wtype = to;
+    if (n_changed) *n_changed = total;
+    return rc;
+}
+int llamago_NarrowModelF16(llama_model* m, uint64_t* n_changed) { return convert_matrices(m, "llamago_NarrowModelF16", ML_TYPE_F32, ML_TYPE_F16, n_changed); }
+int llamago_WidenModelF16(llama_model* m) { return convert_matrices(m, "llamago_WidenModelF16", ML_TYPE_F16, ML_TYPE_F32, nullptr); }
 // Test instrumentation (tests/test_gpu_attention_bound.py: the probe layer): one fp32 tensor of the model replaced by host values.
 int llamago_SetModelTensor(llama_model* m, const char* name, const float* data, uint64_t n) {
     if (!m || !name || !data) return halt_rc("llamago_SetModelTensor: null argument");
@@ -1683,6 +1766,7 @@ int llamago_SetModelTensor(llama_model* m, const char* name, const float* data, 
     ml_tensor* t = llama_ModelTensor(m, name);
     char msg[256];
     if (!t) { snprintf(msg, sizeof msg, "llamago_SetModelTensor: the model has no tensor \"%s\"", name); return halt_rc(msg); }
+    if (t->type == ML_TYPE_F16) { snprintf(msg, sizeof msg, "llamago_SetModelTensor: \"%s\" is f16 (set tensors before llamago_NarrowModelF16)", name); return halt_rc(msg); }
     if (t->type != ML_TYPE_F32) { snprintf(msg, sizeof msg, "llamago_SetModelTensor: \"%s\" is quantised (set tensors before llamago_QuantizeModelQ8)", name); return halt_rc(msg); }
     if (n != nelements(t)) { snprintf(msg, sizeof msg, "llamago_SetModelTensor: \"%s\" has %llu elements, %llu given", name, (unsigned long long)nelements(t), (unsigned long long)n); return halt_rc(msg); }
     lh_ctx* h = model_ctx();

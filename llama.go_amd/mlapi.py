@@ -221,6 +221,13 @@ class MLLib:
     def LoadModel(self, path, ctxSize):
         return Model(self, self._chk(self.lib.llama_LoadModel(os.fsencode(path), ctxSize), "llama_LoadModel"))
 
+    def LoadModelKeepF16(self, path, ctxSize):
+        """llamago_LoadModelKeepF16 (product only): LoadModel, except that a file whose weight matrices are all f16 keeps them f16 in HBM
+        (Model.weight_type == 1); any other file loads as LoadModel loads it."""
+        f = self.lib.llamago_LoadModelKeepF16
+        f.restype, f.argtypes = VP, [C.c_char_p, C.c_uint32]
+        return Model(self, self._chk(f(os.fsencode(path), ctxSize), "llamago_LoadModelKeepF16"))
+
 
 def make_hparams(vocab, embd, mult, heads, layers, ctx=128):
     hp = HParams()
@@ -264,6 +271,31 @@ class Model:
         if f(self.h):
             raise MLError(f"llamago_QuantizeModelQ8: {self.ml.last_error()}")
         return self
+
+    def NarrowF16(self):
+        """llamago_NarrowModelF16 (product only): every weight matrix converted to f16 in HBM (round to nearest even), the f32 copies released.
+        Returns the number of elements whose value changed.  Before any context of the model exists."""
+        f = self.ml.lib.llamago_NarrowModelF16
+        f.restype, f.argtypes = C.c_int, [VP, C.POINTER(c_u64)]
+        n = c_u64(0)
+        if f(self.h, C.byref(n)):
+            raise MLError(f"llamago_NarrowModelF16: {self.ml.last_error()}")
+        return int(n.value)
+
+    def WidenF16(self):
+        """llamago_WidenModelF16 (product only): the inverse - an f32 model again, holding the narrowed values exactly."""
+        f = self.ml.lib.llamago_WidenModelF16
+        f.restype, f.argtypes = C.c_int, [VP]
+        if f(self.h):
+            raise MLError(f"llamago_WidenModelF16: {self.ml.last_error()}")
+        return self
+
+    @property
+    def weight_type(self):
+        """llamago_ModelWeightType (product only): 0 = f32, 1 = f16, 7 = block-int8 weight matrices."""
+        f = self.ml.lib.llamago_ModelWeightType
+        f.restype, f.argtypes = C.c_int, [VP]
+        return int(f(self.h))
 
     def SetTensor(self, name, values):
         """llamago_SetModelTensor (product only, test instrumentation): one fp32 tensor of the model overwritten in HBM; values in the layout read()
