@@ -121,6 +121,27 @@ int llamago_DraftLookup(const uint32_t* window, uint32_t n_window, const lh_look
 int llamago_Verify(llama_context* c, const uint32_t* tokens, uint32_t n, uint32_t past, uint32_t* ids_out, uint32_t* n_accepted, float* logits);
 int llamago_DecodeLookup(llama_context* c, uint32_t first_token, uint32_t past, uint32_t n_steps, const lh_lookup_params* lp, uint32_t* out_tokens,
                          float* logits_last, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap);
+/* Draft-model speculative decoding (lh_llama_decode_draft; the rule, the state left behind and the refusals are stated in llamahip.h): a second model
+ * drafts, the target verifies, the ids are those of llamago_DecodeGreedyResident on the target.  llama_NewContext makes one lh_ctx per context and the loop
+ * needs both plans on one stream, so a PAIR creates its two contexts (one KV cache each, ctxSize positions) over one ml.Context.
+ * llamago_DraftPairTarget / llamago_DraftPairDraft hand them out as ordinary llama_context*: llama_Eval, llama_GreedyDecode, llamago_DecodeLookup and the rest
+ * work on them (one at a time: they share a stream); they belong to the pair - never pass them to llama_ReleaseContext.  The caller evaluates the prompt on
+ * BOTH before llamago_DecodeDraft (the precondition of lh_llama_decode_draft).  llamago_DraftPairReplaceDraft frees the draft context and makes a fresh
+ * one (an empty cache) over another model; the target context stays.  llamago_FreeDraftPair frees both contexts; the models stay the caller's.
+ * llamago_DecodeDraftContexts is the call underneath on any two contexts: those of a pair, or - to be refused - two that do not share a stream, or the same
+ * one twice.  Both Decode calls return 0 or a NEGATIVE LH_E* code, never 1 (the other llamago_* entry points return 1): the code of lh_llama_decode_draft, LH_EINVAL for a
+ * null pair or context, LH_EHIP when a context's stage could not be made (message: ml_LastError).  A caller tells a refusal (LH_EINVAL, LH_EUNSUPPORTED: both
+ * contexts untouched) from a failure by it. */
+typedef struct llama_draft_pair llama_draft_pair;
+llama_draft_pair* llamago_NewDraftPair(llama_model* target_model, llama_model* draft_model, uint32_t ctxSize);
+void llamago_FreeDraftPair(llama_draft_pair* p);
+llama_context* llamago_DraftPairTarget(llama_draft_pair* p);
+llama_context* llamago_DraftPairDraft(llama_draft_pair* p);
+int llamago_DraftPairReplaceDraft(llama_draft_pair* p, llama_model* draft_model);
+int llamago_DecodeDraft(llama_draft_pair* p, uint32_t first_token, uint32_t past, uint32_t n_steps, uint32_t draft_len, uint32_t* out_tokens, float* logits_last,
+                        lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap);
+int llamago_DecodeDraftContexts(llama_context* target, llama_context* draft, uint32_t first_token, uint32_t past, uint32_t n_steps, uint32_t draft_len,
+                                uint32_t* out_tokens, float* logits_last, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap);
 /* The same for sampled generation (lh_sample_rows, lh_llama_decode_sample_lookup; ring view, draw and commit per row are stated in llamahip.h).
  * llamago_SampleRows: the multi-row sampler alone on host arrays, on the model context's device - row r of logits [n_rows][n_logits] sampled as
  * call draw0 + r over the ring behind tokens[1..r].  llamago_SampleDecodeLookup: llama_SampleDecode through verify passes that sample every row -

@@ -325,6 +325,38 @@ int lh_llama_verify(lh_llama* m, const uint32_t* tokens, uint32_t n, uint32_t pa
 int lh_llama_decode_lookup(lh_llama* m, uint32_t first_token, uint32_t past, uint32_t n_steps, const lh_lookup_params* lp,
                            uint32_t* out_tokens, float* logits_last_host, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap);
 
+/* ---- lossless draft-model speculative decoding (greedy): a second model drafts ------------------------------------------
+ * lh_llama_decode_greedy of `target` through verify passes whose drafts come from `draft`, a second whole model with a KV cache of its own on the
+ * same lh_ctx: the target's own block-int8 or f16 form, another seed, a smaller geometry - anything with the same vocabulary (weight_dtype 0, 1 or
+ * 7).  The draft can only change how many passes are needed, never an id.  The rule (tests/draft_model_ref.py restates it):
+ *   state   pos = the position of the pending token t; produced = the ids in the output list; ctx = min(target window, draft window);
+ *           R = draft_len + 1, lowered to the largest row count the TARGET plan's shapes carry (as lh_llama_decode_lookup lowers it); R = 1 = plain
+ *           greedy steps of the target, nothing is drafted.
+ *   a pass  limit = min(ctx - (pos + 1), n_steps - produced - 1), k = min(R - 1, limit): the lookup loop's limit.
+ *     draft   e_0 = t; for j = 0..k the draft model evaluates e_j at position pos + j of its own cache as a one-token step, and e_{j+1} is that
+ *             step's greedy id (lowest index on ties).  The step j = k is there for the draft's cache row only, its id is not used: whatever the
+ *             outcome a <= k, the draft's cache then holds the committed tokens through pos + a - no catch-up step, no condition on past.
+ *     verify  the target evaluates [e_0 .. e_k] at pos .. pos + k as ONE pass of R rows (the rows behind k are filler that never counts); y_i = the
+ *             greedy id of row i; a = the largest a <= k with y_i == e_{i+1} for all i < a.
+ *     commit  y_0 .. y_a go to the output; pos += a + 1, t = y_a, produced += a + 1.
+ *   stats and trace as lh_llama_decode_lookup: drafted += k, accepted += a, empty counts the passes with k = 0, trace[s] = (k_s << 8) | a_s.
+ * The pass is device-resident: k_draft_model_begin (the draft's step parameters, k, filler), R one-token steps of the draft (each id straight
+ * into the target's token table), the target's R-row pass, k_batch_argmax, k_spec_accept - all enqueued on the context's stream with no host
+ * round trip inside a pass or between passes.  The launches of a pass are enqueued kernel by kernel; they are not replayed from a captured graph
+ * (DESIGN 3i says why).  Near the window's end, where ctx - pos < R, narrower passes run; a pass that would stand outside the window is never
+ * enqueued, and should one be, k_draft_model_begin ends the loop in the device state and the call fails (LH_EHIP).  The host looks (one 64-byte
+ * read) where the lookup loop looks.
+ * Precondition (the library cannot check it): both caches hold the same tokens at [0, past).
+ * Afterwards: out_tokens = exactly the n_steps ids of lh_llama_decode_greedy(target, ...) from the same state, logits_last_host byte-equal to its;
+ * the target stands as that loop leaves it (position past + n_steps, every evaluated token in its history, usable by lh_llama_decode_lookup); the
+ * draft holds valid rows and history for [0, past + n_steps) (with R = 1 through one Eval of the evaluated tokens behind the steps); rows behind
+ * that are stale in both caches.  No context swap here: the window bound replaces it.
+ * Refused before anything is enqueued, both contexts untouched and usable: draft == target, different lh_ctx, different vocabularies, draft_len
+ * outside 1..7 (block-int8 target: 1..3), first_token >= vocab, past + n_steps > ctx (LH_EINVAL); a layer-shard stage on either side
+ * (LH_EUNSUPPORTED). */
+int lh_llama_decode_draft(lh_llama* target, lh_llama* draft, uint32_t first_token, uint32_t past, uint32_t n_steps, uint32_t draft_len,
+                          uint32_t* out_tokens, float* logits_last_host, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap);
+
 /* ---- lossless lookup-draft speculative decoding (sampled) ------------------------------------------------------------
  * The uniforms of the device sampler are counter-based (seed, sampling call, rank), so the id of sampling call s is a pure function of the
  * logits row, the lastNTokens ring at that moment and s.  A pass over [pending, d1..dk] therefore samples every row at once, and the kept ids

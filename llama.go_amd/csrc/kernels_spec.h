@@ -175,6 +175,27 @@ __global__ __launch_bounds__(SPEC_TH) void k_spec_accept(const uint32_t* __restr
     if (r == 0) st->k = k;
 }
 
+// ---- a second model drafts (lh_llama_decode_draft; the rule is stated in include/llamahip.h) ----
+// In front of the draft model's one-token steps of a pass of n rows (n <= the table's n_table rows): the draft plan's step parameters become
+// {the pending token, its position, step 0}; st->k = min(n - 1, the loop's limit over ctx = min(target window, draft window)); tok[1..n_table) get
+// the pending token, so every row the draft's steps do not write holds a valid id (filler).  The steps then write their ids into tok[1..n) through
+// k_argmax_advance's argmax_out; entries behind k are filler too and never count (k_spec_accept reads st->k).  The host never enqueues a pass whose
+// pending token stands outside the window.  Should it: the pass must not go through unnoticed, so the loop is ended in the state - n_steps = 0 makes
+// k_spec_accept commit nothing, and the host's look behind the pass fails with "inconsistent state".  The draft's steps still run (the launches are
+// already enqueued) and need rows inside the cache, so they get the last n; the call that did this returns an error.
+__global__ void k_draft_model_begin(SpecState* st, uint32_t* __restrict__ tok, StepParams* __restrict__ draft_sp, uint32_t n, uint32_t n_table, uint32_t ctx) {
+    const uint32_t r = threadIdx.x;
+    const uint32_t pending = tok[0], pos = st->pos;
+    if (r >= 1 && r < n_table && r < SPEC_ROWS_MAX) tok[r] = pending;
+    if (r == 0) {
+        const bool inside = pos < ctx && pos + n <= ctx;        // every row of this pass, on both caches
+        if (!inside) st->n_steps = 0;
+        const uint32_t limit = inside ? spec_limit(pos, st->produced, st->n_steps, ctx) : 0;
+        st->k = n ? (n - 1 < limit ? n - 1 : limit) : 0;
+        draft_sp->token = pending; draft_sp->past = inside ? pos : (ctx - n < ctx ? ctx - n : 0); draft_sp->step = 0; draft_sp->pad = 0;
+    }
+}
+
 // ---- the pods of a batch (lh_batch_decode_lookup): pod i owns rows [i * R, (i + 1) * R) of the pass's table, state st[i] and window win[i][ctx + 1] ----
 // What the host reads between runs of passes: 16 bytes per pod.
 struct SpecPodSum { uint32_t pos, produced, passes, last_a; };

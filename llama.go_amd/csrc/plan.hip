@@ -3096,6 +3096,76 @@ static int spec_decode_lookup(Plan* p, uint32_t first_token, uint32_t past, uint
     return 0;
 }
 
+// ---- lh_llama_decode_draft: a second model drafts (the rule is stated in include/llamahip.h) ------------------------------------------
+// A pass of n rows = k_draft_model_begin (the draft's step parameters, st->k, filler), n one-token steps of the DRAFT plan - the decode step's own
+// kernels, each step's greedy id written straight into the target's tok[j + 1] (the last step is there for the draft's cache row only) - then the
+// target's pass over tok[0..n) exactly as the lookup loop runs it: plan_eval over the row table, k_batch_argmax, k_spec_accept with no next draft.
+// State, table and tokens are the target's Spec; both plans sit on one lh_ctx, so one stream orders everything.  Every pass is enqueued kernel by
+// kernel: the pass as ONE captured graph over both plans is left out (DESIGN 3i says why), so the launches of a pass are not replayed.
+static int draft_enqueue_pass(Plan* p, Plan* d, uint32_t n, uint32_t n_table, uint32_t ctxw) {
+    lh_ctx* ctx = p->ctx;
+    Spec* s = p->spec;
+    int rc;
+    LH_TRACE("k_draft_model_begin/r%u", n);
+    LH_LAUNCH(k_draft_model_begin, dim3(1), dim3(64), 0, ctx->stream, s->st, s->tok, d->sp_dev, n, n_table, ctxw);
+    LH_HIP(ctx, hipGetLastError());
+    for (uint32_t j = 0; j < n; ++j)
+        if ((rc = enqueue_decode(d, d->sp_dev, nullptr, nullptr, 1, j + 1 < n ? s->tok + j + 1 : nullptr))) return rc;
+    const SpecLookup none = {nullptr, 0, 0, 1, 1};
+    return spec_enqueue_pass(p, n, n_table, none, 0);
+}
+static int spec_decode_draft(Plan* p, Plan* d, uint32_t first_token, uint32_t past, uint32_t n_steps, uint32_t R, uint32_t* out_tokens, float* logits_last_host,
+                             lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap) {
+    lh_ctx* ctx = p->ctx;
+    const ModelDesc& md = p->md;
+    const uint32_t ctxw = std::min(md.ctx, d->md.ctx);
+    int rc;
+    // every allocation of both plans, in front of the first pass
+    if ((rc = spec_ensure(p, 0, n_steps))) return rc;
+    if ((rc = plan_ensure_rows(p, R))) return rc;
+    if ((rc = ensure_out_tokens(p, n_steps))) return rc;
+    if ((rc = ensure_out_tokens(d, SPEC_ROWS_MAX))) return rc;
+    Spec* s = p->spec;
+    s->smp = false;
+    SpecToks t;
+    for (uint32_t r = 0; r < SPEC_ROWS_MAX; ++r) t.t[r] = first_token;
+    if ((rc = spec_set(p, past, 0, n_steps, t, 0, R, 1))) return rc;
+    uint32_t pos = past, produced = 0;
+    SpecState hs = {};
+    while (produced < n_steps) {
+        // past + n_steps <= ctxw (checked by the caller) and pos = past + produced: a position is left in both windows
+        const uint32_t n = spec_pass_rows(p, std::min(R, ctxw - pos));
+        if (n == R) {
+            // `produced` and `pos` are exact here; q passes move them on by q..q*R: as many as can neither pass n_steps nor leave the window run unseen
+            const uint32_t q = std::max(1u, std::min((n_steps - produced) / R, (ctxw - pos) / R));
+            for (uint32_t j = 0; j < q; ++j) if ((rc = draft_enqueue_pass(p, d, R, R, ctxw))) return rc;
+        } else if ((rc = draft_enqueue_pass(p, d, n, R, ctxw))) {   // the window's end: a narrower pass
+            return rc;
+        }
+        LH_HIP(ctx, hipMemcpyAsync(&hs, s->st, sizeof hs, hipMemcpyDeviceToHost, ctx->stream));
+        LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (hs.produced <= produced || hs.produced > n_steps || hs.pos != past + hs.produced) LH_FAIL(ctx, LH_EHIP, "lh_llama_decode_draft: a pass left an inconsistent state");
+        pos = hs.pos; produced = hs.produced;
+    }
+    std::vector<uint32_t> ids(n_steps);
+    LH_HIP(ctx, hipMemcpyAsync(ids.data(), spec_out(p), (size_t)n_steps * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (logits_last_host) LH_HIP(ctx, hipMemcpyAsync(logits_last_host, p->logits + (size_t)hs.last_a * md.V, (size_t)md.V * 4, hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<uint16_t> tr;
+    const uint32_t n_tr = trace ? std::min(std::min(trace_cap, hs.passes), s->trace_cap) : 0;
+    if (n_tr) { tr.resize(n_tr); LH_HIP(ctx, hipMemcpyAsync(tr.data(), s->trace, (size_t)n_tr * 2, hipMemcpyDeviceToHost, ctx->stream)); }
+    LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    // step i evaluated (i == 0 ? first_token : id i - 1) at position past + i, on both caches
+    for (uint32_t i = 0; i < n_steps; ++i) {
+        const uint32_t tk = i ? ids[i - 1] : first_token;
+        p->record(past + i, tk);
+        d->record(past + i, tk);
+    }
+    if (out_tokens) memcpy(out_tokens, ids.data(), (size_t)n_steps * 4);
+    if (n_tr) memcpy(trace, tr.data(), (size_t)n_tr * 2);
+    if (stats) { stats->passes = hs.passes; stats->rows = R; stats->drafted = hs.drafted; stats->accepted = hs.accepted; stats->empty = hs.empty; }
+    return 0;
+}
+
 // ---- lh_batch_decode_lookup: the same loop for the pods of a batch -------------------------------------------------------------------
 // A pass = the batched plan_eval of P * R rows on pod 0's plan (row i * R + r = row r of pod i, on pod i's cache: the table lh_batch_feed lays out for
 // P pods fed R tokens each, with the per-row attention kernels), k_batch_argmax over the P * R logits rows, k_spec_accept_pods.  One captured graph.
@@ -3559,6 +3629,46 @@ int lh_llama_decode_lookup(lh_llama* m, uint32_t first_token, uint32_t past, uin
         return LH_OK;
     }
     return spec_decode_lookup(p, first_token, past, n_steps, lp, R, out_tokens, logits_last_host, stats, trace, trace_cap);
+}
+
+int lh_llama_decode_draft(lh_llama* target, lh_llama* draft, uint32_t first_token, uint32_t past, uint32_t n_steps, uint32_t draft_len, uint32_t* out_tokens,
+                          float* logits_last_host, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap) {
+    if (!target || !draft) return LH_EINVAL;
+    lh_ctx* ctx = target->ctx;
+    Plan* p = target->plan;
+    Plan* d = draft->plan;
+    if (!n_steps) LH_FAIL(ctx, LH_EINVAL, "lh_llama_decode_draft: n_steps = 0");
+    const ModelDesc& md = p->md;
+    const ModelDesc& dd = d->md;
+    if (draft == target || d == p) LH_FAIL(ctx, LH_EINVAL, "lh_llama_decode_draft: the draft is the target itself (a draft needs a cache of its own)");
+    if (draft->ctx != ctx) LH_FAIL(ctx, LH_EINVAL, "lh_llama_decode_draft: target and draft belong to different lh_ctx (one stream must order both)");
+    LH_HIP(ctx, hipSetDevice(ctx->device));
+    if (!md.first_stage() || !md.last_stage()) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_llama_decode_draft: the target needs a whole-model plan (layers [%u, %u) of %u)", md.layer0, md.layer1, md.L);
+    if (!dd.first_stage() || !dd.last_stage()) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_llama_decode_draft: the draft needs a whole-model plan (layers [%u, %u) of %u)", dd.layer0, dd.layer1, dd.L);
+    if (dd.V != md.V) LH_FAIL(ctx, LH_EINVAL, "lh_llama_decode_draft: vocabularies differ (target %u, draft %u)", md.V, dd.V);
+    const uint32_t kmax = gemv_rows_max(md.wtype) - 1;
+    if (draft_len < 1 || draft_len > kmax) LH_FAIL(ctx, LH_EINVAL, "lh_llama_decode_draft: draft_len %u (1..%u for the target's weight type)", draft_len, kmax);
+    if (first_token >= md.V) LH_FAIL(ctx, LH_EINVAL, "lh_llama_decode_draft: token id %u outside the vocabulary of %u", first_token, md.V);
+    const uint32_t ctxw = std::min(md.ctx, dd.ctx);
+    if ((uint64_t)past + n_steps > ctxw)
+        LH_FAIL(ctx, LH_EINVAL, "lh_llama_decode_draft: past %u + n_steps %u exceeds the context window of %u (the smaller of target %u and draft %u; this loop does not swap context)",
+                past, n_steps, ctxw, md.ctx, dd.ctx);
+    int rc;
+    const uint32_t R = spec_pass_rows(p, draft_len + 1);
+    if (R == 1) {   // no multi-row pass on the target's shapes: plain greedy steps of the target, nothing is drafted
+        std::vector<uint32_t> ids(n_steps);
+        if ((rc = lh_llama_decode_greedy(target, first_token, past, n_steps, ids.data(), logits_last_host))) return rc;
+        // the draft's cache and history follow in ONE Eval of the tokens the steps evaluated, so that the state both contexts are left in does not depend on R
+        std::vector<uint32_t> ev(n_steps);
+        for (uint32_t i = 0; i < n_steps; ++i) ev[i] = i ? ids[i - 1] : first_token;
+        if ((rc = plan_eval(d, ev.data(), nullptr, nullptr, n_steps, past, true))) return rc;
+        LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (out_tokens) memcpy(out_tokens, ids.data(), (size_t)n_steps * 4);
+        if (stats) { stats->passes = n_steps; stats->rows = 1; stats->drafted = 0; stats->accepted = 0; stats->empty = n_steps; }
+        if (trace) for (uint32_t i = 0; i < n_steps && i < trace_cap; ++i) trace[i] = 0;
+        return LH_OK;
+    }
+    return spec_decode_draft(p, d, first_token, past, n_steps, R, out_tokens, logits_last_host, stats, trace, trace_cap);
 }
 
 }  // extern "C"

@@ -197,6 +197,21 @@ func (st *StageHIP) DecodeLookup(firstToken, pastCount, nSteps, draftMax, ngramM
 	return out, stats
 }
 
+// DecodeDraft is the same greedy loop through verify passes drafted by a SECOND model (lh_llama_decode_draft; the rule is stated in
+// include/llamahip.h): draft is a whole-model stage with a KV cache of its own on the same ContextHIP as st - the target's block-int8 or f16
+// form, or a smaller model with the same vocabulary - and both caches hold the same tokens below pastCount.  Exactly the nSteps ids the
+// target's one-token loop produces; the draft only changes how many passes that takes.  draftLen is 1..7 (block-int8 target: 1..3) and
+// pastCount + nSteps must stay inside both windows (no context swap here).  C++ twin: llamago_DecodeDraft.
+func (st *StageHIP) DecodeDraft(draft *StageHIP, firstToken, pastCount, nSteps, draftLen uint32) ([]uint32, SpecStatsHIP) {
+	out := make([]uint32, nSteps)
+	var stats SpecStatsHIP
+	if rc := C.lh_llama_decode_draft(st.h, draft.h, C.uint32_t(firstToken), C.uint32_t(pastCount), C.uint32_t(nSteps), C.uint32_t(draftLen),
+		(*C.uint32_t)(unsafe.Pointer(&out[0])), nil, (*C.lh_spec_stats)(unsafe.Pointer(&stats)), nil, 0); rc != 0 {
+		hipHalt(st.ctx.hip.ctx)
+	}
+	return out, stats
+}
+
 // DecodeSampleLookup is the generation loop of server.Do (server.go:127-217: ring of ringSize zeros, prompt Eval, then sample -> append -> Eval)
 // through lookup-drafted verify passes that sample every row (lh_llama_decode_sample_lookup): row i of a pass is sampled as call draw + i over
 // the lastNTokens ring as if the draft in front of it had been appended, so the kept ids are exactly the nPredict ids of the one-token sampled

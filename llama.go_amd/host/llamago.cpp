@@ -408,6 +408,7 @@ struct llama_context {  // llama.go:83-88
     std::vector<float> embedding;  // lctx.Embedding (llama.go:88; allocated when ModelParams.Embedding is set, llama.go:414-419)
     lh_llama* resident = nullptr;  // plan handle for the device-resident loop / stages (created on demand)
     bool holds_model = false;
+    bool owns_mlctx = true;        // false: a context of a llama_draft_pair, whose ml.Context belongs to the pair
     struct eval_cache* decode_graph = nullptr;   // the graph of a one-token Eval, kept between calls (see eval_cache)
 };
 
@@ -707,18 +708,20 @@ int llama_SaveModel(const llama_model* mc, const char* fileName, int ftype) {
 }
 
 // ---- context + Eval -----------------------------------------------------------------------------------
-llama_context* llama_NewContext(llama_model* m, uint32_t ctxSize, int maxThreads, int useAVX, int useNEON) {  // llama.go:91-103
+// shared != NULL: the context computes in that ml.Context, which stays its owner's (llamago_NewDraftPair)
+static llama_context* new_context(llama_model* m, uint32_t ctxSize, int maxThreads, int useAVX, int useNEON, ml_context* shared) {
     g_err.clear();
     const uint64_t nlayers = m->layer1 - m->layer0;
     const uint64_t size = (uint64_t)m->hp.embdSize * nlayers * ctxSize;
     if (size > 0xFFFFFFFFull) return (llama_context*)halt("[HALT] KV cache exceeds uint32 element count (ml.Tensor.NE is uint32)");
-    ml_context* mc = ml_NewContext(maxThreads, useAVX, useNEON);
+    ml_context* mc = shared ? shared : ml_NewContext(maxThreads, useAVX, useNEON);
     if (!mc) return nullptr;
     llama_context* c = new llama_context();
     c->model = m;
     c->ctxSize = ctxSize;
     m->hp.ctxSize = ctxSize;
     c->mlctx = mc;
+    c->owns_mlctx = !shared;
     c->K = new_weight(1, (uint32_t)size, 1);  // zero-filled like Go's make([]float32)
     c->V = new_weight(1, (uint32_t)size, 1);
     if (!c->K || !c->V) { llama_ReleaseContext(c); return nullptr; }
@@ -727,13 +730,16 @@ llama_context* llama_NewContext(llama_model* m, uint32_t ctxSize, int maxThreads
     c->holds_model = true;
     return c;
 }
+llama_context* llama_NewContext(llama_model* m, uint32_t ctxSize, int maxThreads, int useAVX, int useNEON) {  // llama.go:91-103
+    return new_context(m, ctxSize, maxThreads, useAVX, useNEON, nullptr);
+}
 void llama_ReleaseContext(llama_context* c) {  // llama.go:105-113
     if (!c) return;
     if (c->resident) lh_llama_destroy(c->resident);
     if (c->mlctx) lh_ctx_sync(c->mlctx->hip);
     eval_cache_free(c->decode_graph);
     free_tensor(c->K); free_tensor(c->V);   // per-pod KV caches go with their context (device memory returns to the pool)
-    ml_ReleaseContext(c->mlctx);
+    if (c->owns_mlctx) ml_ReleaseContext(c->mlctx);
     if (c->holds_model) model_release(c->model);
     delete c;
 }
@@ -1345,6 +1351,60 @@ int llamago_DecodeLookup(llama_context* c, uint32_t first_token, uint32_t past, 
     if (!r) return 1;
     if (lh_llama_decode_lookup(r, first_token, past, n_steps, lp, out_tokens, logits_last, stats, trace, trace_cap)) return halt_rc(lh_last_error(c->mlctx->hip));
     return 0;
+}
+// ---- draft-model speculative decoding (lh_llama_decode_draft): a target and a draft context on ONE ml.Context ----
+// llama_NewContext makes one lh_ctx per context and the loop needs both plans on one stream, so a pair creates its two contexts over a shared one.
+struct llama_draft_pair {
+    ml_context* mlctx = nullptr;
+    llama_context* target = nullptr;
+    llama_context* draft = nullptr;
+    uint32_t ctxSize = 0;
+};
+void llamago_FreeDraftPair(llama_draft_pair* p) {
+    if (!p) return;
+    llama_ReleaseContext(p->draft);
+    llama_ReleaseContext(p->target);
+    ml_ReleaseContext(p->mlctx);
+    delete p;
+}
+llama_draft_pair* llamago_NewDraftPair(llama_model* target_model, llama_model* draft_model, uint32_t ctxSize) {
+    g_err.clear();
+    if (!target_model || !draft_model || !ctxSize) return (llama_draft_pair*)halt("llamago_NewDraftPair: bad arguments");
+    llama_draft_pair* p = new llama_draft_pair();
+    p->ctxSize = ctxSize;
+    p->mlctx = ml_NewContext(1, 0, 0);
+    if (!p->mlctx) { delete p; return nullptr; }
+    p->target = new_context(target_model, ctxSize, 1, 0, 0, p->mlctx);
+    p->draft = p->target ? new_context(draft_model, ctxSize, 1, 0, 0, p->mlctx) : nullptr;
+    if (!p->target || !p->draft) { const std::string e = g_err; llamago_FreeDraftPair(p); g_err = e; return nullptr; }
+    return p;
+}
+llama_context* llamago_DraftPairTarget(llama_draft_pair* p) { return p ? p->target : nullptr; }
+llama_context* llamago_DraftPairDraft(llama_draft_pair* p) { return p ? p->draft : nullptr; }
+int llamago_DraftPairReplaceDraft(llama_draft_pair* p, llama_model* draft_model) {
+    if (!p || !draft_model) return halt_rc("llamago_DraftPairReplaceDraft: bad arguments");
+    llama_context* c = new_context(draft_model, p->ctxSize, 1, 0, 0, p->mlctx);
+    if (!c) return 1;
+    llama_ReleaseContext(p->draft);
+    p->draft = c;
+    return 0;
+}
+int llamago_DecodeDraftContexts(llama_context* target, llama_context* draft, uint32_t first_token, uint32_t past, uint32_t n_steps, uint32_t draft_len,
+                                uint32_t* out_tokens, float* logits_last, lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap) {
+    if (!target || !draft) { g_err = "llamago_DecodeDraft: null context"; return LH_EINVAL; }
+    lh_llama* t = resident(target);
+    lh_llama* d = target == draft ? t : resident(draft);
+    if (!t || !d) return LH_EHIP;   // (the stage could not be made: make_stage left the message)
+    if (const int rc = lh_llama_decode_draft(t, d, first_token, past, n_steps, draft_len, out_tokens, logits_last, stats, trace, trace_cap)) {
+        g_err = lh_last_error(target->mlctx->hip);
+        return rc;
+    }
+    return 0;
+}
+int llamago_DecodeDraft(llama_draft_pair* p, uint32_t first_token, uint32_t past, uint32_t n_steps, uint32_t draft_len, uint32_t* out_tokens, float* logits_last,
+                        lh_spec_stats* stats, uint16_t* trace, uint32_t trace_cap) {
+    if (!p) { g_err = "llamago_DecodeDraft: no pair"; return LH_EINVAL; }
+    return llamago_DecodeDraftContexts(p->target, p->draft, first_token, past, n_steps, draft_len, out_tokens, logits_last, stats, trace, trace_cap);
 }
 int llamago_SampleRows(const float* logits, uint32_t n_rows, uint32_t n_logits, const uint32_t* ring, uint32_t ring_size, uint32_t ring_pos, const uint32_t* tokens,
                        uint32_t topK, float topP, float temp, float repeatPenalty, uint64_t seed, uint64_t draw0, uint32_t* ids_out) {

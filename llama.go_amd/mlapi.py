@@ -507,6 +507,79 @@ class Context:
             self.h = None
 
 
+LH_EINVAL, LH_EUNSUPPORTED = -1, -4   # include/llamahip.h
+
+
+def _decode_draft(ml, fn, head, vocab, first_token, past, n_steps, draft_len, want_logits):
+    """The shared body of llamago_DecodeDraft / llamago_DecodeDraftContexts (head = the pair, or the two contexts)."""
+    fn.restype = C.c_int
+    fn.argtypes = [VP] * len(head) + [c_u32, c_u32, c_u32, c_u32, c_u32p, c_f32p, C.POINTER(SpecStats), C.POINTER(C.c_uint16), c_u32]
+    n = max(int(n_steps), 1)
+    out, st, tr = (c_u32 * n)(), SpecStats(), (C.c_uint16 * n)()
+    lg = np.empty(vocab, dtype=np.float32) if want_logits else None
+    rc = fn(*head, int(first_token), int(past), int(n_steps), int(draft_len), out, lg.ctypes.data_as(c_f32p) if want_logits else None, C.byref(st), tr, n)
+    if rc:
+        e = MLError(f"llamago_DecodeDraft ({rc}): {ml.last_error()}")
+        e.code = rc
+        raise e
+    stats = dict(passes=int(st.passes), rows=int(st.rows), drafted=int(st.drafted), accepted=int(st.accepted), empty=int(st.empty))
+    return [int(t) for t in out[:n_steps]], lg, stats, [(int(v) >> 8, int(v) & 0xFF) for v in tr[:min(st.passes, n)]]
+
+
+def decode_draft_contexts(target, draft, first_token, past, n_steps, draft_len, want_logits=False):
+    """llamago_DecodeDraftContexts: the target's resident greedy loop through verify passes drafted by a second model's context (lh_llama_decode_draft; the
+    rule is stated in include/llamahip.h and restated in tests/draft_model_ref.py).  The contexts of a DraftPair share a stream; any other two are refused.
+    -> (ids, last logits or None, stats dict(passes, rows, drafted, accepted, empty), trace list of (k, a) per pass).  A refusal raises MLError whose
+    `code` is the LH_E* code."""
+    L = target.ml.lib
+    return _decode_draft(target.ml, L.llamago_DecodeDraftContexts, (target.h, draft.h), target.model.hp.vocabSize, first_token, past, n_steps, draft_len, want_logits)
+
+
+class _PairContext(Context):
+    """A context that belongs to a DraftPair: llamago_FreeDraftPair releases it."""
+
+    def free(self):
+        self.h = None
+
+
+class DraftPair:
+    """llamago_NewDraftPair: a target and a draft context (one KV cache each) on ONE stream, for draft-model speculative decoding.  .target and .draft are
+    ordinary Contexts (Eval, GreedyDecode, DecodeLookup, ...) that belong to the pair: free the pair, not them.  Evaluate the prompt on BOTH, then
+    DecodeDraft."""
+
+    def __init__(self, target_model, draft_model, ctx):
+        self.ml = target_model.ml
+        L = self.ml.lib
+        L.llamago_NewDraftPair.restype, L.llamago_NewDraftPair.argtypes = VP, [VP, VP, c_u32]
+        L.llamago_DraftPairTarget.restype, L.llamago_DraftPairTarget.argtypes = VP, [VP]
+        L.llamago_DraftPairDraft.restype, L.llamago_DraftPairDraft.argtypes = VP, [VP]
+        L.llamago_DraftPairReplaceDraft.restype, L.llamago_DraftPairReplaceDraft.argtypes = C.c_int, [VP, VP]
+        L.llamago_FreeDraftPair.restype, L.llamago_FreeDraftPair.argtypes = None, [VP]
+        self.h = self.ml._chk(L.llamago_NewDraftPair(target_model.h, draft_model.h, int(ctx)), "llamago_NewDraftPair")
+        self.target = _PairContext(target_model, L.llamago_DraftPairTarget(self.h))
+        self.draft = _PairContext(draft_model, L.llamago_DraftPairDraft(self.h))
+
+    def ReplaceDraft(self, draft_model):
+        """llamago_DraftPairReplaceDraft: the draft context freed, a fresh one (an empty cache) over draft_model in its place; the target stays."""
+        L = self.ml.lib
+        if L.llamago_DraftPairReplaceDraft(self.h, draft_model.h):      # (on failure the pair keeps its draft, and so does this object)
+            raise MLError(f"llamago_DraftPairReplaceDraft: {self.ml.last_error()}")
+        self.draft.h = None
+        self.draft = _PairContext(draft_model, L.llamago_DraftPairDraft(self.h))
+        return self.draft
+
+    def DecodeDraft(self, first_token, past, n_steps, draft_len, want_logits=False):
+        """llamago_DecodeDraft -> (ids, last logits or None, stats dict, trace list of (k, a)): the shape of Context.DecodeLookup."""
+        L = self.ml.lib
+        return _decode_draft(self.ml, L.llamago_DecodeDraft, (self.h,), self.target.model.hp.vocabSize, first_token, past, n_steps, draft_len, want_logits)
+
+    def free(self):
+        if self.h:
+            self.target.h = self.draft.h = None
+            self.ml.lib.llamago_FreeDraftPair(self.h)
+            self.h = None
+
+
 def usable_threads():
     """Host threads a harness may use: affinity mask capped by the cgroup CPU quota (the GPU box shows 256 logical CPUs under a
     16-CPU quota; oversubscribing the checker's OpenMP loops there is catastrophic)."""
