@@ -66,12 +66,29 @@ int llamago_CacheWrite(llama_context* c, int which, uint64_t off_floats, const f
  * llamago_NarrowModelF16 / llamago_WidenModelF16 (llamago_QuantizeModelQ8's shape; for synthetic models and the tests' f32 twin): the matrices through
  *   lh_buf_narrow_f16 (round to nearest even; *n_changed, optional, = elements whose value changed) / back through lh_buf_widen_f16 (exact), the old
  *   copies released.  Refused (non-zero, ml_LastError) while contexts, batches or pipelines of the model are alive, and on a block-int8 model.
- * llamago_ModelWeightType: 0 (f32) / 1 (f16) / 7 (block-int8).
+ * llamago_ModelWeightType: 0 (f32) / 1 (f16) / 2 (block-int4) / 7 (block-int8).
  * On an f16 model llamago_SetModelTensor (of a matrix), llamago_QuantizeModelQ8 and llama_SaveModel refuse with a message that says so. */
 llama_model* llamago_LoadModelKeepF16(const char* fileName, uint32_t ctxSize);
 int llamago_NarrowModelF16(llama_model* m, uint64_t* n_changed);
 int llamago_WidenModelF16(llama_model* m);
 int llamago_ModelWeightType(const llama_model* m);
+/* Block-int4 weight matrices (ML_TYPE_Q4_0 = dtype 2 of llamahip.h: 20 bytes per 32 weights; norm vectors and tok_embeddings stay f32).  A 4-bit quant
+ * q in [-8, 7] with block scale d IS a block-int8 weight with the same q and d, so every Eval route of such a model produces the bytes its expansion
+ * produces: one row and 2..4 rows on 4-bit forms of the decode stream kernels, every other row count on the int8 kernels behind an exact expansion
+ * pass.
+ * llamago_QuantizeModelQ4 (llamago_QuantizeModelQ8's shape): every weight matrix of an f32 model through lh_buf_quantize_q4, the f32 copies released.
+ * llamago_ExpandModelQ4: the matrices through lh_buf_expand_q4 - a block-int8 model with the same quants and scales.
+ * Both are refused (non-zero, ml_LastError) while contexts, batches or pipelines of the model are alive, and on a model of another weight type.
+ * llamago_ModelWeightType then returns 2 / 7.  On a block-int4 model llamago_SetModelTensor (of a matrix), llamago_QuantizeModelQ8,
+ * llamago_NarrowModelF16 and llama_SaveModel refuse with a message that says so.
+ * llamago_SaveModelQ4: a block-int4 model as a ggjt file of ftype 2 - the matrices as their 20-byte Q4_0 blocks {float d; uint8 qs[16]}, norm vectors
+ *   and tok_embeddings f32.  llama_LoadModel refuses such a file as the reference does (llama.go:956-959).
+ * llamago_LoadModelKeepQ4: llama_LoadModel, except that a file whose weight matrices (seven per layer + output) are ALL Q4_0 has their blocks registered
+ *   as they are (lh_tensor_register dtype 2: every nibble kept, n = 0 included); any other file loads exactly as llama_LoadModel loads it. */
+int llamago_QuantizeModelQ4(llama_model* m);
+int llamago_ExpandModelQ4(llama_model* m);
+int llamago_SaveModelQ4(const llama_model* m, const char* fileName);
+llama_model* llamago_LoadModelKeepQ4(const char* fileName, uint32_t ctxSize);
 
 /* ---- [product] harness helper of the kept decode graph (no GPU needed) -------------------------------------------------- */
 /* The array llama_Eval hands to lh_graph_compute for N tokens (ids 1..N) at pastQuery, as numbers: per tensor 16 int64 = op, dtype, flags, ne[4],

@@ -60,10 +60,13 @@ void* lh_ctx_stream(lh_ctx* ctx);
  *      (llama.go:91-98).  `key` is a caller-chosen stable id (the Go shim uses the address of the
  *      tensor's backing array); registering an existing key returns the existing buffer.  key 0 =
  *      anonymous.  dtype is ml.DType (ml.go:85-94): 0 = f32; 1 = f16 (ml.TYPE_F16, weight matrices only:
- *      host = ne0 * ne1 uint16 halves, row-major [ne1][ne0], kept as halves in device memory); 7 = block-int8
+ *      host = ne0 * ne1 uint16 halves, row-major [ne1][ne0], kept as halves in device memory); 2 = block-int4
+ *      (ml.TYPE_Q4_0, weight matrices only: host = ne0 * ne1 / 32 blocks of 20 bytes {float d; uint8 qs[16]}, w = d * (n - 8),
+ *      element 2j in the low nibble of qs[j]; ne0 = cols, a multiple of 32, ne1 = rows; every nibble is kept); 7 = block-int8
  *      (ours).  host may be NULL (buffer zero-filled, as Go's make([]float32) is).  lh_buf_nfloats of a
- *      dtype-1 or dtype-7 buffer is its logical element count; lh_buf_upload, lh_buf_read and
- *      lh_buf_fill_synth refuse a dtype-1 buffer (LH_EINVAL). -------------------------------------- */
+ *      dtype-1, dtype-2 or dtype-7 buffer is its logical element count; lh_buf_upload, lh_buf_read and
+ *      lh_buf_fill_synth refuse a dtype-1 buffer (LH_EINVAL); lh_buf_upload and lh_buf_fill_synth refuse a
+ *      dtype-2 buffer (LH_EINVAL), lh_buf_read returns its fl32(d * q) as for dtype 7. ------------- */
 int lh_tensor_register(lh_ctx* ctx, uint64_t key, int dtype, const uint32_t ne[4], int persistent,
                        const void* host_or_null, lh_buf* out);
 int lh_buf_upload(lh_ctx* ctx, lh_buf buf, uint64_t off_floats, const float* host, uint64_t n);
@@ -74,7 +77,16 @@ int lh_buf_fill_synth(lh_ctx* ctx, lh_buf buf, uint64_t off_floats, uint64_t n, 
 /* Block-int8 (dtype 7; our format — the reference has none, ml.go:85-94, llama.go:956-959): quantise a registered fp32
  * matrix [rows][cols] on the device into a new buffer (d = max|w|/127 per 32 columns, q = rint(w/d)).  A dtype-7 buffer
  * can also be registered directly from 36-byte interchange blocks {float d; int8 q[32]} with lh_tensor_register. */
-int lh_buf_quantize_q8(lh_ctx* ctx, lh_buf src_f32, uint32_t rows, uint32_t cols, lh_buf* out);   /* a dtype-1 source: LH_EUNSUPPORTED (quantise before narrowing) */
+int lh_buf_quantize_q8(lh_ctx* ctx, lh_buf src_f32, uint32_t rows, uint32_t cols, lh_buf* out);   /* a dtype-1 or dtype-2 source: LH_EUNSUPPORTED (quantise before narrowing; lh_buf_expand_q4) */
+/* Block-int4 (dtype 2).  lh_buf_quantize_q4: a registered fp32 matrix [rows][cols], cols % 32 == 0, quantised on the device (k_quantize_q4) into a new
+ * dtype-2 buffer: d = fl32(max|w| / 7) per 32 columns, q = clamp(rint(fl32(w / d)), -7, 7) (d = 0 -> q = 0; a block with a NaN or an infinity: d = NaN,
+ * q = 0), stored as n = q + 8.  An f16, block-int8 or block-int4 source: LH_EUNSUPPORTED, the message names it.
+ * lh_buf_expand_q4: a dtype-2 buffer as a new dtype-7 buffer with the same q and the same d (k_expand_q4; nothing is requantised): the two hold
+ * identical values, and the decode kernels over either give identical bits.  A source of another dtype: LH_EINVAL.  Both synchronise. */
+int lh_buf_quantize_q4(lh_ctx* ctx, lh_buf src_f32, uint32_t rows, uint32_t cols, lh_buf* out);
+int lh_buf_expand_q4(lh_ctx* ctx, lh_buf src_q4, lh_buf* out_q8);
+/* The 20-byte interchange blocks [block0, block0 + nblocks) of a dtype-2 buffer, exactly as lh_tensor_register takes them (for saving a model). */
+int lh_buf_read_q4(lh_ctx* ctx, lh_buf buf, uint64_t block0, void* dst_blocks, uint64_t nblocks);
 /* f16 (dtype 1).  lh_buf_narrow_f16: a registered fp32 matrix [rows][cols] converted on the device (k_narrow_f16) into a new dtype-1 buffer: round to
  * nearest even, overflow to +-inf, -0 kept; *n_changed (optional) = the elements whose value changed (0 for anything that came from an f16 file).
  * lh_buf_widen_f16: a dtype-1 buffer widened into a new fp32 buffer (k_widen_f16, the pass the prompt routes of an f16 model run in front of their
@@ -190,7 +202,7 @@ typedef struct lh_llama_desc {
     lh_buf tok_embeddings, norm, output;          /* needed on the first / last stage only (0 elsewhere) */
     const lh_llama_layer* layer;                  /* `layers` entries, only [layer0, layer1) are read */
     lh_buf k_cache, v_cache;                      /* embd * (layer1-layer0) * ctx floats each; layer il at slot (il-layer0) */
-    int weight_dtype;                             /* 0 = f32, 1 = f16, 7 = block-int8 matrices; every matrix buffer must be of that dtype (f16: else LH_EINVAL).
+    int weight_dtype;                             /* 0 = f32, 1 = f16, 2 = block-int4, 7 = block-int8 matrices; every matrix buffer must be of that dtype (f16: else LH_EINVAL).
                                                    * f16: one row and 2..8 rows stream the halves (k_gemv_sa_h / k_gemv_rows_h); every other row count runs the
                                                    * fp32 schedule over an fp32 image widened layer by layer - in all cases the bytes an fp32 model holding the
                                                    * same values produces */
@@ -277,7 +289,7 @@ int lh_score_rows(lh_ctx* ctx, const float* logits_host, uint32_t n_rows, uint32
  * out_host[i] for the logits that follow tokens[i].  The [n][vocab] logits never leave the device; n * 32 bytes come back.
  * targets == NULL: the next token, targets[i] = tokens[i+1]; the last row has none and is scored against its own greedy id
  * (target_rank = 0).  The KV cache and the context's token history are left as lh_llama_eval with the same arguments leaves them.
- * Whole-model plans, weight_dtype 0, 1 and 7; a stage that lacks the lm_head (or the embeddings) returns LH_EUNSUPPORTED.  past + n
+ * Whole-model plans, weight_dtype 0, 1, 2 and 7; a stage that lacks the lm_head (or the embeddings) returns LH_EUNSUPPORTED.  past + n
  * beyond the window, a token or a target outside the vocabulary: LH_EINVAL before anything is enqueued. */
 int lh_llama_score(lh_llama* m, const uint32_t* tokens, uint32_t n, uint32_t past, const uint32_t* targets, lh_row_score* out_host);
 
@@ -285,7 +297,7 @@ int lh_llama_score(lh_llama* m, const uint32_t* tokens, uint32_t n, uint32_t pas
  * Every one-token step streams all weights; a pass of 2..8 rows (block-int8: 2..4) rides the same stream with every row bit-identical to
  * its solo step.  So: draft K tokens, evaluate [pending, d1..dK] as ONE pass of the context's own cache (a causal chunk), keep the longest
  * prefix the model itself produced.  The accepted ids and their logits are the bytes lh_llama_decode_greedy produces.  Greedy only,
- * whole-model plans, weight_dtype 0, 1 and 7.
+ * whole-model plans, weight_dtype 0, 1, 2 and 7.
  *
  * The draft rule (tests/speculative_ref.py restates it).  H[0..n) = the tokens at positions 0..n-1 of the window, H[n-1] the pending token;
  * an entry the context does not know (0xFFFFFFFF) never matches anything.  For G from ngram_max down to ngram_min: skip G when n < G or
@@ -327,7 +339,7 @@ int lh_llama_decode_lookup(lh_llama* m, uint32_t first_token, uint32_t past, uin
 
 /* ---- lossless draft-model speculative decoding (greedy): a second model drafts ------------------------------------------
  * lh_llama_decode_greedy of `target` through verify passes whose drafts come from `draft`, a second whole model with a KV cache of its own on the
- * same lh_ctx: the target's own block-int8 or f16 form, another seed, a smaller geometry - anything with the same vocabulary (weight_dtype 0, 1 or
+ * same lh_ctx: the target's own block-int8 or f16 form, another seed, a smaller geometry - anything with the same vocabulary (weight_dtype 0, 1, 2 or
  * 7).  The draft can only change how many passes are needed, never an id.  The rule (tests/draft_model_ref.py restates it):
  *   state   pos = the position of the pending token t; produced = the ids in the output list; ctx = min(target window, draft window);
  *           R = draft_len + 1, lowered to the largest row count the TARGET plan's shapes carry (as lh_llama_decode_lookup lowers it); R = 1 = plain
@@ -441,7 +453,7 @@ int lh_batch_set_sampler(lh_batch* b, const lh_sample_params* sp, uint32_t ring_
  * such a tick fails with LH_EINVAL before anything is enqueued. */
 int lh_batch_decode(lh_batch* b, const uint32_t* first_tokens, const uint32_t* past, uint32_t n_steps, uint32_t* out_tokens, float* logits_last_host);
 /* lh_batch_decode through lookup-drafted verify passes (the draft rule of lh_lookup_params, per pod over the pod's own window; ONE corpus for all pods):
- * speculation and the shared weight stream at once.  Greedy only, whole-model batches, weight_dtype 0, 1 and 7.  With P = the number of pods, every pass has
+ * speculation and the shared weight stream at once.  Greedy only, whole-model batches, weight_dtype 0, 1, 2 and 7.  With P = the number of pods, every pass has
  * P * R rows: row i * R + r is row r of pod i, on pod i's cache at position pos_i + r, holding [pending_i, d_1..d_k, filler = pending_i] - the order in
  * which lh_batch_feed lays out P pods fed R tokens each.  R = draft_max + 1, lowered to the largest R with P * R <= 64 whose row count shares one weight
  * pass on this plan (the predicate behind the feed's sizes_ok); a batch of two or more pods that is not lh_batch_batched takes R = 1.  R = 1 = plain

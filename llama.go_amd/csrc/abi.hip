@@ -288,8 +288,33 @@ void* lh_ctx_stream(lh_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 int lh_tensor_register(lh_ctx* ctx, uint64_t key, int dtype, const uint32_t ne[4], int persistent, const void* host, lh_buf* out) {
     if (!ctx || !ne || !out) LH_FAIL(ctx, LH_EINVAL, "lh_tensor_register: NULL argument");
     (void)persistent;
-    if (dtype != 0 && dtype != 1 && dtype != 7) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_tensor_register: dtype %d not supported (f32, f16 and block-int8 only; the reference loader accepts f32/f16, llama.go:956-959)", dtype);
+    if (dtype != 0 && dtype != 1 && dtype != 2 && dtype != 7) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_tensor_register: dtype %d not supported (f32, f16, block-int4 and block-int8 only; the reference loader accepts f32/f16, llama.go:956-959)", dtype);
     LH_HIP(ctx, hipSetDevice(ctx->device));
+    if (dtype == 2) {   // block-int4 weight matrix from 20-byte blocks { float d; uint8 qs[16] }: every nibble kept as it is
+        if (ne[0] % 32 || ne[2] != 1 || ne[3] != 1 || !ne[0] || !ne[1] || !host) LH_FAIL(ctx, LH_ESHAPE, "lh_tensor_register: block-int4 needs a 2-D matrix with columns %% 32 == 0 and host blocks");
+        const uint64_t nblocks = (uint64_t)ne[0] * ne[1] / 32;
+        auto b = std::make_unique<Buffer>();
+        b->nfloats = (uint64_t)ne[0] * ne[1]; b->dtype = 2; b->rows = ne[1]; b->cols = ne[0]; b->key = key; b->device = ctx->device;
+        b->unchecked = true;
+        const uint64_t qbytes = (b->nfloats / 2 + 255) & ~(uint64_t)255;
+        b->bytes = qbytes + nblocks * 4;
+        void* raw = nullptr;
+        LH_HIP(ctx, hipMalloc((void**)&b->dev, b->bytes));
+        b->scales = (float*)((char*)b->dev + qbytes);
+        hipError_t e = hipMalloc(&raw, nblocks * 20);
+        if (e == hipSuccess) e = hipMemcpy(raw, host, nblocks * 20, hipMemcpyHostToDevice);
+        int rc = e == hipSuccess ? q4_deinterleave_launch(ctx, raw, b->dev, b->scales, nblocks) : 0;
+        if (e == hipSuccess && !rc) e = hipStreamSynchronize(ctx->stream);
+        if (raw) hipFree(raw);
+        if (e != hipSuccess || rc) { hipFree(b->dev); if (rc) return rc; LH_FAIL(ctx, LH_EHIP, "lh_tensor_register: block-int4 upload: %s", hipGetErrorString(e)); }
+        std::lock_guard<std::mutex> lk(ctx->ds->mu);
+        lh_buf id = ctx->ds->next_id++;
+        if (key) ctx->ds->by_key[key] = id;
+        ctx->ds->bufs[id] = std::move(b);
+        ctx->ds->bufs_gen.fetch_add(1, std::memory_order_release);
+        *out = id;
+        return LH_OK;
+    }
     if (dtype == 1) {   // f16 weight matrix: the halves as they are, 2 bytes per element
         if (ne[2] != 1 || ne[3] != 1 || !ne[0] || !ne[1]) LH_FAIL(ctx, LH_ESHAPE, "lh_tensor_register: f16 needs a 2-D matrix");
         auto b = std::make_unique<Buffer>();
@@ -379,6 +404,7 @@ int lh_buf_upload(lh_ctx* ctx, lh_buf buf, uint64_t off, const float* host, uint
     int rc = get_buf(ctx, buf, off, n, &b, "lh_buf_upload");
     if (rc) return rc;
     if (!host) LH_FAIL(ctx, LH_EINVAL, "lh_buf_upload: host is NULL");
+    if (b->dtype == 2) LH_FAIL(ctx, LH_EINVAL, "lh_buf_upload: not an f32 buffer (block-int4: lh_buf_quantize_q4 of an f32 buffer, or lh_tensor_register of blocks)");
     if (b->dtype != 0) LH_FAIL(ctx, LH_EINVAL, "lh_buf_upload: not an f32 buffer");
     LH_HIP(ctx, hipSetDevice(ctx->device));
     LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -393,6 +419,23 @@ int lh_buf_read(lh_ctx* ctx, lh_buf buf, uint64_t off, float* dst, uint64_t n) {
     if (rc) return rc;
     if (!dst) LH_FAIL(ctx, LH_EINVAL, "lh_buf_read: dst is NULL");
     if (b->dtype == 7) return lh_buf_read_q8(ctx, buf, off, dst, n);
+    if (b->dtype == 2) {   // fl32(d * q), as for block-int8
+        LH_HIP(ctx, hipSetDevice(ctx->device));
+        LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        const uint64_t b0 = off / 32, b1 = (off + n + 31) / 32;
+        std::vector<unsigned char> q((b1 - b0) * 16);
+        std::vector<float> sc(b1 - b0);
+        if (b1 > b0) {
+            LH_HIP(ctx, hipMemcpy(q.data(), (unsigned char*)b->dev + b0 * 16, (b1 - b0) * 16, hipMemcpyDeviceToHost));
+            LH_HIP(ctx, hipMemcpy(sc.data(), b->scales + b0, (b1 - b0) * 4, hipMemcpyDeviceToHost));
+        }
+        for (uint64_t i = 0; i < n; ++i) {
+            const uint64_t e = off + i - b0 * 32;
+            const int nib = (q[e / 2] >> (4 * (e & 1))) & 15;
+            dst[i] = sc[e / 32] * (float)(nib - 8);
+        }
+        return LH_OK;
+    }
     if (b->dtype != 0) LH_FAIL(ctx, LH_EINVAL, "lh_buf_read: an f16 buffer holds no floats (lh_buf_widen_f16 makes an fp32 copy)");
     LH_HIP(ctx, hipSetDevice(ctx->device));
     LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -406,6 +449,7 @@ int lh_buf_fill_synth(lh_ctx* ctx, lh_buf buf, uint64_t off, uint64_t n, uint64_
     int rc = get_buf(ctx, buf, off, n, &b, "lh_buf_fill_synth");
     if (rc) return rc;
     if (b->dtype == 1) LH_FAIL(ctx, LH_EINVAL, "lh_buf_fill_synth: not an f32 buffer (f16: fill an f32 buffer, then lh_buf_narrow_f16)");
+    if (b->dtype == 2) LH_FAIL(ctx, LH_EINVAL, "lh_buf_fill_synth: not an f32 buffer (block-int4: fill an f32 buffer, then lh_buf_quantize_q4)");
     LH_HIP(ctx, hipSetDevice(ctx->device));
     const uint64_t key = mix64(seed ^ ((uint64_t)tensor_id * 0xD6E8FEB86659FD93ull));
     uint64_t blocks = (n + 255) / 256;
@@ -422,6 +466,7 @@ int lh_buf_quantize_q8(lh_ctx* ctx, lh_buf src, uint32_t rows, uint32_t cols, lh
     int rc = get_buf(ctx, src, 0, (uint64_t)rows * cols, &sb, "lh_buf_quantize_q8");
     if (rc) return rc;
     if (sb->dtype == 1) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_buf_quantize_q8: the source is f16 (quantise before narrowing)");
+    if (sb->dtype == 2) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_buf_quantize_q8: the source is block-int4 (lh_buf_expand_q4 makes the block-int8 buffer of the same values)");
     if (sb->dtype != 0 || cols % 32) LH_FAIL(ctx, LH_ESHAPE, "lh_buf_quantize_q8: needs an f32 matrix with columns %% 32 == 0");
     LH_HIP(ctx, hipSetDevice(ctx->device));
     const uint64_t n = (uint64_t)rows * cols, nblocks = n / 32;
@@ -491,6 +536,68 @@ int lh_buf_widen_f16(lh_ctx* ctx, lh_buf src, lh_buf* out) {
     hipError_t e = rc ? hipErrorUnknown : hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) { hipFree(b->dev); if (rc) return rc; LH_FAIL(ctx, LH_EHIP, "lh_buf_widen_f16: %s", hipGetErrorString(e)); }
     return add_buffer(ctx, std::move(b), out);
+}
+
+int lh_buf_quantize_q4(lh_ctx* ctx, lh_buf src, uint32_t rows, uint32_t cols, lh_buf* out) {
+    Buffer* sb;
+    if (!out || !rows || !cols) return LH_EINVAL;
+    int rc = get_buf(ctx, src, 0, (uint64_t)rows * cols, &sb, "lh_buf_quantize_q4");
+    if (rc) return rc;
+    if (sb->dtype != 0) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_buf_quantize_q4: the source is %s (only an f32 matrix is quantised to block-int4)", sb->dtype == 1 ? "f16" : sb->dtype == 7 ? "block-int8" : "block-int4");
+    if (cols % 32) LH_FAIL(ctx, LH_ESHAPE, "lh_buf_quantize_q4: needs an f32 matrix with columns %% 32 == 0");
+    LH_HIP(ctx, hipSetDevice(ctx->device));
+    const uint64_t n = (uint64_t)rows * cols, nblocks = n / 32;
+    auto b = std::make_unique<Buffer>();
+    b->nfloats = n; b->dtype = 2; b->rows = rows; b->cols = cols; b->device = ctx->device;
+    b->unchecked = true;
+    const uint64_t qbytes = (n / 2 + 255) & ~(uint64_t)255;
+    b->bytes = qbytes + nblocks * 4;
+    LH_HIP(ctx, hipMalloc((void**)&b->dev, b->bytes));
+    b->scales = (float*)((char*)b->dev + qbytes);
+    rc = quantize_q4_launch(ctx, sb->dev, b->dev, b->scales, nblocks);
+    hipError_t e = rc ? hipErrorUnknown : hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { hipFree(b->dev); if (rc) return rc; LH_FAIL(ctx, LH_EHIP, "lh_buf_quantize_q4: %s", hipGetErrorString(e)); }
+    return add_buffer(ctx, std::move(b), out);
+}
+
+int lh_buf_expand_q4(lh_ctx* ctx, lh_buf src, lh_buf* out) {
+    if (!ctx || !out) return LH_EINVAL;
+    Buffer* sb = find_buffer(ctx->ds, src);
+    if (!sb) LH_FAIL(ctx, LH_EINVAL, "lh_buf_expand_q4: unknown buffer %llu", (unsigned long long)src);
+    if (sb->dtype != 2) LH_FAIL(ctx, LH_EINVAL, "lh_buf_expand_q4: the source must be a block-int4 buffer");
+    LH_HIP(ctx, hipSetDevice(ctx->device));
+    const uint64_t n = sb->nfloats, nblocks = n / 32;
+    auto b = std::make_unique<Buffer>();
+    b->nfloats = n; b->dtype = 7; b->rows = sb->rows; b->cols = sb->cols; b->device = ctx->device;
+    const uint64_t qbytes = (n + 255) & ~(uint64_t)255;
+    b->bytes = qbytes + nblocks * 4;
+    LH_HIP(ctx, hipMalloc((void**)&b->dev, b->bytes));
+    b->scales = (float*)((char*)b->dev + qbytes);
+    int rc = expand_q4_launch(ctx, sb->dev, b->dev, n);
+    hipError_t e = rc ? hipErrorUnknown : hipMemcpyAsync(b->scales, sb->scales, nblocks * 4, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { hipFree(b->dev); if (rc) return rc; LH_FAIL(ctx, LH_EHIP, "lh_buf_expand_q4: %s", hipGetErrorString(e)); }
+    return add_buffer(ctx, std::move(b), out);
+}
+
+int lh_buf_read_q4(lh_ctx* ctx, lh_buf buf, uint64_t block0, void* dst_blocks, uint64_t nblocks) {
+    if (!ctx) return LH_EINVAL;
+    Buffer* b = find_buffer(ctx->ds, buf);
+    if (!b) LH_FAIL(ctx, LH_EINVAL, "lh_buf_read_q4: unknown buffer %llu", (unsigned long long)buf);
+    if (b->dtype != 2 || !dst_blocks) LH_FAIL(ctx, LH_EINVAL, "lh_buf_read_q4: not a block-int4 buffer");
+    const uint64_t total = b->nfloats / 32;
+    if (block0 > total || nblocks > total - block0) LH_FAIL(ctx, LH_EINVAL, "lh_buf_read_q4: blocks [%llu,+%llu) outside the buffer's %llu", (unsigned long long)block0, (unsigned long long)nblocks, (unsigned long long)total);
+    LH_HIP(ctx, hipSetDevice(ctx->device));
+    LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<unsigned char> q(nblocks * 16);
+    std::vector<float> sc(nblocks);
+    if (nblocks) {
+        LH_HIP(ctx, hipMemcpy(q.data(), (unsigned char*)b->dev + block0 * 16, nblocks * 16, hipMemcpyDeviceToHost));
+        LH_HIP(ctx, hipMemcpy(sc.data(), b->scales + block0, nblocks * 4, hipMemcpyDeviceToHost));
+    }
+    unsigned char* o = (unsigned char*)dst_blocks;
+    for (uint64_t i = 0; i < nblocks; ++i) { memcpy(o + i * 20, &sc[i], 4); memcpy(o + i * 20 + 4, &q[i * 16], 16); }
+    return LH_OK;
 }
 
 int lh_buf_read_q8(lh_ctx* ctx, lh_buf buf, uint64_t off, float* dst, uint64_t n) {

@@ -60,10 +60,10 @@ void route_trace(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 // A persistent device buffer (weights / KV cache), shared by every context of the device.
 struct Buffer {
     float* dev = nullptr;
-    uint64_t nfloats = 0;  // f32 elements (for block-int8 and f16: logical elements)
+    uint64_t nfloats = 0;  // f32 elements (for block-int8, block-int4 and f16: logical elements)
     uint64_t bytes = 0;
-    int dtype = 0;              // ml.DType: 0 = f32, 1 = f16 (halves at dev, 2 bytes per element), 7 = block-int8 (planes: int8 quants at dev, fp32 scales at `scales`)
-    float* scales = nullptr;    // block-int8: [rows][cols/32]
+    int dtype = 0;              // ml.DType: 0 = f32, 1 = f16 (halves at dev, 2 bytes per element), 2 = block-int4 (planes: nibbles at dev, two per byte, fp32 scales at `scales`), 7 = block-int8 (planes: int8 quants at dev, fp32 scales at `scales`)
+    float* scales = nullptr;    // block-int8 and block-int4: [rows][cols/32]
     uint32_t rows = 0, cols = 0;
     uint64_t key = 0;
     int device = 0;
@@ -155,7 +155,7 @@ struct lh_ctx {
     // the activation rows of a long-prompt GEMM as three bf16 planes (k_gemm_b9); grows, never shrinks
     uint16_t* xs3 = nullptr;
     uint64_t xs3_elems = 0;
-    // fp32 images of f16 weight matrices for the routes without f16 kernels (Plan::md_wide): one allocation per size asked for at plan_create,
+    // fp32 images of f16 weight matrices / int8 images of block-int4 ones for the routes without kernels of their own (Plan::md_wide): one allocation per size asked for at plan_create,
     // shared by the context's plans of that size, freed with the context - an address handed out never moves
     std::vector<std::pair<uint64_t, float*>> wide;   // (size and kind, address)
     // lh_ctx_time_computes: events around each lh_graph_compute + host time inside it
@@ -174,4 +174,9 @@ inline int select_device(lh_ctx* ctx) { return hipSetDevice(ctx->device) == hipS
 // *changed_dev += the elements whose value changed (k_narrow_f16)
 int widen_f16_launch(lh_ctx* ctx, const void* src_f16, float* dst, uint64_t n);
 int narrow_f16_launch(lh_ctx* ctx, const float* src, void* dst_f16, uint64_t n, unsigned long long* changed_dev);
+// plan.hip (kernels_q4.h), enqueued on the context's stream: the nibble plane of n block-int4 weights -> the int8 plane of the same quants (k_expand_q4);
+// nblocks blocks of 32 floats -> nibble and scale planes (k_quantize_q4); nblocks 20-byte interchange blocks -> planes (k_q4_deinterleave)
+int expand_q4_launch(lh_ctx* ctx, const void* src_q4, void* dst_q8, uint64_t n);
+int quantize_q4_launch(lh_ctx* ctx, const float* src, void* q, float* scales, uint64_t nblocks);
+int q4_deinterleave_launch(lh_ctx* ctx, const void* blocks, void* q, float* scales, uint64_t nblocks);
 }  // namespace lh

@@ -164,7 +164,7 @@ static int run_node(lh_ctx* ctx, const lh_tensor* T, const std::vector<float*>& 
             const lh_tensor &a = T[t.src0], &b = T[t.src1];
             if (a.ne[0] != b.ne[0] || a.ne[2] != b.ne[2] || a.ne[3] != b.ne[3]) LH_FAIL(ctx, LH_ESHAPE, "MulMat: incompatible shapes (ml.go:290-292)");
             if (a.nb[0] != 4 || b.nb[0] != 4) LH_FAIL(ctx, LH_ESHAPE, "MulMat: operands must be contiguous along K (ml.go:1950, 1967)");
-            if (a.dtype != 0) LH_FAIL(ctx, LH_EUNSUPPORTED, "MulMat: %s weights are only supported inside the fused LLaMA plan", a.dtype == 1 ? "f16" : "block-int8");
+            if (a.dtype != 0) LH_FAIL(ctx, LH_EUNSUPPORTED, "MulMat: %s weights are only supported inside the fused LLaMA plan", a.dtype == 1 ? "f16" : a.dtype == 2 ? "block-int4" : "block-int8");
             const bool plain2d = contiguous(a) && contiguous(b) && contiguous(t) && a.ne[2] == 1 && a.ne[3] == 1 && b.ne[2] == 1 && b.ne[3] == 1 &&
                                  a.ne[0] % 4 == 0 && a.ne[0] <= 24576 && a.ne[1] >= 256;
             if (plain2d) {

@@ -110,7 +110,7 @@ inline int graph_check_reach(const lh_tensor* T, uint32_t n_leafs, uint32_t n_no
     const uint32_t total = n_leafs + n_nodes;
     std::vector<uint64_t> size(total, 0);
     u128 scratch = 0;
-    std::vector<int8_t> q8(total, 0);   // owner is a registered buffer of another dtype than f32: that dtype (1 = f16, 7 = block-int8)
+    std::vector<int8_t> q8(total, 0);   // owner is a registered buffer of another dtype than f32: that dtype (1 = f16, 2 = block-int4, 7 = block-int8)
     std::vector<const lh_buf_extent*> sorted;
     for (uint32_t k = 0; k < n_bufs; ++k) sorted.push_back(bufs + k);
     std::sort(sorted.begin(), sorted.end(), [](const lh_buf_extent* a, const lh_buf_extent* b) { return a->id < b->id; });
@@ -148,7 +148,8 @@ inline int graph_check_reach(const lh_tensor* T, uint32_t n_leafs, uint32_t n_no
         const lh_tensor& a = T[ia];
         if (q8[a.storage] || q8[t.storage] || (ib >= 0 && q8[T[ib].storage])) {
             const bool f16 = q8[a.storage] == 1 || q8[t.storage] == 1 || (ib >= 0 && q8[T[ib].storage] == 1);
-            return fail(msg, cap, LH_EUNSUPPORTED, "tensor %u: %s weights are only supported inside the fused LLaMA plan", i, f16 ? "f16" : "block-int8");
+            const bool q4 = q8[a.storage] == 2 || q8[t.storage] == 2 || (ib >= 0 && q8[T[ib].storage] == 2);
+            return fail(msg, cap, LH_EUNSUPPORTED, "tensor %u: %s weights are only supported inside the fused LLaMA plan", i, f16 ? "f16" : q4 ? "block-int4" : "block-int8");
         }
         switch (t.op) {
             case GET_ROWS: {   // ml.go:1711-1750
@@ -247,7 +248,7 @@ inline int graph_check_reach(const lh_tensor* T, uint32_t n_leafs, uint32_t n_no
                 const lh_tensor& b = T[ib];
                 if (a.ne[0] != b.ne[0] || a.ne[2] != b.ne[2] || a.ne[3] != b.ne[3]) return fail(msg, cap, LH_ESHAPE, "tensor %u: MulMat: incompatible shapes (ml.go:290-292)", i);
                 if (a.nb[0] != 4 || b.nb[0] != 4) return fail(msg, cap, LH_ESHAPE, "tensor %u: MulMat: operands must be contiguous along K (ml.go:1950, 1967)", i);
-                if (a.dtype != 0) return fail(msg, cap, LH_EUNSUPPORTED, "tensor %u: MulMat: %s weights are only supported inside the fused LLaMA plan", i, a.dtype == 1 ? "f16" : "block-int8");
+                if (a.dtype != 0) return fail(msg, cap, LH_EUNSUPPORTED, "tensor %u: MulMat: %s weights are only supported inside the fused LLaMA plan", i, a.dtype == 1 ? "f16" : a.dtype == 2 ? "block-int4" : "block-int8");
                 GC_SHAPE(t.ne[0] == a.ne[1] && t.ne[1] == b.ne[1] && t.ne[2] == a.ne[2] && t.ne[3] == a.ne[3], "MulMat: [dst] is not (src0.ne1, src1.ne1, src0.ne2, src0.ne3) (ml.go:295-318)");
                 GC_LAUNCH((rows(a) * b.ne[1] + 3) / 4 <= MAX_GRID, "MulMat: more than 2^33 - 4 outputs in one launch");   // g_mul_mat: one wave per output, four per workgroup
                 break;

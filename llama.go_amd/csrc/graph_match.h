@@ -16,7 +16,7 @@
 //   - weight leafs are owners of registered buffers, packed, at offset 0, inside the buffer; parameter leafs are host-readable owners of exactly
 //     the values the op reads, and every value is castable_u32 before it is cast;
 //   - counts stay inside what graph_check_reach accepts (rope positions, outputs of one MulMat launch, scratch floats per graph).
-// Together these imply graph_check_reach for an f32 graph: an accepted graph is one the node path would run too (block-int8 and f16 weights are exempt
+// Together these imply graph_check_reach for an f32 graph: an accepted graph is one the node path would run too (block-int8, block-int4 and f16 weights are exempt
 // from its dtype rule only - the node path has no kernel for them).  Anything else is not an error: the graph runs node by node.
 //
 // The device is behind `Lookup`: bool lookup(lh_buf id, BufInfo* out).  lh_graph_compute answers from its buffer table; lh_graph_match from the
@@ -102,7 +102,7 @@ struct Matcher {
         claimed[dst] = 1;
         return scratch_add(n0 * n1 * n2);
     }
-    // persistent weight leaf of the expected shape.  Matrices may be f32, f16 or block-int8 (all the same dtype within a model); norm vectors and
+    // persistent weight leaf of the expected shape.  Matrices may be f32, f16, block-int4 or block-int8 (all the same dtype within a model); norm vectors and
     // the embedding table are always f32.  (Strides count fp32-sized logical elements for every dtype, as they do for block-int8.)
     bool weight(int i, uint32_t ne0, uint32_t ne1, bool matrix, int32_t* slot) {
         if (i < 0 || (uint32_t)i >= n_leafs) return false;
@@ -110,8 +110,8 @@ struct Matcher {
         if (t.op != gc::NONE || !t.buf || !at(i, i, 0) || !packed(i, ne0, ne1, 1)) return false;
         BufInfo b;
         if (!lookup(t.buf, &b) || b.nfloats < (uint64_t)ne0 * ne1 || b.dtype != (int)t.dtype) return false;
-        if (b.dtype != 0 && !(matrix && (b.dtype == 7 || b.dtype == 1))) return false;
-        if (b.dtype == 7 && (b.has_shape ? (b.rows != ne1 || b.cols != ne0) : b.nfloats != (uint64_t)ne0 * ne1)) return false;
+        if (b.dtype != 0 && !(matrix && (b.dtype == 7 || b.dtype == 2 || b.dtype == 1))) return false;
+        if ((b.dtype == 7 || b.dtype == 2) && (b.has_shape ? (b.rows != ne1 || b.cols != ne0) : b.nfloats != (uint64_t)ne0 * ne1)) return false;
         if (matrix) {
             if (wtype_seen < 0) wtype_seen = b.dtype;
             else if (wtype_seen != b.dtype) return false;

@@ -28,7 +28,7 @@ struct ModelDesc {
     uint32_t cache_layer0 = 0;        // layer stored in slot 0 of the caches
     const float *tok_emb = nullptr, *norm = nullptr, *output = nullptr;
     const float* s_output = nullptr;  // block-int8: scales of the output matrix
-    int wtype = 0;                    // dtype of the weight matrices: 0 = f32, 1 = f16 (halves at the pointers), 7 = block-int8 (norms and embeddings stay f32)
+    int wtype = 0;                    // dtype of the weight matrices: 0 = f32, 1 = f16 (halves at the pointers), 2 = block-int4 (nibble planes at the pointers, scales at s_*), 7 = block-int8 (norms and embeddings stay f32)
     std::vector<LayerW> layers;       // indexed by absolute layer id
     float *kc = nullptr, *vc = nullptr;
     std::shared_ptr<std::vector<uint32_t>> kv_hist;   // the K cache buffer's token history (Buffer::kv_hist); not part of same()
@@ -54,8 +54,11 @@ struct Plan {
     uint32_t s3_rows = 0;
     // f16 plans (md.wtype == 1).  Step and Rows stream the halves (kernels_f16.h); every other route runs the fp32 schedule of a wtype-0 model of
     // the same shapes over an exact fp32 image: md_wide is md with wtype 0, EVERY layer's matrices at wide_layer (the image of the layer being
-    // evaluated, widened in front of its launches: widen_layer) and output at wide_out.  The images belong to the context (lh_ctx::wide), are sized
+    // evaluated, widened in front of its launches: route_layer) and output at wide_out.  The images belong to the context (lh_ctx::wide), are sized
     // at plan_create and never move, so a captured graph may hold their addresses without a generation in its key.
+    // Block-int4 plans (md.wtype == 2) use the same three fields: Step, Rows and Q8Steps stream the nibbles (kernels_q4.h); Planes and Prefill run
+    // the block-int8 schedule over md_wide = md with wtype 7, whose quant pointers point into wide_layer / wide_out - here INT8 images of 4 d^2 + 3 d F
+    // and V d BYTES behind the float* type, filled by k_expand_q4 - and whose s_* pointers are the model's own scale planes.
     ModelDesc md_wide;
     float *wide_layer = nullptr, *wide_out = nullptr;
     float* emb = nullptr;                    // LH_T_OUTPUT on llama.Eval's `embeddings`: the final norm rows [emb_cap][d]

@@ -14,6 +14,7 @@
 #include "kernels_gemm_b9.h"
 #include "kernels_rows.h"
 #include "kernels_f16.h"
+#include "kernels_q4.h"
 #include "kernels_attn_seg.h"
 #include "kernels_attn_share.h"
 #include "kernels_spec.h"
@@ -132,13 +133,34 @@ int narrow_f16_launch(lh_ctx* ctx, const float* src, void* dst_f16, uint64_t n, 
     LH_HIP(ctx, hipGetLastError());
     return 0;
 }
-// an fp32 image of nfloats elements that lives as long as the context and never moves (lh_ctx::wide); kind 0 = a layer's matrices, 1 = the output
-// matrix (a layer image and an output image of the same size stay two allocations: a route reads both)
-static int wide_image(lh_ctx* ctx, uint64_t nfloats, int kind, float** out) {
-    const uint64_t key = (nfloats << 1) | (uint64_t)kind;
+// ---- block-int4 (kernels_q4.h) ----
+int expand_q4_launch(lh_ctx* ctx, const void* src_q4, void* dst_q8, uint64_t n) {
+    if (g_prepare_only || g_only) return 0;
+    TraceScope ts_(ctx->stream, "expand_q4");
+    LH_TRACE("k_expand_q4");
+    const uint64_t n8 = n / 16;   // 8-byte units of the nibble plane
+    LH_LAUNCH(k_expand_q4, dim3((unsigned)std::min<uint64_t>(std::max<uint64_t>((n8 + 255) / 256, 1), 16384)), dim3(256), 0, ctx->stream, (const u2*)src_q4, (u4*)dst_q8, n8);
+    LH_HIP(ctx, hipGetLastError());
+    return 0;
+}
+int quantize_q4_launch(lh_ctx* ctx, const float* src, void* q, float* scales, uint64_t nblocks) {
+    LH_LAUNCH(k_quantize_q4, dim3((unsigned)std::min<uint64_t>(std::max<uint64_t>((nblocks + 255) / 256, 1), 65535)), dim3(256), 0, ctx->stream, src, (unsigned char*)q, scales, nblocks);
+    LH_HIP(ctx, hipGetLastError());
+    return 0;
+}
+int q4_deinterleave_launch(lh_ctx* ctx, const void* blocks, void* q, float* scales, uint64_t nblocks) {
+    LH_LAUNCH(k_q4_deinterleave, dim3((unsigned)std::min<uint64_t>(std::max<uint64_t>((nblocks + 255) / 256, 1), 65535)), dim3(256), 0, ctx->stream, (const unsigned int*)blocks, (unsigned char*)q, scales, nblocks);
+    LH_HIP(ctx, hipGetLastError());
+    return 0;
+}
+// an image of n elements of elem_bytes each (fp32 of f16 matrices, int8 of block-int4 ones) that lives as long as the context and never moves
+// (lh_ctx::wide); kind 0 = a layer's matrices, 1 = the output matrix (a layer image and an output image of the same size stay two allocations: a
+// route reads both).  The element size is part of the key: an int8 image and an fp32 image of equal count do not alias.
+static int wide_image(lh_ctx* ctx, uint64_t n, uint64_t elem_bytes, int kind, float** out) {
+    const uint64_t key = (n << 4) | (elem_bytes << 1) | (uint64_t)kind;
     for (const auto& w : ctx->wide) if (w.first == key) { *out = w.second; return 0; }
     float* dev = nullptr;
-    if (hipMalloc((void**)&dev, nfloats * 4) != hipSuccess) LH_FAIL(ctx, LH_ENOMEM, "plan: no memory for the fp32 image of f16 weights (%llu floats)", (unsigned long long)nfloats);
+    if (hipMalloc((void**)&dev, n * elem_bytes) != hipSuccess) LH_FAIL(ctx, LH_ENOMEM, "plan: no memory for the %s image of %s weights (%llu elements)", elem_bytes == 4 ? "fp32" : "int8", elem_bytes == 4 ? "f16" : "block-int4", (unsigned long long)n);
     ctx->wide.emplace_back(key, dev);
     *out = dev;
     return 0;
@@ -206,9 +228,60 @@ static int gemv_f32(lh_ctx* ctx, const GemvArgs& a, const char* name);
 template <int PRO, int EPI, int MAP>
 static int gemv_f16(lh_ctx* ctx, const GemvArgs& a, const char* name);
 
+template <int KI, int U, int TPR, int PRO, int EPI, int MAP, int THR = TH>
+static int launch_gemv_q4(lh_ctx* ctx, const GemvArgs& a, const char* name, uint64_t bytes) {
+    static bool flags[16] = {};
+    int rc = set_lds_once(ctx, k_gemv_q4s<KI, U, TPR, PRO, EPI, MAP, THR>, FAT_LDS, flags);
+    if (rc) return rc;
+    if (skip_launch(name)) return 0;
+    ProfScope ps(ctx->stream, name, bytes);
+    GemvArgs b = a;
+    b.wg_q = (a.M / 2) / (uint32_t)ctx->ds->num_cu; b.wg_r = (a.M / 2) % (uint32_t)ctx->ds->num_cu;   // wg_row_block
+    LH_TRACE("k_gemv_q4s<%d,%d,%d,%d>", KI, U, TPR, THR);
+    LH_LAUNCH((k_gemv_q4s<KI, U, TPR, PRO, EPI, MAP, THR>), dim3(ctx->ds->num_cu), dim3(THR), FAT_LDS, ctx->stream, b);
+    LH_HIP(ctx, hipGetLastError());
+    return 0;
+}
+// LLAMAHIP_Q4_U = 2 / 4 / 8: rows in flight of the K = 4096 launches (a measurement switch: the sweep of tools/bench_q4.py; README, debug switches);
+// anything else: the shipped choice
+static int q4_u_override() {
+    static const int v = getenv("LLAMAHIP_Q4_U") ? atoi(getenv("LLAMAHIP_Q4_U")) : 0;
+    return v;
+}
+// block-int4 GEMV (kernels_q4.h): gemv_q8's launch forms - KI, TPR and the workgroup size per shape fix the lane -> column map and the cross-wave order,
+// hence the bits.  U is not part of the sums.  Only the K <= 4096 forms of 256 threads were swept; every other form (KI = 3, the 1024-thread forms,
+// k_gemv_q4_rows) carries twice int8's count (a row of nibbles is half the bytes) as an UNMEASURED starting point.
+template <int PRO, int EPI, int MAP>
+static int gemv_q4(lh_ctx* ctx, const GemvArgs& a, const char* name) {
+    if (a.K % 32 || ((EPI == EPI_QKV_ROPE || EPI == EPI_SILU_MUL) && a.M % 2))
+        LH_FAIL(ctx, LH_ESHAPE, "gemv_q4 %s: K=%u must be a multiple of 32%s", name, a.K, a.M % 2 ? " and the row count even" : "");
+    if ((uint64_t)a.M / ctx->ds->num_cu + 4 > (uint64_t)TH) LH_FAIL(ctx, LH_EUNSUPPORTED, "gemv_q4 %s: M=%u exceeds %d rows per workgroup", name, a.M, TH - 4);
+    const uint32_t K16 = a.K / 16;
+    const uint64_t bytes = (uint64_t)a.M * a.K / 32 * 20;
+    const uint32_t rows_wg = a.M / (uint32_t)ctx->ds->num_cu;
+    if (rows_wg + 4 <= 250) {
+        if (K16 <= 256) {
+            if (q4_u_override() == 4) return launch_gemv_q4<1, 4, 256, PRO, EPI, MAP, 256>(ctx, a, name, bytes);
+            if (q4_u_override() == 2) return launch_gemv_q4<1, 2, 256, PRO, EPI, MAP, 256>(ctx, a, name, bytes);
+            if (q4_u_override() == 8) return launch_gemv_q4<1, 8, 256, PRO, EPI, MAP, 256>(ctx, a, name, bytes);
+            // (swept, tools/bench_q4.py -> profiles/q4_decode.txt: U = 4 gives the fastest decode loop of U = 2 / 4 / 8; between 4 and 8 the single launches
+            // differ by less than two runs of the sweep do.  Doubling int8's counts (6 for wq|wk|wv, 4 elsewhere) bought nothing: the unpack, not the
+            // bytes in flight, is what the wave waits for)
+            return launch_gemv_q4<1, 4, 256, PRO, EPI, MAP, 256>(ctx, a, name, bytes);
+        }
+        if (K16 > 512 && K16 <= 768) return launch_gemv_q4<3, 4, 256, PRO, EPI, MAP, 256>(ctx, a, name, bytes);
+    }
+    if (K16 <= 256) return rows_wg >= 32 ? launch_gemv_q4<1, 4, 256, PRO, EPI, MAP>(ctx, a, name, bytes) : launch_gemv_q4<1, 2, 256, PRO, EPI, MAP>(ctx, a, name, bytes);
+    if (K16 <= 512) return launch_gemv_q4<2, 4, 256, PRO, EPI, MAP>(ctx, a, name, bytes);
+    if (K16 <= 1024) return launch_gemv_q4<1, 4, 1024, PRO, EPI, MAP>(ctx, a, name, bytes);
+    if (K16 <= 2048) return launch_gemv_q4<2, 4, 1024, PRO, EPI, MAP>(ctx, a, name, bytes);
+    LH_FAIL(ctx, LH_EUNSUPPORTED, "gemv_q4 %s: K=%u exceeds the supported 32768 columns", name, a.K);
+}
+
 template <int PRO, int EPI, int MAP>
 static int gemv(lh_ctx* ctx, const GemvArgs& a, const char* name, int wtype = 0) {
     if (wtype == 1) return gemv_f16<PRO, EPI, MAP>(ctx, a, name);
+    if (wtype == 2) return gemv_q4<PRO, EPI, MAP>(ctx, a, name);
     return wtype == 7 ? gemv_q8<PRO, EPI, MAP>(ctx, a, name) : gemv_f32<PRO, EPI, MAP>(ctx, a, name);
 }
 
@@ -399,6 +472,29 @@ static int gemv_q8_rows_nc(lh_ctx* ctx, const GemvRowsArgs& a, const char* name)
     if (a.K / 16 <= 256) return launch_gemv_q8_rows<1, U, NC, PRO, EPI, MAP>(ctx, a, name, bytes);
     return launch_gemv_q8_rows<3, (NC <= 2 ? 2 : 1), NC, PRO, EPI, MAP>(ctx, a, name, bytes);
 }
+// block-int4 twin (k_gemv_q4_rows): gemv_q8_rows_nc's shapes, limits and launch forms, twice its weight rows in flight
+template <int KI, int U, int NC, int PRO, int EPI, int MAP>
+static int launch_gemv_q4_rows(lh_ctx* ctx, const GemvRowsArgs& a, const char* name, uint64_t bytes) {
+    static bool flags[16] = {};
+    int rc = set_lds_once(ctx, k_gemv_q4_rows<KI, U, 256, 256, NC, PRO, EPI, MAP>, FAT_LDS, flags);
+    if (rc) return rc;
+    if (g_prepare_only) return 0;
+    ProfScope ps(ctx->stream, name, bytes);
+    GemvRowsArgs b = a;
+    b.wg_q = (a.M / 2) / (uint32_t)ctx->ds->num_cu; b.wg_r = (a.M / 2) % (uint32_t)ctx->ds->num_cu;   // wg_row_block
+    LH_TRACE("k_gemv_q4_rows<%d,%d,%d>", KI, U, NC);
+    LH_LAUNCH((k_gemv_q4_rows<KI, U, 256, 256, NC, PRO, EPI, MAP>), dim3(ctx->ds->num_cu), dim3(256), FAT_LDS, ctx->stream, b);
+    LH_HIP(ctx, hipGetLastError());
+    return 0;
+}
+template <int NC, int PRO, int EPI, int MAP>
+static int gemv_q4_rows_nc(lh_ctx* ctx, const GemvRowsArgs& a, const char* name) {
+    if (!gemv_q8_rows_shape_ok(ctx, a.M, a.K)) LH_FAIL(ctx, LH_ESHAPE, "gemv_q4_rows %s: %u x %u has no instantiation", name, a.M, a.K);
+    const uint64_t bytes = (uint64_t)a.M * a.K / 32 * 20;
+    constexpr int U = NC <= 2 ? 8 : 4;
+    if (a.K / 16 <= 256) return launch_gemv_q4_rows<1, U, NC, PRO, EPI, MAP>(ctx, a, name, bytes);
+    return launch_gemv_q4_rows<3, (NC <= 2 ? 4 : 2), NC, PRO, EPI, MAP>(ctx, a, name, bytes);
+}
 // f16 twin (k_gemv_rows_h): gemv_rows_nc's shapes and limits (the activation registers are the same), twice its weight rows in flight
 template <int KI, int U, int THR, int NC, int PRO, int EPI, int MAP>
 static int launch_gemv_rows_h(lh_ctx* ctx, const GemvRowsArgs& a, const char* name, uint64_t bytes) {
@@ -448,19 +544,21 @@ static int gemv_rows(lh_ctx* ctx, const GemvRowsArgs& a, const char* name, int w
         return a.n <= 2 ? gemv_rows_h_nc<2, PRO, EPI, MAP>(ctx, a, name) : gemv_rows_h_nc<4, PRO, EPI, MAP>(ctx, a, name);
     }
     if (wtype == 7) return a.n <= 2 ? gemv_q8_rows_nc<2, PRO, EPI, MAP>(ctx, a, name) : gemv_q8_rows_nc<4, PRO, EPI, MAP>(ctx, a, name);
+    if (wtype == 2) return a.n <= 2 ? gemv_q4_rows_nc<2, PRO, EPI, MAP>(ctx, a, name) : gemv_q4_rows_nc<4, PRO, EPI, MAP>(ctx, a, name);
     if (a.n > 4) return gemv_rows_nc<8, PRO, EPI, MAP>(ctx, a, name);
     return a.n <= 2 ? gemv_rows_nc<2, PRO, EPI, MAP>(ctx, a, name) : gemv_rows_nc<4, PRO, EPI, MAP>(ctx, a, name);
 }
 // rows the decode stream carries: fp32 and f16 up to 8 (round 4; 32 FMAs per 16-byte load = a sixth of a CU's vector rate at the stream's pace),
-// block-int8 up to 4 (its 16 converts + 16 NC FMAs per load saturate the vector ALU from there on)
+// block-int8 and block-int4 up to 4 (their 16 converts + 16 NC FMAs per load saturate the vector ALU from there on)
 static constexpr uint32_t GEMV_ROWS_MAX_F32 = 8, GEMV_ROWS_MAX_Q8 = 4;
-static uint32_t gemv_rows_max(int wtype) { return wtype == 7 ? GEMV_ROWS_MAX_Q8 : GEMV_ROWS_MAX_F32; }
+static uint32_t gemv_rows_max(int wtype) { return wtype == 7 || wtype == 2 ? GEMV_ROWS_MAX_Q8 : GEMV_ROWS_MAX_F32; }
 // every launch of a layer (and the lm_head on the last stage) has an n-row instantiation
 static bool rows_path_ok(lh_ctx* ctx, const ModelDesc& m, uint32_t n) {
     if (n > gemv_rows_max(m.wtype)) return false;
     const uint32_t nc = n <= 2 ? 2 : (n <= 4 ? 4 : 8);
     // (f16: the fp32 predicate - k_gemv_rows_h keeps k_gemv_rows' activation registers and takes no more for its weight slots)
-    auto ok = [&](uint32_t M, uint32_t K, bool norm) { return m.wtype == 7 ? gemv_q8_rows_shape_ok(ctx, M, K) : ((m.wtype == 0 || m.wtype == 1) && gemv_rows_shape_ok(ctx, M, K, nc, norm)); };
+    // (block-int4: the int8 predicate - k_gemv_q4_rows takes k_gemv_q8_rows' launch forms)
+    auto ok = [&](uint32_t M, uint32_t K, bool norm) { return m.wtype == 7 || m.wtype == 2 ? gemv_q8_rows_shape_ok(ctx, M, K) : ((m.wtype == 0 || m.wtype == 1) && gemv_rows_shape_ok(ctx, M, K, nc, norm)); };
     return m.hd % 2 == 0 && m.d % 4 == 0 && ok(3 * m.d, m.d, true) && ok(m.d, m.d, false) && ok(2 * m.F, m.d, true) && ok(m.d, m.F, false) && (!m.last_stage() || ok(m.V, m.d, true));
 }
 
@@ -1448,10 +1546,10 @@ int plan_ensure_rows(Plan* p, uint32_t n) {
     if (n > 1) { rc |= re(&p->qraw, nd); rc |= re(&p->kraw, nd); rc |= re(&p->vraw, nd); rc |= re(&p->a1, nf); rc |= re(&p->a3, nf); }
     if (m.last_stage()) rc |= re(&p->logits, (size_t)n * m.V);
     if (rc) return LH_EHIP;
-    if (n > 1 && (m.wtype == 7 || m.wtype == 0 || m.wtype == 1)) {   // the activations as planes: every row of a block-int8 plan, up to k_stream_b9's 64 rows of an fp32 one (f16: the fp32 schedule)
+    if (n > 1 && (m.wtype == 7 || m.wtype == 0 || m.wtype == 1 || m.wtype == 2)) {   // the activations as planes: every row of a block-int8 plan, up to k_stream_b9's 64 rows of an fp32 one (f16: the fp32 schedule; block-int4: the int8 one)
         if (p->s3) LH_HIP(ctx, hipFree(p->s3));
         p->s3 = nullptr;
-        p->s3_rows = m.wtype == 7 ? n : std::min<uint32_t>(n, B9S_MAX_ROWS);
+        p->s3_rows = m.wtype == 7 || m.wtype == 2 ? n : std::min<uint32_t>(n, B9S_MAX_ROWS);
         LH_HIP(ctx, hipMalloc((void**)&p->s3, (size_t)3 * p->s3_rows * (2 * (size_t)m.d + m.F) * 2));
     }
     if (p->tokens_dev) LH_HIP(ctx, hipFree(p->tokens_dev));
@@ -1480,7 +1578,7 @@ int plan_create(lh_ctx* ctx, const ModelDesc& md, Plan** out) {
     if (rc) { plan_destroy(p); return rc; }
     if (md.wtype == 1) {   // the fp32 images of the widened routes (Plan::md_wide): sized here, once
         const uint64_t d = md.d, F = md.F;
-        if ((rc = wide_image(ctx, 4 * d * d + 3 * d * F, 0, &p->wide_layer)) || (md.last_stage() && (rc = wide_image(ctx, (uint64_t)md.V * d, 1, &p->wide_out)))) { plan_destroy(p); return rc; }
+        if ((rc = wide_image(ctx, 4 * d * d + 3 * d * F, 4, 0, &p->wide_layer)) || (md.last_stage() && (rc = wide_image(ctx, (uint64_t)md.V * d, 4, 1, &p->wide_out)))) { plan_destroy(p); return rc; }
         p->md_wide = md;
         p->md_wide.wtype = 0;
         p->md_wide.output = p->wide_out;
@@ -1488,6 +1586,19 @@ int plan_create(lh_ctx* ctx, const ModelDesc& md, Plan** out) {
         for (uint32_t il = md.layer0; il < md.layer1; ++il) {
             LayerW& L = p->md_wide.layers[il];
             L.wq = w; L.wk = w + d * d; L.wv = w + 2 * d * d; L.wo = w + 3 * d * d; L.w1 = w + 4 * d * d; L.w3 = w + 4 * d * d + d * F; L.w2 = w + 4 * d * d + 2 * d * F;
+        }
+    }
+    if (md.wtype == 2) {   // block-int4: the int8 images of the expanded routes, sized here, once; the shadow keeps the model's own scale planes (s_*)
+        const uint64_t d = md.d, F = md.F;
+        if ((rc = wide_image(ctx, 4 * d * d + 3 * d * F, 1, 0, &p->wide_layer)) || (md.last_stage() && (rc = wide_image(ctx, (uint64_t)md.V * d, 1, 1, &p->wide_out)))) { plan_destroy(p); return rc; }
+        p->md_wide = md;
+        p->md_wide.wtype = 7;
+        p->md_wide.output = p->wide_out;
+        const char* w = (const char*)p->wide_layer;
+        auto at = [&](uint64_t off) { return (const float*)(w + off); };
+        for (uint32_t il = md.layer0; il < md.layer1; ++il) {
+            LayerW& L = p->md_wide.layers[il];
+            L.wq = at(0); L.wk = at(d * d); L.wv = at(2 * d * d); L.wo = at(3 * d * d); L.w1 = at(4 * d * d); L.w3 = at(4 * d * d + d * F); L.w2 = at(4 * d * d + 2 * d * F);
         }
     }
     p->hist =md.kv_hist ? md.kv_hist : std::make_shared<std::vector<uint32_t>>();
@@ -1847,7 +1958,8 @@ static float attn_scale(const ModelDesc& m) { return (float)(1.0 / sqrt((double)
 // What a route's schedule is chosen for and runs on: the plan's model - or, for an f16 model, its fp32 shadow (Plan::md_wide), so that eval_route picks
 // what it picks for a wtype-0 model of the same shapes.  Step and Rows, which the same predicates admit for both, run on the model itself (sched_md is
 // not asked there); Skinny, Planes and Prefill open with it and see an fp32 model.
-static const ModelDesc& sched_md(const Plan* p) { return p->md.wtype == 1 ? p->md_wide : p->md; }
+// A block-int4 model (wtype 2) has a block-int8 shadow in the same way: Step, Rows and Q8Steps run on the nibbles, Planes and Prefill on the int8 image.
+static const ModelDesc& sched_md(const Plan* p) { return p->md.wtype == 1 || p->md.wtype == 2 ? p->md_wide : p->md; }
 // The matrices of layer il for a route that works on m (sched_md): the model's own, or the fp32 image after enqueuing its widening - one exact pass
 // (k_widen_f16) per matrix in front of the layer's launches; the stream orders it behind the launches of the layer before, which read the same image.
 static const LayerW& route_layer(Plan* p, const ModelDesc& m, uint32_t il) {
@@ -1857,17 +1969,24 @@ static const LayerW& route_layer(Plan* p, const ModelDesc& m, uint32_t il) {
     const uint64_t dd = (uint64_t)m.d * m.d, dF = (uint64_t)m.d * m.F;
     const float* src[7] = {S.wq, S.wk, S.wv, S.wo, S.w1, S.w3, S.w2};
     const float* dst[7] = {W.wq, W.wk, W.wv, W.wo, W.w1, W.w3, W.w2};
-    for (int k = 0; k < 7; ++k) widen_f16_launch(p->ctx, src[k], (float*)dst[k], k < 4 ? dd : dF);   // (a launch error surfaces at the layer's hipGetLastError)
+    for (int k = 0; k < 7; ++k) {   // (a launch error surfaces at the layer's hipGetLastError)
+        if (p->md.wtype == 2) expand_q4_launch(p->ctx, src[k], (void*)dst[k], k < 4 ? dd : dF);
+        else widen_f16_launch(p->ctx, src[k], (float*)dst[k], k < 4 ? dd : dF);
+    }
     return W;
 }
 // the output matrix for a route's lm_head of more than one row (or over planes): as above
 static const float* route_output(Plan* p, const ModelDesc& m) {
-    if (&m == &p->md_wide) widen_f16_launch(p->ctx, p->md.output, p->wide_out, (uint64_t)m.V * m.d);
+    if (&m == &p->md_wide) {
+        if (p->md.wtype == 2) expand_q4_launch(p->ctx, p->md.output, p->wide_out, (uint64_t)m.V * m.d);
+        else widen_f16_launch(p->ctx, p->md.output, p->wide_out, (uint64_t)m.V * m.d);
+    }
     return m.output;
 }
-// the output matrix for ONE logits row on the decode stream: an f16 model's halves as they are (k_gemv_sa_h computes the bits k_gemv_sa would over the image)
+// the output matrix for ONE logits row on the decode stream: an f16 model's halves / a block-int4 model's nibbles as they are (k_gemv_sa_h / k_gemv_q4s
+// compute the bits k_gemv_sa / k_gemv_q8s would over the image)
 struct HeadRow { const float* w; int wtype; };
-static HeadRow head_row(const Plan* p, const ModelDesc& m) { return &m == &p->md_wide ? HeadRow{p->md.output, 1} : HeadRow{m.output, m.wtype}; }
+static HeadRow head_row(const Plan* p, const ModelDesc& m) { return &m == &p->md_wide ? HeadRow{p->md.output, p->md.wtype} : HeadRow{m.output, m.wtype}; }
 // The logits rows of the last stage, first row and count: all n as the reference evaluates them (llama.go:372-384), or the last one alone, which is all
 // llama.Eval reads (llama.go:394-401), for callers that say so (LH_GRAPH_LAST_ROW_LOGITS, the lh_llama_* entry points) - in its usual place.
 struct LogitsRows { uint32_t r0, nr; };
@@ -2304,12 +2423,13 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
         { TraceScope ts_(ctx->stream, "rmsnorm_rows_final"); LH_LAUNCH(k_rmsnorm_rows, dim3(nr), dim3(256), 0, ctx->stream, x + (size_t)r0 * d, m.norm, p->h + (size_t)r0 * d, d); }
         if (m.wtype == 7) {
             if (nr >= Q8_GEMM_MIN_ROWS) {
-                if ((rc = gemm_q8(ctx, m.output, m.s_output, p->h + (size_t)r0 * d, p->logits + (size_t)r0 * m.V, nullptr, m.V, d, nr, d, m.V, "gemm_q8_lmhead"))) return rc;
-            } else {   // a few rows (the last row of a long prompt): the int8 GEMV row by row
+                if ((rc = gemm_q8(ctx, route_output(p, m), m.s_output, p->h + (size_t)r0 * d, p->logits + (size_t)r0 * m.V, nullptr, m.V, d, nr, d, m.V, "gemm_q8_lmhead"))) return rc;
+            } else {   // a few rows (the last row of a long prompt): the int8 GEMV row by row (one row of a block-int4 model: on its nibbles)
+                const HeadRow hw = nr == 1 ? head_row(p, m) : HeadRow{route_output(p, m), 7};
                 for (uint32_t i = 0; i < nr; ++i) {
                     GemvArgs ga = {};
-                    ga.w[0] = m.output; ga.ws[0] = m.s_output; ga.M = m.V; ga.K = d; ga.x = p->h + (size_t)(r0 + i) * d; ga.y = p->logits + (size_t)(r0 + i) * m.V;
-                    if ((rc = gemv<PRO_PLAIN, EPI_STORE, MAP_SINGLE>(ctx, ga, "gemv_lmhead_row", 7))) return rc;
+                    ga.w[0] = hw.w; ga.ws[0] = m.s_output; ga.M = m.V; ga.K = d; ga.x = p->h + (size_t)(r0 + i) * d; ga.y = p->logits + (size_t)(r0 + i) * m.V;
+                    if ((rc = gemv<PRO_PLAIN, EPI_STORE, MAP_SINGLE>(ctx, ga, "gemv_lmhead_row", hw.wtype))) return rc;
                 }
             }
         } else if (nr == 1) {   // the one row llama.Eval reads: the decode weight stream (76 us on 7B; the column kernel took 122)
@@ -2355,7 +2475,7 @@ int plan_eval(Plan* p, const uint32_t* tokens_host, const float* x_in_dev, float
         case EvalRoute::Planes:
             rc = eval_planes(p, c, x);
             if (rc != ST_NA) return rc;
-            if (m.wtype == 7) LH_FAIL(ctx, LH_ESHAPE, "block-int8 Eval of %u rows: the plan's shape has no k_stream_q8b launch", n);
+            if (sched_md(p).wtype == 7) LH_FAIL(ctx, LH_ESHAPE, "block-int8 Eval of %u rows: the plan's shape has no k_stream_q8b launch", n);
             break;   // fp32: ST_NA comes back before anything but the embedding is enqueued, and the fp32-MFMA route takes the Eval
         case EvalRoute::Prefill: break;
     }
@@ -3422,7 +3542,7 @@ int lh_llama_create(lh_ctx* ctx, const lh_llama_desc* desc, lh_llama** out) {
     if (!ctx || !desc || !out) LH_FAIL(ctx, LH_EINVAL, "lh_llama_create: NULL argument");
     *out = nullptr;
     LH_HIP(ctx, hipSetDevice(ctx->device));
-    if (desc->weight_dtype != 0 && desc->weight_dtype != 1 && desc->weight_dtype != 7) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_llama_create: weight dtype %d not supported", desc->weight_dtype);
+    if (desc->weight_dtype != 0 && desc->weight_dtype != 1 && desc->weight_dtype != 2 && desc->weight_dtype != 7) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_llama_create: weight dtype %d not supported", desc->weight_dtype);
     ModelDesc md;
     md.V = desc->vocab; md.d = desc->embd; md.H = desc->heads; md.L = desc->layers; md.F = desc->ff; md.ctx = desc->ctx;
     if (!md.H || !md.d || md.d % md.H) LH_FAIL(ctx, LH_ESHAPE, "lh_llama_create: bad embd/heads");
@@ -3445,7 +3565,7 @@ int lh_llama_create(lh_ctx* ctx, const lh_llama_desc* desc, lh_llama** out) {
         if (!bf) LH_FAIL(ctx, LH_EINVAL, "lh_llama_create: %s is not a registered buffer", what);
         if (md.wtype == 1 && bf->dtype != 1) LH_FAIL(ctx, LH_EINVAL, "lh_llama_create: weight_dtype 1 (f16) but %s is a dtype-%d buffer: every matrix of an f16 model must be f16", what, bf->dtype);
         if (bf->nfloats < rows * cols || bf->dtype != md.wtype) LH_FAIL(ctx, LH_ESHAPE, "lh_llama_create: %s has the wrong size or dtype", what);
-        if (md.wtype == 7 && (bf->rows != rows || bf->cols != cols)) LH_FAIL(ctx, LH_ESHAPE, "lh_llama_create: %s block-int8 shape mismatch", what);
+        if ((md.wtype == 7 || md.wtype == 2) && (bf->rows != rows || bf->cols != cols)) LH_FAIL(ctx, LH_ESHAPE, "lh_llama_create: %s %s shape mismatch", what, md.wtype == 7 ? "block-int8" : "block-int4");
         *dst = bf->dev;
         *sc = bf->scales;
         return 0;

@@ -381,7 +381,7 @@ struct llama_layer { ml_tensor *attentionNorm, *wq, *wk, *wv, *wo, *ffn_norm, *w
 struct llama_model {  // llama.go:181-193
     llama_hparams hp;
     uint32_t ffSize;
-    int wtype = ML_TYPE_F32;  // dtype of the weight matrices (ML_TYPE_Q8_0 after llamago_QuantizeModelQ8; ML_TYPE_F16 after llamago_NarrowModelF16 / llamago_LoadModelKeepF16)
+    int wtype = ML_TYPE_F32;  // dtype of the weight matrices (ML_TYPE_Q8_0 after llamago_QuantizeModelQ8; ML_TYPE_F16 after llamago_NarrowModelF16 / llamago_LoadModelKeepF16; ML_TYPE_Q4_0 after llamago_QuantizeModelQ4)
     ml_tensor *tokEmbeddings = nullptr, *norm = nullptr, *output = nullptr;
     std::vector<llama_layer> layers;
     uint32_t layer0, layer1;
@@ -583,13 +583,17 @@ static bool is_matrix_name(const char* name) {   // the seven matrices of a laye
     for (const char* mn : mats) if (!strcmp(dot + 1, mn)) return true;
     return false;
 }
-static llama_model* load_model(const char* fileName, uint32_t ctxSize, bool keep_f16);
-llama_model* llama_LoadModel(const char* fileName, uint32_t ctxSize) { return load_model(fileName, ctxSize, false); }
-llama_model* llamago_LoadModelKeepF16(const char* fileName, uint32_t ctxSize) { return load_model(fileName, ctxSize, true); }
+static llama_model* load_model(const char* fileName, uint32_t ctxSize, int keep);
+llama_model* llama_LoadModel(const char* fileName, uint32_t ctxSize) { return load_model(fileName, ctxSize, 0); }
+llama_model* llamago_LoadModelKeepF16(const char* fileName, uint32_t ctxSize) { return load_model(fileName, ctxSize, ML_TYPE_F16); }
+llama_model* llamago_LoadModelKeepQ4(const char* fileName, uint32_t ctxSize) { return load_model(fileName, ctxSize, ML_TYPE_Q4_0); }
 int llamago_ModelWeightType(const llama_model* m) { return m ? m->wtype : -1; }
-// keep_f16: when EVERY weight matrix of the file is f16, the halves go to HBM as they are (dtype 1; norm vectors and tok_embeddings f32 as ever);
-// any other file loads exactly as without the flag
-static llama_model* load_model(const char* fileName, uint32_t ctxSize, bool keep_f16) {
+// keep = ML_TYPE_F16: when EVERY weight matrix of the file is f16, the halves go to HBM as they are (dtype 1; norm vectors and tok_embeddings f32 as
+// ever); keep = ML_TYPE_Q4_0: the same for a file whose matrices are all Q4_0 - the 20-byte blocks are registered as they are (dtype 2).
+// Any other file loads exactly as without the flag (a Q4_0 tensor then meets llama_LoadModel's own refusal).
+static size_t file_bytes(uint32_t dtype, uint64_t n) { return dtype == ML_TYPE_F16 ? n * 2 : dtype == ML_TYPE_Q4_0 ? n / 32 * 20 : n * 4; }
+static llama_model* load_model(const char* fileName, uint32_t ctxSize, int keep) {
+    bool keep_native = keep != 0;   // the matrices stay in the file's own format (f16 or Q4_0, whichever `keep` names) - until the pre-scan says otherwise
     FILE* f = fopen(fileName, "rb");
     if (!f) return (llama_model*)halt("[ERROR] cannot open model file");
     if (rd_u32(f) != LLAMA_FILE_MAGIC) { fclose(f); return (llama_model*)halt("[ERROR] Invalid model file! Wrong MAGIC in header"); }  // llama.go:722-732
@@ -601,7 +605,7 @@ static llama_model* load_model(const char* fileName, uint32_t ctxSize, bool keep
     hp.layersCount = rd_u32(f); hp.rotCount = rd_u32(f); hp.f16 = rd_u32(f);  // llama.go:743-749
     if (!hp.vocabSize || !hp.embdSize || !hp.headsCount || !hp.layersCount || !hp.multSize) { fclose(f); return (llama_model*)halt("[ERROR] Invalid model file! Bad hyper-parameters"); }
     for (uint32_t i = 0; i < hp.vocabSize; i++) { const uint32_t len = rd_u32(f); fseek(f, (long)len + 4, SEEK_CUR); }  // vocab llama.go:799-811 (not on the hot path)
-    if (keep_f16) {   // a first pass over the tensor headers: are all 7 * layers + 1 matrices there, and f16?
+    if (keep_native) {   // a first pass over the tensor headers: are all 7 * layers + 1 matrices there, and f16?
         const long data0 = ftell(f);
         const uint32_t d = hp.embdSize, F = ff_size(hp.embdSize, hp.multSize), V = hp.vocabSize;
         uint64_t mats = 0;
@@ -612,21 +616,23 @@ static llama_model* load_model(const char* fileName, uint32_t ctxSize, bool keep
             uint64_t n = 1;
             for (uint32_t i = 0; i < dims; i++) n *= rd_u32(f);
             char name[256];
-            if (nameLen >= sizeof name || fread(name, 1, nameLen, f) != nameLen) { keep_f16 = false; break; }
+            if (nameLen >= sizeof name || fread(name, 1, nameLen, f) != nameLen) { keep_native = false; break; }
             name[nameLen] = 0;
-            if (is_matrix_name(name)) { if (dtype != ML_TYPE_F16) { keep_f16 = false; break; } mats++; }
-            if (n > (uint64_t)std::max(V, F) * d || (dtype != ML_TYPE_F16 && dtype != ML_TYPE_F32)) { keep_f16 = false; break; }   // (the load below reports what is wrong)
+            if (is_matrix_name(name)) { if (dtype != (uint32_t)keep || (keep == ML_TYPE_Q4_0 && (dims != 2 || n % 32))) { keep_native = false; break; } mats++; }
+            else if (dtype != ML_TYPE_F16 && dtype != ML_TYPE_F32) { keep_native = false; break; }
+            if (n > (uint64_t)std::max(V, F) * d) { keep_native = false; break; }   // (the load below reports what is wrong)
             const long off = (ftell(f) + 31) & ~31L;
-            if (fseek(f, off + (long)(n * (dtype == ML_TYPE_F16 ? 2 : 4)), SEEK_SET)) { keep_f16 = false; break; }
+            if (fseek(f, off + (long)file_bytes(dtype, n), SEEK_SET)) { keep_native = false; break; }
         }
-        if (mats != 7ull * hp.layersCount + 1) keep_f16 = false;
+        if (mats != 7ull * hp.layersCount + 1) keep_native = false;
         fseek(f, data0, SEEK_SET);
     }
-    llama_model* m = alloc_model(&hp, 0, 0, !keep_f16);
+    llama_model* m = alloc_model(&hp, 0, 0, !keep_native);
     if (!m) { fclose(f); return nullptr; }
     lh_ctx* h = model_ctx();
     std::vector<float> bounce;
     std::vector<uint16_t> half;
+    std::vector<unsigned char> blocks;
     for (;;) {  // llama.go:889-969
         const uint32_t dims = rd_u32(f);
         if (dims < 1 || dims > 2) break;
@@ -643,7 +649,15 @@ static llama_model* load_model(const char* fileName, uint32_t ctxSize, bool keep
         off = (off + 31) & ~31L;  // 32-byte alignment llama.go:926-933
         fseek(f, off, SEEK_SET);
         const uint64_t n = nelements(t);
-        if (keep_f16 && is_matrix_name(name)) {   // the halves as they are: no fp32 bounce, no fp32 copy in HBM
+        if (keep_native && keep == ML_TYPE_Q4_0 && is_matrix_name(name)) {   // the 20-byte blocks as they are (every nibble kept)
+            blocks.resize(file_bytes(ML_TYPE_Q4_0, n));
+            if (t->buf || dtype != ML_TYPE_Q4_0 || fread(blocks.data(), 1, blocks.size(), f) != blocks.size()) { fclose(f); llama_FreeModel(m); return (llama_model*)halt("[ERROR] Failed to read Q4_0 tensor from model!"); }
+            const uint32_t ne4[4] = {t->ne[0], t->ne[1], 1, 1};
+            if (lh_tensor_register(h, 0, ML_TYPE_Q4_0, ne4, 1, blocks.data(), &t->buf)) { g_err = lh_last_error(h); fclose(f); llama_FreeModel(m); return nullptr; }
+            t->type = ML_TYPE_Q4_0;
+            continue;
+        }
+        if (keep_native && is_matrix_name(name)) {   // the halves as they are: no fp32 bounce, no fp32 copy in HBM
             half.resize(n);
             if (t->buf || dtype != ML_TYPE_F16 || fread(half.data(), 2, n, f) != n) { fclose(f); llama_FreeModel(m); return (llama_model*)halt("[ERROR] Failed to read FP16 tensor from model!"); }
             const uint32_t ne4[4] = {t->ne[0], t->ne[1], 1, 1};
@@ -662,7 +676,7 @@ static llama_model* load_model(const char* fileName, uint32_t ctxSize, bool keep
         if (lh_buf_upload(h, t->buf, 0, bounce.data(), n)) { g_err = lh_last_error(h); fclose(f); llama_FreeModel(m); return nullptr; }
     }
     fclose(f);
-    if (keep_f16) m->wtype = ML_TYPE_F16;
+    if (keep_native) m->wtype = keep;
     return m;
 }
 
@@ -670,12 +684,19 @@ static void wr_u32(FILE* f, uint32_t v) { unsigned char b[4] = {(unsigned char)v
 static int wr_tensor(FILE* f, const char* name, ml_tensor* t, int ftype) {  // scripts/convert-pth-to-ggml.py:196-232
     const uint32_t dims = t->dims;
     const bool as16 = ftype == 1 && dims == 2;
-    wr_u32(f, dims); wr_u32(f, (uint32_t)strlen(name)); wr_u32(f, as16 ? 1u : 0u);
+    const bool as_q4 = ftype == ML_TYPE_Q4_0 && t->type == ML_TYPE_Q4_0;   // the matrices of a block-int4 model: their blocks as they are; everything else f32
+    wr_u32(f, dims); wr_u32(f, (uint32_t)strlen(name)); wr_u32(f, as_q4 ? (uint32_t)ML_TYPE_Q4_0 : as16 ? 1u : 0u);
     for (uint32_t i = 0; i < dims; i++) wr_u32(f, t->ne[i]);
     fwrite(name, 1, strlen(name), f);
     long off = ftell(f);
     while (off % 32) { fputc(0, f); off++; }
     const uint64_t n = nelements(t);
+    if (as_q4) {
+        lh_ctx* h = model_ctx();
+        std::vector<unsigned char> blocks(n / 32 * 20);
+        if (!h || lh_buf_read_q4(h, t->buf, 0, blocks.data(), n / 32)) return halt_rc(h ? lh_last_error(h) : "no device context");
+        return fwrite(blocks.data(), 1, blocks.size(), f) != blocks.size();
+    }
     std::vector<float> host(n);
     if (ml_TensorRead(nullptr, t, host.data(), n)) return 1;
     if (as16) { std::vector<uint16_t> hh(n); for (uint64_t i = 0; i < n; i++) hh[i] = f32_to_f16(host[i]); fwrite(hh.data(), 2, n, f); }
@@ -685,6 +706,8 @@ static int wr_tensor(FILE* f, const char* name, ml_tensor* t, int ftype) {  // s
 int llama_SaveModel(const llama_model* mc, const char* fileName, int ftype) {
     llama_model* m = (llama_model*)mc;
     if (m->layer0 != 0 || m->layer1 != m->hp.layersCount) return halt_rc("llama_SaveModel: partial (layer-sharded) model");
+    if (m->wtype == ML_TYPE_Q4_0 && ftype != ML_TYPE_Q4_0) return halt_rc("llama_SaveModel: the model's matrices are block-int4 in HBM (llamago_SaveModelQ4 writes them as they are)");
+    if (ftype == ML_TYPE_Q4_0 && m->wtype != ML_TYPE_Q4_0) return halt_rc("llamago_SaveModelQ4: the model's matrices are not block-int4 (llamago_QuantizeModelQ4 first)");
     if (m->wtype == ML_TYPE_F16) return halt_rc("llama_SaveModel: the model's matrices are f16 in HBM; saving f16 models is not supported (llamago_WidenModelF16 first)");
     FILE* f = fopen(fileName, "wb");
     if (!f) return halt_rc("llama_SaveModel: cannot open file");
@@ -705,6 +728,13 @@ int llama_SaveModel(const llama_model* mc, const char* fileName, int ftype) {
     }
     fclose(f);
     return rc;
+}
+
+// A block-int4 model as a ggjt file of ftype 2: the matrices as 20-byte Q4_0 blocks, norm vectors and tok_embeddings f32.  llamago_LoadModelKeepQ4
+// reads it back without touching a block; llama_LoadModel refuses it as the reference does (llama.go:956-959).
+int llamago_SaveModelQ4(const llama_model* m, const char* fileName) {
+    if (!m || !fileName) return halt_rc("llamago_SaveModelQ4: null argument");
+    return llama_SaveModel(m, fileName, ML_TYPE_Q4_0);
 }
 
 // ---- context + Eval -----------------------------------------------------------------------------------
@@ -1762,6 +1792,7 @@ int llamago_PipelineSync(llama_pipeline* p) { return lh_ctx_sync(p->mlctx->hip) 
 int llamago_QuantizeModelQ8(llama_model* m) {
     if (m->wtype == ML_TYPE_Q8_0) return 0;
     if (m->wtype == ML_TYPE_F16) return halt_rc("llamago_QuantizeModelQ8: the model's matrices are f16 (quantise before narrowing)");
+    if (m->wtype == ML_TYPE_Q4_0) return halt_rc("llamago_QuantizeModelQ8: the model's matrices are block-int4 (llamago_ExpandModelQ4 makes the block-int8 model of the same values)");
     { std::lock_guard<std::mutex> lk(m->mu);
       if (m->users > 0) return halt_rc("llamago_QuantizeModelQ8: contexts of this model are alive (their plans address the f32 weights); quantise before creating contexts"); }
     lh_ctx* h = model_ctx();
@@ -1790,7 +1821,8 @@ static int convert_matrices(llama_model* m, const char* who, int from, int to, u
     char msg[256];
     if (!m) { snprintf(msg, sizeof msg, "%s: null argument", who); return halt_rc(msg); }
     if (m->wtype == to) { if (n_changed) *n_changed = 0; return 0; }
-    if (m->wtype != from) { snprintf(msg, sizeof msg, "%s: the model's matrices are dtype %d, not %s", who, m->wtype, from == ML_TYPE_F32 ? "f32" : "f16"); return halt_rc(msg); }
+    auto tname = [](int t) { return t == ML_TYPE_F32 ? "f32" : t == ML_TYPE_F16 ? "f16" : t == ML_TYPE_Q4_0 ? "block-int4" : "block-int8"; };
+    if (m->wtype != from) { snprintf(msg, sizeof msg, "%s: the model's matrices are %s (dtype %d), not %s", who, tname(m->wtype), m->wtype, tname(from)); return halt_rc(msg); }
     { std::lock_guard<std::mutex> lk(m->mu);
       if (m->users > 0) { snprintf(msg, sizeof msg, "%s: contexts of this model are alive (their plans address the weights); convert before creating contexts", who); return halt_rc(msg); } }
     lh_ctx* h = model_ctx();
@@ -1800,7 +1832,9 @@ static int convert_matrices(llama_model* m, const char* who, int from, int to, u
         if (!t) return 0;
         lh_buf nb = 0;
         uint64_t ch = 0;
-        if (to == ML_TYPE_F16 ? lh_buf_narrow_f16(h, t->buf, t->ne[1], t->ne[0], &nb, &ch) : lh_buf_widen_f16(h, t->buf, &nb)) return halt_rc(lh_last_error(h));
+        const int e = to == ML_TYPE_F16 ? lh_buf_narrow_f16(h, t->buf, t->ne[1], t->ne[0], &nb, &ch) : to == ML_TYPE_Q4_0 ? lh_buf_quantize_q4(h, t->buf, t->ne[1], t->ne[0], &nb)
+                    : to == ML_TYPE_Q8_0 ? lh_buf_expand_q4(h, t->buf, &nb) : lh_buf_widen_f16(h, t->buf, &nb);
+        if (e) return halt_rc(lh_last_error(h));
         lh_buf_free(h, t->buf);
         t->buf = nb;
         t->type = to;
@@ -1818,6 +1852,14 @@ static int convert_matrices(llama_model* m, const char* who, int from, int to, u
 }
 int llamago_NarrowModelF16(llama_model* m, uint64_t* n_changed) { return convert_matrices(m, "llamago_NarrowModelF16", ML_TYPE_F32, ML_TYPE_F16, n_changed); }
 int llamago_WidenModelF16(llama_model* m) { return convert_matrices(m, "llamago_WidenModelF16", ML_TYPE_F16, ML_TYPE_F32, nullptr); }
+// Block-int4 (ML_TYPE_Q4_0, dtype 2 of the C-ABI; format in csrc/kernels_q4.h): llamago_QuantizeModelQ8's shape.  Quantise: every weight MATRIX of an f32
+// model through lh_buf_quantize_q4, the f32 copies released.  Expand: the block-int8 model with the same quants and scales (lh_buf_expand_q4; nothing is
+// requantised) - the tests' way to a twin that runs only the int8 kernels.
+int llamago_QuantizeModelQ4(llama_model* m) { return convert_matrices(m, "llamago_QuantizeModelQ4", ML_TYPE_F32, ML_TYPE_Q4_0, nullptr); }
+int llamago_ExpandModelQ4(llama_model* m) {
+    if (m && m->wtype != ML_TYPE_Q4_0) return halt_rc("llamago_ExpandModelQ4: the model's matrices are not block-int4");
+    return convert_matrices(m, "llamago_ExpandModelQ4", ML_TYPE_Q4_0, ML_TYPE_Q8_0, nullptr);
+}
 // Test instrumentation (tests/test_gpu_attention_bound.py: the probe layer): one fp32 tensor of the model replaced by host values.
 int llamago_SetModelTensor(llama_model* m, const char* name, const float* data, uint64_t n) {
     if (!m || !name || !data) return halt_rc("llamago_SetModelTensor: null argument");
@@ -1827,6 +1869,7 @@ int llamago_SetModelTensor(llama_model* m, const char* name, const float* data, 
     char msg[256];
     if (!t) { snprintf(msg, sizeof msg, "llamago_SetModelTensor: the model has no tensor \"%s\"", name); return halt_rc(msg); }
     if (t->type == ML_TYPE_F16) { snprintf(msg, sizeof msg, "llamago_SetModelTensor: \"%s\" is f16 (set tensors before llamago_NarrowModelF16)", name); return halt_rc(msg); }
+    if (t->type == ML_TYPE_Q4_0) { snprintf(msg, sizeof msg, "llamago_SetModelTensor: \"%s\" is block-int4 (set tensors before llamago_QuantizeModelQ4)", name); return halt_rc(msg); }
     if (t->type != ML_TYPE_F32) { snprintf(msg, sizeof msg, "llamago_SetModelTensor: \"%s\" is quantised (set tensors before llamago_QuantizeModelQ8)", name); return halt_rc(msg); }
     if (n != nelements(t)) { snprintf(msg, sizeof msg, "llamago_SetModelTensor: \"%s\" has %llu elements, %llu given", name, (unsigned long long)nelements(t), (unsigned long long)n); return halt_rc(msg); }
     lh_ctx* h = model_ctx();

@@ -228,6 +228,13 @@ class MLLib:
         f.restype, f.argtypes = VP, [C.c_char_p, C.c_uint32]
         return Model(self, self._chk(f(os.fsencode(path), ctxSize), "llamago_LoadModelKeepF16"))
 
+    def LoadModelKeepQ4(self, path, ctxSize):
+        """llamago_LoadModelKeepQ4 (product only): LoadModel, except that a file whose weight matrices are all Q4_0 keeps their blocks as they are in
+        HBM (Model.weight_type == 2); any other file loads as LoadModel loads it."""
+        f = self.lib.llamago_LoadModelKeepQ4
+        f.restype, f.argtypes = VP, [C.c_char_p, C.c_uint32]
+        return Model(self, self._chk(f(os.fsencode(path), ctxSize), "llamago_LoadModelKeepQ4"))
+
 
 def make_hparams(vocab, embd, mult, heads, layers, ctx=128):
     hp = HParams()
@@ -290,9 +297,33 @@ class Model:
             raise MLError(f"llamago_WidenModelF16: {self.ml.last_error()}")
         return self
 
+    def QuantizeQ4(self):
+        """llamago_QuantizeModelQ4 (product only): every weight matrix quantised to block-int4 in HBM (20 bytes per 32 weights), the f32 copies
+        released.  Before any context of the model exists."""
+        f = self.ml.lib.llamago_QuantizeModelQ4
+        f.restype, f.argtypes = C.c_int, [VP]
+        if f(self.h):
+            raise MLError(f"llamago_QuantizeModelQ4: {self.ml.last_error()}")
+        return self
+
+    def SaveQ4(self, path):
+        """llamago_SaveModelQ4 (product only): a block-int4 model as a ggjt file of ftype 2 (LoadModelKeepQ4 reads it back block for block)."""
+        f = self.ml.lib.llamago_SaveModelQ4
+        f.restype, f.argtypes = C.c_int, [VP, C.c_char_p]
+        if f(self.h, os.fsencode(path)):
+            raise MLError(f"llamago_SaveModelQ4: {self.ml.last_error()}")
+
+    def ExpandQ4(self):
+        """llamago_ExpandModelQ4 (product only): a block-int4 model as the block-int8 model with the same quants and scales (identical values)."""
+        f = self.ml.lib.llamago_ExpandModelQ4
+        f.restype, f.argtypes = C.c_int, [VP]
+        if f(self.h):
+            raise MLError(f"llamago_ExpandModelQ4: {self.ml.last_error()}")
+        return self
+
     @property
     def weight_type(self):
-        """llamago_ModelWeightType (product only): 0 = f32, 1 = f16, 7 = block-int8 weight matrices."""
+        """llamago_ModelWeightType (product only): 0 = f32, 1 = f16, 2 = block-int4, 7 = block-int8 weight matrices."""
         f = self.ml.lib.llamago_ModelWeightType
         f.restype, f.argtypes = C.c_int, [VP]
         return int(f(self.h))

@@ -9,7 +9,8 @@ in one process with plain lh_llama_decode_greedy; the table shows medians and th
   excess = t_pass - ((K + 1) * t_draft_step + t_verify) next to the spread of that sum; and, to say where an excess goes, a call of ONE id (one
       pass) against the cost of every further pass of the 96-id call.
 The weights are synthetic: the acceptance of a block-int8 twin of RANDOM weights is what this run measured, not a model result.
-usage: python tools/bench_draft_model.py [--layers 32] [--reps 3] [--ids 96] [--out profiles/draft_model.txt]"""
+--draft q4: the target's block-int4 form (Model.QuantizeQ4) as the draft instead: 20/36 of the int8 draft's bytes per drafted id.
+usage: python tools/bench_draft_model.py [--layers 32] [--reps 3] [--ids 96] [--draft q8|q4] [--out profiles/draft_model.txt | profiles/draft_model_q4.txt]"""
 import argparse, json, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -21,14 +22,20 @@ ap.add_argument("--layers", type=int, default=32)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--ids", type=int, default=96)
 ap.add_argument("--ctx", type=int, default=128)
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "draft_model.txt"))
+ap.add_argument("--out", default=None, help="default: profiles/draft_model.txt (--draft q8) or profiles/draft_model_q4.txt (--draft q4)")
+ap.add_argument("--draft", choices=("q8", "q4"), default="q8")
 args = ap.parse_args()
+if args.out is None:
+    args.out = os.path.join(ROOT, "profiles", "draft_model_q4.txt" if args.draft == "q4" else "draft_model.txt")
 prod = load_product()
 KS, n, ctx, past = (1, 3, 5, 7), args.ids, args.ctx, len(PROMPT)
 
 kw = dict(SHAPES["7B"]); kw["layers"] = args.layers
 target_model = prod.NewSyntheticModel(make_hparams(**kw, ctx=ctx), 1234)
-draft_model = prod.NewSyntheticModel(make_hparams(**kw, ctx=ctx), 1234).QuantizeQ8()
+draft_model = prod.NewSyntheticModel(make_hparams(**kw, ctx=ctx), 1234)
+draft_model = draft_model.QuantizeQ4() if args.draft == "q4" else draft_model.QuantizeQ8()
+DRAFT = "QuantizeQ4" if args.draft == "q4" else "QuantizeQ8"
+DRAFT_FMT = "block-int4" if args.draft == "q4" else "block-int8"
 pair = DraftPair(target_model, draft_model, ctx)
 first = int(np.argmax(pair.target.Eval(PROMPT, 0)))
 pair.draft.Eval(PROMPT, 0)
@@ -73,10 +80,10 @@ med = {k: sorted(v)[len(v) // 2] for k, v in ts.items()}
 spr = {k: max(v) - min(v) for k, v in ts.items()}
 
 t_step, t_dstep = med["greedy"] / n, med["draft_step"] / n
-out = ["# tools/bench_draft_model.py: synthetic 7B fp32 target (%d layers), its QuantizeQ8 twin as draft, ctx %d, %d ids, %d repeats (median, spread = max - min)" % (args.layers, ctx, n, args.reps),
+out = ["# tools/bench_draft_model.py: synthetic 7B fp32 target (%d layers), its %s twin as draft, ctx %d, %d ids, %d repeats (median, spread = max - min)" % (args.layers, DRAFT, ctx, n, args.reps),
        "# acceptance on RANDOM weights is an artefact of the synthetic model, not a model result; there is no speed-up gate",
        "plain greedy (target): %.3f ms/step  %.1f tok/s  (spread of the %d-id run %.2f ms)" % (t_step, 1e3 / t_step, n, spr["greedy"]),
-       "draft plain resident step (block-int8 twin): %.3f ms/step  %.1f tok/s  (spread of the run %.2f ms)" % (t_dstep, 1e3 / t_dstep, spr["draft_step"]),
+       "draft plain resident step (%s twin): %.3f ms/step  %.1f tok/s  (spread of the run %.2f ms)" % (DRAFT_FMT, t_dstep, 1e3 / t_dstep, spr["draft_step"]),
        "",
        "draft_len rows passes  ms/pass  accepted/drafted  acc/pass  tok/s   vs greedy  break-even acc/pass | t_verify(R)  (K+1)*t_dstep  excess    spread of the parts  same ids"]
 rows = []

@@ -1,11 +1,11 @@
-"""Perplexity of a token sequence under a model on the MI355X, fp32 and (--int8) the same model after QuantizeQ8: the log-probs are reduced on
+"""Perplexity of a token sequence under a model on the MI355X, fp32 and (--int8 / --int4) the same model after QuantizeQ8 / QuantizeQ4: the log-probs are reduced on
 the device (lh_llama_score), only 32 bytes per token come back.  The project has no tokenizer: token ids come from a .npy (--ids), from a
 seeded generator (--random N) or, by default, from the committed golden run (the 8-token prompt + the 100 ids the checker decoded).
 Convention (include/llamago_ext.h, llamago_Perplexity): windows of --ctx tokens, each from position 0 in Evals of at most --chunk rows,
 row i against token i+1, a window's last row not scored.  Prints one JSON line; `ms` = wall time of the whole scored pass (median of --reps,
 after one warm-up pass), `probe_gbps` (--probe) = what a bare read of one chunk's [rows][vocab] logits reaches on this box.
 On synthetic (random) weights the figures say little about real models: they exercise the path and compare the two weight formats.
-usage: python tools/perplexity.py (--model file.bin | --synthetic) [--shape 7B] [--layers L] [--ctx 1024] [--chunk 512] [--ids ids.npy | --random N] [--int8]"""
+usage: python tools/perplexity.py (--model file.bin | --synthetic) [--shape 7B] [--layers L] [--ctx 1024] [--chunk 512] [--ids ids.npy | --random N] [--int8] [--int4]"""
 import argparse
 import json
 import math
@@ -29,6 +29,7 @@ ap.add_argument("--chunk", type=int, default=0, help="rows per Eval (0: 512)")
 ap.add_argument("--ids", help=".npy of token ids")
 ap.add_argument("--random", type=int, default=0, help="this many seeded random ids instead of the golden sequence")
 ap.add_argument("--int8", action="store_true", help="also the same model after QuantizeQ8, and the difference")
+ap.add_argument("--int4", action="store_true", help="also the same model after QuantizeQ4 (block-int4), and the difference")
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--probe", action="store_true")
 args = ap.parse_args()
@@ -45,10 +46,12 @@ def load_model():
     return prod.NewSyntheticModel(make_hparams(**kw, ctx=args.ctx), 1234)
 
 
-def run(int8):
+def run(wtype):
     m = load_model()
-    if int8:
+    if wtype == 7:
         m.QuantizeQ8()
+    if wtype == 2:
+        m.QuantizeQ4()
     V = m.hp.vocabSize
     if args.ids:
         ids = [int(t) for t in np.load(args.ids).ravel()]
@@ -70,9 +73,13 @@ def run(int8):
 
 
 out = {"model": args.model or f"synthetic {args.shape}" + (f" x{args.layers} layers" if args.layers else ""), "ctx": args.ctx, "chunk": args.chunk or 512}
-out["fp32"], out["n_tokens"], V = run(False)
+out["fp32"], out["n_tokens"], V = run(0)
+if args.int4:
+    out["int4"], _, _ = run(2)
+    out["perplexity_int4_minus_fp32"] = out["int4"]["perplexity"] - out["fp32"]["perplexity"]
+    out["nll_per_token_int4_minus_fp32"] = out["int4"]["nll_sum"] / out["int4"]["n_scored"] - out["fp32"]["nll_sum"] / out["fp32"]["n_scored"]
 if args.int8:
-    out["int8"], _, _ = run(True)
+    out["int8"], _, _ = run(7)
     out["perplexity_int8_minus_fp32"] = out["int8"]["perplexity"] - out["fp32"]["perplexity"]
     out["nll_per_token_int8_minus_fp32"] = out["int8"]["nll_sum"] / out["int8"]["n_scored"] - out["fp32"]["nll_sum"] / out["fp32"]["n_scored"]
 if args.probe:
