@@ -72,6 +72,13 @@ llama_model* llamago_LoadModelKeepF16(const char* fileName, uint32_t ctxSize);
 int llamago_NarrowModelF16(llama_model* m, uint64_t* n_changed);
 int llamago_WidenModelF16(llama_model* m);
 int llamago_ModelWeightType(const llama_model* m);
+/* lh_ctx_set_f16_stream / lh_ctx_f16_stream (llamahip.h) on the lh_ctx the context / the batch evaluates in: with on != 0 the Evals of 2..128 rows of an
+ * f16 model that take the stream kernels read the model's halves (k_stream_mm2_h / k_stream_dma_h) instead of an fp32 image widened in front of every
+ * layer - the same bytes ("Native stream kernels").  Off by default (LLAMAHIP_F16_STREAM=1 turns it on for contexts created afterwards); without
+ * effect on models of another weight type.  The setters return non-zero (ml_LastError) on a null argument; the getters 0 | 1.
+ * llamago_BatchSetF16Stream / llamago_BatchF16Stream (declared with the batch below): the same for a batch's ticks, feeds and speculative passes. */
+int llamago_SetF16Stream(llama_context* c, int on);
+int llamago_F16Stream(llama_context* c);
 /* Block-int4 weight matrices (ML_TYPE_Q4_0 = dtype 2 of llamahip.h: 20 bytes per 32 weights; norm vectors and tok_embeddings stay f32).  A 4-bit quant
  * q in [-8, 7] with block scale d IS a block-int8 weight with the same q and d, so every Eval route of such a model produces the bytes its expansion
  * produces: one row and 2..4 rows on 4-bit forms of the decode stream kernels, every other row count on the int8 kernels behind an exact expansion
@@ -183,6 +190,8 @@ typedef struct llama_batch llama_batch;
 llama_batch* llamago_NewBatch(llama_model* m, uint32_t ctxSize, uint32_t pods);
 void llamago_FreeBatch(llama_batch* b);
 int llamago_BatchBatched(llama_batch* b);            /* lh_batch_batched */
+int llamago_BatchSetF16Stream(llama_batch* b, int on);   /* llamago_SetF16Stream on the lh_ctx the batch evaluates in */
+int llamago_BatchF16Stream(llama_batch* b);
 /* Test instrumentation: llamago_CacheRead / llamago_CacheWrite on the KV cache of pod `pod` (also fails on a pod outside the batch). */
 int llamago_BatchCacheRead(llama_batch* b, uint32_t pod, int which, uint64_t off_floats, float* dst, uint64_t n);
 int llamago_BatchCacheWrite(llama_batch* b, uint32_t pod, int which, uint64_t off_floats, const float* src, uint64_t n);

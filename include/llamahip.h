@@ -93,6 +93,19 @@ int lh_buf_read_q4(lh_ctx* ctx, lh_buf buf, uint64_t block0, void* dst_blocks, u
  * fp32 kernels); exact for every half, a NaN stays a NaN.  Both synchronise.  A source of the wrong dtype: LH_EINVAL. */
 int lh_buf_narrow_f16(lh_ctx* ctx, lh_buf src_f32, uint32_t rows, uint32_t cols, lh_buf* out, uint64_t* n_changed);
 int lh_buf_widen_f16(lh_ctx* ctx, lh_buf src_f16, lh_buf* out_f32);
+/* f16 models on the weight-stream MFMA kernels of 2..128 rows (csrc/kernels_stream_f16.h).  lh_ctx_set_f16_stream(ctx, on): with on != 0 every Eval of an
+ * f16 plan of this context that takes the prefill route hands the stream launches the model's own halves (k_stream_mm2_h / k_stream_dma_h) and widens a
+ * matrix only directly in front of a launch that reads fp32 - it replaces the k_widen_f16 pass per matrix and layer in front of the fp32 stream kernels
+ * (weight_dtype below), byte for byte the same results.  Off by default; the initial value is LLAMAHIP_F16_STREAM=1 of the environment, read once in
+ * lh_ctx_create.  Read at every Eval; accepted and without effect for fp32, block-int8 and block-int4 plans.  A change makes every captured graph of an f16
+ * plan on the context that may hold a stream launch run eagerly once and be captured anew.  lh_ctx_f16_stream: the current value (0 | 1; ctx NULL: 0). */
+int lh_ctx_set_f16_stream(lh_ctx* ctx, int on);
+int lh_ctx_f16_stream(lh_ctx* ctx);
+/* Where k_stream_dma_h keeps a half (csrc/stream_f16_layout.h; pure host functions, for checks): byte offset, in the weight part of a ring image of
+ * kc-column chunks (64 | 128), of 16-byte granule g (columns 8 g .. 8 g + 7 of the chunk) of image row r (< 128) / of the 8 bytes MFMA lane (r16, slot) reads of
+ * tile slot t (< 8) for k-block kb (< kc / 16) of the chunk.  An argument out of range: -1. */
+int64_t lh_stream_f16_image_off(uint32_t kc, uint32_t r, uint32_t g);
+int64_t lh_stream_f16_read_off(uint32_t kc, uint32_t t, uint32_t r16, uint32_t kb, uint32_t slot);
 /* Dequantised fp32 values of a dtype-7 buffer (w = fl32(d*q)), for checks. */
 int lh_buf_read_q8(lh_ctx* ctx, lh_buf buf, uint64_t off, float* dst, uint64_t n);
 int lh_buf_free(lh_ctx* ctx, lh_buf buf);

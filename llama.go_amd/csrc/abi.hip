@@ -2,6 +2,7 @@
 // C-ABI entry points declared in include/llamahip.h.
 #include "common.h"
 #include "kernels_q8_pack.h"
+#include "stream_f16_layout.h"
 #include <stdarg.h>
 #include <math.h>
 #include <algorithm>
@@ -272,8 +273,26 @@ int lh_ctx_create(int device, void* stream, lh_ctx** out) {
         if (e != hipSuccess) { delete c; LH_FAIL(nullptr, LH_EHIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
         c->own_stream = true;
     }
+    const char* hs = getenv("LLAMAHIP_F16_STREAM");
+    c->f16_stream = hs && hs[0] == '1' ? 1 : 0;
     *out = c;
     return LH_OK;
+}
+
+int lh_ctx_set_f16_stream(lh_ctx* ctx, int on) {
+    if (!ctx) return LH_EINVAL;
+    const int v = on ? 1 : 0;
+    if (v != ctx->f16_stream) { ctx->f16_stream = v; ++ctx->f16_stream_gen; }
+    return LH_OK;
+}
+int lh_ctx_f16_stream(lh_ctx* ctx) { return ctx ? ctx->f16_stream : 0; }
+int64_t lh_stream_f16_image_off(uint32_t kc, uint32_t r, uint32_t g) {
+    if ((kc != 64 && kc != 128) || r >= 128 || g >= kc / 8) return -1;
+    return (int64_t)lh::stream_h_granule_off(kc, r, g);
+}
+int64_t lh_stream_f16_read_off(uint32_t kc, uint32_t t, uint32_t r16, uint32_t kb, uint32_t slot) {
+    if ((kc != 64 && kc != 128) || t >= 8 || r16 >= 16 || kb >= kc / 16 || slot >= 4) return -1;
+    return (int64_t)lh::stream_h_read_off(kc, t, r16, kb, slot);
 }
 
 int lh_ctx_sync(lh_ctx* ctx) {

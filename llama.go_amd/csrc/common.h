@@ -152,6 +152,10 @@ struct lh_ctx {
     float* splitk = nullptr;
     uint64_t splitk_floats = 0;
     uint64_t splitk_gen = 0;
+    // lh_ctx_set_f16_stream: f16 plans hand the stream kernels of their prefill route the model's halves (kernels_stream_f16.h).  A switch that chooses a
+    // kernel (graph_cache.h): f16_stream_gen counts the changes and is part of the key of every captured graph of an f16 plan that may hold a stream launch
+    int f16_stream = 0;
+    uint64_t f16_stream_gen = 0;
     // the activation rows of a long-prompt GEMM as three bf16 planes (k_gemm_b9); grows, never shrinks
     uint16_t* xs3 = nullptr;
     uint64_t xs3_elems = 0;

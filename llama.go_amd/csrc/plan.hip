@@ -14,6 +14,7 @@
 #include "kernels_gemm_b9.h"
 #include "kernels_rows.h"
 #include "kernels_f16.h"
+#include "kernels_stream_f16.h"
 #include "kernels_q4.h"
 #include "kernels_attn_seg.h"
 #include "kernels_attn_share.h"
@@ -895,8 +896,11 @@ static int stream_nct(uint32_t n) { return (int)((n + 15) / 16); }
 static int stream_kc(uint32_t n) { return n <= 48 ? 128 : 64; }
 static constexpr uint32_t stream_max_rows() { return STREAM_ROWS_BUILT; }
 
+// wdt (here and down the chain): the dtype of the matrices a.w[] points at - 0 = fp32, 1 = f16 (the model's own halves: the _h kernel of the SAME
+// template arguments, kernels_stream_f16.h).  Every predicate that answers ST_NA is the fp32 chain's, the LDS sizes of fp32 images included: an f16
+// model must stream exactly the matrices its widened twin streams, or the two take kernels of different summation order.
 template <int MAXT, int NCT, int KC>
-static int launch_stream(lh_ctx* ctx, const StreamArgs& a, const char* name) {
+static int launch_stream(lh_ctx* ctx, const StreamArgs& a, const char* name, int wdt = 0) {
     static bool flags[16] = {};
     // k_stream_mm2 (loader waves + MFMA waves, two LDS images); shapes whose two images do not fit have no launch here (round 1's kernel in which
     // every wave loaded and multiplied took them until round 6: no LLaMA shape reached it - tests/test_gpu_zz_routes.py; tools/kernels_stream_mm_r1.h)
@@ -905,6 +909,20 @@ static int launch_stream(lh_ctx* ctx, const StreamArgs& a, const char* name) {
     if (stream2_lds_bytes(MAXT, NCT, KC2) > 160 * 1024) return ST_NA;
     const uint32_t grid = a.ksplit > 1 ? (uint32_t)ctx->ds->num_cu / a.ksplit * a.ksplit : (uint32_t)ctx->ds->num_cu;
     const size_t lds = std::max<size_t>(stream2_lds_bytes(MAXT, NCT, KC2), 82 * 1024);   // one workgroup per CU
+    if (wdt == 1) {
+        // (from two column tiles on every launch of the chain without a folded norm is k_stream_dma's: only the one-column-tile forms are built)
+        if constexpr (NCT == 1) {
+            static bool flags_h[16] = {};
+            auto kern = k_stream_mm2_h<MAXT, NCT, KC2>;
+            if (const int rh = set_lds_once(ctx, kern, lds, flags_h)) return rh;
+            if (g_prepare_only) return 0;
+            ProfScope ps(ctx->stream, name, (uint64_t)a.groups * a.M * a.K * 2);
+            LH_TRACE("k_stream_mm2_h<%d,%d,%d>/s%u", MAXT, NCT, KC2, a.ksplit > 1 ? a.ksplit : 1u);
+            LH_LAUNCH_AS("k_stream_mm2_h", kern, dim3(grid), dim3(2 * ST_TH), lds, ctx->stream, a);
+            LH_HIP(ctx, hipGetLastError());
+            return 0;
+        } else LH_FAIL(ctx, LH_EUNSUPPORTED, "%s: k_stream_mm2_h is not built for %d column tiles", name, NCT);
+    }
     int rc = set_lds_once(ctx, k_stream_mm2<MAXT, NCT, KC2>, lds, flags);
     if (rc) return rc;
     if (g_prepare_only) return 0;
@@ -939,13 +957,53 @@ static int launch_stream_dma(lh_ctx* ctx, const StreamArgs& a, const char* name)
     LH_HIP(ctx, hipGetLastError());
     return 0;
 }
+// k_stream_dma_h (kernels_stream_f16.h): the same shape on f16 weights.  Ring depth: the weight part of an image is half as large, so more images fit;
+// shipped: as many as fit up to four with 64-column chunks (the fp32 cap) and up to three with 128-column chunks (fp32: the two that fit).  Probe builds
+// (-DSTREAM_H_NIMG64=5; -DSTREAM_H_NIMG64=3 -DSTREAM_H_NIMG128=2) measured within 2 % of these at 9..160 rows, no consistent winner
+// (profiles/f16_stream.txt); the sums do not depend on the depth.
+#ifndef STREAM_H_NIMG64
+#define STREAM_H_NIMG64 4
+#endif
+#ifndef STREAM_H_NIMG128
+#define STREAM_H_NIMG128 3
+#endif
+constexpr int dma_h_nimg_fit(int maxt, int nct, int kc, int cap) {
+    int n = (int)(160 * 1024 / stream_dma_h_image_bytes(maxt, nct, kc));
+    return n < cap ? n : cap;
+}
+template <int MAXT, int NCT, int KC, int CS = 1>
+static int launch_stream_dma_h(lh_ctx* ctx, const StreamArgs& a, const char* name) {
+    constexpr int NIMG = dma_h_nimg_fit(MAXT, NCT, KC, KC == 64 ? STREAM_H_NIMG64 : STREAM_H_NIMG128);
+    static_assert(NIMG >= 2, "ring");
+    static bool flags[16] = {};
+    auto kern = k_stream_dma_h<MAXT, NCT, KC, NIMG, false, CS>;
+    const size_t lds = std::max<size_t>((size_t)NIMG * stream_dma_h_image_bytes(MAXT, NCT, KC), 82 * 1024);   // one workgroup per CU
+    int rc = set_lds_once(ctx, kern, lds, flags);
+    if (rc) return rc;
+    if (g_prepare_only) return 0;
+    const uint32_t grid = a.ksplit > 1 ? (uint32_t)ctx->ds->num_cu / a.ksplit * a.ksplit : (uint32_t)ctx->ds->num_cu;
+    ProfScope ps(ctx->stream, name, (uint64_t)a.groups * a.M * a.K * 2);
+    LH_TRACE("k_stream_dma_h<%d,%d,%d,%d,%d,%d>/s%u", MAXT, NCT, KC, NIMG, 0, CS, a.ksplit > 1 ? a.ksplit : 1u);
+    LH_LAUNCH_AS("k_stream_dma_h", kern, dim3(grid), dim3(2 * ST_TH), lds, ctx->stream, a);
+    LH_HIP(ctx, hipGetLastError());
+    return 0;
+}
 // variants: 0 = 64-column chunks, as many images as fit (<= 4); 2 = 128-column chunks, two images; 1 / 3 = the same with pipelined operands
 // (measured round 4, profiles/r04_stream_dma_variants.txt: the operand pipeline buys nothing on two to six column tiles - the LDS
 // latency behind a barrier is not what idles the matrix pipe - so only the eight-column-tile launches are built with it)
 template <int MAXT, int NCT>
-static int launch_stream_dma_v(lh_ctx* ctx, const StreamArgs& a, const char* name, int v) {
+static int launch_stream_dma_v(lh_ctx* ctx, const StreamArgs& a, const char* name, int v, int wdt = 0) {
     constexpr int N64 = dma_nimg_fit(MAXT, NCT, 64, 4), N128 = dma_nimg_fit(MAXT, NCT, 128, 2);
     static_assert(N64 >= 2, "two images of 64-column chunks always fit");
+    if (wdt == 1) {   // the chunk length and the column split the fp32 branch below picks (the operand pipeline, v == 1, is no shipped default: not built)
+        if (v != 0 && v != 2) LH_FAIL(ctx, LH_EUNSUPPORTED, "%s: k_stream_dma_h has no pipelined variant", name);
+        if constexpr (NCT == 8) return launch_stream_dma_h<MAXT, NCT, 64, 2>(ctx, a, name);
+        else if constexpr (NCT == 7) return launch_stream_dma_h<MAXT, NCT, 64>(ctx, a, name);
+        else {
+            if constexpr (N128 >= 2) if (v == 2) return launch_stream_dma_h<MAXT, NCT, 128>(ctx, a, name);
+            return launch_stream_dma_h<MAXT, NCT, 64>(ctx, a, name);
+        }
+    }
     if constexpr (NCT == 8) {   // eight column tiles: MFMA waves as 2 K-groups x 2 column halves, 64-column chunks
         static_assert(dma_pipe_ok(MAXT, NCT / 2), "column split");
         if (v == 1) return launch_stream_dma<MAXT, NCT, 64, N64, true, 2>(ctx, a, name);
@@ -965,15 +1023,15 @@ static int stream_dma_default_variant(int maxt, int nct) { return (nct == 2 && m
 // load instruction, more bytes in flight) measured slower on the other 7B shapes, and a chunk-major copy of the weights (contiguous
 // runs per workgroup) gained 2-13 % at twice the footprint: profiles/r02c_stream_mm_check.txt.
 template <int MAXT, int NCT>
-static int launch_stream_kc(lh_ctx* ctx, const StreamArgs& a, const char* name) {
-    if constexpr (NCT >= 4) return launch_stream<MAXT, NCT, 64>(ctx, a, name);
+static int launch_stream_kc(lh_ctx* ctx, const StreamArgs& a, const char* name, int wdt = 0) {
+    if constexpr (NCT >= 4) return launch_stream<MAXT, NCT, 64>(ctx, a, name, wdt);
     else {
-        if (MAXT == 1 && a.K > 4096 && a.K % 256 == 0) return launch_stream<MAXT, NCT, (MAXT == 1 ? 256 : 128)>(ctx, a, name);
-        return launch_stream<MAXT, NCT, 128>(ctx, a, name);
+        if (MAXT == 1 && a.K > 4096 && a.K % 256 == 0) return launch_stream<MAXT, NCT, (MAXT == 1 ? 256 : 128)>(ctx, a, name, wdt);
+        return launch_stream<MAXT, NCT, 128>(ctx, a, name, wdt);
     }
 }
 template <int MAXT, int NCT>
-static int launch_stream_nct(lh_ctx* ctx, const StreamArgs& a, const char* name) {
+static int launch_stream_nct(lh_ctx* ctx, const StreamArgs& a, const char* name, int wdt = 0) {
     // (one column tile, 9..16 rows, stays on k_stream_mm2 with the norm folded into the launch.  Round 5 built the sixteen-equal-waves LDS-DMA
     // structure of k_stream_q8b for it, norm folded on the operand-read side (tools/kernels_stream_eq.h): correct, and slower on every 7B launch -
     // w1|w3 72.0 us against 66-67, wq|wk|wv 43.3 / 39.5, wo 32.0 / 17.6, w2 79.3 / 37.6 at 16 rows - a workgroup barrier of sixteen waves costs
@@ -981,22 +1039,22 @@ static int launch_stream_nct(lh_ctx* ctx, const StreamArgs& a, const char* name)
     if constexpr (NCT >= 2) {
         // (one column tile, 9..16 rows, stays on k_stream_mm2 with the norm folded into the launch: on the LDS-DMA kernel with the norm's own launch
         // in front it measured 6.12-6.14 ms per Eval against 5.63-5.68, 16 pods 5.91 against 5.81 ms per tick - profiles/r04_stream_one_column_tile_probe.txt)
-        if (!a.ws[0] && !a.gamma && !a.tiled) return launch_stream_dma_v<MAXT, NCT>(ctx, a, name, stream_dma_default_variant(MAXT, NCT));
+        if (!a.ws[0] && !a.gamma && !a.tiled) return launch_stream_dma_v<MAXT, NCT>(ctx, a, name, stream_dma_default_variant(MAXT, NCT), wdt);
     }
     if constexpr (NCT > 6) return ST_NA;   // (k_stream_mm2 holds MAXT x NCT accumulator tiles per wave: up to six column tiles)
-    else return launch_stream_kc<MAXT, NCT>(ctx, a, name);
+    else return launch_stream_kc<MAXT, NCT>(ctx, a, name, wdt);
 }
 template <int MAXT>
-static int launch_stream_n(lh_ctx* ctx, const StreamArgs& a, const char* name) {
-    if (a.n <= 16) return launch_stream_nct<MAXT, 1>(ctx, a, name);
-    if (a.n <= 32) return launch_stream_nct<MAXT, 2>(ctx, a, name);
-    if (a.n <= 48) return launch_stream_nct<MAXT, 3>(ctx, a, name);
-    if (a.n <= 64) return launch_stream_nct<MAXT, 4>(ctx, a, name);
+static int launch_stream_n(lh_ctx* ctx, const StreamArgs& a, const char* name, int wdt = 0) {
+    if (a.n <= 16) return launch_stream_nct<MAXT, 1>(ctx, a, name, wdt);
+    if (a.n <= 32) return launch_stream_nct<MAXT, 2>(ctx, a, name, wdt);
+    if (a.n <= 48) return launch_stream_nct<MAXT, 3>(ctx, a, name, wdt);
+    if (a.n <= 64) return launch_stream_nct<MAXT, 4>(ctx, a, name, wdt);
     if constexpr (MAXT <= 6) {   // (8 x 5 / 8 x 6 accumulator tiles do not fit the registers: those launches take the tile GEMM)
-        if (a.n <= 80) return launch_stream_nct<MAXT, 5>(ctx, a, name);
-        if (a.n <= 96) return launch_stream_nct<MAXT, 6>(ctx, a, name);
-        if (a.n <= 112) return launch_stream_nct<MAXT, 7>(ctx, a, name);   // 97..128 rows (round 4): seven / eight column tiles, fp32 weights only
-        return launch_stream_nct<MAXT, 8>(ctx, a, name);
+        if (a.n <= 80) return launch_stream_nct<MAXT, 5>(ctx, a, name, wdt);
+        if (a.n <= 96) return launch_stream_nct<MAXT, 6>(ctx, a, name, wdt);
+        if (a.n <= 112) return launch_stream_nct<MAXT, 7>(ctx, a, name, wdt);   // 97..128 rows (round 4): seven / eight column tiles, fp32 weights only
+        return launch_stream_nct<MAXT, 8>(ctx, a, name, wdt);
     }
     return ST_NA;
 }
@@ -1016,12 +1074,12 @@ static int with_stream_maxt(uint32_t maxt, F&& f) {
         default: return ST_NA;
     }
 }
-static int launch_stream_maxt(lh_ctx* ctx, const StreamArgs& a, const char* name, uint32_t maxt) {
-    return with_stream_maxt(maxt, [&](auto mt) { return launch_stream_n<decltype(mt)::value>(ctx, a, name); });
+static int launch_stream_maxt(lh_ctx* ctx, const StreamArgs& a, const char* name, uint32_t maxt, int wdt = 0) {
+    return with_stream_maxt(maxt, [&](auto mt) { return launch_stream_n<decltype(mt)::value>(ctx, a, name, wdt); });
 }
 // returns ST_NA when the shape is not one the kernel is built for (the caller then takes the tile GEMM)
 static int gemm_stream_group(lh_ctx* ctx, const float* x, uint32_t ldx, uint32_t groups, const float* const* w, float* const* y, const float* const* r, uint32_t M,
-                             uint32_t K, uint32_t n, uint32_t ldy, const char* name, const StreamArgs* fused = nullptr) {
+                             uint32_t K, uint32_t n, uint32_t ldy, const char* name, const StreamArgs* fused = nullptr, int wdt = 0) {
     if (n > stream_max_rows() || groups > 3 || M % 16 || K % 128 || ldx % 4 || ldy % 4 || ((uintptr_t)x & 15)) return ST_NA;
     const uint32_t ncu = (uint32_t)ctx->ds->num_cu, T = M / 16 * groups;
     // ST_EPI_SILU_MUL deals (w1, w3) tile pairs: twice the pairs' ceiling
@@ -1038,7 +1096,7 @@ static int gemm_stream_group(lh_ctx* ctx, const float* x, uint32_t ldx, uint32_t
         a.w[g] = w[g]; a.y[g] = y ? y[g] : nullptr; a.r[g] = r ? r[g] : nullptr;
         if (((uintptr_t)w[g] & 15) || ((uintptr_t)a.y[g] & 15) || (a.r[g] && ((uintptr_t)a.r[g] & 15))) return ST_NA;
     }
-    return launch_stream_maxt(ctx, a, name, maxt);
+    return launch_stream_maxt(ctx, a, name, maxt, wdt);
 }
 
 // Single-tile matrices (wo, w2: one 16-row tile per CU) at 17..48 rows: pairs of workgroups split the contraction (StreamArgs::ksplit), so a
@@ -1047,7 +1105,7 @@ static int gemm_stream_group(lh_ctx* ctx, const float* x, uint32_t ldx, uint32_t
 // stream_mm_check, profiles/r02d_stream_ksplit.txt): w2 55.6 -> 45.6 us, wo 23.9 -> 22.0 us; at 16 rows nothing (37.7 -> 37.0, 17.9 -> 21.1).
 // returns ST_NA when not applicable (the caller takes the one-launch path).
 static int gemm_stream_split(lh_ctx* ctx, const float* w, const float* x, uint32_t ldx, uint32_t M, uint32_t K, uint32_t n, const float* resid,
-                             float* y, const float* gamma, float* h, const char* name) {
+                             float* y, const float* gamma, float* h, const char* name, int wdt = 0) {
     // pairs: four-way splits measured no better, standalone (w2 at 32 / 48 rows: 45.6 / 62.2 us in pairs, 47.6 / 60.6 in fours, + a longer
     // reduce pass) and in the model (40 / 48 tokens: 8.94 / 9.01 ms vs 9.08 / 9.24)
     const uint32_t S = 2u;
@@ -1062,7 +1120,7 @@ static int gemm_stream_split(lh_ctx* ctx, const float* w, const float* x, uint32
     StreamArgs a = {};
     a.x = x; a.groups = 1; a.M = M; a.K = K; a.n = n; a.ldx = ldx; a.ldy = M; a.w[0] = w; a.y[0] = ctx->splitk;
     a.ksplit = S; a.ysplit = (uint64_t)n * M;
-    const int rs = launch_stream_maxt(ctx, a, name, maxt);
+    const int rs = launch_stream_maxt(ctx, a, name, maxt, wdt);
     if (rs) return rs;
     if (g_prepare_only) return 0;
     StreamReduceArgs r = {};
@@ -1251,12 +1309,25 @@ static int launch_gemm_b9(lh_ctx* ctx, GemmArgs a, const char* name, uint32_t sp
 // fused != nullptr: GEMM_EPI_SILU_MUL (w = {w1, w3}, y[0] = gated output [n][M]) or GEMM_EPI_QKV_ROPE (w = {wq, wk, wv}; outputs in *fused) in
 // the epilogue of the LDS-DMA tile GEMM; returns ST_NA when the launch cannot take it (short prompt, split-K, register-staged kernel) and
 // the caller runs the plain GEMM + the separate pass.
+// The halves behind fp32 image slots (an f16 plan with lh_ctx_set_f16_stream on, eval_prefill): w[g] of the launch names the image slot of a matrix
+// whose n halves are at half[g] and which is NOT widened yet.  A stream launch reads the halves (k_stream_*_h); a launch of any other kernel widens
+// the matrix into its slot first, directly in front of itself (HalfSrc::widen: k_widen_f16 per matrix), and reads the image as ever.
+struct HalfSrc {
+    const float* half[3];
+    uint64_t n;
+    bool* wide[3];   // the caller's "slot holds the matrix" flags
+    void widen(lh_ctx* ctx, const float* const* w, uint32_t groups) const {
+        for (uint32_t g = 0; g < groups; ++g)
+            if (!*wide[g]) { widen_f16_launch(ctx, half[g], (float*)w[g], n); *wide[g] = true; }   // (a launch error surfaces at the layer's hipGetLastError)
+    }
+};
 int gemm_mfma_group(lh_ctx* ctx, const float* x, uint32_t ldx, uint32_t groups, const float* const* w, float* const* y, const float* const* r, uint32_t M,
-                    uint32_t K, uint32_t n, uint32_t ldy, const char* name, const GemmArgs* fused = nullptr, bool split_ok = true) {
+                    uint32_t K, uint32_t n, uint32_t ldy, const char* name, const GemmArgs* fused = nullptr, bool split_ok = true, const HalfSrc* hs = nullptr) {
     if (n <= stream_max_rows() && !fused) {
-        const int rs = gemm_stream_group(ctx, x, ldx, groups, w, y, r, M, K, n, ldy, name);
+        const int rs = gemm_stream_group(ctx, x, ldx, groups, hs ? hs->half : w, y, r, M, K, n, ldy, name, nullptr, hs ? 1 : 0);
         if (rs != ST_NA) return rs;
     }
+    if (hs) hs->widen(ctx, w, groups);
     GemmArgs a = {};
     if (fused) a = *fused;
     a.x = x; a.groups = groups; a.N = n; a.M = M; a.K = K; a.ldx = ldx; a.ldy = ldy;
@@ -1300,8 +1371,8 @@ int gemm_mfma_group(lh_ctx* ctx, const float* x, uint32_t ldx, uint32_t groups, 
 }
 
 static int gemm_mfma(lh_ctx* ctx, const float* w, const float* x, float* y, const float* resid, uint32_t M, uint32_t K, uint32_t n, uint32_t ldx,
-                     uint32_t ldy, const char* name, bool split_ok) {
-    return gemm_mfma_group(ctx, x, ldx, 1, &w, &y, resid ? &resid : nullptr, M, K, n, ldy, name, nullptr, split_ok);
+                     uint32_t ldy, const char* name, bool split_ok, const HalfSrc* hs = nullptr) {
+    return gemm_mfma_group(ctx, x, ldx, 1, &w, &y, resid ? &resid : nullptr, M, K, n, ldy, name, nullptr, split_ok, hs);
 }
 
 // Y[n][M] = X[n][K] . W[M][K]^T (+ resid).  N >= 32: fp32 MFMA GEMM (compute-bound side); smaller N: the weight-streaming
@@ -1310,16 +1381,24 @@ static constexpr uint32_t MFMA_MIN_ROWS = 9;
 // block-int8: below this many tokens single-token steps on the int8 stream (2.1 ms each on 7B) beat the dequantising GEMM
 static constexpr uint32_t Q8_GEMM_MIN_ROWS = 9;
 // split_ok = false: the operands may hold values outside split_exact_values' range (common.h) - no launch on the bf16-split GEMM
+static int gemm_small_n_src(lh_ctx* ctx, const float* w, const float* x, float* y, const float* resid, uint32_t M, uint32_t K, uint32_t n,
+                            uint32_t ldx, uint32_t ldy, const char* name, bool split_ok, const HalfSrc* hs);
 int gemm_small_n(lh_ctx* ctx, const float* w, const float* x, float* y, const float* resid, uint32_t M, uint32_t K, uint32_t n,
                  uint32_t ldx, uint32_t ldy, const char* name, bool split_ok = true) {
+    return gemm_small_n_src(ctx, w, x, y, resid, M, K, n, ldx, ldy, name, split_ok, nullptr);
+}
+// hs: see HalfSrc (w is then the image slot of a matrix that is not widened yet)
+static int gemm_small_n_src(lh_ctx* ctx, const float* w, const float* x, float* y, const float* resid, uint32_t M, uint32_t K, uint32_t n,
+                            uint32_t ldx, uint32_t ldy, const char* name, bool split_ok, const HalfSrc* hs) {
     if (K % 4) LH_FAIL(ctx, LH_ESHAPE, "gemm %s: K=%u must be a multiple of 4", name, K);
     // from 9 rows on the MFMA GEMM (64-row tiles, split-K) beats two or more passes of the 8-column weight stream (7B, one Eval:
     // 8 rows 10.0 ms and 16 rows 18.4 ms on the stream; 17 rows 11.1 ms on the MFMA path)
-    if (n >= MFMA_MIN_ROWS && K % GBK == 0 && ldx % 4 == 0) return gemm_mfma(ctx, w, x, y, resid, M, K, n, ldx, ldy, name, split_ok);
+    if (n >= MFMA_MIN_ROWS && K % GBK == 0 && ldx % 4 == 0) return gemm_mfma(ctx, w, x, y, resid, M, K, n, ldx, ldy, name, split_ok, hs);
     if (n >= 2) {   // 2..8 rows on the general path: the streaming MFMA kernel
-        const int rs = gemm_stream_group(ctx, x, ldx, 1, &w, &y, resid ? &resid : nullptr, M, K, n, ldy, name);
+        const int rs = gemm_stream_group(ctx, x, ldx, 1, hs ? hs->half : &w, &y, resid ? &resid : nullptr, M, K, n, ldy, name, nullptr, hs ? 1 : 0);
         if (rs != ST_NA) return rs;
     }
+    if (hs) hs->widen(ctx, &w, 1);
     const uint32_t K4 = K / 4;
     const int ki = (int)((K4 + TH - 1) / TH);
     // activation columns per pass: what fits the 128 registers of a 1024-thread workgroup without scratch (ISA-checked per instantiation)
@@ -1960,6 +2039,14 @@ static float attn_scale(const ModelDesc& m) { return (float)(1.0 / sqrt((double)
 // not asked there); Skinny, Planes and Prefill open with it and see an fp32 model.
 // A block-int4 model (wtype 2) has a block-int8 shadow in the same way: Step, Rows and Q8Steps run on the nibbles, Planes and Prefill on the int8 image.
 static const ModelDesc& sched_md(const Plan* p) { return p->md.wtype == 1 || p->md.wtype == 2 ? p->md_wide : p->md; }
+// lh_ctx_set_f16_stream in the key of a captured graph whose launches may hold a stream launch (ticks, speculative passes): the switch and the count of its
+// changes for an f16 plan, 0 for every other plan (the switch does nothing there).  f16_stream_sync, in front of CapturedGraph::run: a changed value also
+// clears the warm bits - the kernels the new value chooses set their LDS attribute at their first launch (set_lds_once), which must be an eager one.
+static uint64_t f16_stream_key(const Plan* p) { return p->md.wtype == 1 ? (p->ctx->f16_stream_gen << 1) | (uint64_t)p->ctx->f16_stream : 0; }
+template <typename G>
+static void f16_stream_sync(G& graph, uint64_t* seen, uint64_t now) {
+    if (*seen != now) { graph.warm = 0; *seen = now; }
+}
 // The matrices of layer il for a route that works on m (sched_md): the model's own, or the fp32 image after enqueuing its widening - one exact pass
 // (k_widen_f16) per matrix in front of the layer's launches; the stream orders it behind the launches of the layer before, which read the same image.
 static const LayerW& route_layer(Plan* p, const ModelDesc& m, uint32_t il) {
@@ -2298,8 +2385,20 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
     const bool two_pass = !bc && m.wtype == 0 && n > stream_max_rows() && n <= two_pass_max && n <= 2 * stream_max_rows() && d % GBK == 0 && F % GBK == 0 && stream_shape_ok(ctx, m);
     const uint32_t sb = two_pass ? (n + 1) / 2 : n;   // rows per pass of the stream kernels
     bool h_ready = false;   // p->h already holds this layer's RMSNorm * attn_norm rows (written by the previous layer's w2 reduce pass)
+    // f16 plan with lh_ctx_set_f16_stream on: the stream launch sites read the model's own halves (k_stream_mm2_h / k_stream_dma_h), and a matrix is
+    // widened into its slot of the layer image only when a launch that reads fp32 is about to read it (HalfSrc) - a layer whose launches all stream
+    // enqueues no k_widen_f16.  m is then the fp32 shadow, so every decision below is the widened twin's.
+    const bool hstream = &m == &p->md_wide && p->md.wtype == 1 && ctx->f16_stream;
+    const int wdt = hstream ? 1 : 0;
     for (uint32_t il = m.layer0; il < m.layer1; ++il) {
-        const LayerW& L = route_layer(p, m, il);
+        const LayerW& L = hstream ? m.layers[il] : route_layer(p, m, il);   // (hstream: the image slots, nothing in them yet)
+        const LayerW& LS = hstream ? p->md.layers[il] : L;                  // what a stream launch reads
+        bool wide[7] = {};                                                  // wq wk wv wo w1 w3 w2: the slot holds the matrix
+        const uint64_t dd_ = (uint64_t)d * d, dF_ = (uint64_t)d * F;
+        const HalfSrc hqkv = {{LS.wq, LS.wk, LS.wv}, dd_, {&wide[0], &wide[1], &wide[2]}}, hq = {{LS.wq}, dd_, {&wide[0]}}, hk = {{LS.wk}, dd_, {&wide[1]}},
+                      hv = {{LS.wv}, dd_, {&wide[2]}}, ho = {{LS.wo}, dd_, {&wide[3]}}, h13 = {{LS.w1, LS.w3}, dF_, {&wide[4], &wide[5]}}, h1 = {{LS.w1}, dF_, {&wide[4]}},
+                      h3 = {{LS.w3}, dF_, {&wide[5]}}, h2 = {{LS.w2}, dF_, {&wide[6]}};
+        auto src = [&](const HalfSrc& h) -> const HalfSrc* { return hstream ? &h : nullptr; };
         const size_t slot = (size_t)(il - m.cache_layer0) * m.ctx * d;
         const bool mfma = prefill_mfma(m, n);
         const bool q8 = m.wtype == 7;
@@ -2308,6 +2407,7 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
         const bool ksp = sb > 16 && sb <= stream_max_rows() && !q8 && mfma;
         bool hf_ready = false;
         const float* wqkv[3] = {L.wq, L.wk, L.wv};
+        const float* wqkv_s[3] = {LS.wq, LS.wk, LS.wv};
         const float* sqkv[3] = {L.s_wq, L.s_wk, L.s_wv};
         float* yqkv[3] = {p->qraw, p->kraw, p->vraw};
         // RoPE + cache append in the GEMM's epilogue (no rope_store pass, no raw q/k/v round trip): where each row goes
@@ -2320,7 +2420,7 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
             // (folded up to 16 rows: -3..5 % per Eval; at 17..32 rows the extra staging work of the loader waves eats the saved launch)
             StreamArgs fa = fq;
             fa.gamma = L.attn_norm;
-            const int rs = gemm_stream_group(ctx, x, d, 3, wqkv, nullptr, nullptr, d, d, n, d, "stream_norm_wqkv_rope", &fa);
+            const int rs = gemm_stream_group(ctx, x, d, 3, wqkv_s, nullptr, nullptr, d, d, n, d, "stream_norm_wqkv_rope", &fa, wdt);
             if (rs < 0) return rs;
             qkv_roped = rs == 0;
         }
@@ -2334,20 +2434,21 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
             for (uint32_t b0 = 0; b0 < n && sb <= stream_max_rows(); b0 += sb) {
                 StreamArgs fb = fq;
                 fb.q_out = p->q + (size_t)b0 * d; fb.past = past + b0;
-                if ((rs = gemm_stream_group(ctx, p->h + (size_t)b0 * d, d, 3, wqkv, nullptr, nullptr, d, d, std::min(sb, n - b0), d, "stream_wqkv_rope", &fb))) break;
+                if ((rs = gemm_stream_group(ctx, p->h + (size_t)b0 * d, d, 3, wqkv_s, nullptr, nullptr, d, d, std::min(sb, n - b0), d, "stream_wqkv_rope", &fb, wdt))) break;
             }
             if (rs == ST_NA && n > 64) {   // long prompts: the same epilogue in the tile GEMM
                 GemmArgs ga = {};
                 ga.epi = GEMM_EPI_QKV_ROPE; ga.q_out = p->q; ga.k_cache = m.kc + slot; ga.v_cache = m.vc + slot; ga.rope = rope; ga.hd = m.hd; ga.past = past;
+                if (hstream) hqkv.widen(ctx, wqkv, 3);
                 rs = gemm_mfma_group(ctx, p->h, d, 3, wqkv, nullptr, nullptr, d, d, n, d, "gemm_wqkv_rope", &ga);
             }
             if (rs < 0) return rs;
             qkv_roped = rs == 0;
-            if (!qkv_roped && (rc = gemm_mfma_group(ctx, p->h, d, 3, wqkv, yqkv, nullptr, d, d, n, d, "gemm_wqkv"))) return rc;
+            if (!qkv_roped && (rc = gemm_mfma_group(ctx, p->h, d, 3, wqkv, yqkv, nullptr, d, d, n, d, "gemm_wqkv", nullptr, true, src(hqkv)))) return rc;
         } else {
-            if ((rc = gemm_small_n(ctx, L.wq, p->h, p->qraw, nullptr, d, d, n, d, d, "gemm_wq"))) return rc;
-            if ((rc = gemm_small_n(ctx, L.wk, p->h, p->kraw, nullptr, d, d, n, d, d, "gemm_wk"))) return rc;
-            if ((rc = gemm_small_n(ctx, L.wv, p->h, p->vraw, nullptr, d, d, n, d, d, "gemm_wv"))) return rc;
+            if ((rc = gemm_small_n_src(ctx, L.wq, p->h, p->qraw, nullptr, d, d, n, d, d, "gemm_wq", true, src(hq)))) return rc;
+            if ((rc = gemm_small_n_src(ctx, L.wk, p->h, p->kraw, nullptr, d, d, n, d, d, "gemm_wk", true, src(hk)))) return rc;
+            if ((rc = gemm_small_n_src(ctx, L.wv, p->h, p->vraw, nullptr, d, d, n, d, d, "gemm_wv", true, src(hv)))) return rc;
         }
         if (!qkv_roped) { TraceScope ts_(ctx->stream, "rope_store"); LH_LAUNCH(k_rope_store, dim3(n), dim3(256), 0, ctx->stream, (const float*)p->qraw, (const float*)p->kraw, (const float*)p->vraw, p->q, m.kc + slot,
                            m.vc + slot, rope, d, m.hd, past, rows, (uint64_t)slot); }
@@ -2355,14 +2456,15 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
         int wo_rs = ST_NA;
         if (ksp) {
             for (uint32_t b0 = 0; b0 < n; b0 += sb)
-                if ((wo_rs = gemm_stream_split(ctx, L.wo, p->attn + (size_t)b0 * d, d, d, d, std::min(sb, n - b0), x + (size_t)b0 * d, p->xb + (size_t)b0 * d, L.ffn_norm, p->h + (size_t)b0 * d, "stream_wo_ksplit"))) break;
+                if ((wo_rs = gemm_stream_split(ctx, LS.wo, p->attn + (size_t)b0 * d, d, d, d, std::min(sb, n - b0), x + (size_t)b0 * d, p->xb + (size_t)b0 * d, L.ffn_norm, p->h + (size_t)b0 * d, "stream_wo_ksplit", wdt))) break;
             if (wo_rs < 0) return wo_rs;
             hf_ready = wo_rs == 0;
         }
         if (wo_rs == 0) {
         } else if (q8) { if ((rc = gemm_q8(ctx, L.wo, L.s_wo, p->attn, p->xb, x, d, d, n, d, d, "gemm_q8_wo"))) return rc; }
-        else if ((rc = gemm_small_n(ctx, L.wo, p->attn, p->xb, x, d, d, n, d, d, "gemm_wo"))) return rc;
+        else if ((rc = gemm_small_n_src(ctx, L.wo, p->attn, p->xb, x, d, d, n, d, d, "gemm_wo", true, src(ho)))) return rc;
         const float* w13[2] = {L.w1, L.w3};
+        const float* w13_s[2] = {LS.w1, LS.w3};
         const float* s13[2] = {L.s_w1, L.s_w3};
         float* y13[2] = {p->a1, p->a3};
         float* yg[2] = {p->g, nullptr};
@@ -2370,7 +2472,7 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
             StreamArgs fa = {};
             fa.epi = ST_EPI_SILU_MUL;
             fa.gamma = L.ffn_norm;
-            const int rs = gemm_stream_group(ctx, p->xb, d, 2, w13, yg, nullptr, F, d, n, F, "stream_norm_w1w3_silu", &fa);
+            const int rs = gemm_stream_group(ctx, p->xb, d, 2, w13_s, yg, nullptr, F, d, n, F, "stream_norm_w1w3_silu", &fa, wdt);
             if (rs < 0) return rs;
             gated = rs == 0;
         }
@@ -2384,19 +2486,20 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
             int rs = ST_NA;
             for (uint32_t b0 = 0; b0 < n && sb <= stream_max_rows(); b0 += sb) {
                 float* ygb[2] = {p->g + (size_t)b0 * F, nullptr};
-                if ((rs = gemm_stream_group(ctx, p->h + (size_t)b0 * d, d, 2, w13, ygb, nullptr, F, d, std::min(sb, n - b0), F, "stream_w1w3_silu", &fa))) break;
+                if ((rs = gemm_stream_group(ctx, p->h + (size_t)b0 * d, d, 2, w13_s, ygb, nullptr, F, d, std::min(sb, n - b0), F, "stream_w1w3_silu", &fa, wdt))) break;
             }
             if (rs == ST_NA && n > 64) {
                 GemmArgs ga = {};
                 ga.epi = GEMM_EPI_SILU_MUL;
+                if (hstream) h13.widen(ctx, w13, 2);
                 rs = gemm_mfma_group(ctx, p->h, d, 2, w13, yg, nullptr, F, d, n, F, "gemm_w1w3_silu", &ga);
             }
             if (rs < 0) return rs;
             gated = rs == 0;
-            if (!gated && (rc = gemm_mfma_group(ctx, p->h, d, 2, w13, y13, nullptr, F, d, n, F, "gemm_w1w3"))) return rc;
+            if (!gated && (rc = gemm_mfma_group(ctx, p->h, d, 2, w13, y13, nullptr, F, d, n, F, "gemm_w1w3", nullptr, true, src(h13)))) return rc;
         } else {
-            if ((rc = gemm_small_n(ctx, L.w1, p->h, p->a1, nullptr, F, d, n, d, F, "gemm_w1"))) return rc;
-            if ((rc = gemm_small_n(ctx, L.w3, p->h, p->a3, nullptr, F, d, n, d, F, "gemm_w3"))) return rc;
+            if ((rc = gemm_small_n_src(ctx, L.w1, p->h, p->a1, nullptr, F, d, n, d, F, "gemm_w1", true, src(h1)))) return rc;
+            if ((rc = gemm_small_n_src(ctx, L.w3, p->h, p->a3, nullptr, F, d, n, d, F, "gemm_w3", true, src(h3)))) return rc;
         }
         if (!gated) { TraceScope ts_(ctx->stream, "silu_mul"); LH_LAUNCH(k_silu_mul, dim3(std::min<uint64_t>(((uint64_t)n * F + 255) / 256, 4096)), dim3(256), 0, ctx->stream, (const float*)p->a1,
                            (const float*)p->a3, p->g, (uint64_t)n * F); }
@@ -2406,13 +2509,13 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
         if (ksp) {
             const float* next_gamma = last ? nullptr : m.layers[il + 1].attn_norm;   // the next layer's first norm rides on the reduce pass
             for (uint32_t b0 = 0; b0 < n; b0 += sb)
-                if ((w2_rs = gemm_stream_split(ctx, L.w2, p->g + (size_t)b0 * F, F, d, F, std::min(sb, n - b0), p->xb + (size_t)b0 * d, y + (size_t)b0 * d, next_gamma, p->h + (size_t)b0 * d, "stream_w2_ksplit"))) break;
+                if ((w2_rs = gemm_stream_split(ctx, LS.w2, p->g + (size_t)b0 * F, F, d, F, std::min(sb, n - b0), p->xb + (size_t)b0 * d, y + (size_t)b0 * d, next_gamma, p->h + (size_t)b0 * d, "stream_w2_ksplit", wdt))) break;
             if (w2_rs < 0) return w2_rs;
             h_ready = w2_rs == 0 && next_gamma != nullptr;
         }
         if (w2_rs == 0) {
         } else if (q8) { if ((rc = gemm_q8(ctx, L.w2, L.s_w2, p->g, y, p->xb, d, F, n, F, d, "gemm_q8_w2"))) return rc; }
-        else if ((rc = gemm_small_n(ctx, L.w2, p->g, y, p->xb, d, F, n, F, d, "gemm_w2"))) return rc;
+        else if ((rc = gemm_small_n_src(ctx, L.w2, p->g, y, p->xb, d, F, n, F, d, "gemm_w2", true, src(h2)))) return rc;
         x = p->xa;
         LH_HIP(ctx, hipGetLastError());
     }
@@ -2520,8 +2623,10 @@ struct Batch {
         float* x_out;
         uint64_t splitk_gen, scratch_gen, smp_gen;
         uint32_t sampling, per_pod, shared, share_qb;   // (share_qb: 0 unless shared)
+        uint64_t f16_stream;                            // f16_stream_key: 0 unless the pods are f16 plans
     };
     CapturedGraph<TickKey> tick;
+    uint64_t f16_seen = 0;         // f16_stream_sync: the key value the tick / the speculative pass last ran with
     uint64_t scratch_gen() const { uint64_t g = 0; for (const Plan* p : pods) g += p->scratch_gen; return g; }   // grows when any pod's scratch moved
     bool per_pod = false;          // LLAMAHIP_SAMPLE_PER_POD=1: one sampler launch per row (read where the tick is enqueued)
     // host mirror of the rows' positions (rows_dev[i].pos): the tick kernels advance them in device memory with no bound of their own, so
@@ -2659,7 +2764,8 @@ static int batch_tick_unchecked(Batch* b, const float* x_in, float* x_out) {
     const char* pp = getenv("LLAMAHIP_SAMPLE_PER_POD");
     b->per_pod = pp && pp[0] == '1';
     if ((rc = share_prepare(b))) return rc;   // the block table of the pods that share a prefix, re-sent when it changed (outside the captured graph)
-    const Batch::TickKey key = {x_in, x_out, ctx->splitk_gen, b->scratch_gen(), b->smp_gen, b->sampling, b->per_pod, b->shared, b->shared ? b->share_qb : 0};
+    const Batch::TickKey key = {x_in, x_out, ctx->splitk_gen, b->scratch_gen(), b->smp_gen, b->sampling, b->per_pod, b->shared, b->shared ? b->share_qb : 0, f16_stream_key(p0)};
+    f16_stream_sync(b->tick, &b->f16_seen, key.f16_stream);
     return b->tick.run(ctx, p0->use_graph, 0, key, " (batch tick)", [&] { return batch_enqueue_tick(b, x_in, x_out); });
 }
 
@@ -3032,8 +3138,10 @@ struct Spec {
         uint64_t splitk_gen, scratch_gen;
         uint32_t smp, smp_small;       // sampled route: the kernel variant (topK <= 64 or not) and the ring pointer
         uint32_t* ring;
+        uint64_t f16_stream;           // f16_stream_key
     };
     CapturedGraph<Key> pass;
+    uint64_t f16_seen = 0;
 };
 static void spec_free(Plan* p) {
     Spec* s = p->spec;
@@ -3098,7 +3206,8 @@ static int spec_enqueue_pass(Plan* p, uint32_t n, uint32_t n_table, const SpecLo
 static int spec_pass(Plan* p, uint32_t R, const SpecLookup& lp) {
     lh_ctx* ctx = p->ctx;
     Spec* s = p->spec;
-    const Spec::Key key = {R, s->trace_cap, lp, spec_out(p), s->trace, ctx->splitk_gen, p->scratch_gen, s->smp, s->smp && p->smp_topk <= 64, s->smp ? p->ring_dev : nullptr};
+    const Spec::Key key = {R, s->trace_cap, lp, spec_out(p), s->trace, ctx->splitk_gen, p->scratch_gen, s->smp, s->smp && p->smp_topk <= 64, s->smp ? p->ring_dev : nullptr, f16_stream_key(p)};
+    f16_stream_sync(s->pass, &s->f16_seen, key.f16_stream);
     return s->pass.run(ctx, p->use_graph, R, key, " (speculative pass)", [&] { return spec_enqueue_pass(p, R, R, lp, 1); });
 }
 static int spec_set(Plan* p, uint32_t pos, uint32_t produced, uint32_t n_steps, const SpecToks& toks, uint32_t k, uint32_t n_rows, int reset) {
@@ -3315,8 +3424,10 @@ struct BatchSpec {
         SampleState* ss;
         uint32_t* ring;
         uint64_t ring_cap;
+        uint64_t f16_stream;           // f16_stream_key
     };
     CapturedGraph<Key> pass;
+    uint64_t f16_seen = 0;
 };
 static void batch_spec_free(Batch* b) {
     BatchSpec* s = b->spec;
@@ -3391,7 +3502,8 @@ static int batch_spec_enqueue_pass(Batch* b, uint32_t R, const SpecLookup& lp) {
 static int batch_spec_pass(Batch* b, uint32_t R, const SpecLookup& lp) {
     lh_ctx* ctx = b->ctx;
     BatchSpec* s = b->spec;
-    BatchSpec::Key key = {R, s->trace_cap, lp, s->trace, ctx->splitk_gen, b->scratch_gen(), s->smp, 0, nullptr, nullptr, 0};
+    BatchSpec::Key key = {R, s->trace_cap, lp, s->trace, ctx->splitk_gen, b->scratch_gen(), s->smp, 0, nullptr, nullptr, 0, f16_stream_key(b->pods[0])};
+    f16_stream_sync(s->pass, &s->f16_seen, key.f16_stream);
     if (s->smp) { key.small_k = b->smp_topk <= 64; key.ss = b->ss_dev; key.ring = b->ring_dev; key.ring_cap = b->ring_cap; }
     return s->pass.run(ctx, b->pods[0]->use_graph, b->B * R - 1, key, " (batch speculative pass)", [&] { return batch_spec_enqueue_pass(b, R, lp); });
 }

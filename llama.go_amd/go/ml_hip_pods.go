@@ -467,6 +467,21 @@ func (bt *BatchHIP) SetKeepCount(keep uint32) {
 	}
 }
 
+// SetF16Stream / SetF16StreamHIP: lh_ctx_set_f16_stream on the lh_ctx the batch / the context evaluates in - the Evals of 2..128 rows of an f16 model
+// that take the stream kernels read the model's halves instead of an fp32 image widened in front of every layer (DESIGN 3k).  Same bytes; off by
+// default; without effect on models of another weight type.
+func (bt *BatchHIP) SetF16Stream(on bool) { bt.ctx.SetF16StreamHIP(on) }
+func (ctx *Context) SetF16StreamHIP(on bool) {
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	if rc := C.lh_ctx_set_f16_stream(ctx.hip.ctx, v); rc != 0 {
+		hipHalt(ctx.hip.ctx)
+	}
+}
+func (ctx *Context) F16StreamHIP() bool { return C.lh_ctx_f16_stream(ctx.hip.ctx) != 0 }
+
 func (bt *BatchHIP) Release() { C.lh_batch_destroy(bt.b) }
 
 // NewPipelineHIP: `stages[i]` is this rank's stage of stream i (NewStageHIP over the rank's layer range: the stream's own KV

@@ -1918,6 +1918,16 @@ int llamago_BatchCacheWrite(llama_batch* p, uint32_t pod, int which, uint64_t of
     }
     return rc;
 }
+int llamago_SetF16Stream(llama_context* c, int on) {
+    if (!c || !c->mlctx || !c->mlctx->hip) return halt_rc("llamago_SetF16Stream: bad arguments");
+    return lh_ctx_set_f16_stream(c->mlctx->hip, on);
+}
+int llamago_F16Stream(llama_context* c) { return c && c->mlctx ? lh_ctx_f16_stream(c->mlctx->hip) : 0; }
+int llamago_BatchSetF16Stream(llama_batch* b, int on) {
+    if (!b || !b->mlctx || !b->mlctx->hip) return halt_rc("llamago_BatchSetF16Stream: bad arguments");
+    return lh_ctx_set_f16_stream(b->mlctx->hip, on);
+}
+int llamago_BatchF16Stream(llama_batch* b) { return b && b->mlctx ? lh_ctx_f16_stream(b->mlctx->hip) : 0; }
 int llamago_TimeComputes(llama_context* c, int on) { return c && c->mlctx && c->mlctx->hip ? lh_ctx_time_computes(c->mlctx->hip, on) : 1; }
 int llamago_ComputeStats(llama_context* c, uint64_t* calls, double* wall_us, double* device_us) {
     lh_compute_stats st = {};

@@ -402,6 +402,21 @@ class Context:
             raise MLError(f"llamago_GreedyContinue: {self.ml.last_error()}")
         return [int(t) for t in out[:n_steps]]
 
+    def SetF16Stream(self, on=True):
+        """llamago_SetF16Stream: Evals of an f16 model that take the stream kernels (2..128 rows) read the model's halves instead of a widened image."""
+        L = self.ml.lib
+        L.llamago_SetF16Stream.restype = C.c_int
+        L.llamago_SetF16Stream.argtypes = [VP, C.c_int]
+        if L.llamago_SetF16Stream(self.h, 1 if on else 0):
+            raise MLError(f"llamago_SetF16Stream: {self.ml.last_error()}")
+
+    @property
+    def f16_stream(self):
+        L = self.ml.lib
+        L.llamago_F16Stream.restype = C.c_int
+        L.llamago_F16Stream.argtypes = [VP]
+        return bool(L.llamago_F16Stream(self.h))
+
     def TimeComputes(self, on=True):
         """lh_ctx_time_computes: HIP events around every lh_graph_compute of this context; zeroes the sums."""
         L = self.ml.lib
@@ -1028,6 +1043,21 @@ class Batch:
         self.model, self.ml, self.pods = model, model.ml, pods
         self.h = self.ml._chk(self.ml.lib.llamago_NewBatch(model.h, ctxSize, pods), "llamago_NewBatch")
         self.batched = bool(self.ml.lib.llamago_BatchBatched(self.h))
+
+    def SetF16Stream(self, on=True):
+        """llamago_BatchSetF16Stream: Context.SetF16Stream for the ticks, feeds and speculative passes of this batch."""
+        L = self.ml.lib
+        L.llamago_BatchSetF16Stream.restype = C.c_int
+        L.llamago_BatchSetF16Stream.argtypes = [VP, C.c_int]
+        if L.llamago_BatchSetF16Stream(self.h, 1 if on else 0):
+            raise MLError(f"llamago_BatchSetF16Stream: {self.ml.last_error()}")
+
+    @property
+    def f16_stream(self):
+        L = self.ml.lib
+        L.llamago_BatchF16Stream.restype = C.c_int
+        L.llamago_BatchF16Stream.argtypes = [VP]
+        return bool(L.llamago_BatchF16Stream(self.h))
 
     def GreedyDecode(self, prompts, n_predict, want_logits=False):
         """Every pod: its prompt as one Eval, then greedy steps; returns per pod the ids llama_GreedyDecode gives for its prompt alone."""
