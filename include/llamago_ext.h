@@ -79,6 +79,12 @@ int llamago_ModelWeightType(const llama_model* m);
  * llamago_BatchSetF16Stream / llamago_BatchF16Stream (declared with the batch below): the same for a batch's ticks, feeds and speculative passes. */
 int llamago_SetF16Stream(llama_context* c, int on);
 int llamago_F16Stream(llama_context* c);
+/* lh_ctx_set_f16_tiles / lh_ctx_f16_tiles (llamahip.h) on the lh_ctx the context evaluates in: with on != 0 the Evals of more than 128 rows of an f16 model
+ * run their k_gemm_b9 launches on the model's halves (k_gemm_b9_h: six bf16 products per tile pair instead of eight, no widening pass in front) - the same
+ * bytes ("Native tile GEMM").  Off by default (LLAMAHIP_F16_TILES=1 turns it on for contexts created afterwards); without effect on models of
+ * another weight type; independent of llamago_SetF16Stream.  The setter returns non-zero (ml_LastError) on a null argument; the getter 0 | 1. */
+int llamago_SetF16Tiles(llama_context* c, int on);
+int llamago_F16Tiles(llama_context* c);
 /* Block-int4 weight matrices (ML_TYPE_Q4_0 = dtype 2 of llamahip.h: 20 bytes per 32 weights; norm vectors and tok_embeddings stay f32).  A 4-bit quant
  * q in [-8, 7] with block scale d IS a block-int8 weight with the same q and d, so every Eval route of such a model produces the bytes its expansion
  * produces: one row and 2..4 rows on 4-bit forms of the decode stream kernels, every other row count on the int8 kernels behind an exact expansion

@@ -106,6 +106,21 @@ int lh_ctx_f16_stream(lh_ctx* ctx);
  * tile slot t (< 8) for k-block kb (< kc / 16) of the chunk.  An argument out of range: -1. */
 int64_t lh_stream_f16_image_off(uint32_t kc, uint32_t r, uint32_t g);
 int64_t lh_stream_f16_read_off(uint32_t kc, uint32_t t, uint32_t r16, uint32_t kb, uint32_t slot);
+/* f16 models on the bf16 tile GEMM of prompts beyond 128 rows (csrc/kernels_gemm_f16.h).  lh_ctx_set_f16_tiles(ctx, on): with on != 0 every k_gemm_b9 launch
+ * of an f16 plan's prefill route reads the model's own halves (k_gemm_b9_h: six exact bf16 products instead of eight, no k_widen_f16 pass in front), where the
+ * widened twin launches k_gemm_b9 and with its split count; every other launch of the route widens what it reads directly in front of itself.  Byte for byte
+ * the same results.  Off by default; the initial value is LLAMAHIP_F16_TILES=1 of the environment, read once in lh_ctx_create.  Read at every Eval; accepted
+ * and without effect for fp32, block-int8 and block-int4 plans; independent of lh_ctx_set_f16_stream.  No captured graph holds such a launch (more than 128
+ * rows), so a change re-captures nothing.  lh_ctx_f16_tiles: the current value (0 | 1; ctx NULL: 0). */
+int lh_ctx_set_f16_tiles(lh_ctx* ctx, int on);
+int lh_ctx_f16_tiles(lh_ctx* ctx);
+/* The pure pieces of k_gemm_b9_h (csrc/gemm_f16_layout.h; host functions, for checks).  lh_gemm_f16_split: *w = the fp32 bits of half h, *r1 = the bits of
+ * w - (w & 0xffff0000): the kernel's hi / mid parts are their top 16 bits.  lh_gemm_f16_piece: DMA piece p (< 40) of a ring stage, lane (< 64): out = {byte
+ * offset in the stage, tile row fetched (plane-local for p < 24), source granule of the row's 64 slab bytes}.  lh_gemm_f16_w_read_off: byte offset in the stage
+ * of the 8 halves lane (li < 32, lh < 2) of wave wm (< 8) reads for k-step kk (< 2).  An argument out of range: -1. */
+void lh_gemm_f16_split(uint16_t h, uint32_t* w, uint32_t* r1);
+int lh_gemm_f16_piece(uint32_t p, uint32_t lane, uint32_t out[3]);
+int64_t lh_gemm_f16_w_read_off(uint32_t wm, uint32_t li, uint32_t lh, uint32_t kk);
 /* Dequantised fp32 values of a dtype-7 buffer (w = fl32(d*q)), for checks. */
 int lh_buf_read_q8(lh_ctx* ctx, lh_buf buf, uint64_t off, float* dst, uint64_t n);
 int lh_buf_free(lh_ctx* ctx, lh_buf buf);

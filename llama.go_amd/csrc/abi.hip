@@ -3,6 +3,7 @@
 #include "common.h"
 #include "kernels_q8_pack.h"
 #include "stream_f16_layout.h"
+#include "gemm_f16_layout.h"
 #include <stdarg.h>
 #include <math.h>
 #include <algorithm>
@@ -275,6 +276,8 @@ int lh_ctx_create(int device, void* stream, lh_ctx** out) {
     }
     const char* hs = getenv("LLAMAHIP_F16_STREAM");
     c->f16_stream = hs && hs[0] == '1' ? 1 : 0;
+    const char* ht = getenv("LLAMAHIP_F16_TILES");
+    c->f16_tiles = ht && ht[0] == '1' ? 1 : 0;
     *out = c;
     return LH_OK;
 }
@@ -286,6 +289,24 @@ int lh_ctx_set_f16_stream(lh_ctx* ctx, int on) {
     return LH_OK;
 }
 int lh_ctx_f16_stream(lh_ctx* ctx) { return ctx ? ctx->f16_stream : 0; }
+int lh_ctx_set_f16_tiles(lh_ctx* ctx, int on) {
+    if (!ctx) return LH_EINVAL;
+    ctx->f16_tiles = on ? 1 : 0;
+    return LH_OK;
+}
+int lh_ctx_f16_tiles(lh_ctx* ctx) { return ctx ? ctx->f16_tiles : 0; }
+void lh_gemm_f16_split(uint16_t h, uint32_t* w, uint32_t* r1) {
+    if (w && r1) lh::gemm_h_split(h, w, r1);
+}
+int lh_gemm_f16_piece(uint32_t p, uint32_t lane, uint32_t out[3]) {
+    if (p >= lh::GH_PIECES || lane >= 64 || !out) return -1;
+    out[0] = lh::gemm_h_piece_dst(p, lane); out[1] = lh::gemm_h_piece_row(p, lane); out[2] = lh::gemm_h_piece_granule(p, lane);
+    return 0;
+}
+int64_t lh_gemm_f16_w_read_off(uint32_t wm, uint32_t li, uint32_t lh_, uint32_t kk) {
+    if (wm >= 8 || li >= 32 || lh_ >= 2 || kk >= 2) return -1;
+    return (int64_t)lh::gemm_h_w_read_off(wm, li, lh_, kk);
+}
 int64_t lh_stream_f16_image_off(uint32_t kc, uint32_t r, uint32_t g) {
     if ((kc != 64 && kc != 128) || r >= 128 || g >= kc / 8) return -1;
     return (int64_t)lh::stream_h_granule_off(kc, r, g);

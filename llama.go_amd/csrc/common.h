@@ -156,6 +156,10 @@ struct lh_ctx {
     // kernel (graph_cache.h): f16_stream_gen counts the changes and is part of the key of every captured graph of an f16 plan that may hold a stream launch
     int f16_stream = 0;
     uint64_t f16_stream_gen = 0;
+    // lh_ctx_set_f16_tiles: f16 plans hand the k_gemm_b9 launches of their prefill route the model's halves (k_gemm_b9_h, kernels_gemm_f16.h).  No key
+    // holds it: k_gemm_b9 takes more than 128 rows (gemm_b9_ok), and every captured graph - ticks of at most 64 pods, speculative passes of a few rows,
+    // the decode step - enqueues fewer, so the launch the switch chooses is always an eager one.
+    int f16_tiles = 0;
     // the activation rows of a long-prompt GEMM as three bf16 planes (k_gemm_b9); grows, never shrinks
     uint16_t* xs3 = nullptr;
     uint64_t xs3_elems = 0;

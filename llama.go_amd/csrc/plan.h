@@ -57,7 +57,8 @@ struct Plan {
     // evaluated, widened in front of its launches: route_layer) and output at wide_out.  The images belong to the context (lh_ctx::wide), are sized
     // at plan_create and never move, so a captured graph may hold their addresses without a generation in its key.
     // (With lh_ctx_set_f16_stream on, Prefill's stream launches read the halves themselves and a matrix is widened into its slot of wide_layer only in
-    // front of a launch that reads fp32: eval_prefill, kernels_stream_f16.h.)
+    // front of a launch that reads fp32: eval_prefill, kernels_stream_f16.h.  With lh_ctx_set_f16_tiles on the same holds for its k_gemm_b9 launches:
+    // kernels_gemm_f16.h.)
     // Block-int4 plans (md.wtype == 2) use the same three fields: Step, Rows and Q8Steps stream the nibbles (kernels_q4.h); Planes and Prefill run
     // the block-int8 schedule over md_wide = md with wtype 7, whose quant pointers point into wide_layer / wide_out - here INT8 images of 4 d^2 + 3 d F
     // and V d BYTES behind the float* type, filled by k_expand_q4 - and whose s_* pointers are the model's own scale planes.

@@ -15,6 +15,7 @@
 #include "kernels_rows.h"
 #include "kernels_f16.h"
 #include "kernels_stream_f16.h"
+#include "kernels_gemm_f16.h"
 #include "kernels_q4.h"
 #include "kernels_attn_seg.h"
 #include "kernels_attn_share.h"
@@ -1273,11 +1274,22 @@ static int gemm_q8b_split(lh_ctx* ctx, const float* wq, const float* wsc, const 
 static bool gemm_b9_ok(const GemmArgs& a) {
     return a.N > 128 && !a.causal && a.splits <= 1 && gemm_dma_ok(a) && a.K >= 16 * GBK && a.K % 8 == 0;
 }
-static int launch_gemm_b9(lh_ctx* ctx, GemmArgs a, const char* name, uint32_t splits) {
+// wdt = 1: a.w[] are the halves of an f16 model (k_gemm_b9_h, kernels_gemm_f16.h) - the same tiles, split count, k_split3_rows in front and reduce pass
+// behind; the ring depth is the half kernel's own and no part of the sums.  Its stage is 40 KB, so three fit: synthetic 7B, one Eval of 193 / 512 / 1024
+// tokens 19.5 / 38.6 / 69.4 ms with three stages against 20.2 / 39.1 / 69.3 with two (-DB9H_NST=2; profiles/f16_tiles.txt) - three ship.
+// -DB9H_PRODUCTS=8 issues the two products of the weights' zero plane as well (the fallback, had six not been byte-equal on the GPU).
+#ifndef B9H_NST
+#define B9H_NST 3
+#endif
+#ifndef B9H_PRODUCTS
+#define B9H_PRODUCTS 6
+#endif
+static int launch_gemm_b9(lh_ctx* ctx, GemmArgs a, const char* name, uint32_t splits, int wdt = 0) {
     auto kern = k_gemm_b9<1, 8, 4, 1, 2>;
-    const size_t lds = 2 * gemm_b9_stage_bytes(128, 256);
-    static bool flags[16] = {};
-    int rc = set_lds_once(ctx, kern, lds, flags);
+    auto kern_h = k_gemm_b9_h<1, 8, 4, 1, B9H_NST, B9H_PRODUCTS>;
+    const size_t lds = wdt == 1 ? gemm_b9_h_lds_bytes(B9H_NST) : 2 * gemm_b9_stage_bytes(128, 256);
+    static bool flags[16] = {}, flags_h[16] = {};
+    int rc = wdt == 1 ? set_lds_once(ctx, kern_h, lds, flags_h) : set_lds_once(ctx, kern, lds, flags);
     if (rc) return rc;
     if (!ensure_xs3(ctx, (uint64_t)3 * a.N * a.K)) LH_FAIL(ctx, LH_ENOMEM, "%s: planes of %u x %u activations", name, a.N, a.K);
     a.xs = ctx->xs3; a.xs_plane = (uint64_t)a.N * a.K; a.ldxs = a.K;
@@ -1294,9 +1306,14 @@ static int launch_gemm_b9(lh_ctx* ctx, GemmArgs a, const char* name, uint32_t sp
         LH_LAUNCH(k_split3_rows, dim3(a.N), dim3(256), 0, ctx->stream, sa);
     }
     const uint64_t items = (uint64_t)((a.N + 127) / 128) * ((a.M + 255) / 256) * a.groups * (splits > 1 ? splits : 1);
-    ProfScope ps(ctx->stream, name, (uint64_t)a.M * a.K * 4 * a.groups);
-    LH_TRACE("k_gemm_b9<1,8,4,1,2>/s%u", splits > 1 ? splits : 1u);
-    LH_LAUNCH_AS("k_gemm_b9", kern, dim3((uint32_t)std::min<uint64_t>(items, (uint64_t)ctx->ds->num_cu)), dim3(512), lds, ctx->stream, a);
+    ProfScope ps(ctx->stream, name, (uint64_t)a.M * a.K * (wdt == 1 ? 2 : 4) * a.groups);
+    if (wdt == 1) {
+        LH_TRACE("k_gemm_b9_h<1,8,4,1,%d>/s%u", B9H_NST, splits > 1 ? splits : 1u);
+        LH_LAUNCH_AS("k_gemm_b9_h", kern_h, dim3((uint32_t)std::min<uint64_t>(items, (uint64_t)ctx->ds->num_cu)), dim3(512), lds, ctx->stream, a);
+    } else {
+        LH_TRACE("k_gemm_b9<1,8,4,1,2>/s%u", splits > 1 ? splits : 1u);
+        LH_LAUNCH_AS("k_gemm_b9", kern, dim3((uint32_t)std::min<uint64_t>(items, (uint64_t)ctx->ds->num_cu)), dim3(512), lds, ctx->stream, a);
+    }
     if (splits > 1) {
         const uint64_t quads = (uint64_t)a.groups * a.N * (a.M / 4);
         LH_TRACE("k_splitk_reduce");
@@ -1309,25 +1326,44 @@ static int launch_gemm_b9(lh_ctx* ctx, GemmArgs a, const char* name, uint32_t sp
 // fused != nullptr: GEMM_EPI_SILU_MUL (w = {w1, w3}, y[0] = gated output [n][M]) or GEMM_EPI_QKV_ROPE (w = {wq, wk, wv}; outputs in *fused) in
 // the epilogue of the LDS-DMA tile GEMM; returns ST_NA when the launch cannot take it (short prompt, split-K, register-staged kernel) and
 // the caller runs the plain GEMM + the separate pass.
-// The halves behind fp32 image slots (an f16 plan with lh_ctx_set_f16_stream on, eval_prefill): w[g] of the launch names the image slot of a matrix
-// whose n halves are at half[g] and which is NOT widened yet.  A stream launch reads the halves (k_stream_*_h); a launch of any other kernel widens
-// the matrix into its slot first, directly in front of itself (HalfSrc::widen: k_widen_f16 per matrix), and reads the image as ever.
+// The halves behind fp32 image slots (an f16 plan with lh_ctx_set_f16_stream or lh_ctx_set_f16_tiles on, eval_prefill): w[g] of the launch names the
+// image slot of a matrix whose n halves are at half[g] and which is NOT widened yet.  A stream launch reads the halves (k_stream_*_h) if `stream` is set,
+// a k_gemm_b9 launch reads them (k_gemm_b9_h) if `tiles` is set; every other launch widens the matrix into its slot first, directly in front of itself
+// (HalfSrc::widen: k_widen_f16 per matrix), and reads the image as ever.
 struct HalfSrc {
     const float* half[3];
     uint64_t n;
     bool* wide[3];   // the caller's "slot holds the matrix" flags
+    bool stream, tiles;
     void widen(lh_ctx* ctx, const float* const* w, uint32_t groups) const {
         for (uint32_t g = 0; g < groups; ++g)
             if (!*wide[g]) { widen_f16_launch(ctx, half[g], (float*)w[g], n); *wide[g] = true; }   // (a launch error surfaces at the layer's hipGetLastError)
     }
 };
+// One launch site of the stream chain over matrices that may still be halves: launch(w, wdt) is the site's gemm_stream_group / gemm_stream_split call.
+// hs->stream: the halves as they are.  Otherwise the launch reads the image, which is widened only if the chain HAS a launch for the shape - asked with
+// a prepare-only pass, which enqueues nothing - so that a widening pass never stands in front of a launch that does not read it.
+template <typename F>
+static int stream_src(lh_ctx* ctx, const HalfSrc* hs, const float* const* w, uint32_t groups, F&& launch) {
+    if (!hs) return launch(w, 0);
+    if (hs->stream) return launch(hs->half, 1);
+    const bool was = g_prepare_only;
+    g_prepare_only = true;
+    const int rs = launch(w, 0);
+    g_prepare_only = was;
+    if (rs || was) return rs;
+    hs->widen(ctx, w, groups);
+    return launch(w, 0);
+}
 int gemm_mfma_group(lh_ctx* ctx, const float* x, uint32_t ldx, uint32_t groups, const float* const* w, float* const* y, const float* const* r, uint32_t M,
                     uint32_t K, uint32_t n, uint32_t ldy, const char* name, const GemmArgs* fused = nullptr, bool split_ok = true, const HalfSrc* hs = nullptr) {
     if (n <= stream_max_rows() && !fused) {
-        const int rs = gemm_stream_group(ctx, x, ldx, groups, hs ? hs->half : w, y, r, M, K, n, ldy, name, nullptr, hs ? 1 : 0);
+        const int rs = stream_src(ctx, hs, w, groups, [&](const float* const* ws, int wdt) { return gemm_stream_group(ctx, x, ldx, groups, ws, y, r, M, K, n, ldy, name, nullptr, wdt); });
         if (rs != ST_NA) return rs;
     }
-    if (hs) hs->widen(ctx, w, groups);
+    // (hs: every decision below is taken on the image slots' addresses, the widened twin's; the matrices are widened directly in front of the launch chosen -
+    // or not at all where it is k_gemm_b9 and the halves may be read)
+    auto wide = [&]() { if (hs) hs->widen(ctx, w, groups); };
     GemmArgs a = {};
     if (fused) a = *fused;
     a.x = x; a.groups = groups; a.N = n; a.M = M; a.K = K; a.ldx = ldx; a.ldy = ldy;
@@ -1348,7 +1384,7 @@ int gemm_mfma_group(lh_ctx* ctx, const float* x, uint32_t ldx, uint32_t groups, 
         if (fused->epi == GEMM_EPI_QKV_ROPE && (fused->hd % 2 || M % fused->hd)) return ST_NA;
     }
     // up to 64 rows: 64 x 128 tiles (half the matrix work of a 128-row tile whose upper half would be padding)
-    if (n <= 64) return launch_gemm<2, 2, 1, 2>(ctx, a, name);
+    if (n <= 64) { wide(); return launch_gemm<2, 2, 1, 2>(ctx, a, name); }
     const double c128 = cost(128, 1.0), c160 = cost(160, 1.03), c64 = cost(64, 1.10);
     if (split_ok && gemm_b9_ok(a)) {
         const uint64_t tiles9 = (uint64_t)tn * ((a.M + 255) / 256) * a.groups;
@@ -1363,8 +1399,18 @@ int gemm_mfma_group(lh_ctx* ctx, const float* x, uint32_t ldx, uint32_t groups, 
                 const double c = (double)((tiles9 * s2 + ncu - 1) / ncu) * ((nkf + s2 - 1) / s2 + 8) * 256 * B9_SLAB * unit + (double)(s2 + 1) * a.groups * n * a.M * 4.0 / 4e6 + 5.0;
                 if (c < c9 * 0.95) { c9 = c; s9 = s2; }
             }
-        if (c9 < 0.97 * std::min(c128, std::min(c160, c64))) return launch_gemm_b9(ctx, a, name, s9);
+        if (c9 < 0.97 * std::min(c128, std::min(c160, c64))) {
+            bool halves = hs && hs->tiles && !a.ldw;
+            for (uint32_t g = 0; halves && g < groups; ++g) halves = ((uintptr_t)hs->half[g] & 15) == 0;
+            if (halves) {
+                for (uint32_t g = 0; g < groups; ++g) a.w[g] = hs->half[g];
+                return launch_gemm_b9(ctx, a, name, s9, 1);
+            }
+            wide();
+            return launch_gemm_b9(ctx, a, name, s9);
+        }
     }
+    wide();
     if (c160 < c128 && c160 <= c64) return launch_gemm<4, 1, 1, 5>(ctx, a, name);
     if (c64 < c128) return launch_gemm<2, 2, 2, 1>(ctx, a, name);
     return launch_gemm<2, 2, 2, 2>(ctx, a, name);
@@ -1395,7 +1441,7 @@ static int gemm_small_n_src(lh_ctx* ctx, const float* w, const float* x, float* 
     // 8 rows 10.0 ms and 16 rows 18.4 ms on the stream; 17 rows 11.1 ms on the MFMA path)
     if (n >= MFMA_MIN_ROWS && K % GBK == 0 && ldx % 4 == 0) return gemm_mfma(ctx, w, x, y, resid, M, K, n, ldx, ldy, name, split_ok, hs);
     if (n >= 2) {   // 2..8 rows on the general path: the streaming MFMA kernel
-        const int rs = gemm_stream_group(ctx, x, ldx, 1, hs ? hs->half : &w, &y, resid ? &resid : nullptr, M, K, n, ldy, name, nullptr, hs ? 1 : 0);
+        const int rs = stream_src(ctx, hs, &w, 1, [&](const float* const* ws, int wdt) { return gemm_stream_group(ctx, x, ldx, 1, ws, &y, resid ? &resid : nullptr, M, K, n, ldy, name, nullptr, wdt); });
         if (rs != ST_NA) return rs;
     }
     if (hs) hs->widen(ctx, &w, 1);
@@ -2388,17 +2434,20 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
     // f16 plan with lh_ctx_set_f16_stream on: the stream launch sites read the model's own halves (k_stream_mm2_h / k_stream_dma_h), and a matrix is
     // widened into its slot of the layer image only when a launch that reads fp32 is about to read it (HalfSrc) - a layer whose launches all stream
     // enqueues no k_widen_f16.  m is then the fp32 shadow, so every decision below is the widened twin's.
-    const bool hstream = &m == &p->md_wide && p->md.wtype == 1 && ctx->f16_stream;
-    const int wdt = hstream ? 1 : 0;
+    // lh_ctx_set_f16_tiles: the same hand-out for the tile GEMM - a k_gemm_b9 launch reads the halves (k_gemm_b9_h, kernels_gemm_f16.h).  Either switch
+    // makes the matrices lazy; which launches read halves is each switch's own (HalfSrc::stream / ::tiles).
+    const bool f16p = &m == &p->md_wide && p->md.wtype == 1;
+    const bool hstream = f16p && ctx->f16_stream, htiles = f16p && ctx->f16_tiles, lazy = hstream || htiles;
     for (uint32_t il = m.layer0; il < m.layer1; ++il) {
-        const LayerW& L = hstream ? m.layers[il] : route_layer(p, m, il);   // (hstream: the image slots, nothing in them yet)
-        const LayerW& LS = hstream ? p->md.layers[il] : L;                  // what a stream launch reads
+        const LayerW& L = lazy ? m.layers[il] : route_layer(p, m, il);      // (lazy: the image slots, nothing in them yet)
+        const LayerW& LS = lazy ? p->md.layers[il] : L;                     // the model's own matrices
         bool wide[7] = {};                                                  // wq wk wv wo w1 w3 w2: the slot holds the matrix
         const uint64_t dd_ = (uint64_t)d * d, dF_ = (uint64_t)d * F;
-        const HalfSrc hqkv = {{LS.wq, LS.wk, LS.wv}, dd_, {&wide[0], &wide[1], &wide[2]}}, hq = {{LS.wq}, dd_, {&wide[0]}}, hk = {{LS.wk}, dd_, {&wide[1]}},
-                      hv = {{LS.wv}, dd_, {&wide[2]}}, ho = {{LS.wo}, dd_, {&wide[3]}}, h13 = {{LS.w1, LS.w3}, dF_, {&wide[4], &wide[5]}}, h1 = {{LS.w1}, dF_, {&wide[4]}},
-                      h3 = {{LS.w3}, dF_, {&wide[5]}}, h2 = {{LS.w2}, dF_, {&wide[6]}};
-        auto src = [&](const HalfSrc& h) -> const HalfSrc* { return hstream ? &h : nullptr; };
+        const HalfSrc hqkv = {{LS.wq, LS.wk, LS.wv}, dd_, {&wide[0], &wide[1], &wide[2]}, hstream, htiles}, hq = {{LS.wq}, dd_, {&wide[0]}, hstream, htiles},
+                      hk = {{LS.wk}, dd_, {&wide[1]}, hstream, htiles}, hv = {{LS.wv}, dd_, {&wide[2]}, hstream, htiles}, ho = {{LS.wo}, dd_, {&wide[3]}, hstream, htiles},
+                      h13 = {{LS.w1, LS.w3}, dF_, {&wide[4], &wide[5]}, hstream, htiles}, h1 = {{LS.w1}, dF_, {&wide[4]}, hstream, htiles},
+                      h3 = {{LS.w3}, dF_, {&wide[5]}, hstream, htiles}, h2 = {{LS.w2}, dF_, {&wide[6]}, hstream, htiles};
+        auto src = [&](const HalfSrc& h) -> const HalfSrc* { return lazy ? &h : nullptr; };
         const size_t slot = (size_t)(il - m.cache_layer0) * m.ctx * d;
         const bool mfma = prefill_mfma(m, n);
         const bool q8 = m.wtype == 7;
@@ -2407,7 +2456,6 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
         const bool ksp = sb > 16 && sb <= stream_max_rows() && !q8 && mfma;
         bool hf_ready = false;
         const float* wqkv[3] = {L.wq, L.wk, L.wv};
-        const float* wqkv_s[3] = {LS.wq, LS.wk, LS.wv};
         const float* sqkv[3] = {L.s_wq, L.s_wk, L.s_wv};
         float* yqkv[3] = {p->qraw, p->kraw, p->vraw};
         // RoPE + cache append in the GEMM's epilogue (no rope_store pass, no raw q/k/v round trip): where each row goes
@@ -2420,7 +2468,7 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
             // (folded up to 16 rows: -3..5 % per Eval; at 17..32 rows the extra staging work of the loader waves eats the saved launch)
             StreamArgs fa = fq;
             fa.gamma = L.attn_norm;
-            const int rs = gemm_stream_group(ctx, x, d, 3, wqkv_s, nullptr, nullptr, d, d, n, d, "stream_norm_wqkv_rope", &fa, wdt);
+            const int rs = stream_src(ctx, src(hqkv), wqkv, 3, [&](const float* const* ws, int wdt) { return gemm_stream_group(ctx, x, d, 3, ws, nullptr, nullptr, d, d, n, d, "stream_norm_wqkv_rope", &fa, wdt); });
             if (rs < 0) return rs;
             qkv_roped = rs == 0;
         }
@@ -2434,13 +2482,12 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
             for (uint32_t b0 = 0; b0 < n && sb <= stream_max_rows(); b0 += sb) {
                 StreamArgs fb = fq;
                 fb.q_out = p->q + (size_t)b0 * d; fb.past = past + b0;
-                if ((rs = gemm_stream_group(ctx, p->h + (size_t)b0 * d, d, 3, wqkv_s, nullptr, nullptr, d, d, std::min(sb, n - b0), d, "stream_wqkv_rope", &fb, wdt))) break;
+                if ((rs = stream_src(ctx, src(hqkv), wqkv, 3, [&](const float* const* ws, int wdt) { return gemm_stream_group(ctx, p->h + (size_t)b0 * d, d, 3, ws, nullptr, nullptr, d, d, std::min(sb, n - b0), d, "stream_wqkv_rope", &fb, wdt); }))) break;
             }
             if (rs == ST_NA && n > 64) {   // long prompts: the same epilogue in the tile GEMM
                 GemmArgs ga = {};
                 ga.epi = GEMM_EPI_QKV_ROPE; ga.q_out = p->q; ga.k_cache = m.kc + slot; ga.v_cache = m.vc + slot; ga.rope = rope; ga.hd = m.hd; ga.past = past;
-                if (hstream) hqkv.widen(ctx, wqkv, 3);
-                rs = gemm_mfma_group(ctx, p->h, d, 3, wqkv, nullptr, nullptr, d, d, n, d, "gemm_wqkv_rope", &ga);
+                rs = gemm_mfma_group(ctx, p->h, d, 3, wqkv, nullptr, nullptr, d, d, n, d, "gemm_wqkv_rope", &ga, true, src(hqkv));
             }
             if (rs < 0) return rs;
             qkv_roped = rs == 0;
@@ -2456,7 +2503,7 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
         int wo_rs = ST_NA;
         if (ksp) {
             for (uint32_t b0 = 0; b0 < n; b0 += sb)
-                if ((wo_rs = gemm_stream_split(ctx, LS.wo, p->attn + (size_t)b0 * d, d, d, d, std::min(sb, n - b0), x + (size_t)b0 * d, p->xb + (size_t)b0 * d, L.ffn_norm, p->h + (size_t)b0 * d, "stream_wo_ksplit", wdt))) break;
+                if ((wo_rs = stream_src(ctx, src(ho), &L.wo, 1, [&](const float* const* ws, int wdt) { return gemm_stream_split(ctx, ws[0], p->attn + (size_t)b0 * d, d, d, d, std::min(sb, n - b0), x + (size_t)b0 * d, p->xb + (size_t)b0 * d, L.ffn_norm, p->h + (size_t)b0 * d, "stream_wo_ksplit", wdt); }))) break;
             if (wo_rs < 0) return wo_rs;
             hf_ready = wo_rs == 0;
         }
@@ -2464,7 +2511,6 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
         } else if (q8) { if ((rc = gemm_q8(ctx, L.wo, L.s_wo, p->attn, p->xb, x, d, d, n, d, d, "gemm_q8_wo"))) return rc; }
         else if ((rc = gemm_small_n_src(ctx, L.wo, p->attn, p->xb, x, d, d, n, d, d, "gemm_wo", true, src(ho)))) return rc;
         const float* w13[2] = {L.w1, L.w3};
-        const float* w13_s[2] = {LS.w1, LS.w3};
         const float* s13[2] = {L.s_w1, L.s_w3};
         float* y13[2] = {p->a1, p->a3};
         float* yg[2] = {p->g, nullptr};
@@ -2472,7 +2518,7 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
             StreamArgs fa = {};
             fa.epi = ST_EPI_SILU_MUL;
             fa.gamma = L.ffn_norm;
-            const int rs = gemm_stream_group(ctx, p->xb, d, 2, w13_s, yg, nullptr, F, d, n, F, "stream_norm_w1w3_silu", &fa, wdt);
+            const int rs = stream_src(ctx, src(h13), w13, 2, [&](const float* const* ws, int wdt) { return gemm_stream_group(ctx, p->xb, d, 2, ws, yg, nullptr, F, d, n, F, "stream_norm_w1w3_silu", &fa, wdt); });
             if (rs < 0) return rs;
             gated = rs == 0;
         }
@@ -2486,13 +2532,12 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
             int rs = ST_NA;
             for (uint32_t b0 = 0; b0 < n && sb <= stream_max_rows(); b0 += sb) {
                 float* ygb[2] = {p->g + (size_t)b0 * F, nullptr};
-                if ((rs = gemm_stream_group(ctx, p->h + (size_t)b0 * d, d, 2, w13_s, ygb, nullptr, F, d, std::min(sb, n - b0), F, "stream_w1w3_silu", &fa, wdt))) break;
+                if ((rs = stream_src(ctx, src(h13), w13, 2, [&](const float* const* ws, int wdt) { return gemm_stream_group(ctx, p->h + (size_t)b0 * d, d, 2, ws, ygb, nullptr, F, d, std::min(sb, n - b0), F, "stream_w1w3_silu", &fa, wdt); }))) break;
             }
             if (rs == ST_NA && n > 64) {
                 GemmArgs ga = {};
                 ga.epi = GEMM_EPI_SILU_MUL;
-                if (hstream) h13.widen(ctx, w13, 2);
-                rs = gemm_mfma_group(ctx, p->h, d, 2, w13, yg, nullptr, F, d, n, F, "gemm_w1w3_silu", &ga);
+                rs = gemm_mfma_group(ctx, p->h, d, 2, w13, yg, nullptr, F, d, n, F, "gemm_w1w3_silu", &ga, true, src(h13));
             }
             if (rs < 0) return rs;
             gated = rs == 0;
@@ -2509,7 +2554,7 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
         if (ksp) {
             const float* next_gamma = last ? nullptr : m.layers[il + 1].attn_norm;   // the next layer's first norm rides on the reduce pass
             for (uint32_t b0 = 0; b0 < n; b0 += sb)
-                if ((w2_rs = gemm_stream_split(ctx, LS.w2, p->g + (size_t)b0 * F, F, d, F, std::min(sb, n - b0), p->xb + (size_t)b0 * d, y + (size_t)b0 * d, next_gamma, p->h + (size_t)b0 * d, "stream_w2_ksplit", wdt))) break;
+                if ((w2_rs = stream_src(ctx, src(h2), &L.w2, 1, [&](const float* const* ws, int wdt) { return gemm_stream_split(ctx, ws[0], p->g + (size_t)b0 * F, F, d, F, std::min(sb, n - b0), p->xb + (size_t)b0 * d, y + (size_t)b0 * d, next_gamma, p->h + (size_t)b0 * d, "stream_w2_ksplit", wdt); }))) break;
             if (w2_rs < 0) return w2_rs;
             h_ready = w2_rs == 0 && next_gamma != nullptr;
         }
@@ -2540,6 +2585,10 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
             const HeadRow hw = head_row(p, m);
             ga.w[0] = hw.w; ga.M = m.V; ga.K = d; ga.x = p->h + (size_t)r0 * d; ga.y = p->logits + (size_t)r0 * m.V;
             if ((rc = gemv<PRO_PLAIN, EPI_STORE, MAP_SINGLE>(ctx, ga, "gemv_lmhead_row", hw.wtype))) return rc;
+        } else if (htiles) {   // the output matrix lazily: halves where the twin's launch is k_gemm_b9, one widening pass directly in front of any other launch
+            bool wide_out = false;
+            const HalfSrc hout = {{p->md.output}, (uint64_t)m.V * d, {&wide_out}, false, true};
+            if ((rc = gemm_small_n_src(ctx, m.output, p->h + (size_t)r0 * d, p->logits + (size_t)r0 * m.V, nullptr, m.V, d, nr, d, m.V, "gemm_lmhead", true, &hout))) return rc;
         } else if ((rc = gemm_small_n(ctx, route_output(p, m), p->h + (size_t)r0 * d, p->logits + (size_t)r0 * m.V, nullptr, m.V, d, nr, d, m.V, "gemm_lmhead"))) return rc;
     }
     LH_HIP(ctx, hipGetLastError());

@@ -482,6 +482,20 @@ func (ctx *Context) SetF16StreamHIP(on bool) {
 }
 func (ctx *Context) F16StreamHIP() bool { return C.lh_ctx_f16_stream(ctx.hip.ctx) != 0 }
 
+// SetF16TilesHIP: lh_ctx_set_f16_tiles on the lh_ctx the context evaluates in - the Evals of more than 128 rows of an f16 model run their k_gemm_b9
+// launches on the model's halves (k_gemm_b9_h, six bf16 products instead of eight) instead of an fp32 image widened in front of every layer (DESIGN 3k).
+// Same bytes; off by default; without effect on models of another weight type; independent of SetF16StreamHIP.
+func (ctx *Context) SetF16TilesHIP(on bool) {
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	if rc := C.lh_ctx_set_f16_tiles(ctx.hip.ctx, v); rc != 0 {
+		hipHalt(ctx.hip.ctx)
+	}
+}
+func (ctx *Context) F16TilesHIP() bool { return C.lh_ctx_f16_tiles(ctx.hip.ctx) != 0 }
+
 func (bt *BatchHIP) Release() { C.lh_batch_destroy(bt.b) }
 
 // NewPipelineHIP: `stages[i]` is this rank's stage of stream i (NewStageHIP over the rank's layer range: the stream's own KV

@@ -1923,6 +1923,11 @@ int llamago_SetF16Stream(llama_context* c, int on) {
     return lh_ctx_set_f16_stream(c->mlctx->hip, on);
 }
 int llamago_F16Stream(llama_context* c) { return c && c->mlctx ? lh_ctx_f16_stream(c->mlctx->hip) : 0; }
+int llamago_SetF16Tiles(llama_context* c, int on) {
+    if (!c || !c->mlctx || !c->mlctx->hip) return halt_rc("llamago_SetF16Tiles: bad arguments");
+    return lh_ctx_set_f16_tiles(c->mlctx->hip, on);
+}
+int llamago_F16Tiles(llama_context* c) { return c && c->mlctx ? lh_ctx_f16_tiles(c->mlctx->hip) : 0; }
 int llamago_BatchSetF16Stream(llama_batch* b, int on) {
     if (!b || !b->mlctx || !b->mlctx->hip) return halt_rc("llamago_BatchSetF16Stream: bad arguments");
     return lh_ctx_set_f16_stream(b->mlctx->hip, on);

@@ -417,6 +417,21 @@ class Context:
         L.llamago_F16Stream.argtypes = [VP]
         return bool(L.llamago_F16Stream(self.h))
 
+    def SetF16Tiles(self, on=True):
+        """llamago_SetF16Tiles: Evals of an f16 model beyond 128 rows run their k_gemm_b9 launches on the model's halves (k_gemm_b9_h) instead of a widened image."""
+        L = self.ml.lib
+        L.llamago_SetF16Tiles.restype = C.c_int
+        L.llamago_SetF16Tiles.argtypes = [VP, C.c_int]
+        if L.llamago_SetF16Tiles(self.h, 1 if on else 0):
+            raise MLError(f"llamago_SetF16Tiles: {self.ml.last_error()}")
+
+    @property
+    def f16_tiles(self):
+        L = self.ml.lib
+        L.llamago_F16Tiles.restype = C.c_int
+        L.llamago_F16Tiles.argtypes = [VP]
+        return bool(L.llamago_F16Tiles(self.h))
+
     def TimeComputes(self, on=True):
         """lh_ctx_time_computes: HIP events around every lh_graph_compute of this context; zeroes the sums."""
         L = self.ml.lib
