@@ -79,6 +79,13 @@ int llamago_ModelWeightType(const llama_model* m);
  * llamago_BatchSetF16Stream / llamago_BatchF16Stream (declared with the batch below): the same for a batch's ticks, feeds and speculative passes. */
 int llamago_SetF16Stream(llama_context* c, int on);
 int llamago_F16Stream(llama_context* c);
+/* lh_ctx_set_q4_stream / lh_ctx_q4_stream (llamahip.h) on the lh_ctx the context / the batch evaluates in: with on != 0 the Evals of a block-int4 model over
+ * activation planes (5..64 rows of a tick, 5..88 of a prompt) read the model's nibbles (k_stream_q4b) instead of an int8 image expanded in front of every
+ * layer - the same bytes ("Native stream kernel").  Off by default (LLAMAHIP_Q4_STREAM=1 turns it on for contexts created afterwards); without
+ * effect on models of another weight type.  The setters return non-zero (ml_LastError) on a null argument; the getters 0 | 1.
+ * llamago_BatchSetQ4Stream / llamago_BatchQ4Stream (declared with the batch below): the same for a batch's ticks, feeds and speculative passes. */
+int llamago_SetQ4Stream(llama_context* c, int on);
+int llamago_Q4Stream(llama_context* c);
 /* lh_ctx_set_f16_tiles / lh_ctx_f16_tiles (llamahip.h) on the lh_ctx the context evaluates in: with on != 0 the Evals of more than 128 rows of an f16 model
  * run their k_gemm_b9 launches on the model's halves (k_gemm_b9_h: six bf16 products per tile pair instead of eight, no widening pass in front) - the same
  * bytes ("Native tile GEMM").  Off by default (LLAMAHIP_F16_TILES=1 turns it on for contexts created afterwards); without effect on models of
@@ -198,6 +205,8 @@ void llamago_FreeBatch(llama_batch* b);
 int llamago_BatchBatched(llama_batch* b);            /* lh_batch_batched */
 int llamago_BatchSetF16Stream(llama_batch* b, int on);   /* llamago_SetF16Stream on the lh_ctx the batch evaluates in */
 int llamago_BatchF16Stream(llama_batch* b);
+int llamago_BatchSetQ4Stream(llama_batch* b, int on);    /* llamago_SetQ4Stream on the lh_ctx the batch evaluates in */
+int llamago_BatchQ4Stream(llama_batch* b);
 /* Test instrumentation: llamago_CacheRead / llamago_CacheWrite on the KV cache of pod `pod` (also fails on a pod outside the batch). */
 int llamago_BatchCacheRead(llama_batch* b, uint32_t pod, int which, uint64_t off_floats, float* dst, uint64_t n);
 int llamago_BatchCacheWrite(llama_batch* b, uint32_t pod, int which, uint64_t off_floats, const float* src, uint64_t n);

@@ -121,6 +121,23 @@ int lh_ctx_f16_tiles(lh_ctx* ctx);
 void lh_gemm_f16_split(uint16_t h, uint32_t* w, uint32_t* r1);
 int lh_gemm_f16_piece(uint32_t p, uint32_t lane, uint32_t out[3]);
 int64_t lh_gemm_f16_w_read_off(uint32_t wm, uint32_t li, uint32_t lh, uint32_t kk);
+/* Block-int4 models on the bf16 stream kernel of 5..64 rows of a tick / 5..88 of a prompt (csrc/kernels_stream_q4b.h).  lh_ctx_set_q4_stream(ctx, on): with
+ * on != 0 every Eval of a block-int4 plan of this context that takes the route over activation planes hands the k_stream_q8b launch sites the model's own
+ * nibble planes and scale planes (k_stream_q4b) and enqueues no k_expand_q4 pass for a matrix that only such launches read; a launch that still reads int8
+ * (prompts from 89 rows, a fallback) gets its matrix expanded directly in front of itself.  Byte for byte the same results: the schedule, every kernel
+ * shape and every sum are the int8 twin's.  Off by default; the initial value is LLAMAHIP_Q4_STREAM=1 of the environment, read once in lh_ctx_create.  Read
+ * at every Eval; accepted and without effect for fp32, f16 and block-int8 plans; independent of the f16 switches.  A change makes every captured graph of a
+ * block-int4 plan on the context that may hold a stream launch run eagerly once and be captured anew.  lh_ctx_q4_stream: the current value (0 | 1; ctx NULL: 0). */
+int lh_ctx_set_q4_stream(lh_ctx* ctx, int on);
+int lh_ctx_q4_stream(lh_ctx* ctx);
+/* Where k_stream_q4b keeps a nibble (csrc/stream_q4_layout.h; pure host functions, for checks): byte offset, in the weight part of a ring image of kc-column
+ * chunks (128 | 256 | 512), of 16-byte granule g (quant block g: columns 32 g .. 32 g + 31 of the chunk) of image row r (< 128) / of the 4 bytes MFMA lane
+ * (r16, slot) reads of tile slot t (< 8) for quant block kb (< kc / 32) of the chunk.  An argument out of range: -1.
+ * lh_stream_q4_operand: the kernel's nibble -> bf16 conversion on the host - the eight nibbles of `nibbles` (nibble k = bits 4 k .. 4 k + 3) as the four
+ * dwords of the MFMA operand (out[j] = the bf16 of n_2j - 8 in the low half, of n_2j+1 - 8 in the high half). */
+int64_t lh_stream_q4_image_off(uint32_t kc, uint32_t r, uint32_t g);
+int64_t lh_stream_q4_read_off(uint32_t kc, uint32_t t, uint32_t r16, uint32_t kb, uint32_t slot);
+void lh_stream_q4_operand(uint32_t nibbles, uint32_t out[4]);
 /* Dequantised fp32 values of a dtype-7 buffer (w = fl32(d*q)), for checks. */
 int lh_buf_read_q8(lh_ctx* ctx, lh_buf buf, uint64_t off, float* dst, uint64_t n);
 int lh_buf_free(lh_ctx* ctx, lh_buf buf);

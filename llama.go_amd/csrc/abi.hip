@@ -3,6 +3,7 @@
 #include "common.h"
 #include "kernels_q8_pack.h"
 #include "stream_f16_layout.h"
+#include "stream_q4_layout.h"
 #include "gemm_f16_layout.h"
 #include <stdarg.h>
 #include <math.h>
@@ -278,6 +279,8 @@ int lh_ctx_create(int device, void* stream, lh_ctx** out) {
     c->f16_stream = hs && hs[0] == '1' ? 1 : 0;
     const char* ht = getenv("LLAMAHIP_F16_TILES");
     c->f16_tiles = ht && ht[0] == '1' ? 1 : 0;
+    const char* qs = getenv("LLAMAHIP_Q4_STREAM");
+    c->q4_stream = qs && qs[0] == '1' ? 1 : 0;
     *out = c;
     return LH_OK;
 }
@@ -295,6 +298,24 @@ int lh_ctx_set_f16_tiles(lh_ctx* ctx, int on) {
     return LH_OK;
 }
 int lh_ctx_f16_tiles(lh_ctx* ctx) { return ctx ? ctx->f16_tiles : 0; }
+int lh_ctx_set_q4_stream(lh_ctx* ctx, int on) {
+    if (!ctx) return LH_EINVAL;
+    const int v = on ? 1 : 0;
+    if (v != ctx->q4_stream) { ctx->q4_stream = v; ++ctx->q4_stream_gen; }
+    return LH_OK;
+}
+int lh_ctx_q4_stream(lh_ctx* ctx) { return ctx ? ctx->q4_stream : 0; }
+int64_t lh_stream_q4_image_off(uint32_t kc, uint32_t r, uint32_t g) {
+    if ((kc != 128 && kc != 256 && kc != 512) || r >= 128 || g >= kc / 32) return -1;
+    return (int64_t)lh::stream_q4_granule_off(kc, r, g);
+}
+int64_t lh_stream_q4_read_off(uint32_t kc, uint32_t t, uint32_t r16, uint32_t kb, uint32_t slot) {
+    if ((kc != 128 && kc != 256 && kc != 512) || t >= 8 || r16 >= 16 || kb >= kc / 32 || slot >= 4) return -1;
+    return (int64_t)lh::stream_q4_read_off(kc, t, r16, kb, slot);
+}
+void lh_stream_q4_operand(uint32_t nibbles, uint32_t out[4]) {
+    if (out) lh::stream_q4_operand(nibbles, out);
+}
 void lh_gemm_f16_split(uint16_t h, uint32_t* w, uint32_t* r1) {
     if (w && r1) lh::gemm_h_split(h, w, r1);
 }

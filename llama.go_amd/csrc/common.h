@@ -160,6 +160,10 @@ struct lh_ctx {
     // holds it: k_gemm_b9 takes more than 128 rows (gemm_b9_ok), and every captured graph - ticks of at most 64 pods, speculative passes of a few rows,
     // the decode step - enqueues fewer, so the launch the switch chooses is always an eager one.
     int f16_tiles = 0;
+    // lh_ctx_set_q4_stream: block-int4 plans hand the k_stream_q8b launch sites of their Planes route the model's nibbles (k_stream_q4b,
+    // kernels_stream_q4b.h).  A switch that chooses a kernel, like f16_stream: q4_stream_gen counts the changes for the same captured graphs' keys
+    int q4_stream = 0;
+    uint64_t q4_stream_gen = 0;
     // the activation rows of a long-prompt GEMM as three bf16 planes (k_gemm_b9); grows, never shrinks
     uint16_t* xs3 = nullptr;
     uint64_t xs3_elems = 0;

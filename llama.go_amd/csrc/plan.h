@@ -62,6 +62,8 @@ struct Plan {
     // Block-int4 plans (md.wtype == 2) use the same three fields: Step, Rows and Q8Steps stream the nibbles (kernels_q4.h); Planes and Prefill run
     // the block-int8 schedule over md_wide = md with wtype 7, whose quant pointers point into wide_layer / wide_out - here INT8 images of 4 d^2 + 3 d F
     // and V d BYTES behind the float* type, filled by k_expand_q4 - and whose s_* pointers are the model's own scale planes.
+    // (With lh_ctx_set_q4_stream on, Planes' launch sites read the nibble planes themselves - k_stream_q4b, kernels_stream_q4b.h - and a matrix is expanded
+    // into its slot only directly in front of a launch that reads int8: eval_planes / eval_prefill, Q4Src.)
     ModelDesc md_wide;
     float *wide_layer = nullptr, *wide_out = nullptr;
     float* emb = nullptr;                    // LH_T_OUTPUT on llama.Eval's `embeddings`: the final norm rows [emb_cap][d]

@@ -10,6 +10,7 @@
 #include "kernels_sample.h"
 #include "kernels_stream.h"
 #include "kernels_stream_q8b.h"
+#include "kernels_stream_q4b.h"
 #include "kernels_stream_b9.h"
 #include "kernels_gemm_b9.h"
 #include "kernels_rows.h"
@@ -1138,11 +1139,39 @@ constexpr int q8b_nimg_fit(int maxt, int xr, int kc) {
     const int n = (int)(160 * 1024 / stream_q8b_image_bytes(maxt, xr, kc));
     return n < 3 ? n : 3;   // (a fourth image measured 1-4 % slower on every 7B launch where it fits, profiles/r05_q8b_probe.txt)
 }
+// wdt (here and down the chain): the dtype of the matrices a.w[] points at - 7 = the int8 quants, 2 = the nibble planes of a block-int4 model (k_stream_q4b,
+// kernels_stream_q4b.h: the kernel of the SAME MAXT, NCT, KC and XR).  Every predicate that answers ST_NA and every choice that reaches the sums - MAXT,
+// NCT / XR, KC with its q8b_nimg_fit conditions, the K-split - is the int8 chain's, taken from the INT8 image's sizes: a block-int4 model must take exactly
+// the launches its expanded twin takes.  Only the ring depth is the 4-bit kernel's own: as many of its smaller images as fit in 160 KB, up to Q4B_NIMG_CAP.
+// Shipped: three, the int8 cap, which gives a third image to the shapes whose int8 ring holds two; whether a fourth (-DQ4B_NIMG_CAP=4) is slower as it
+// measured for int8 is recorded in profiles/q4_stream.txt.  The sums do not depend on the depth.
+#ifndef Q4B_NIMG_CAP
+#define Q4B_NIMG_CAP 3
+#endif
+constexpr int q4b_nimg_fit(int maxt, int xr, int kc) {
+    const int n = (int)(160 * 1024 / stream_q4b_image_bytes(maxt, xr, kc));
+    return n < Q4B_NIMG_CAP ? n : Q4B_NIMG_CAP;
+}
 template <int MAXT, int NCT, int KC, int XR>
-static int launch_stream_q8b(lh_ctx* ctx, const StreamArgs& a, const char* name) {
+static int launch_stream_q8b(lh_ctx* ctx, const StreamArgs& a, const char* name, int wdt = 7) {
     constexpr int NIMG = q8b_nimg_fit(MAXT, XR, KC);
     if constexpr (NIMG < 2) return ST_NA;
-    else {
+    else if (wdt == 2) {
+        constexpr int NIMG4 = q4b_nimg_fit(MAXT, XR, KC);
+        static_assert(NIMG4 >= NIMG, "the 4-bit image is the smaller one");
+        static bool flags4[16] = {};
+        auto kern = k_stream_q4b<MAXT, NCT, KC, NIMG4, XR>;
+        const size_t lds = std::max<size_t>((size_t)NIMG4 * stream_q4b_image_bytes(MAXT, XR, KC), 82 * 1024);   // one workgroup per CU
+        int rc = set_lds_once(ctx, kern, lds, flags4);
+        if (rc) return rc;
+        if (g_prepare_only) return 0;
+        const uint32_t grid = a.ksplit > 1 ? (uint32_t)ctx->ds->num_cu / a.ksplit * a.ksplit : (uint32_t)ctx->ds->num_cu;
+        ProfScope ps(ctx->stream, name, (uint64_t)a.groups * a.M * a.K / 32 * 20);
+        LH_TRACE("k_stream_q4b<%d,%d,%d,%d,%d>/s%u", MAXT, NCT, KC, NIMG4, XR, a.ksplit > 1 ? a.ksplit : 1u);
+        LH_LAUNCH_AS("k_stream_q4b", kern, dim3(grid), dim3(Q8B_TH), lds, ctx->stream, a);
+        LH_HIP(ctx, hipGetLastError());
+        return 0;
+    } else {
         static bool flags[16] = {};
         auto kern = k_stream_q8b<MAXT, NCT, KC, NIMG, XR>;
         const size_t lds = std::max<size_t>((size_t)NIMG * stream_q8b_image_bytes(MAXT, XR, KC), 82 * 1024);   // one workgroup per CU
@@ -1158,24 +1187,24 @@ static int launch_stream_q8b(lh_ctx* ctx, const StreamArgs& a, const char* name)
     }
 }
 template <int MAXT, int NCT, int XR>
-static int launch_stream_q8b_kc(lh_ctx* ctx, const StreamArgs& a, const char* name) {
+static int launch_stream_q8b_kc(lh_ctx* ctx, const StreamArgs& a, const char* name, int wdt = 7) {
     const uint32_t S = a.ksplit > 1 ? a.ksplit : 1u;
-    if constexpr (NCT == 1 && MAXT <= 3 && q8b_nimg_fit(MAXT, XR, 512) >= 2) { if (a.K % 512 == 0 && a.K / 512 >= S) return launch_stream_q8b<MAXT, NCT, 512, XR>(ctx, a, name); }
-    if constexpr (NCT <= 2 && q8b_nimg_fit(MAXT, XR, 256) >= 2) { if (a.K % 256 == 0 && a.K / 256 >= S) return launch_stream_q8b<MAXT, NCT, 256, XR>(ctx, a, name); }
+    if constexpr (NCT == 1 && MAXT <= 3 && q8b_nimg_fit(MAXT, XR, 512) >= 2) { if (a.K % 512 == 0 && a.K / 512 >= S) return launch_stream_q8b<MAXT, NCT, 512, XR>(ctx, a, name, wdt); }
+    if constexpr (NCT <= 2 && q8b_nimg_fit(MAXT, XR, 256) >= 2) { if (a.K % 256 == 0 && a.K / 256 >= S) return launch_stream_q8b<MAXT, NCT, 256, XR>(ctx, a, name, wdt); }
     if (a.K / 128 < S) return ST_NA;
-    return launch_stream_q8b<MAXT, NCT, 128, XR>(ctx, a, name);
+    return launch_stream_q8b<MAXT, NCT, 128, XR>(ctx, a, name, wdt);
 }
 template <int MAXT>
-static int launch_stream_q8b_n(lh_ctx* ctx, const StreamArgs& a, const char* name) {
-    if (a.n <= 8) return launch_stream_q8b_kc<MAXT, 1, 8>(ctx, a, name);
-    if (a.n <= 16) return launch_stream_q8b_kc<MAXT, 1, 16>(ctx, a, name);
-    if (a.n <= 32) return launch_stream_q8b_kc<MAXT, 2, 32>(ctx, a, name);
-    if (a.n <= 48) return launch_stream_q8b_kc<MAXT, 3, 48>(ctx, a, name);
-    if (a.n <= 64) return launch_stream_q8b_kc<MAXT, 4, 64>(ctx, a, name);
+static int launch_stream_q8b_n(lh_ctx* ctx, const StreamArgs& a, const char* name, int wdt = 7) {
+    if (a.n <= 8) return launch_stream_q8b_kc<MAXT, 1, 8>(ctx, a, name, wdt);
+    if (a.n <= 16) return launch_stream_q8b_kc<MAXT, 1, 16>(ctx, a, name, wdt);
+    if (a.n <= 32) return launch_stream_q8b_kc<MAXT, 2, 32>(ctx, a, name, wdt);
+    if (a.n <= 48) return launch_stream_q8b_kc<MAXT, 3, 48>(ctx, a, name, wdt);
+    if (a.n <= 64) return launch_stream_q8b_kc<MAXT, 4, 64>(ctx, a, name, wdt);
     return ST_NA;
 }
-static int launch_stream_q8b_maxt(lh_ctx* ctx, const StreamArgs& a, const char* name, uint32_t maxt) {
-    return with_stream_maxt(maxt, [&](auto mt) { return launch_stream_q8b_n<decltype(mt)::value>(ctx, a, name); });
+static int launch_stream_q8b_maxt(lh_ctx* ctx, const StreamArgs& a, const char* name, uint32_t maxt, int wdt = 7) {
+    return with_stream_maxt(maxt, [&](auto mt) { return launch_stream_q8b_n<decltype(mt)::value>(ctx, a, name, wdt); });
 }
 // ---- k_stream_b9 (kernels_stream_b9.h, round 6): fp32 weights x the same three bf16 planes, eight of the nine exact bf16 products per weight on the bf16 matrix pipe.
 // Wave-specialised like k_stream_dma (four loader waves, four MFMA waves); up to four column tiles (64 rows), 64-column chunks, as many images
@@ -1218,9 +1247,10 @@ static int launch_stream_b9_maxt(lh_ctx* ctx, const StreamArgs& a, const char* n
 }
 static bool stream_b9_built(uint32_t maxt, uint32_t n) { return maxt >= 1 && maxt <= 8 && n >= 1 && n <= 64 && !(maxt > 6 && n > 48); }
 // groups (<= 3) matrices of equal shape - block-int8 (wsc: their scale planes) or fp32 (wsc[g] == nullptr: k_stream_b9) - times the same activation
-// planes in ONE launch; fused: the epilogue (RoPE + cache append | silu * mul)
+// planes in ONE launch; fused: the epilogue (RoPE + cache append | silu * mul).  wdt = 2: wq[] are the nibble planes of a block-int4 model (the alignment
+// checks below then hold for the nibble planes' addresses).
 static int gemm_q8b_group(lh_ctx* ctx, const uint16_t* xs, uint64_t xs_plane, uint32_t ldxs, uint32_t groups, const float* const* wq, const float* const* wsc, float* const* y,
-                          const float* const* r, uint32_t M, uint32_t K, uint32_t n, uint32_t ldy, const char* name, const StreamArgs* fused = nullptr) {
+                          const float* const* r, uint32_t M, uint32_t K, uint32_t n, uint32_t ldy, const char* name, const StreamArgs* fused = nullptr, int wdt = 7) {
     if (n == 0 || n > STREAM_ROWS_Q8 || groups > 3 || M % 16 || K % 128 || ldxs % 8 || ldy % 4 || ((uintptr_t)xs & 15) || (xs_plane * 2) % 16) return ST_NA;
     const uint32_t ncu = (uint32_t)ctx->ds->num_cu, T = M / 16 * groups;
     const uint32_t maxt = (fused && fused->epi == ST_EPI_SILU_MUL) ? 2 * ((M / 16 + ncu - 1) / ncu) : (T + ncu - 1) / ncu;
@@ -1233,7 +1263,7 @@ static int gemm_q8b_group(lh_ctx* ctx, const uint16_t* xs, uint64_t xs_plane, ui
         a.w[g] = wq[g]; a.ws[g] = wsc[g]; a.y[g] = y ? y[g] : nullptr; a.r[g] = r ? r[g] : nullptr;
         if (((uintptr_t)wq[g] & 15) || ((uintptr_t)a.y[g] & 15) || (a.r[g] && ((uintptr_t)a.r[g] & 15)) || ((uintptr_t)a.ws[g] & 15)) return ST_NA;
     }
-    return a.ws[0] ? launch_stream_q8b_maxt(ctx, a, name, maxt) : launch_stream_b9_maxt(ctx, a, name, maxt);
+    return a.ws[0] ? launch_stream_q8b_maxt(ctx, a, name, maxt, wdt) : launch_stream_b9_maxt(ctx, a, name, maxt);
 }
 // One matrix as groups of S workgroups that split the contraction (a workgroup then holds S times the rows for a 1 / S of K: the single-tile
 // matrices wo and w2 read S times less of X out of L2 and run S times fewer, longer chunk loops), k_stream_reduce_norm adds the S partials +
@@ -1246,7 +1276,7 @@ static uint32_t q8b_split_groups(uint32_t nchunks, uint32_t ncu) {   // S: fours
     return S;
 }
 static int gemm_q8b_split(lh_ctx* ctx, const float* wq, const float* wsc, const uint16_t* xs, uint64_t xs_plane, uint32_t ldxs, uint32_t M, uint32_t K, uint32_t n,
-                          const float* resid, float* y, const float* gamma, float* h, uint16_t* hs, uint64_t hs_plane, const char* name) {
+                          const float* resid, float* y, const float* gamma, float* h, uint16_t* hs, uint64_t hs_plane, const char* name, int wdt = 7) {
     if (n == 0 || n > STREAM_ROWS_Q8 || M % 16 || M > 8192 || M % 4 || K % 128 || ldxs % 8 || ((uintptr_t)xs & 15) || (xs_plane * 2) % 16) return ST_NA;
     if ((((uintptr_t)wq | (uintptr_t)y | (uintptr_t)resid | (uintptr_t)gamma | (uintptr_t)h | (uintptr_t)hs | (uintptr_t)wsc) & 15)) return ST_NA;
     const uint32_t ncu = (uint32_t)ctx->ds->num_cu, nchunks = wsc ? K / (K % 256 == 0 ? 256u : 128u) : K / (uint32_t)B9S_KC;
@@ -1256,7 +1286,7 @@ static int gemm_q8b_split(lh_ctx* ctx, const float* wq, const float* wsc, const 
     StreamArgs a = {};
     a.xs = xs; a.xs_plane = xs_plane; a.ldxs = ldxs; a.groups = 1; a.M = M; a.K = K; a.n = n; a.ldy = M; a.w[0] = wq; a.ws[0] = wsc; a.y[0] = ctx->splitk;
     a.ksplit = S; a.ysplit = (uint64_t)n * M;
-    const int rs = wsc ? launch_stream_q8b_maxt(ctx, a, name, maxt) : launch_stream_b9_maxt(ctx, a, name, maxt);
+    const int rs = wsc ? launch_stream_q8b_maxt(ctx, a, name, maxt, wdt) : launch_stream_b9_maxt(ctx, a, name, maxt);
     if (rs) return rs;
     if (g_prepare_only) return 0;
     StreamReduceArgs r = {};
@@ -2088,7 +2118,13 @@ static const ModelDesc& sched_md(const Plan* p) { return p->md.wtype == 1 || p->
 // lh_ctx_set_f16_stream in the key of a captured graph whose launches may hold a stream launch (ticks, speculative passes): the switch and the count of its
 // changes for an f16 plan, 0 for every other plan (the switch does nothing there).  f16_stream_sync, in front of CapturedGraph::run: a changed value also
 // clears the warm bits - the kernels the new value chooses set their LDS attribute at their first launch (set_lds_once), which must be an eager one.
-static uint64_t f16_stream_key(const Plan* p) { return p->md.wtype == 1 ? (p->ctx->f16_stream_gen << 1) | (uint64_t)p->ctx->f16_stream : 0; }
+// A block-int4 plan carries lh_ctx_set_q4_stream in the same field in the same way (its k_stream_q8b launch sites then launch k_stream_q4b): one key field, the
+// switch of the plan's own weight type - a plan has one weight type, so the two switches never meet in one key.
+static uint64_t f16_stream_key(const Plan* p) {
+    if (p->md.wtype == 1) return (p->ctx->f16_stream_gen << 1) | (uint64_t)p->ctx->f16_stream;
+    if (p->md.wtype == 2) return (p->ctx->q4_stream_gen << 1) | (uint64_t)p->ctx->q4_stream;
+    return 0;
+}
 template <typename G>
 static void f16_stream_sync(G& graph, uint64_t* seen, uint64_t now) {
     if (*seen != now) { graph.warm = 0; *seen = now; }
@@ -2115,6 +2151,33 @@ static const float* route_output(Plan* p, const ModelDesc& m) {
         else widen_f16_launch(p->ctx, p->md.output, p->wide_out, (uint64_t)m.V * m.d);
     }
     return m.output;
+}
+// The nibbles behind int8 image slots (a block-int4 plan with lh_ctx_set_q4_stream on: eval_planes, eval_prefill): w[g] of a launch names the image slot
+// of a matrix whose n quants lie 4-bit at nib[g] and which is NOT expanded yet (HalfSrc's pattern).  expand: k_expand_q4 per matrix into its slot,
+// directly in front of a launch that reads int8.
+struct Q4Src {
+    const float* nib[3];
+    uint64_t n;
+    void expand(lh_ctx* ctx, const float* const* w, uint32_t groups) const {
+        for (uint32_t g = 0; g < groups; ++g) expand_q4_launch(ctx, nib[g], (void*)w[g], n);   // (a launch error surfaces at the layer's hipGetLastError)
+    }
+};
+// One k_stream_q8b launch site over matrices that may still be nibbles: launch(w, wdt) is the site's gemm_q8b_group / gemm_q8b_split call.  The nibbles as
+// they are where the 4-bit chain has the launch (every ST_NA of it is the int8 chain's, except the alignment of the nibble planes themselves); otherwise
+// the int8 launch over the image, which is expanded only if that launch exists - asked with a prepare-only pass, which enqueues nothing - so that an
+// expansion pass never stands in front of a launch that does not read it.
+template <typename F>
+static int q4_stream_src(lh_ctx* ctx, const Q4Src* qs, const float* const* w, uint32_t groups, F&& launch) {
+    if (!qs) return launch(w, 7);
+    int rs = launch(qs->nib, 2);
+    if (rs != ST_NA) return rs;
+    const bool was = g_prepare_only;
+    g_prepare_only = true;
+    rs = launch(w, 7);
+    g_prepare_only = was;
+    if (rs || was) return rs;
+    qs->expand(ctx, w, groups);
+    return launch(w, 7);
 }
 // the output matrix for ONE logits row on the decode stream: an f16 model's halves / a block-int4 model's nibbles as they are (k_gemv_sa_h / k_gemv_q4s
 // compute the bits k_gemv_sa / k_gemv_q8s would over the image)
@@ -2339,8 +2402,16 @@ static int eval_planes(Plan* p, const EvalCall& c, const float* x) {
     int rc;
 #define PLANES_TRY(expr, what) do { if ((rc = (expr))) { if (rc == ST_NA) LH_FAIL(ctx, LH_ESHAPE, "Eval of %u rows over activation planes: no launch for %s (embd %u, ff %u, weight type %u)", n, what, d, F, m.wtype); return rc; } } while (0)
     bool h_ready = false;
+    // block-int4 plan with lh_ctx_set_q4_stream on: the launch sites read the model's own nibble planes (k_stream_q4b; the scale planes are the model's own
+    // either way) and a matrix is expanded into its slot of the layer image only in front of a launch that reads int8 (Q4Src) - a layer whose launches
+    // all stream enqueues no k_expand_q4.  m is the int8 shadow, so every decision here and down the chain is the expanded twin's.
+    const bool q4s = &m == &p->md_wide && p->md.wtype == 2 && ctx->q4_stream;
     for (uint32_t il = m.layer0; il < m.layer1; ++il) {
-        const LayerW& L = route_layer(p, m, il);
+        const LayerW& L = q4s ? m.layers[il] : route_layer(p, m, il);       // (q4s: the image slots, nothing in them yet)
+        const LayerW& LS = q4s ? p->md.layers[il] : L;                       // the model's own matrices
+        const uint64_t dd_ = (uint64_t)d * d, dF_ = (uint64_t)d * F;
+        const Q4Src qqkv = {{LS.wq, LS.wk, LS.wv}, dd_}, qo = {{LS.wo}, dd_}, q13 = {{LS.w1, LS.w3}, dF_}, q2 = {{LS.w2}, dF_};
+        auto src = [&](const Q4Src& q) -> const Q4Src* { return q4s ? &q : nullptr; };
         const size_t slot = (size_t)(il - m.cache_layer0) * m.ctx * d;
         if (!h_ready) { TraceScope ts_(ctx->stream, "rmsnorm_rows_s3"); if (!g_prepare_only) LH_LAUNCH(k_rmsnorm_rows_s3, dim3(n), dim3(256), 0, ctx->stream, x, L.attn_norm, (float*)nullptr, hs, pd, d); }
         {   // wq|wk|wv -> RoPE(Q, new K rows) -> K, V appended   (llama.go:263-297)
@@ -2352,14 +2423,16 @@ static int eval_planes(Plan* p, const EvalCall& c, const float* x) {
             for (uint32_t b0 = 0; b0 < n; b0 += STREAM_ROWS_Q8) {   // (a prompt of 65..128 tokens: two passes over the weights, still 1.5x faster than the tile GEMM)
                 const uint32_t nb = std::min(STREAM_ROWS_Q8, n - b0);
                 fq.q_out = p->q + (size_t)b0 * d; fq.past = past + b0;
-                PLANES_TRY(gemm_q8b_group(ctx, hs + (size_t)b0 * d, pd, d, 3, wqkv, sqkv, nullptr, nullptr, d, d, nb, d, m.wtype == 7 ? "q8b_wqkv_rope" : "b9s_wqkv_rope", &fq), "wq|wk|wv");
+                PLANES_TRY(q4_stream_src(ctx, src(qqkv), wqkv, 3, [&](const float* const* ws, int wdt) {
+                    return gemm_q8b_group(ctx, hs + (size_t)b0 * d, pd, d, 3, ws, sqkv, nullptr, nullptr, d, d, nb, d, m.wtype == 7 ? "q8b_wqkv_rope" : "b9s_wqkv_rope", &fq, wdt); }), "wq|wk|wv");
             }
         }
         if ((rc = eval_attention(p, c, slot, scale, true, as, pd))) return rc;   // merged heads -> planes (mfma: this route's shapes all have the grouped MFMA launches)
         // wo + residual + RMSNorm * ffn_norm -> planes   (llama.go:336-351)
         for (uint32_t b0 = 0; b0 < n; b0 += STREAM_ROWS_Q8)
-            PLANES_TRY(gemm_q8b_split(ctx, L.wo, L.s_wo, as + (size_t)b0 * d, pd, d, d, d, std::min(STREAM_ROWS_Q8, n - b0), x + (size_t)b0 * d, p->xb + (size_t)b0 * d, L.ffn_norm, nullptr,
-                                   hs + (size_t)b0 * d, pd, m.wtype == 7 ? "q8b_wo_ksplit" : "b9s_wo_ksplit"), "wo");
+            PLANES_TRY(q4_stream_src(ctx, src(qo), &L.wo, 1, [&](const float* const* ws, int wdt) {
+                return gemm_q8b_split(ctx, ws[0], L.s_wo, as + (size_t)b0 * d, pd, d, d, d, std::min(STREAM_ROWS_Q8, n - b0), x + (size_t)b0 * d, p->xb + (size_t)b0 * d, L.ffn_norm, nullptr,
+                                      hs + (size_t)b0 * d, pd, m.wtype == 7 ? "q8b_wo_ksplit" : "b9s_wo_ksplit", wdt); }), "wo");
         {   // w1|w3 -> silu(w1 h) * (w3 h) -> planes   (llama.go:354-361)
             const float* w13[2] = {L.w1, L.w3};
             const float* s13[2] = {L.s_w1, L.s_w3};
@@ -2367,7 +2440,8 @@ static int eval_planes(Plan* p, const EvalCall& c, const float* x) {
             fa.epi = ST_EPI_SILU_MUL; fa.ys = gs; fa.ys_plane = pf; fa.ldys = F;
             for (uint32_t b0 = 0; b0 < n; b0 += STREAM_ROWS_Q8) {
                 fa.ys = gs + (size_t)b0 * F;
-                PLANES_TRY(gemm_q8b_group(ctx, hs + (size_t)b0 * d, pd, d, 2, w13, s13, nullptr, nullptr, F, d, std::min(STREAM_ROWS_Q8, n - b0), F, m.wtype == 7 ? "q8b_w1w3_silu" : "b9s_w1w3_silu", &fa), "w1|w3");
+                PLANES_TRY(q4_stream_src(ctx, src(q13), w13, 2, [&](const float* const* ws, int wdt) {
+                    return gemm_q8b_group(ctx, hs + (size_t)b0 * d, pd, d, 2, ws, s13, nullptr, nullptr, F, d, std::min(STREAM_ROWS_Q8, n - b0), F, m.wtype == 7 ? "q8b_w1w3_silu" : "b9s_w1w3_silu", &fa, wdt); }), "w1|w3");
             }
         }
         {   // w2 + residual (+ the next layer's first norm, or the final norm, on the reduce pass)   (llama.go:363-372)
@@ -2375,8 +2449,9 @@ static int eval_planes(Plan* p, const EvalCall& c, const float* x) {
             float* y = (last && !m.last_stage()) ? x_out_dev : p->xa;
             const float* next_gamma = !last ? m.layers[il + 1].attn_norm : (m.last_stage() ? m.norm : nullptr);
             for (uint32_t b0 = 0; b0 < n; b0 += STREAM_ROWS_Q8)
-                PLANES_TRY(gemm_q8b_split(ctx, L.w2, L.s_w2, gs + (size_t)b0 * F, pf, F, d, F, std::min(STREAM_ROWS_Q8, n - b0), p->xb + (size_t)b0 * d, y + (size_t)b0 * d, next_gamma,
-                                       (last && m.last_stage()) ? p->h + (size_t)b0 * d : nullptr, next_gamma ? hs + (size_t)b0 * d : nullptr, pd, m.wtype == 7 ? "q8b_w2_ksplit" : "b9s_w2_ksplit"), "w2");
+                PLANES_TRY(q4_stream_src(ctx, src(q2), &L.w2, 1, [&](const float* const* ws, int wdt) {
+                    return gemm_q8b_split(ctx, ws[0], L.s_w2, gs + (size_t)b0 * F, pf, F, d, F, std::min(STREAM_ROWS_Q8, n - b0), p->xb + (size_t)b0 * d, y + (size_t)b0 * d, next_gamma,
+                                          (last && m.last_stage()) ? p->h + (size_t)b0 * d : nullptr, next_gamma ? hs + (size_t)b0 * d : nullptr, pd, m.wtype == 7 ? "q8b_w2_ksplit" : "b9s_w2_ksplit", wdt); }), "w2");
             h_ready = next_gamma != nullptr;
         }
         x = p->xa;
@@ -2384,11 +2459,14 @@ static int eval_planes(Plan* p, const EvalCall& c, const float* x) {
     }
     if (m.last_stage()) {   // lm_head on the rows the caller reads (llama.go:374-384, 394-401); hs / p->h hold RMSNorm * norm of every row
         const auto [r0, nr] = logits_rows(c);
-        const float* wv = route_output(p, m); const float* sv = m.s_output; float* yv = p->logits + (size_t)r0 * m.V;   // (m.output below: the same address)
+        const float* wv = q4s ? m.output : route_output(p, m); const float* sv = m.s_output; float* yv = p->logits + (size_t)r0 * m.V;   // (m.output below: the same address)
+        const Q4Src qout = {{p->md.output}, (uint64_t)m.V * d};
+        const uint32_t hrow0 = r0;   // (a structured binding is not captured by a lambda before C++20)
         for (uint32_t b0 = 0; b0 < nr; b0 += STREAM_ROWS_Q8) {
             float* yb = yv + (size_t)b0 * m.V;
             const uint32_t nb = std::min(STREAM_ROWS_Q8, nr - b0);
-            rc = gemm_q8b_group(ctx, hs + (size_t)(r0 + b0) * d, pd, d, 1, &wv, &sv, &yb, nullptr, m.V, d, nb, m.V, m.wtype == 7 ? "q8b_lmhead" : "b9s_lmhead");
+            rc = q4_stream_src(ctx, q4s ? &qout : nullptr, &wv, 1, [&](const float* const* ws, int wdt) {
+                return gemm_q8b_group(ctx, hs + (size_t)(hrow0 + b0) * d, pd, d, 1, ws, &sv, &yb, nullptr, m.V, d, nb, m.V, m.wtype == 7 ? "q8b_lmhead" : "b9s_lmhead", nullptr, wdt); });
             if (rc == ST_NA && m.wtype == 0 && nb > 1 && m.V % 32 == 0) {
                 // fp32 output matrix with eight row tiles per workgroup next to four column tiles (7B at 49..64 rows): no k_stream_b9 launch of that shape - the two halves
                 // of the vocabulary have one each (four row tiles).  64 pods, 7B: 172 us on k_stream_dma -> see profiles/r06_lmhead_halves.txt
@@ -2438,9 +2516,15 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
     // makes the matrices lazy; which launches read halves is each switch's own (HalfSrc::stream / ::tiles).
     const bool f16p = &m == &p->md_wide && p->md.wtype == 1;
     const bool hstream = f16p && ctx->f16_stream, htiles = f16p && ctx->f16_tiles, lazy = hstream || htiles;
+    // block-int4 plan with lh_ctx_set_q4_stream on: no launch of this route reads nibbles (k_gemm_q8b3 and the dequantising GEMM read int8), so every matrix
+    // is expanded - directly in front of the launch that reads it (q4x below) instead of in front of the layer, the one place an expansion stands under
+    // the switch (eval_planes, Q4Src).  A plan whose shapes have no k_stream_q8b schedule never launches k_stream_q4b: the switch leaves it alone entirely.
+    const bool q4s = &m == &p->md_wide && p->md.wtype == 2 && ctx->q4_stream && q8b_shape_ok(ctx, m);
     for (uint32_t il = m.layer0; il < m.layer1; ++il) {
-        const LayerW& L = lazy ? m.layers[il] : route_layer(p, m, il);      // (lazy: the image slots, nothing in them yet)
-        const LayerW& LS = lazy ? p->md.layers[il] : L;                     // the model's own matrices
+        const LayerW& L = (lazy || q4s) ? m.layers[il] : route_layer(p, m, il);   // (lazy, q4s: the image slots, nothing in them yet)
+        const LayerW& LS = (lazy || q4s) ? p->md.layers[il] : L;                  // the model's own matrices
+        const Q4Src qqkv = {{LS.wq, LS.wk, LS.wv}, (uint64_t)d * d}, qo = {{LS.wo}, (uint64_t)d * d}, q13 = {{LS.w1, LS.w3}, (uint64_t)d * F}, q2 = {{LS.w2}, (uint64_t)d * F};
+        auto q4x = [&](const Q4Src& q, const float* const* w, uint32_t groups) { if (q4s) q.expand(ctx, w, groups); };
         bool wide[7] = {};                                                  // wq wk wv wo w1 w3 w2: the slot holds the matrix
         const uint64_t dd_ = (uint64_t)d * d, dF_ = (uint64_t)d * F;
         const HalfSrc hqkv = {{LS.wq, LS.wk, LS.wv}, dd_, {&wide[0], &wide[1], &wide[2]}, hstream, htiles}, hq = {{LS.wq}, dd_, {&wide[0]}, hstream, htiles},
@@ -2476,6 +2560,7 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
         h_ready = false;
         if (qkv_roped) {
         } else if (q8) {   // (prompts beyond k_stream_q8b's 64 rows)
+            q4x(qqkv, wqkv, 3);
             if ((rc = gemm_q8_group(ctx, p->h, d, 3, wqkv, sqkv, yqkv, nullptr, d, d, n, d, "gemm_q8_wqkv"))) return rc;
         } else if (mfma) {
             int rs = ST_NA;
@@ -2508,7 +2593,7 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
             hf_ready = wo_rs == 0;
         }
         if (wo_rs == 0) {
-        } else if (q8) { if ((rc = gemm_q8(ctx, L.wo, L.s_wo, p->attn, p->xb, x, d, d, n, d, d, "gemm_q8_wo"))) return rc; }
+        } else if (q8) { q4x(qo, &L.wo, 1); if ((rc = gemm_q8(ctx, L.wo, L.s_wo, p->attn, p->xb, x, d, d, n, d, d, "gemm_q8_wo"))) return rc; }
         else if ((rc = gemm_small_n_src(ctx, L.wo, p->attn, p->xb, x, d, d, n, d, d, "gemm_wo", true, src(ho)))) return rc;
         const float* w13[2] = {L.w1, L.w3};
         const float* s13[2] = {L.s_w1, L.s_w3};
@@ -2525,6 +2610,7 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
         if (!gated && !hf_ready) { TraceScope ts_(ctx->stream, "rmsnorm_rows_f"); LH_LAUNCH(k_rmsnorm_rows, dim3(n), dim3(256), 0, ctx->stream, (const float*)p->xb, L.ffn_norm, p->h, d); }
         if (gated) {
         } else if (q8) {
+            q4x(q13, w13, 2);
             if ((rc = gemm_q8_group(ctx, p->h, d, 2, w13, s13, y13, nullptr, F, d, n, F, "gemm_q8_w1w3"))) return rc;
         } else if (mfma) {
             StreamArgs fa = {};   // short prompts: silu(w1 h) * (w3 h) in the epilogue of (w1, w3) tile pairs
@@ -2559,7 +2645,7 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
             h_ready = w2_rs == 0 && next_gamma != nullptr;
         }
         if (w2_rs == 0) {
-        } else if (q8) { if ((rc = gemm_q8(ctx, L.w2, L.s_w2, p->g, y, p->xb, d, F, n, F, d, "gemm_q8_w2"))) return rc; }
+        } else if (q8) { q4x(q2, &L.w2, 1); if ((rc = gemm_q8(ctx, L.w2, L.s_w2, p->g, y, p->xb, d, F, n, F, d, "gemm_q8_w2"))) return rc; }
         else if ((rc = gemm_small_n_src(ctx, L.w2, p->g, y, p->xb, d, F, n, F, d, "gemm_w2", true, src(h2)))) return rc;
         x = p->xa;
         LH_HIP(ctx, hipGetLastError());

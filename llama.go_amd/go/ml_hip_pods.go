@@ -482,6 +482,21 @@ func (ctx *Context) SetF16StreamHIP(on bool) {
 }
 func (ctx *Context) F16StreamHIP() bool { return C.lh_ctx_f16_stream(ctx.hip.ctx) != 0 }
 
+// SetQ4Stream / SetQ4StreamHIP: lh_ctx_set_q4_stream on the lh_ctx the batch / the context evaluates in - the Evals of a block-int4 model over activation
+// planes (5..64 rows of a tick, 5..88 of a prompt) read the model's nibbles instead of an int8 image expanded in front of every layer (DESIGN 3l).  Same
+// bytes; off by default; without effect on models of another weight type.
+func (bt *BatchHIP) SetQ4Stream(on bool) { bt.ctx.SetQ4StreamHIP(on) }
+func (ctx *Context) SetQ4StreamHIP(on bool) {
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	if rc := C.lh_ctx_set_q4_stream(ctx.hip.ctx, v); rc != 0 {
+		hipHalt(ctx.hip.ctx)
+	}
+}
+func (ctx *Context) Q4StreamHIP() bool { return C.lh_ctx_q4_stream(ctx.hip.ctx) != 0 }
+
 // SetF16TilesHIP: lh_ctx_set_f16_tiles on the lh_ctx the context evaluates in - the Evals of more than 128 rows of an f16 model run their k_gemm_b9
 // launches on the model's halves (k_gemm_b9_h, six bf16 products instead of eight) instead of an fp32 image widened in front of every layer (DESIGN 3k).
 // Same bytes; off by default; without effect on models of another weight type; independent of SetF16StreamHIP.

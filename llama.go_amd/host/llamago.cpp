@@ -1923,6 +1923,16 @@ int llamago_SetF16Stream(llama_context* c, int on) {
     return lh_ctx_set_f16_stream(c->mlctx->hip, on);
 }
 int llamago_F16Stream(llama_context* c) { return c && c->mlctx ? lh_ctx_f16_stream(c->mlctx->hip) : 0; }
+int llamago_SetQ4Stream(llama_context* c, int on) {
+    if (!c || !c->mlctx || !c->mlctx->hip) return halt_rc("llamago_SetQ4Stream: bad arguments");
+    return lh_ctx_set_q4_stream(c->mlctx->hip, on);
+}
+int llamago_Q4Stream(llama_context* c) { return c && c->mlctx ? lh_ctx_q4_stream(c->mlctx->hip) : 0; }
+int llamago_BatchSetQ4Stream(llama_batch* b, int on) {
+    if (!b || !b->mlctx || !b->mlctx->hip) return halt_rc("llamago_BatchSetQ4Stream: bad arguments");
+    return lh_ctx_set_q4_stream(b->mlctx->hip, on);
+}
+int llamago_BatchQ4Stream(llama_batch* b) { return b && b->mlctx ? lh_ctx_q4_stream(b->mlctx->hip) : 0; }
 int llamago_SetF16Tiles(llama_context* c, int on) {
     if (!c || !c->mlctx || !c->mlctx->hip) return halt_rc("llamago_SetF16Tiles: bad arguments");
     return lh_ctx_set_f16_tiles(c->mlctx->hip, on);

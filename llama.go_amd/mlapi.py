@@ -417,6 +417,21 @@ class Context:
         L.llamago_F16Stream.argtypes = [VP]
         return bool(L.llamago_F16Stream(self.h))
 
+    def SetQ4Stream(self, on=True):
+        """llamago_SetQ4Stream: Evals of a block-int4 model over activation planes (5..88 rows) read the model's nibbles instead of an expanded int8 image."""
+        L = self.ml.lib
+        L.llamago_SetQ4Stream.restype = C.c_int
+        L.llamago_SetQ4Stream.argtypes = [VP, C.c_int]
+        if L.llamago_SetQ4Stream(self.h, 1 if on else 0):
+            raise MLError(f"llamago_SetQ4Stream: {self.ml.last_error()}")
+
+    @property
+    def q4_stream(self):
+        L = self.ml.lib
+        L.llamago_Q4Stream.restype = C.c_int
+        L.llamago_Q4Stream.argtypes = [VP]
+        return bool(L.llamago_Q4Stream(self.h))
+
     def SetF16Tiles(self, on=True):
         """llamago_SetF16Tiles: Evals of an f16 model beyond 128 rows run their k_gemm_b9 launches on the model's halves (k_gemm_b9_h) instead of a widened image."""
         L = self.ml.lib
@@ -1058,6 +1073,21 @@ class Batch:
         self.model, self.ml, self.pods = model, model.ml, pods
         self.h = self.ml._chk(self.ml.lib.llamago_NewBatch(model.h, ctxSize, pods), "llamago_NewBatch")
         self.batched = bool(self.ml.lib.llamago_BatchBatched(self.h))
+
+    def SetQ4Stream(self, on=True):
+        """llamago_BatchSetQ4Stream: Context.SetQ4Stream for the ticks, feeds and speculative passes of this batch."""
+        L = self.ml.lib
+        L.llamago_BatchSetQ4Stream.restype = C.c_int
+        L.llamago_BatchSetQ4Stream.argtypes = [VP, C.c_int]
+        if L.llamago_BatchSetQ4Stream(self.h, 1 if on else 0):
+            raise MLError(f"llamago_BatchSetQ4Stream: {self.ml.last_error()}")
+
+    @property
+    def q4_stream(self):
+        L = self.ml.lib
+        L.llamago_BatchQ4Stream.restype = C.c_int
+        L.llamago_BatchQ4Stream.argtypes = [VP]
+        return bool(L.llamago_BatchQ4Stream(self.h))
 
     def SetF16Stream(self, on=True):
         """llamago_BatchSetF16Stream: Context.SetF16Stream for the ticks, feeds and speculative passes of this batch."""
