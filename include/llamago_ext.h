@@ -58,6 +58,10 @@ int llamago_SetModelTensor(llama_model* m, const char* name, const float* data, 
  * (declared with the batch below). */
 int llamago_CacheRead(llama_context* c, int which, uint64_t off_floats, float* dst, uint64_t n);
 int llamago_CacheWrite(llama_context* c, int which, uint64_t off_floats, const float* src, uint64_t n);
+/* Test instrumentation: lh_ctx_poison_weight_images (llamahip.h) on the lh_ctx the context / the batch evaluates in - every fp32 image of f16 matrices and
+ * every int8 image of block-int4 ones filled with 0xFF bytes behind the work already enqueued.  Returns the bytes filled (0 for an f32 or block-int8 model,
+ * and before the first plan exists), -1 (ml_LastError) on a null argument or a HIP error.  llamago_BatchPoisonWeightImages is declared with the batch below. */
+int64_t llamago_PoisonWeightImages(llama_context* c);
 /* f16 weight matrices kept f16 in HBM (ML_TYPE_F16 = dtype 1 of llamahip.h; norm vectors and tok_embeddings stay f32).  Every Eval route of such a model
  * produces the bytes an f32 model holding the same values produces: one row and 2..8 rows on f16 forms of the decode stream kernels, every other row
  * count on the f32 kernels behind an exact widening pass.
@@ -210,6 +214,7 @@ int llamago_BatchQ4Stream(llama_batch* b);
 /* Test instrumentation: llamago_CacheRead / llamago_CacheWrite on the KV cache of pod `pod` (also fails on a pod outside the batch). */
 int llamago_BatchCacheRead(llama_batch* b, uint32_t pod, int which, uint64_t off_floats, float* dst, uint64_t n);
 int llamago_BatchCacheWrite(llama_batch* b, uint32_t pod, int which, uint64_t off_floats, const float* src, uint64_t n);
+int64_t llamago_BatchPoisonWeightImages(llama_batch* b);   /* llamago_PoisonWeightImages on the lh_ctx the batch evaluates in */
 /* Every pod: its prompt as one Eval, then n_predict - 1 greedy steps of ALL pods per weight pass.  out[i * n_predict + s] = s-th id
  * of pod i (= llama_GreedyDecode of that prompt alone); logits (optional): [pods][vocab] of the last tick. */
 int llamago_BatchGreedyDecode(llama_batch* b, const uint32_t* const* prompts, const uint32_t* n_prompt, uint32_t n_predict, uint32_t* out, float* logits);

@@ -138,6 +138,11 @@ int lh_ctx_q4_stream(lh_ctx* ctx);
 int64_t lh_stream_q4_image_off(uint32_t kc, uint32_t r, uint32_t g);
 int64_t lh_stream_q4_read_off(uint32_t kc, uint32_t t, uint32_t r16, uint32_t kb, uint32_t slot);
 void lh_stream_q4_operand(uint32_t nibbles, uint32_t out[4]);
+/* Test instrumentation.  The context owns one fp32 (f16 plans) or int8 (block-int4 plans) image of ONE layer's matrices and one of the output matrix per plan
+ * size; every route that reads an image fills the slots it reads in front of its own launches.  lh_ctx_poison_weight_images fills every such image with 0xFF
+ * bytes (NaN as fp32, quant -1 as int8), enqueued on the context's stream, and stores the bytes filled (0: the context has no f16 or block-int4 plan).  A
+ * launch that reads a slot its own call did not fill then computes from poison instead of from what the call before left there. */
+int lh_ctx_poison_weight_images(lh_ctx* ctx, uint64_t* bytes);
 /* Dequantised fp32 values of a dtype-7 buffer (w = fl32(d*q)), for checks. */
 int lh_buf_read_q8(lh_ctx* ctx, lh_buf buf, uint64_t off, float* dst, uint64_t n);
 int lh_buf_free(lh_ctx* ctx, lh_buf buf);

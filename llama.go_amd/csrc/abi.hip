@@ -305,6 +305,21 @@ int lh_ctx_set_q4_stream(lh_ctx* ctx, int on) {
     return LH_OK;
 }
 int lh_ctx_q4_stream(lh_ctx* ctx) { return ctx ? ctx->q4_stream : 0; }
+// Test instrumentation: every image of lh_ctx::wide filled with 0xFF bytes (NaN in an fp32 image, quant -1 in an int8 one), enqueued on the stream behind
+// whatever read the images last.  The byte count of an image is in its key (wide_image, plan.hip): elements << 4 | element bytes << 1 | kind.
+int lh_ctx_poison_weight_images(lh_ctx* ctx, uint64_t* bytes) {
+    if (!ctx || !bytes) return LH_EINVAL;
+    *bytes = 0;
+    if (ctx->wide.empty()) return LH_OK;
+    int rc = lh::select_device(ctx);
+    if (rc) LH_FAIL(ctx, rc, "lh_ctx_poison_weight_images: hipSetDevice failed");
+    for (const auto& w : ctx->wide) {
+        const uint64_t n = (w.first >> 4) * ((w.first >> 1) & 7);
+        LH_HIP(ctx, hipMemsetAsync(w.second, 0xFF, n, ctx->stream));
+        *bytes += n;
+    }
+    return LH_OK;
+}
 int64_t lh_stream_q4_image_off(uint32_t kc, uint32_t r, uint32_t g) {
     if ((kc != 128 && kc != 256 && kc != 512) || r >= 128 || g >= kc / 32) return -1;
     return (int64_t)lh::stream_q4_granule_off(kc, r, g);

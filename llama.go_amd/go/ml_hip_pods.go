@@ -511,6 +511,17 @@ func (ctx *Context) SetF16TilesHIP(on bool) {
 }
 func (ctx *Context) F16TilesHIP() bool { return C.lh_ctx_f16_tiles(ctx.hip.ctx) != 0 }
 
+// PoisonWeightImagesHIP / (*BatchHIP).PoisonWeightImages (test instrumentation): lh_ctx_poison_weight_images on the lh_ctx the context / the batch evaluates in - the fp32 / int8 images of f16 /
+// block-int4 matrices filled with 0xFF bytes behind the work already enqueued.  Returns the bytes filled (0: no such image exists).
+func (ctx *Context) PoisonWeightImagesHIP() uint64 {
+	var n C.uint64_t
+	if rc := C.lh_ctx_poison_weight_images(ctx.hip.ctx, &n); rc != 0 {
+		hipHalt(ctx.hip.ctx)
+	}
+	return uint64(n)
+}
+func (bt *BatchHIP) PoisonWeightImages() uint64 { return bt.ctx.PoisonWeightImagesHIP() }
+
 func (bt *BatchHIP) Release() { C.lh_batch_destroy(bt.b) }
 
 // NewPipelineHIP: `stages[i]` is this rank's stage of stream i (NewStageHIP over the rank's layer range: the stream's own KV

@@ -1918,6 +1918,14 @@ int llamago_BatchCacheWrite(llama_batch* p, uint32_t pod, int which, uint64_t of
     }
     return rc;
 }
+static int64_t poison_weight_images(const char* who, ml_context* mlctx) {
+    if (!mlctx || !mlctx->hip) { halt_rc((std::string(who) + ": bad arguments").c_str()); return -1; }
+    uint64_t bytes = 0;
+    if (lh_ctx_poison_weight_images(mlctx->hip, &bytes)) { halt_rc((std::string(who) + ": " + lh_last_error(mlctx->hip)).c_str()); return -1; }
+    return (int64_t)bytes;
+}
+int64_t llamago_PoisonWeightImages(llama_context* c) { return poison_weight_images("llamago_PoisonWeightImages", c ? c->mlctx : nullptr); }
+int64_t llamago_BatchPoisonWeightImages(llama_batch* b) { return poison_weight_images("llamago_BatchPoisonWeightImages", b ? b->mlctx : nullptr); }
 int llamago_SetF16Stream(llama_context* c, int on) {
     if (!c || !c->mlctx || !c->mlctx->hip) return halt_rc("llamago_SetF16Stream: bad arguments");
     return lh_ctx_set_f16_stream(c->mlctx->hip, on);

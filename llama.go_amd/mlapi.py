@@ -577,6 +577,17 @@ class Context:
         """llamago_CacheWrite (product only, test instrumentation): the floats `values` written at float offset `off` of the K / V cache."""
         _cache_write(self.ml, "llamago_CacheWrite", (self.h,), which, off, values)
 
+    def PoisonWeightImages(self):
+        """llamago_PoisonWeightImages (product only, test instrumentation): the fp32 / int8 images of f16 / block-int4 matrices on this context's lh_ctx
+        filled with 0xFF bytes (NaN / quant -1) behind the work already enqueued -> the bytes filled (0: no such image exists)."""
+        L = self.ml.lib
+        L.llamago_PoisonWeightImages.restype = C.c_int64
+        L.llamago_PoisonWeightImages.argtypes = [VP]
+        n = L.llamago_PoisonWeightImages(self.h)
+        if n < 0:
+            raise MLError(f"llamago_PoisonWeightImages: {self.ml.last_error()}")
+        return int(n)
+
     def free(self):
         if self.h:
             self.ml.lib.llama_ReleaseContext(self.h)
@@ -1275,6 +1286,16 @@ class Batch:
     def CacheWrite(self, pod, which, off, values):
         """llamago_BatchCacheWrite (test instrumentation): Context.CacheWrite on pod `pod`'s cache."""
         _cache_write(self.ml, "llamago_BatchCacheWrite", (self.h, int(pod)), which, off, values)
+
+    def PoisonWeightImages(self):
+        """llamago_BatchPoisonWeightImages (test instrumentation): Context.PoisonWeightImages on the lh_ctx the batch evaluates in."""
+        L = self.ml.lib
+        L.llamago_BatchPoisonWeightImages.restype = C.c_int64
+        L.llamago_BatchPoisonWeightImages.argtypes = [VP]
+        n = L.llamago_BatchPoisonWeightImages(self.h)
+        if n < 0:
+            raise MLError(f"llamago_BatchPoisonWeightImages: {self.ml.last_error()}")
+        return int(n)
 
     def free(self):
         if self.h:

@@ -1,4 +1,4 @@
-"""Session harness: scripts of calls on ONE long-lived object (a solo Context or a Batch), held to fresh twins across re-captures.
+"""Session harness: scripts of calls on ONE long-lived object (a solo Context, a Batch or a DraftPair), held to fresh twins across re-captures.
 
 Every other GPU test of the suite runs its call on a fresh object.  What they cannot see is a captured hipGraph that outlives something it holds: a
 re-allocated scratch buffer, the sampler variant of the previous call, a ring that moved.  Nothing faults then and no single call is wrong - the ids
@@ -14,6 +14,13 @@ row counts, which tests/test_gpu_llama.py::test_results_are_bitwise_reproducible
   trace        on the long-lived object only: "a launch replayed from a captured graph records nothing" (include/llamahip.h, lh_route_trace), so a step
                declared `replay` must record no entry of its captured part and one declared `capture` / `eager` must record some.  Without this a
                script could pass by never replaying anything.
+
+Two more things are done to the long-lived object alone.  The lh_ctx switches that choose a kernel (Step.env names that start with "lh:" - SWITCHES
+below) are set on it and never on the twins, like the environment switches: the twins are the unswitched runs, so every step also holds switch-on bytes to
+switch-off bytes.  And in front of EVERY step its context's weight images (the fp32 image of an f16 model's matrices, the int8 image of a block-int4
+model's: one layer and the output matrix, shared by every plan of a size) are filled with 0xFF bytes (llamago_PoisonWeightImages): a launch that reads an
+image slot which this call's own launches - or the replayed graph's own launches - did not fill computes from NaN / quant -1 and differs from both twins,
+whatever ran before and however many layers the model has.
 
 A step is `essential` (it changes what later results may depend on: cache rows below the final position, ring, draw counter, token history) or a
 `detour` (by the API's contract its effects are gone when the next essential step runs).  The module needs no GPU: a backend is anything with
@@ -47,12 +54,14 @@ class Step:
     equals: int = None              # index of an earlier step whose result this one must repeat byte for byte
     twin: "Step" = None             # what the eager twin runs instead (same result keys), e.g. one long run as two shorter ones
     note: str = ""
+    want: tuple = ()                # patterns of which each must match some entry of the long-lived object's route trace: the kernel family the step is there for
+    wantnot: tuple = ()             # ... of which none may match any (tests/test_gpu_session.py asserts both; the toy has no kernel families)
 
 
 @dataclass(frozen=True)
 class Script:
     name: str
-    kind: str                       # "solo" / "batch"
+    kind: str                       # "solo" / "batch" / "pair" (a DraftPair: steps name their side, "target.Eval", "draft.Decode", or the pair's own calls)
     shape: str                      # key of mlapi.SHAPES
     ctx: int
     steps: tuple
@@ -88,15 +97,19 @@ def classify(trace, pattern):
     return [e for e in trace if rx.search(e)]
 
 
-def run_script(script, backend, weights, report=None, trace_strict=True):
+ORACLES = ("trace", "eager", "fresh", "repeat")
+
+
+def run_script(script, backend, weights, report=None, trace_strict=True, ask=ORACLES):
     """Runs `script` on three objects of `backend` and raises SessionMismatch at the first step an oracle refuses.  report (a list) receives one
     line per step: index, call, role, the declared and the observed trace class - the evidence that each trigger fired and was replayed.
-    Returns the long-lived object's route trace of every step."""
+    ask: the oracles that may refuse, asked in the order of ORACLES (all of them, except where tests/test_session_cpu.py shows what ONE oracle says of a
+    mutant that an earlier one reports first; the twins run every step either way).  Returns the long-lived object's route trace of every step."""
     objs, traces = {}, []
     try:
-        objs["long"] = backend.open(script, weights, eager=False)
-        objs["eager"] = backend.open(script, weights, eager=True)
-        objs["fresh"] = backend.open(script, weights, eager=False)
+        objs["long"] = backend.open(script, weights, eager=False, role="long")
+        objs["eager"] = backend.open(script, weights, eager=True, role="eager")
+        objs["fresh"] = backend.open(script, weights, eager=False, role="fresh")
         results, switched = [], {}
         for i, st in enumerate(script.steps):
             where = f"script {script.name} [{weights}] step {i} ({st.call} {_brief(st.args)})"
@@ -121,25 +134,25 @@ def run_script(script, backend, weights, report=None, trace_strict=True):
             if st.trace in (EAGER, CAPTURE) and not entries:
                 bad = (f"{where}: oracle trace: declared {st.trace}, but the route trace holds no entry of the captured part "
                        f"(the whole call replayed: the trigger in front of it did not fire)")
-            if bad and trace_strict:
+            if bad and trace_strict and "trace" in ask:
                 raise SessionMismatch(bad)
             if bad and report is not None:
                 report.append("  TRACE MISMATCH " + bad)
             twin, twin_trace = objs["eager"].call(st.twin or st, traced=True)
-            if st.trace == REPLAY and not classify(twin_trace, st.graph_entries):
+            if "eager" in ask and st.trace == REPLAY and not classify(twin_trace, st.graph_entries):
                 raise SessionMismatch(f"{where}: oracle eager twin: the twin itself recorded no launch of the captured part - it replays a graph of its own "
                                       f"and would repeat a stale one byte for byte (was it created, and were its plans made, under LLAMAHIP_NO_GRAPH=1?)")
             d = first_difference(got, twin)
-            if d:
+            if d and "eager" in ask:
                 raise SessionMismatch(f"{where}: oracle eager twin: {d}")
             if st.role == ESSENTIAL:
                 fresh, _ = objs["fresh"].call(st, traced=False)
                 d = first_difference(got, fresh)
-                if d:
+                if d and "fresh" in ask:
                     raise SessionMismatch(f"{where}: oracle fresh twin: {d}")
             if st.equals is not None:
                 d = first_difference(got, results[st.equals])
-                if d:
+                if d and "repeat" in ask:
                     raise SessionMismatch(f"{where}: oracle repeat of step {st.equals}: {d}")
     finally:
         for o in objs.values():
@@ -212,26 +225,48 @@ class EnvPatch:
         self.saved = {}
 
 
+# the lh_ctx switches a Step.env entry may name ("1" on, None / "0" off) -> the setter of mlapi.Context / mlapi.Batch
+SWITCHES = {"lh:f16_stream": "SetF16Stream", "lh:q4_stream": "SetQ4Stream", "lh:f16_tiles": "SetF16Tiles"}
+WIDE = ("f16", "q4")   # the weight types whose plans read a context-owned image (Plan::md_wide)
+# the pairs of a "pair" script, by the target's weight type: (draft's weight type, draft's seed, the seed of ReplaceDraft's model).  The f16 draft has the
+# target's SHAPE and another seed: both plans then share one image on the pair's lh_ctx (wide_image keys by size), two models' matrices pass through it
+PAIRS = {"f32": ("q8", 4321, 777), "f16": ("f16", 4321, 777), "q4": ("f32", 4321, 777)}
+MODEL_SEED = 1234
+
+
 class ProductBackend:
-    """models(shape, weights) -> an mlapi.Model (kept by the caller); monkeypatch: pytest's, for the environment switches."""
+    """models(shape, weights, seed=MODEL_SEED) -> an mlapi.Model (kept by the caller); monkeypatch: pytest's, for the environment switches."""
 
     def __init__(self, models, monkeypatch):
         self.models, self.mp = models, monkeypatch
+        self.switches = {}
 
     def setenv(self, name, value):
-        if value is None:
+        if name in SWITCHES:
+            self.switches[name] = value == "1"
+        elif value is None:
             self.mp.delenv(name, raising=False)
         else:
             self.mp.setenv(name, value)
 
     def restore_env(self):
+        self.switches = {}
         self.mp.undo()
 
-    def open(self, script, weights, eager):
+    def open(self, script, weights, eager, role="long"):
         model = self.models(script.shape, weights)
-        make = (lambda: _SoloSession(model, script.ctx)) if script.kind == "solo" else (lambda: _BatchSession(model, script.ctx, script.pods))
+        wide = weights in WIDE
+        if script.kind == "pair":
+            dw, dseed, rseed = PAIRS[weights]
+            draft, repl = self.models(script.shape, dw, dseed), self.models(script.shape, dw, rseed)
+            wide = wide or dw in WIDE
+            make = lambda: _PairSession(model, draft, repl, script.ctx)   # noqa: E731
+        elif script.kind == "solo":
+            make = lambda: _SoloSession(model, script.ctx)   # noqa: E731
+        else:
+            make = lambda: _BatchSession(model, script.ctx, script.pods)   # noqa: E731
         obj = _under_no_graph(self.mp, eager, make)
-        obj.mp, obj.eager = self.mp, eager
+        obj.mp, obj.eager, obj.backend, obj.long, obj.wide = self.mp, eager, self, role == "long", wide
         return obj
 
 
@@ -247,28 +282,53 @@ def _under_no_graph(mp, eager, fn):
 
 
 class _Session:
-    mp, eager = None, False
+    mp, eager, backend, long, wide, has_plan = None, False, None, False, False, False
+
+    def _front(self):
+        """What only the long-lived object gets in front of a step: the lh_ctx switches as the script has them now (a setter that repeats the value changes
+        nothing), then the poison.  The images exist from the first plan on (wide_image in plan_create; a solo context and the contexts of a pair make their
+        plans lazily): from then on the fill must report bytes for an f16 / block-int4 context, and it must never report any for an fp32 / block-int8 one."""
+        if not self.long:
+            return
+        dev = self.device_object()
+        for name, setter in SWITCHES.items():
+            if hasattr(dev, setter):
+                getattr(dev, setter)(self.backend.switches.get(name, False))
+        n = dev.PoisonWeightImages()
+        if self.wide:
+            assert (n > 0) == self.has_plan, f"PoisonWeightImages filled {n} bytes on an f16 / block-int4 context {'with' if self.has_plan else 'without'} plans"
+        else:
+            assert n == 0, f"PoisonWeightImages filled {n} bytes on a context of fp32 / block-int8 plans"
 
     def call(self, st, traced):
         """Every call of the eager twin runs under LLAMAHIP_NO_GRAPH=1: plans, and the contexts a step opens, are made lazily inside calls."""
         from llama_go_amd.mlapi import route_trace
-        fn = getattr(self, st.call)
+        self._front()
+        side, _, name = st.call.rpartition(".")
+        fn = getattr(getattr(self, side) if side else self, name)
+        if name not in ("SetKeepCount", "CacheImage"):
+            self.has_plan = True
         if traced:
             return _under_no_graph(self.mp, self.eager, lambda: route_trace(lambda: fn(**st.args)))
         return _under_no_graph(self.mp, self.eager, lambda: fn(**st.args)), []
 
 
 class _SoloSession(_Session):
-    def __init__(self, model, ctx):
+    def __init__(self, model, ctx, context=None):
+        """context: a Context that belongs to someone else (a side of a DraftPair), not freed here."""
         self.model, self.ctx = model, ctx
-        self.c = model.NewContext(ctx)
+        self.c, self.owned = model.NewContext(ctx) if context is None else context, context is None
         self.others = {}
+
+    def device_object(self):
+        return self.c
 
     def close(self):
         for o in self.others.values():
             o.free()
         self.others = {}
-        self.c.free()
+        if self.owned:
+            self.c.free()
 
     # every method returns a dict of arrays: everything the call hands back
     def Eval(self, tokens, past):
@@ -341,6 +401,10 @@ class _BatchSession(_Session):
         self.model, self.ctx, self.pods = model, ctx, pods
         self.b = Batch(model, ctx, pods)
         self.sampling = False
+        self.has_plan = True   # (a batch makes its pods' plans when it is made)
+
+    def device_object(self):
+        return self.b
 
     def close(self):
         self.b.free()
@@ -425,3 +489,34 @@ class _BatchSession(_Session):
             return {"ids": _u32(ids)}
         finally:
             o.free()
+
+
+class _PairSession(_Session):
+    """A DraftPair: .target and .draft are solo sessions over the pair's two contexts (a step names its side: "target.Eval", "draft.Decode"); the pair's own
+    calls are DecodeDraft, ReplaceDraft and a CacheImage of both sides."""
+
+    def __init__(self, target_model, draft_model, replacement_model, ctx):
+        from llama_go_amd.mlapi import DraftPair
+        self.ctx, self.replacement = ctx, replacement_model
+        self.pair = DraftPair(target_model, draft_model, ctx)
+        self.target = _SoloSession(target_model, ctx, self.pair.target)
+        self.draft = _SoloSession(draft_model, ctx, self.pair.draft)
+
+    def device_object(self):
+        return self.pair.target   # (both sides evaluate in the pair's one lh_ctx: its switches, its images)
+
+    def close(self):
+        self.pair.free()
+
+    def DecodeDraft(self, first, past, n, draft_len):
+        ids, lg, st, tr = self.pair.DecodeDraft(first, past, n, draft_len, want_logits=True)
+        return {"ids": _u32(ids), "logits": lg, "stats": _stats(st), "passes": _pairs(tr)}
+
+    def ReplaceDraft(self):
+        """The draft context freed beside the target's live graphs, a fresh one over another model of the draft's shape and type in its place."""
+        self.draft = _SoloSession(self.replacement, self.ctx, self.pair.ReplaceDraft(self.replacement))
+        return {}
+
+    def CacheImage(self, pos, draft_pos):
+        t, d = self.target.CacheImage(pos), self.draft.CacheImage(draft_pos)
+        return {"k": t["k"], "v": t["v"], "draft_k": d["k"], "draft_v": d["v"]}

@@ -11,6 +11,18 @@ Mutants (ToyBackend(mutant=...)):
   detour_leaves_row    a Score at position P also overwrites cache row P - 1
   draw_not_restored    SampleDecode does not restart the draw counter
   twin_not_eager       (a mutant of the harness's footing, not of the product) the object opened as the eager twin captures graphs like any other
+  switch_not_in_key    the stream switch is no field of the lookup pass's key (and nothing clears its warm bits): a toggle replays the graph of the other value.  The bytes are
+                       equal by design - both values compute the same - so only the TRACE oracle can report it
+  warm_not_cleared     a switch change re-keys the tick but leaves its warm bit: the kernel the new value chooses has its first launch inside a capture, without the attribute
+                       an eager launch sets (Dev.lds), and the graph computes garbage
+  image_site_unfilled  under the stream switch the multi-row launch site reads its image slot without filling it: right bytes as long as an earlier call left the right
+                       matrix there (the toy WITHOUT poison passes), garbage once the image is poisoned between steps
+  draft_leaves_smp     a draft run does not reset Spec::smp: behind a sampled lookup run it samples
+  replace_frees_out    ReplaceDraft frees the TARGET's output list with the draft's and gives the plan a new one, dropping no graph: the resident graph writes into the freed list
+
+The device in miniature (Dev) is what one lh_ctx owns: the stream switch with its generation counter, the grow-only split-K buffer, the kernel attributes set by eager launches,
+and the weight image - one slot per launch site, filled by a call in front of its read (with the matrix of the plan's model: the two plans of a pair share the slots) and
+poisoned in front of every step of the long-lived object.
 """
 import numpy as np
 
@@ -53,6 +65,48 @@ class Buf:
         self.freed = True
 
 
+IMAGE_SITES = ("rows",)   # the multi-row launch sites that read the image (Plan.eval of >= 2 rows, a feed pass, a pods x R pass)
+
+
+class Dev:
+    """What an lh_ctx owns (see the module's docstring).  own: the Step.env name of the stream switch of the plans' weight type, or None (fp32, block-int8: key 0)."""
+
+    def __init__(self, be, weights, poison):
+        self.be, self.poison = be, poison
+        self.own = {"f16": "lh:f16_stream", "q4": "lh:q4_stream"}.get(weights)
+        self.sw, self.gen = False, 0
+        self.image, self.lds = {}, set()
+        self.splitk_cap, self.splitk_gen = 0, 0
+
+    def begin_call(self):
+        """lh_ctx_set_*_stream as the harness has it now (a change counts), then the poison"""
+        v = self.own is not None and self.be.env.get(self.own) == "1"
+        if v != self.sw:
+            self.sw, self.gen = v, self.gen + 1
+        if self.poison:
+            self.image.clear()
+
+    def stream_key(self):
+        return (self.gen << 1) | int(self.sw) if self.own else 0
+
+    def variant(self):
+        return "h" if self.sw else "w"
+
+    def ensure_splitk(self, n):
+        if n > self.splitk_cap:
+            self.splitk_cap, self.splitk_gen = n, self.splitk_gen + 1
+
+    def weights(self, site, model):
+        """The launch site's matrix: 0 when it reads the right one, garbage otherwise.  Under the switch the site reads the model's own halves / nibbles; without it the
+        call fills the slot in front of the read."""
+        if self.sw:
+            if self.be.mutant != "image_site_unfilled":
+                return 0
+        else:
+            self.image[site] = model
+        return 0 if self.image.get(site) == model else mix(POISON, 5)
+
+
 class Cache:
     def __init__(self, ctx):
         self.ctx, self.rows, self.hist = ctx, [0] * ctx, [None] * ctx
@@ -71,8 +125,8 @@ class Plan:
     """One plan over a cache: scratch for n_cap rows, the decode graphs, the sampler and lookup state of the resident calls."""
     STEP, ADV1, ADVN, SMP1, SMPN = range(5)
 
-    def __init__(self, be, cache, eager, trace):
-        self.be, self.cache, self.use_graph, self.trace = be, cache, not eager, trace
+    def __init__(self, be, cache, eager, trace, dev, model="M"):
+        self.be, self.cache, self.use_graph, self.trace, self.dev, self.model = be, cache, not eager, trace, dev, model
         self.n_cap, self.scratch, self.scratch_gen = 0, None, 0
         self.graphs = {}
         self.sp = {"token": 0, "past": 0, "step": 0}
@@ -80,7 +134,7 @@ class Plan:
         self.ring, self.ring_cap, self.smp_topk = None, 0, 0
         self.ss = {"topK": 0, "seed": 0, "draw": 0, "ring_size": 1, "ring_pos": 0}
         self.score_cap, self.keep = 0, 0
-        self.spec_warm, self.spec_graph, self.spec_corpus = set(), None, None
+        self.spec_warm, self.spec_graph, self.spec_corpus, self.spec_seen, self.spec_smp = set(), None, None, 0, False
         self.ensure_rows(1)
 
     def drop(self, slots):
@@ -107,10 +161,10 @@ class Plan:
         self.drop([Plan.ADV1] if self.be.mutant == "partial_invalidation" else [Plan.ADV1, Plan.ADVN, Plan.SMP1, Plan.SMPN])
 
     # ---- kernels: they work on the buffers they are handed, which a graph fixes at capture ----
-    def k_rows(self, scratch, tokens, past):
+    def k_rows(self, scratch, tokens, past, w=0):
         for i, t in enumerate(tokens):
             self.cache.write(past + i, t)
-            scratch.w(i, self.cache.chain(past + i))
+            scratch.w(i, self.cache.chain(past + i) ^ w)
 
     def k_decode(self, scratch, out, ring, variant, adv):
         sp = self.sp
@@ -161,8 +215,10 @@ class Plan:
             self.launch(Plan.STEP, 1, 0)
             return
         self.ensure_rows(n)
+        if n >= 89:
+            self.dev.ensure_splitk(n)   # (the tile GEMMs' split-K buffer / planes, the context's: grow-only)
         self.trace.append(f"k_attention/hd64/n{n}")
-        self.k_rows(self.scratch, tokens, past)
+        self.k_rows(self.scratch, tokens, past, self.dev.weights("rows", self.model) if n >= 2 else 0)
 
     def resident(self, first, past, n, sampled, step0):
         """resident_steps_swapping: the steps, with the reference's context swap whenever the window is full."""
@@ -200,7 +256,12 @@ class Plan:
     # ---- lookup-draft passes (spec_pass): eager the first time at a row count, then a graph behind a staleness key ----
     def spec_pass(self, R, lp, smp, out_off, left):
         corpus = self.spec_corpus
-        key = (R, lp, id(corpus), id(self.out), out_off, self.scratch_gen, smp, smp and self.smp_topk <= 64, id(self.ring) if smp else 0)
+        keyed = self.be.mutant != "switch_not_in_key"
+        now = self.dev.stream_key() if keyed else 0
+        key = (R, lp, id(corpus), id(self.out), out_off, self.scratch_gen, self.dev.splitk_gen, smp, smp and self.smp_topk <= 64, id(self.ring) if smp else 0, now)
+        if self.spec_seen != now:   # f16_stream_sync: the kernels the new value chooses have their first launch in an eager pass
+            self.spec_warm.clear()
+            self.spec_seen = now
         bufs = (self.scratch, self.out, self.ring, self.variant())
         if not self.use_graph or R not in self.spec_warm:
             self.spec_warm.add(R)
@@ -214,15 +275,18 @@ class Plan:
             bufs = self.spec_graph[1]
         return self.k_spec(*bufs, R, smp, out_off, left)
 
-    def k_spec(self, scratch, out, ring, variant, R, smp, out_off, left):
-        """One pass: the pending token and the accepted part of a draft of R - 1, one id each; the rejected rows stay behind in the cache above the position."""
+    def k_spec(self, scratch, out, ring, variant, R, smp, out_off, left, draft=None):
+        """One pass: the pending token and the accepted part of a draft of R - 1, one id each; the rejected rows stay behind in the cache above the position.
+        draft: the cache of a draft model, whose state decides how much is accepted and which follows the accepted tokens."""
         sp = self.sp
-        m = min(1 + mix(self.cache.chain(max(sp["past"] - 1, 0)), R) % R, left)
+        m = min(1 + mix(self.cache.chain(max(sp["past"] - 1, 0)), R, *([draft.chain(max(sp["past"] - 1, 0))] if draft else [])) % R, left)
         for i in range(m):
             self.cache.write(sp["past"], sp["token"])
             scratch.w(i, self.cache.chain(sp["past"]))
             tok = sample(scratch.r(i), self.ss, ring, 0, variant) if smp else greedy(scratch.r(i))
             out.w(out_off + sp["step"], tok)
+            if draft:
+                draft.write(sp["past"], sp["token"])
             sp["token"], sp["past"], sp["step"] = tok, sp["past"] + 1, sp["step"] + 1
         for i in range(m, R):
             if sp["past"] + i - m < self.cache.ctx:
@@ -236,6 +300,7 @@ class Plan:
         if corpus is not None and (self.spec_corpus is None or len(corpus) > len(self.spec_corpus.d)):
             self.spec_corpus = Buf(len(corpus))
         self.sp.update(token=first, past=past, step=0)
+        self.spec_smp = smp
         passes = []
         while self.sp["step"] < n:
             m = self.spec_pass(R, (draft_max, ngram_max, ngram_min, len(corpus or ())), smp, out_off, n - self.sp["step"])
@@ -265,14 +330,15 @@ def _u64(x):
 class ToySolo:
     """A context: one cache, the plan llama_Eval runs on and the plan of the resident calls."""
 
-    def __init__(self, be, ctx, eager):
-        self.be, self.ctx, self.eager, self.trace = be, ctx, eager, []
+    def __init__(self, be, ctx, eager, dev, model="M", trace=None):
+        self.be, self.ctx, self.eager, self.dev, self.trace = be, ctx, eager, dev, [] if trace is None else trace
         self.cache = Cache(ctx)
-        self.ml, self.res = Plan(be, self.cache, eager, self.trace), Plan(be, self.cache, eager, self.trace)
+        self.ml, self.res = Plan(be, self.cache, eager, self.trace, dev, model), Plan(be, self.cache, eager, self.trace, dev, model)
         self.other, self.embedding = None, False
 
     def call(self, st, traced):
         del self.trace[:]
+        self.dev.begin_call()
         return getattr(self, st.call)(**st.args), list(self.trace)
 
     def close(self):
@@ -357,7 +423,7 @@ class ToySolo:
         return {"k": _u64(self.cache.rows[:pos]), "v": _u64([r ^ 1 for r in self.cache.rows[:pos]])}
 
     def OpenOther(self, ctx, tokens, past):
-        self.other = ToySolo(self.be, ctx, self.eager)
+        self.other = ToySolo(self.be, ctx, self.eager, Dev(self.be, None, False))
         return self.other.Eval(tokens, past)
 
     def CloseOther(self):
@@ -369,21 +435,22 @@ class ToyBatch:
     """`pods` caches with a plan each; the ticks run on pod 0's plan.  batch_tick_unchecked's warm flag, graph and staleness key; the feed schedule's
     passes; the sharing groups of lh_batch_fork; the pods x R lookup passes."""
 
-    def __init__(self, be, ctx, pods, eager):
-        self.be, self.ctx, self.B, self.trace = be, ctx, pods, []
+    def __init__(self, be, ctx, pods, eager, dev):
+        self.be, self.ctx, self.B, self.dev, self.trace = be, ctx, pods, dev, []
         self.use_graph = not eager
         self.caches = [Cache(ctx) for _ in range(pods)]
-        self.plans = [Plan(be, c, eager, self.trace) for c in self.caches]
+        self.plans = [Plan(be, c, eager, self.trace, dev) for c in self.caches]
         self.plans[0].ensure_rows(pods)
         self.pos, self.tok = [0] * pods, [0] * pods
         self.sampling, self.ss, self.ring, self.ring_cap, self.ring_size, self.smp_topk = False, [None] * pods, None, 0, 0, 0
-        self.warm, self.graph_ = False, None
-        self.splitk_cap, self.splitk_gen, self.feed_cap = 0, 0, 0
+        self.warm, self.graph_, self.seen = False, None, 0
+        self.feed_cap = 0
         self.gid, self.glen, self.next_gid, self.sent = [None] * pods, [0] * pods, 0, None
-        self.spec_warm, self.spec_graph = set(), None
+        self.spec_warm, self.spec_graph, self.spec_seen = set(), None, 0
 
     def call(self, st, traced):
         del self.trace[:]
+        self.dev.begin_call()
         return getattr(self, st.call)(**st.args), list(self.trace)
 
     def close(self):
@@ -393,8 +460,7 @@ class ToyBatch:
         return sum(p.scratch_gen for p in self.plans)
 
     def ensure_splitk(self, n):
-        if n > self.splitk_cap:
-            self.splitk_cap, self.splitk_gen = n, self.splitk_gen + 1
+        self.dev.ensure_splitk(n)
 
     # ---- sharing groups ----
     def leave(self, pod):
@@ -426,10 +492,10 @@ class ToyBatch:
         return self.share_info()
 
     # ---- ticks ----
-    def k_tick(self, scratch, ring, variant, sampling):
+    def k_tick(self, scratch, ring, variant, sampling, broken=0):
         for i in range(self.B):
             self.caches[i].write(self.pos[i], self.tok[i])
-            scratch.w(i, self.caches[i].chain(self.pos[i]))
+            scratch.w(i, self.caches[i].chain(self.pos[i]) ^ broken)
             c = scratch.r(i)
             self.tok[i] = sample(c, self.ss[i], ring, i * self.ring_cap, variant) if sampling else greedy(c)
 
@@ -445,18 +511,25 @@ class ToyBatch:
                 self.trace.append("share_table/b1")
                 self.sent = table
             shared = bool(table) and any(g is not None for g in self.gid)
-            key = (self.splitk_gen, self.scratch_gen(), self.sampling, env.get("LLAMAHIP_SAMPLE_PER_POD") == "1", shared,
-                   int(env.get("LLAMAHIP_SHARE_QB", 4)) if shared else 0)
-            bufs = (self.plans[0].scratch, self.ring, "small" if self.smp_topk <= 64 else "large", self.sampling)
+            now = self.dev.stream_key()
+            key = (self.dev.splitk_gen, self.scratch_gen(), self.sampling, env.get("LLAMAHIP_SAMPLE_PER_POD") == "1", shared,
+                   int(env.get("LLAMAHIP_SHARE_QB", 4)) if shared else 0, now)
+            if self.seen != now:   # f16_stream_sync
+                self.seen = now
+                if self.be.mutant != "warm_not_cleared":
+                    self.warm = False
+            bufs = (self.plans[0].scratch, self.ring, "small" if self.smp_topk <= 64 else "large", self.sampling, 0)
             if not self.use_graph or not self.warm:
                 self.warm = True
+                self.dev.lds.add(self.dev.variant())   # an eager launch sets the kernel's attribute
                 self.trace.append(f"k_attention/rows/hd64/n{self.B}")
             else:
                 if self.graph_ and self.graph_[0] != key:
                     self.graph_ = None
                 if not self.graph_:
                     self.trace.append(f"k_attention/rows/hd64/n{self.B}")
-                    self.graph_ = (key, bufs)
+                    # a kernel whose first launch stands inside a capture runs without its attribute: the graph computes garbage
+                    self.graph_ = (key, bufs[:4] + (0 if self.dev.variant() in self.dev.lds else POISON,))
                 bufs = self.graph_[1]
             self.k_tick(*bufs)
             self.pos = [p + 1 for p in self.pos]
@@ -487,7 +560,7 @@ class ToyBatch:
             self.plans[0].ensure_rows(FEED_PASS_ROWS)
             self.feed_cap = max(self.feed_cap, len(rows))
         last = np.zeros((self.B, 8), dtype=np.uint64)
-        ids = [0xFFFFFFFF] * self.B
+        ids, wimg = [0xFFFFFFFF] * self.B, 0
         for i, t in enumerate(tokens):
             if len(t) >= FEED_SOLO_MIN:
                 self.trace.append(f"feed_pass/solo/n{len(t)}")
@@ -498,6 +571,7 @@ class ToyBatch:
             chunk = rows[k:k + FEED_PASS_ROWS]
             self.trace.append(f"feed_pass/batched/n{len(chunk)}")
             self.trace.append(f"k_attention_seg/hd64/qb4/n{len(chunk)}")
+            wimg = self.dev.weights("rows", "M")   # (a feed pass reads the image, or the halves under the switch)
             if len(chunk) > 16:
                 self.ensure_splitk(len(chunk))
             for i, j in chunk:
@@ -505,7 +579,7 @@ class ToyBatch:
                 self.caches[i].write(past[i] + j, tokens[i][j])
         for i, t in enumerate(tokens):
             if t:
-                c = self.caches[i].chain(past[i] + len(t) - 1)
+                c = self.caches[i].chain(past[i] + len(t) - 1) ^ (wimg if len(t) < FEED_SOLO_MIN else 0)
                 self.tok[i], self.pos[i], ids[i], last[i] = greedy(c), past[i] + len(t), greedy(c), logits(c)
         return {"ids": _u32(ids), "last": last}
 
@@ -545,8 +619,13 @@ class ToyBatch:
             self.written(i, past[i])
         ids, passes = [[] for _ in range(self.B)], [[] for _ in range(self.B)]
         while any(len(x) < n for x in ids):
-            key = (R, (draft_max, ngram_max, ngram_min), self.splitk_gen, self.scratch_gen(), smp,
-                   (self.smp_topk <= 64, id(self.ring), self.ring_cap) if smp else ())
+            now = self.dev.stream_key()
+            key = (R, (draft_max, ngram_max, ngram_min), self.dev.splitk_gen, self.scratch_gen(), smp,
+                   (self.smp_topk <= 64, id(self.ring), self.ring_cap) if smp else (), now)
+            if self.spec_seen != now:   # f16_stream_sync
+                self.spec_warm.clear()
+                self.spec_seen = now
+            wimg = self.dev.weights("rows", "M")   # (a pass of pods x R rows reads the image or the halves; a replayed graph holds its own fills)
             bufs = (p0.scratch, self.ring, "small" if self.smp_topk <= 64 else "large")
             if not self.use_graph or self.B * R not in self.spec_warm:
                 self.spec_warm.add(self.B * R)
@@ -566,7 +645,7 @@ class ToyBatch:
                 m = min(1 + mix(self.caches[i].chain(max(self.pos[i] - 1, 0)), R) % R, left)
                 for r in range(m):
                     self.caches[i].write(self.pos[i], self.tok[i])
-                    scratch.w(i * R + r, self.caches[i].chain(self.pos[i]))
+                    scratch.w(i * R + r, self.caches[i].chain(self.pos[i]) ^ wimg)
                     c = scratch.r(i * R + r)
                     self.tok[i] = sample(c, self.ss[i], ring, i * self.ring_cap, variant) if smp else greedy(c)
                     ids[i].append(self.tok[i])
@@ -593,14 +672,67 @@ class ToyBatch:
         return {"k": _u64(rows), "v": _u64([r ^ 1 for r in rows])}
 
     def OtherBatch(self, pods, prompts, ticks):
-        o = ToyBatch(self.be, self.ctx, pods, not self.use_graph)
+        o = ToyBatch(self.be, self.ctx, pods, not self.use_graph, Dev(self.be, None, False))
         ids = [list(o.Prompt(prompts)["ids"])] + [list(o.Tick()["ids"]) for _ in range(ticks)]
         return {"ids": _u32(ids)}
 
 
+class ToyPair:
+    """A draft pair: two contexts (a cache and two plans each) on ONE device - its switch, its split-K buffer, its image, whose slots both models' matrices pass through -
+    and the draft runs, which work on the TARGET's speculative state and run the draft's steps eagerly (spec_decode_draft)."""
+
+    def __init__(self, be, ctx, eager, dev):
+        self.be, self.ctx, self.eager, self.dev, self.trace = be, ctx, eager, dev, []
+        self.target = ToySolo(be, ctx, eager, dev, "T", self.trace)
+        self.draft = ToySolo(be, ctx, eager, dev, "D", self.trace)
+        self.replaced = 0
+
+    def call(self, st, traced):
+        del self.trace[:]
+        self.dev.begin_call()
+        side, _, name = st.call.rpartition(".")
+        return getattr(getattr(self, side) if side else self, name)(**st.args), list(self.trace)
+
+    def close(self):
+        pass
+
+    def DecodeDraft(self, first, past, n, draft_len):
+        p, d, R = self.target.res, self.draft.res, draft_len + 1
+        p.ensure_rows(R)
+        p.ensure_out(n)
+        d.ensure_out(8)
+        if self.be.mutant != "draft_leaves_smp":
+            p.spec_smp = False
+        p.sp.update(token=first, past=past, step=0)
+        passes = []
+        while p.sp["step"] < n:   # (no captured pass: the draft's steps stand between the target's passes, all of it eager)
+            self.trace.append(f"k_attention/rows/hd64/n{R}")
+            m = p.k_spec(p.scratch, p.out, p.ring, p.variant(), R, p.spec_smp, 0, n - p.sp["step"], self.draft.cache)
+            passes.append((R - 1, m - 1))
+        ids = [p.out.r(i) for i in range(n)]
+        st = [len(passes), R, sum(x[0] for x in passes), sum(x[1] for x in passes), 0]
+        return {"ids": _u32(ids), "logits": logits(self.target.cache.chain(past + n - 1)), "stats": _u32([st]), "passes": _u32(passes).reshape(-1, 2)}
+
+    def ReplaceDraft(self):
+        for pl in (self.draft.ml, self.draft.res):
+            for b in (pl.scratch, pl.out, pl.ring):
+                if b:
+                    b.free()
+        if self.be.mutant == "replace_frees_out" and self.target.res.out:
+            self.target.res.out.free()
+            self.target.res.out = Buf(self.target.res.out_cap)
+        self.replaced += 1
+        self.draft = ToySolo(self.be, self.ctx, self.eager, self.dev, f"D{self.replaced}", self.trace)
+        return {}
+
+    def CacheImage(self, pos, draft_pos):
+        t, d = self.target.CacheImage(pos), self.draft.CacheImage(draft_pos)
+        return {"k": t["k"], "v": t["v"], "draft_k": d["k"], "draft_v": d["v"]}
+
+
 class ToyBackend:
-    def __init__(self, mutant=None):
-        self.mutant, self.env = mutant, {}
+    def __init__(self, mutant=None, poison=True):
+        self.mutant, self.env, self.poison = mutant, {}, poison
 
     def setenv(self, name, value):
         if value is None:
@@ -611,6 +743,9 @@ class ToyBackend:
     def restore_env(self):
         self.env.clear()
 
-    def open(self, script, weights, eager):
+    def open(self, script, weights, eager, role="long"):
         eager = eager and self.mutant != "twin_not_eager"
-        return ToySolo(self, script.ctx, eager) if script.kind == "solo" else ToyBatch(self, script.ctx, script.pods, eager)
+        dev = Dev(self, weights, self.poison and role == "long")   # (the image is poisoned in front of the long-lived object's steps only)
+        if script.kind == "pair":
+            return ToyPair(self, script.ctx, eager, dev)
+        return ToySolo(self, script.ctx, eager, dev) if script.kind == "solo" else ToyBatch(self, script.ctx, script.pods, eager, dev)

@@ -59,6 +59,9 @@ def twins(product, hp, seed=77, prepare=None):
     return out
 
 
+poisoned = WP.poisoned
+
+
 def seeded_cache(ctxs, hp, layers, ctx):
     """the same seeded finite values in the K and V caches of every context: rows below `past` that no Eval of the test wrote"""
     rng = np.random.default_rng(5)
@@ -197,7 +200,7 @@ def test_step_and_rows_are_byte_equal_to_the_widened_model(product, shape):
         for past in (0, 37):
             for n in (1, 2, 3, 4, 5, 8):
                 toks = [int(t) for t in rng.integers(0, hp.vocabSize, n)]
-                la, tr = route_trace(lambda: ca.Eval(toks, past))
+                la, tr = route_trace(lambda: poisoned(ca).Eval(toks, past))
                 assert fused(product, ca) == 1
                 lb = cb.Eval(toks, past)
                 assert np.isfinite(lb).all() and np.abs(lb).max() > 0
@@ -230,7 +233,7 @@ def test_subnormal_output_weights_reach_the_logits(product):
     ca, cb = A.NewContext(STEP_CTX, 1), B.NewContext(STEP_CTX, 1)
     try:
         for toks in ([7], [3, 99, 1024, 5]):
-            la, lb = ca.Eval(toks, 0), cb.Eval(toks, 0)
+            la, lb = poisoned(ca).Eval(toks, 0), cb.Eval(toks, 0)
             assert same(la, lb)
             assert np.count_nonzero(la) > V // 2          # a conversion that flushed subnormals would leave (mostly) zeros
     finally:
@@ -248,7 +251,7 @@ def test_widened_route_runs_the_fp32_schedule_byte_equal(product):
     try:
         for n, past in ((9, 0), (17, 0), (64, 0), (130, 0), (9, 37), (17, 37), (64, 37), (130, 37), (9, 0)):   # (9 again behind 130: the image does not move)
             toks = [int(t) for t in rng.integers(0, hp.vocabSize, n)]
-            la, ta = route_trace(lambda: ca.Eval(toks, past))
+            la, ta = route_trace(lambda: poisoned(ca).Eval(toks, past))
             assert fused(product, ca) == 1
             lb, tb = route_trace(lambda: cb.Eval(toks, past))
             assert same(la, lb), (n, past, float(np.abs(la - lb).max()))
@@ -325,7 +328,7 @@ def test_batch_ticks(small_twins, pods):
         b = Batch(m, 64, pods)
         try:
             assert b.batched, "these shapes must take the one-pass route"
-            res.append(b.GreedyDecode(prompts, 6, want_logits=True))
+            res.append(poisoned(b, m is A).GreedyDecode(prompts, 6, want_logits=True))
         finally:
             b.free()
     (ia, la), (ib, lb) = res
@@ -346,7 +349,7 @@ def test_batch_feed(small_twins):
     for m in (A, B):
         b = Batch(m, 64, 3)
         try:
-            res.append(b.Feed(toks, [0, 0, 0], want_logits=True, want_rows=True))
+            res.append(poisoned(b, m is A).Feed(toks, [0, 0, 0], want_logits=True, want_rows=True))
         finally:
             b.free()
     (ia, la, ra), (ib, lb, rb) = res

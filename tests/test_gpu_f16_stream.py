@@ -14,7 +14,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import weight_probe_ref as WP         # noqa: E402
-from test_gpu_f16 import families, same, seeded_cache, twins   # noqa: E402
+from test_gpu_f16 import families, poisoned, same, seeded_cache, twins   # noqa: E402
 from llama_go_amd.mlapi import SHAPES, Batch, make_hparams, route_trace   # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -89,7 +89,7 @@ def test_solo_evals_are_byte_equal_and_take_the_twins_kernels(big, n):
         if past + n > BIG_CTX:
             continue
         toks = [int(t) for t in rng.integers(0, hp.vocabSize, n)]
-        la, ta = route_trace(lambda: ca.Eval(toks, past))
+        la, ta = route_trace(lambda: poisoned(ca).Eval(toks, past))
         lb, tb = route_trace(lambda: cb.Eval(toks, past))
         assert np.isfinite(lb).all() and np.abs(lb).max() > 0
         assert same(la, lb), (n, past, float(np.abs(la - lb).max()))
@@ -113,7 +113,7 @@ def test_switch_off_is_the_widened_route(big):
     toks = [int(t) for t in np.random.default_rng(7).integers(0, hp.vocabSize, 17)]
     ca.SetF16Stream(False)
     try:
-        la, ta = route_trace(lambda: ca.Eval(toks, 0))
+        la, ta = route_trace(lambda: poisoned(ca).Eval(toks, 0))
     finally:
         ca.SetF16Stream(True)
     lb, tb = route_trace(lambda: cb.Eval(toks, 0))
@@ -139,7 +139,7 @@ def test_small_shapes_and_mixed_layers(product, shape, layers):
             for past in (0, 11):
                 toks = [int(t) for t in rng.integers(0, hp.vocabSize, n)]
                 lb, tb = route_trace(lambda: cb.Eval(toks, past))
-                la, ta = route_trace(lambda: ca.Eval(toks, past))
+                la, ta = route_trace(lambda: poisoned(ca).Eval(toks, past))
                 assert same(la, lb), (shape, n, past, float(np.abs(la - lb).max()))
                 for ra, rb in zip(cache_rows(ca, hp, layers, ctx, past, n), cache_rows(cb, hp, layers, ctx, past, n)):
                     assert same(ra, rb), (shape, n, past)
@@ -201,7 +201,7 @@ def test_subnormals_zeros_and_the_largest_halves(product):
     try:
         for n in (9, 17):                                                    # conversion in the loader waves (k_stream_mm2_h) / in the MFMA waves (k_stream_dma_h)
             toks = [int(t) for t in rng.integers(0, hp.vocabSize, n)]
-            la, ta = route_trace(lambda: ca.Eval(toks, 0))
+            la, ta = route_trace(lambda: poisoned(ca).Eval(toks, 0))
             lb, lc = cb.Eval(toks, 0), cc.Eval(toks, 0)
             assert H_KERNELS[0 if n == 9 else 1] in families(ta), ta
             assert np.isfinite(lb).all()
@@ -233,7 +233,7 @@ def test_batch_ticks(small_twins, pods):
             if m is A:
                 b.SetF16Stream(True)
                 assert b.f16_stream is True
-            (ids, lg), tr = route_trace(lambda: b.GreedyDecode(prompts, 5, want_logits=True))   # four ticks: eager, captured, replayed twice
+            (ids, lg), tr = route_trace(lambda: poisoned(b, m is A).GreedyDecode(prompts, 5, want_logits=True))   # four ticks: eager, captured, replayed twice
             res.append((ids, lg, tr))
         finally:
             b.free()
@@ -254,8 +254,8 @@ def test_batch_feed(small_twins):
         try:
             if m is A:
                 b.SetF16Stream(True)
-            first, t1 = route_trace(lambda: b.Feed(toks, [0, 0, 0], want_logits=True, want_rows=True))      # 15 rows in one pass
-            second, t2 = route_trace(lambda: b.Feed(more, [5, 5, 5], want_logits=True, want_rows=True))     # 12 rows at past > 0
+            first, t1 = route_trace(lambda: poisoned(b, m is A).Feed(toks, [0, 0, 0], want_logits=True, want_rows=True))      # 15 rows in one pass
+            second, t2 = route_trace(lambda: poisoned(b, m is A).Feed(more, [5, 5, 5], want_logits=True, want_rows=True))     # 12 rows at past > 0
             res.append((first, second, t1 + t2))
         finally:
             b.free()
@@ -272,13 +272,13 @@ def test_toggle_between_ticks_captures_anew(small_twins):
     prompts = [[int(t) for t in rng.integers(0, hp.vocabSize, 3)] for _ in range(pods)]
     ba, bb = Batch(A, 64, pods), Batch(B, 64, pods)
     try:
-        first = ba.Prompt(prompts)
+        first = poisoned(ba).Prompt(prompts)
         assert first == bb.Prompt(prompts)
         past = [3] * pods
         for seg, on in enumerate((False, True, False, False)):
             ba.SetF16Stream(on)
             assert ba.f16_stream is on
-            (ia, la), ta = route_trace(lambda: ba.Decode(first, past, 3, want_logits=True))
+            (ia, la), ta = route_trace(lambda: poisoned(ba).Decode(first, past, 3, want_logits=True))
             ib, lb = bb.Decode(first, past, 3, want_logits=True)
             assert ia == ib and same(la, lb), seg
             fa = families(ta)

@@ -15,7 +15,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import weight_probe_ref as WP         # noqa: E402
-from test_gpu_f16 import families, same, seeded_cache, twins   # noqa: E402
+from test_gpu_f16 import families, poisoned, same, seeded_cache, twins   # noqa: E402
 from test_gpu_f16_stream import widen_runs   # noqa: E402
 from llama_go_amd.mlapi import make_hparams, route_trace   # noqa: E402
 
@@ -69,7 +69,7 @@ def cache_rows(c, hp, layers, ctx, past, n):
 
 
 def eval_pair(ca, cb, hp, layers, ctx, toks, past):
-    la, ta = route_trace(lambda: ca.Eval(toks, past))
+    la, ta = route_trace(lambda: poisoned(ca).Eval(toks, past))
     lb, tb = route_trace(lambda: cb.Eval(toks, past))
     n = len(toks)
     assert np.isfinite(lb).all() and np.abs(lb).max() > 0
@@ -194,7 +194,7 @@ def test_both_switches_and_toggles(big):
 def test_score_over_193_tokens(big):
     hp, ca, cb = big
     toks = [int(t) for t in np.random.default_rng(60).integers(0, hp.vocabSize, 193)]
-    sa, ta = route_trace(lambda: ca.Score(toks, 0))
+    sa, ta = route_trace(lambda: poisoned(ca).Score(toks, 0))
     sb, tb = route_trace(lambda: cb.Score(toks, 0))
     assert len(sa) == 193 and sa.dtype == sb.dtype
     for field in sa.dtype.names:                           # per-row log-probs, argmax, rank ...: every field by bytes

@@ -58,6 +58,9 @@ def twins(product, hp, seed=77):
     return out
 
 
+poisoned = WP.poisoned
+
+
 def seeded_cache(ctxs, hp, layers, ctx):
     """the same seeded finite values in the K and V caches of every context: rows below `past` that no Eval of the test wrote"""
     rng = np.random.default_rng(5)
@@ -254,7 +257,7 @@ def test_step_and_rows_are_byte_equal_to_the_expanded_model(product, shape):
         for past in (0, 37):
             for n in (1, 2, 3, 4, 5):
                 toks = [int(t) for t in rng.integers(0, hp.vocabSize, n)]
-                la, tr = route_trace(lambda: ca.Eval(toks, past))
+                la, tr = route_trace(lambda: poisoned(ca).Eval(toks, past))
                 assert fused(product, ca) == 1
                 lb = cb.Eval(toks, past)
                 assert np.isfinite(lb).all() and np.abs(lb).max() > 0
@@ -288,7 +291,7 @@ def test_expanded_route_runs_the_int8_schedule_byte_equal(product):
         cases = [(n, past) for past in (0, 37) for n in (5, 9, 64, 89, 130)] + [(5, 0)]       # (5 again behind 130: the image does not move)
         for n, past in cases:
             toks = [int(t) for t in rng.integers(0, hp.vocabSize, n)]
-            la, ta = route_trace(lambda: ca.Eval(toks, past))
+            la, ta = route_trace(lambda: poisoned(ca).Eval(toks, past))
             assert fused(product, ca) == 1
             lb, tb = route_trace(lambda: cb.Eval(toks, past))
             assert same(la, lb), (n, past, float(np.abs(la - lb).max()))
@@ -376,7 +379,7 @@ def test_batch_ticks(small_twins, pods):
         b = Batch(m, 64, pods)
         try:
             assert b.batched, "these shapes must take the one-pass route"
-            res.append(b.GreedyDecode(prompts, 6, want_logits=True))
+            res.append(poisoned(b, m is A).GreedyDecode(prompts, 6, want_logits=True))
         finally:
             b.free()
     (ia, la), (ib, lb) = res
@@ -397,7 +400,7 @@ def test_batch_feed(small_twins):
     for m in (A, B):
         b = Batch(m, 64, 3)
         try:
-            res.append(b.Feed(toks, [0, 0, 0], want_logits=True, want_rows=True))
+            res.append(poisoned(b, m is A).Feed(toks, [0, 0, 0], want_logits=True, want_rows=True))
         finally:
             b.free()
     (ia, la, ra), (ib, lb, rb) = res
@@ -413,11 +416,11 @@ def test_batch_fork_with_a_shared_prefix(small_twins):
     for m in (A, B):
         b = Batch(m, 64, 3)
         try:
-            b.Feed([prefix, [1], [2]], [0, 0, 0])
+            poisoned(b, m is A).Feed([prefix, [1], [2]], [0, 0, 0])
             b.Fork(0, [1, 2], len(prefix))
-            pending = b.Feed(sfx, [len(prefix)] * 3)
+            pending = poisoned(b, m is A).Feed(sfx, [len(prefix)] * 3)
             pos = [len(prefix) + len(s) for s in sfx]
-            res.append((pending, b.ShareInfo()) + tuple(b.Decode(pending, pos, 8, want_logits=True)))
+            res.append((pending, b.ShareInfo()) + tuple(poisoned(b, m is A).Decode(pending, pos, 8, want_logits=True)))
         finally:
             b.free()
     (pa, sa, ia, la), (pb, sb, ib, lb) = res
@@ -546,7 +549,7 @@ def test_saved_q4_file_loads_back_block_for_block(product, tmp_path):
     ca, ck = A.NewContext(32, 1), K.NewContext(32, 1)
     try:
         for toks, past in ((FILE_SMALL_PROMPT, 0), ([5], 7), ([9, 8, 7], 8), (list(range(1, 14)), 11)):
-            assert same(ca.Eval(toks, past), ck.Eval(toks, past)), (toks, past)
+            assert same(poisoned(ca).Eval(toks, past), ck.Eval(toks, past)), (toks, past)
     finally:
         ca.free(); ck.free(); A.free(); K.free()
 
@@ -598,6 +601,6 @@ def test_q4_file_with_a_matrix_that_is_not_q4_loads_as_llama_loadmodel_loads_it(
     assert K.weight_type == 2
     ca, ck = A.NewContext(32, 1), K.NewContext(32, 1)
     try:
-        assert same(ca.Eval(FILE_SMALL_PROMPT, 0), ck.Eval(FILE_SMALL_PROMPT, 0))
+        assert same(poisoned(ca).Eval(FILE_SMALL_PROMPT, 0), ck.Eval(FILE_SMALL_PROMPT, 0))
     finally:
         ca.free(); ck.free(); A.free(); K.free()

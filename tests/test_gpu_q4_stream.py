@@ -16,7 +16,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import q4_ref as Q                    # noqa: E402
 import weight_probe_ref as WP         # noqa: E402
-from test_gpu_q4 import SHAPE_KW, families, parse_ggjt, same, seeded_cache, twins, write_ggjt   # noqa: E402
+from test_gpu_q4 import SHAPE_KW, families, parse_ggjt, poisoned, same, seeded_cache, twins, write_ggjt   # noqa: E402
 from llama_go_amd.mlapi import SHAPES, Batch, make_hparams, route_trace   # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -89,7 +89,7 @@ def test_solo_evals_are_byte_equal_and_take_the_twins_kernels(solo):
         rng = np.random.default_rng(100 + n)
         for past in (0, past1):
             toks = [int(t) for t in rng.integers(0, hp.vocabSize, n)]
-            la, ta = route_trace(lambda: ca.Eval(toks, past))
+            la, ta = route_trace(lambda: poisoned(ca).Eval(toks, past))
             lb, tb = route_trace(lambda: cb.Eval(toks, past))
             assert np.isfinite(lb).all() and np.abs(lb).max() > 0
             assert same(la, lb), (shape, n, past, float(np.abs(la - lb).max()))
@@ -114,11 +114,11 @@ def test_switch_off_is_the_expanded_route(solo):
     shape, hp, ca, cb = solo
     layers = SOLO[shape][0]
     toks = [int(t) for t in np.random.default_rng(7).integers(0, hp.vocabSize, 17)]
-    la_on = ca.Eval(toks, 0)
+    la_on = poisoned(ca).Eval(toks, 0)
     ca.SetQ4Stream(False)
     try:
         assert ca.q4_stream is False
-        la, ta = route_trace(lambda: ca.Eval(toks, 0))
+        la, ta = route_trace(lambda: poisoned(ca).Eval(toks, 0))
     finally:
         ca.SetQ4Stream(True)
     lb, tb = route_trace(lambda: cb.Eval(toks, 0))
@@ -193,7 +193,7 @@ def test_raw_blocks_nibble_zero_all_fifteen_zero_and_nan_scales(product, tmp_pat
     try:
         for n, past in ((5, 0), (16, 3), (33, 7)):
             toks = [int(t) for t in rng.integers(0, hp.vocabSize, n)]
-            la, ta = route_trace(lambda: ca.Eval(toks, past))
+            la, ta = route_trace(lambda: poisoned(ca).Eval(toks, past))
             lb, tb = route_trace(lambda: cb.Eval(toks, past))
             la, lb = np.asarray(la).reshape(-1, hp.vocabSize), np.asarray(lb).reshape(-1, hp.vocabSize)
             assert np.isnan(lb[:, nan_row]).all() and np.isfinite(np.delete(lb, nan_row, axis=1)).all() and np.abs(np.nan_to_num(lb)).max() > 0
@@ -262,7 +262,7 @@ def test_greedy_ticks(small_twins, pods):
     hp = small_twins[0]
     rng = np.random.default_rng(60 + pods)
     prompts = [[int(t) for t in rng.integers(0, hp.vocabSize, 2 + i % 3)] for i in range(pods)]
-    ((i1, l1), t1), ((i0, l0), t0), ((ib, lb), tb) = three_legs(small_twins, pods, lambda b: b.GreedyDecode(prompts, 5, want_logits=True))   # four ticks: eager, captured, replayed twice
+    ((i1, l1), t1), ((i0, l0), t0), ((ib, lb), tb) = three_legs(small_twins, pods, lambda b: poisoned(b, b.model.weight_type == 2).GreedyDecode(prompts, 5, want_logits=True))   # four ticks: eager, captured, replayed twice
     assert i1 == i0 == ib and same(l1, lb) and same(l0, lb)
     assert "k_stream_q4b" in families(t1) and "k_expand_q4" not in families(t1) and mapped(t1, tb), (t1, tb)
     assert "k_stream_q4b" not in families(t0) and "k_expand_q4" in families(t0) and mapped(t0, tb), (t0, tb)
@@ -275,9 +275,9 @@ def test_sampled_ticks(small_twins, pods):
     prompts = [[int(t) for t in rng.integers(0, hp.vocabSize, 3)] for _ in range(pods)]
 
     def run(b):
-        first = b.Prompt(prompts)
+        first = poisoned(b, b.model.weight_type == 2).Prompt(prompts)
         b.SetSampler(topK=40, seed=9)
-        return b.Decode(first, [3] * pods, 4, want_logits=True)
+        return poisoned(b, b.model.weight_type == 2).Decode(first, [3] * pods, 4, want_logits=True)
     ((i1, l1), t1), ((i0, l0), _), ((ib, lb), tb) = three_legs(small_twins, pods, run)
     assert i1 == i0 == ib and same(l1, lb) and same(l0, lb)
     assert "k_stream_q4b" in families(t1) and mapped(t1, tb), (t1, tb)
@@ -291,8 +291,8 @@ def test_feed_of_a_joining_prompt(small_twins):
     join = [[int(t) for t in rng.integers(0, hp.vocabSize, 24)]] + [[]] * (pods - 1)          # one pod joins with a 24-token prompt
 
     def run(b):
-        first = b.Feed(toks, [0] * pods, want_logits=True, want_rows=True)                     # 15 rows in one pass
-        second = b.Feed(join, [3] + [0] * (pods - 1), want_logits=True, want_rows=True)        # 24 rows of one pod at past 3
+        first = poisoned(b, b.model.weight_type == 2).Feed(toks, [0] * pods, want_logits=True, want_rows=True)                     # 15 rows in one pass
+        second = poisoned(b, b.model.weight_type == 2).Feed(join, [3] + [0] * (pods - 1), want_logits=True, want_rows=True)        # 24 rows of one pod at past 3
         return first, second
     ((f1, s1), t1), ((f0, s0), _), ((fb, sb), tb) = three_legs(small_twins, pods, run)
     for x, y in ((f1, fb), (s1, sb), (f0, fb), (s0, sb)):
@@ -307,8 +307,8 @@ def test_lookup_passes_of_sixteen_rows(small_twins):
     prompts = [[int(t) for t in rng.integers(0, hp.vocabSize, 6)] for _ in range(pods)]
 
     def run(b):
-        first = b.Prompt(prompts)
-        return b.DecodeLookup(first, [6] * pods, 12, R - 1, want_logits=True)
+        first = poisoned(b, b.model.weight_type == 2).Prompt(prompts)
+        return poisoned(b, b.model.weight_type == 2).DecodeLookup(first, [6] * pods, 12, R - 1, want_logits=True)
     ((i1, l1, s1, p1), t1), ((i0, l0, s0, p0), _), ((ib, lb, sb, pb), tb) = three_legs(small_twins, pods, run)
     assert i1 == i0 == ib and same(l1, lb) and same(l0, lb) and s1 == s0 == sb and p1 == p0 == pb
     assert any(e.startswith("k_stream_q4b<") and e[e.index("<") + 1:e.index(">")].split(",")[4] == "16" for e in t1), t1   # a 16-row pass (XR = 16) on the 4-bit kernel
@@ -322,13 +322,13 @@ def test_toggle_between_ticks_captures_anew(small_twins):
     prompts = [[int(t) for t in rng.integers(0, hp.vocabSize, 3)] for _ in range(pods)]
     ba, bb = Batch(A, 64, pods), Batch(B, 64, pods)
     try:
-        first = ba.Prompt(prompts)
+        first = poisoned(ba).Prompt(prompts)
         assert first == bb.Prompt(prompts)
         past = [3] * pods
         for seg, on in enumerate((False, True, False, False)):
             ba.SetQ4Stream(on)
             assert ba.q4_stream is on
-            (ia, la), ta = route_trace(lambda: ba.Decode(first, past, 3, want_logits=True))
+            (ia, la), ta = route_trace(lambda: poisoned(ba).Decode(first, past, 3, want_logits=True))
             ib, lb = bb.Decode(first, past, 3, want_logits=True)
             assert ia == ib and same(la, lb), seg
             fa = families(ta)

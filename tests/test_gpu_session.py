@@ -6,6 +6,11 @@ rewound position, samplers reconfigured, lookup runs among plain ones, feeds and
 (every plan of which is made under LLAMAHIP_NO_GRAPH=1, and which is seen to launch where the other replays), to a fresh twin that runs the essential steps only, and to the route trace: the step behind a trigger must capture
 again, the same step repeated must replay.  All comparisons are byte equalities of everything a step returns; a failure names script, step, oracle and the
 first differing element.  Measured on an MI355X: every case takes 0.03 - 0.7 s (the 4100-id run is the longest); DESIGN.md lists them.
+
+All four weight types run every script (f16 through NarrowF16, block-int4 through QuantizeQ4); the switch scripts run for f16 and block-int4, the tile script for f16,
+the pair scripts for the three pairs of session_ref.PAIRS.  The long-lived object alone gets the lh_ctx switches a script sets, and in front of every step its
+context's weight images are filled with 0xFF (llamago_PoisonWeightImages): see session_ref.py.  A step's `want` / `wantnot` patterns - the kernel family it is there
+for - are asserted on its route trace here.
 """
 import os
 import re
@@ -15,7 +20,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import session_cases as sc  # noqa: E402
-from session_ref import EnvPatch, ProductBackend, run_script  # noqa: E402
+from session_ref import MODEL_SEED, EnvPatch, ProductBackend, run_script  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -24,29 +29,47 @@ CAN_CAPTURE = ("Decode", "SampleDecode", "DecodeLookup", "SampleDecodeLookup", "
 _TRACES = {}   # (script, weights) -> the long-lived object's trace of every step, for test_no_captured_step_sizes_a_gemm_buffer
 
 
-@pytest.fixture(scope="module")
-def models(product):
-    """One synthetic model per (shape, weight type) for the whole module; contexts and batches come and go on them."""
+def _model_maker(product):
+    """-> (get(shape, weights, seed), the dict of what it made): one synthetic model per (shape, weight type, seed); f16 through NarrowF16, block-int4 through QuantizeQ4."""
     from llama_go_amd.mlapi import SHAPES, make_hparams
     made = {}
 
-    def get(shape, weights):
-        if (shape, weights) not in made:
-            m = product.NewSyntheticModel(make_hparams(**SHAPES[shape], ctx=512), 1234)
-            made[(shape, weights)] = m.QuantizeQ8() if weights == "q8" else m
-        return made[(shape, weights)]
+    def get(shape, weights, seed=MODEL_SEED):
+        if (shape, weights, seed) not in made:
+            m = product.NewSyntheticModel(make_hparams(**{**SHAPES, **sc.SHAPES}[shape], ctx=512), seed)
+            if weights == "q8":
+                m.QuantizeQ8()
+            elif weights == "f16":
+                m.NarrowF16()
+            elif weights == "q4":
+                m.QuantizeQ4()
+            made[(shape, weights, seed)] = m
+        return made[(shape, weights, seed)]
 
+    return get, made
+
+
+@pytest.fixture(scope="module")
+def models(product):
+    """One synthetic model per (shape, weight type, seed) for the whole module; contexts, batches and pairs come and go on them."""
+    get, made = _model_maker(product)
     yield get
     for m in made.values():
         m.free()
 
 
 def _run(name, weights, models, monkeypatch):
-    report = []
+    report, script = [], sc.SCRIPTS[name](weights)
     try:
-        _TRACES[(name, weights)] = run_script(sc.SCRIPTS[name](weights), ProductBackend(models, monkeypatch), weights, report=report)
+        _TRACES[(name, weights)] = run_script(script, ProductBackend(models, monkeypatch), weights, report=report)
     finally:
         print("\n".join(report))   # (pytest shows it for a failing case: which triggers fired, which steps replayed, up to the step that did not hold)
+    for i, (st, trace) in enumerate(zip(script.steps, _TRACES[(name, weights)])):   # the kernel family each step is there for
+        for rx in st.want:
+            assert any(re.search(rx, e) for e in trace), f"script {name} [{weights}] step {i} ({st.call}): no launch matches {rx} among {sorted(set(trace))}"
+        for rx in st.wantnot:
+            bad = [e for e in trace if re.search(rx, e)]
+            assert not bad, f"script {name} [{weights}] step {i} ({st.call}): launches {bad[0]}, which matches {rx}"
     return _TRACES[(name, weights)]
 
 
@@ -71,18 +94,25 @@ def test_no_captured_step_sizes_a_gemm_buffer(models, monkeypatch):
     for name, weights in sc.CASES:
         traces = _TRACES.get((name, weights)) or _run(name, weights, models, monkeypatch)
         for i, (st, trace) in enumerate(zip(sc.SCRIPTS[name](weights).steps, traces)):
-            if st.call in CAN_CAPTURE or (st.call == "Eval" and len(st.args["tokens"]) == 1):   # whatever it is declared: an `eager` lookup run captures its second pass
+            call = st.call.rpartition(".")[2]   # (a pair's steps name their side)
+            if call in CAN_CAPTURE or (call == "Eval" and len(st.args["tokens"]) == 1):   # whatever it is declared: an `eager` lookup run captures its second pass
                 bad = [e for e in trace if re.match(r"k_gemm_|k_splitk_reduce|k_split3_rows", e)]
                 assert not bad, f"script {name} [{weights}] step {i} ({st.call}) can capture and launches {bad[0]}"
-    for weights, want in (("f32", r"^k_gemm_glds<.*>/s([2-9]|\d\d)$"), ("q8", r"^k_gemm_q8b3<4>/s\d+$")):
+    # (f16 runs the fp32 tile GEMM over its widened image, block-int4 k_gemm_q8b3 over its expanded one: the entries are the twins', with the widening / expanding passes in front)
+    for weights, want in (("f32", r"^k_gemm_glds<.*>/s([2-9]|\d\d)$"), ("q8", r"^k_gemm_q8b3<4>/s\d+$"), ("f16", r"^k_gemm_glds<.*>/s([2-9]|\d\d)$"), ("q4", r"^k_gemm_q8b3<4>/s\d+$")):
         script = sc.SCRIPTS["solo.growing_prompts"](weights)
         i = max(k for k, st in enumerate(script.steps) if st.fires and st.fires[-1] in ("ensure_splitk", "ensure_xs3"))
         trace = _TRACES[("solo.growing_prompts", weights)][i]
         assert any(re.match(want, e) for e in trace), f"solo.growing_prompts [{weights}] step {i}: no tile GEMM among {sorted(set(trace))}"
-        if weights == "f32":
+        if weights in sc.LIKE_F32:
             assert "k_splitk_reduce" in trace
         else:
             assert "k_split3_rows" in trace
+        if weights in ("f16", "q4"):
+            assert ("k_widen_f16" if weights == "f16" else "k_expand_q4") in trace
+    # the tile script's own statement: with lh_ctx_set_f16_tiles on, the 193-row prompt takes the half kernel (each such step's `want` is asserted where it runs)
+    tiles = sc.SCRIPTS["solo.tiles_and_stream"]("f16")
+    assert sum(1 for st in tiles.steps if any("k_gemm_b9_h" in rx for rx in st.want)) == 2
 
 
 def test_longer_window_in_a_fresh_process(built):
@@ -92,19 +122,13 @@ def test_longer_window_in_a_fresh_process(built):
     MUST grow it under the live decode graphs."""
     import subprocess
     r = subprocess.run([sys.executable, os.path.abspath(__file__)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
-    assert r.returncode == 0 and "longer window: 2 cases hold" in r.stdout, r.stdout[-3000:]
+    assert r.returncode == 0 and f"longer window: {len(sc.WEIGHTS)} cases hold" in r.stdout, r.stdout[-3000:]
 
 
 if __name__ == "__main__":   # the child of test_longer_window_in_a_fresh_process
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    from llama_go_amd.mlapi import SHAPES, load_product, make_hparams
-    prod, made = load_product(), {}
-
-    def get(shape, weights):
-        if (shape, weights) not in made:
-            m = prod.NewSyntheticModel(make_hparams(**SHAPES[shape], ctx=512), 1234)
-            made[(shape, weights)] = m.QuantizeQ8() if weights == "q8" else m
-        return made[(shape, weights)]
+    from llama_go_amd.mlapi import load_product
+    get, made = _model_maker(load_product())
 
     for w in sc.WEIGHTS:
         rep = []

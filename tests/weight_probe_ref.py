@@ -517,3 +517,21 @@ def ratio(y, ref):
         return float("inf")
     with np.errstate(divide="ignore", invalid="ignore"):
         return float(np.where(err == 0, 0.0, err / ref["bound"]).max())
+
+
+def poisoned(obj, on=True):
+    """Test instrumentation in front of a call of model A's context or batch (on = False: the twin, returned untouched): the context-owned weight images - ONE
+    layer's matrices and the output matrix, which every layer passes through - filled with 0xFF bytes, NaN as fp32 and quant -1 as int8.  A launch that reads a slot
+    this call did not fill itself then computes from poison instead of from what the call before left there (with one layer: always the right matrix).  The fill
+    must report bytes wherever images exist - a batch of an f16 / block-int4 model from its creation, a context from its second call (its plans are made lazily by
+    the first) - and none on an fp32 / block-int8 model.  -> obj"""
+    if not on:
+        return obj
+    n = obj.PoisonWeightImages()
+    calls = getattr(obj, "_poisoned_calls", 0)
+    obj._poisoned_calls = calls + 1
+    if obj.model.weight_type not in (1, 2):
+        assert n == 0, f"{n} bytes of weight images on a context of an fp32 / block-int8 model"
+    elif hasattr(obj, "pods") or calls >= 1:
+        assert n > 0, "no weight image was filled on a context of an f16 / block-int4 model that has plans"
+    return obj
