@@ -138,6 +138,24 @@ int lh_ctx_q4_stream(lh_ctx* ctx);
 int64_t lh_stream_q4_image_off(uint32_t kc, uint32_t r, uint32_t g);
 int64_t lh_stream_q4_read_off(uint32_t kc, uint32_t t, uint32_t r16, uint32_t kb, uint32_t slot);
 void lh_stream_q4_operand(uint32_t nibbles, uint32_t out[4]);
+/* Block-int4 models on the bf16 tile GEMM of prompts from 89 rows (csrc/kernels_gemm_q4.h).  lh_ctx_set_q4_tiles(ctx, on): with on != 0 every Eval of a
+ * block-int4 plan of this context that takes the prefill route hands its k_gemm_q8b3 launches - the four of a layer and the multi-row lm_head - the model's
+ * own nibble planes and scale planes (k_gemm_q4b3) and enqueues no k_expand_q4 pass for them; a launch of that route that still reads int8 (k_gemm_q8: a K
+ * that is no multiple of 128, a shape the cost model gives to it) gets its matrices expanded directly in front of itself.  Byte for byte the same results:
+ * the launch choice, the split-K count and every sum are the int8 twin's.  Off by default; the initial value is LLAMAHIP_Q4_TILES=1 of the environment, read
+ * once in lh_ctx_create.  Read at every Eval; accepted and without effect for fp32, f16 and block-int8 plans; independent of lh_ctx_set_q4_stream (with
+ * that one off, Evals of up to 88 rows keep the image expanded in front of every layer).  No captured graph holds a launch the switch chooses.
+ * lh_ctx_q4_tiles: the current value (0 | 1; ctx NULL: 0). */
+int lh_ctx_set_q4_tiles(lh_ctx* ctx, int on);
+int lh_ctx_q4_tiles(lh_ctx* ctx);
+/* Where k_gemm_q4b3 keeps a nibble (csrc/gemm_q4_layout.h; pure host functions, for checks).  lh_gemm_q4_w_off: byte offset, in the weight part of the LDS
+ * ring (two slab pairs of 8 KB), of byte `byte` (< 16: columns 2 byte, 2 byte + 1 of the slab's 32) of tile row `row` (< 256) of slab `slab`.
+ * lh_gemm_q4_dma_lane: what lane `lane` (< 64) of wave `wave`'s (< 8) LDS-DMA instruction for a slab pair moves - out[0] = tile row, out[1] = which slab of
+ * the pair (its 16 bytes land at lh_gemm_q4_w_off(2 pair + out[1], out[0], 0)).  lh_gemm_q4_read_off: offset of the 8 bytes MFMA lane (li < 32, lh < 2) of
+ * wave `wave` reads for slab `slab` (dword st of them: columns 16 lh + 8 st .. + 7 of tile row 32 wave + li).  An argument out of range: -1. */
+int64_t lh_gemm_q4_w_off(uint32_t slab, uint32_t row, uint32_t byte);
+int lh_gemm_q4_dma_lane(uint32_t wave, uint32_t lane, uint32_t out[2]);
+int64_t lh_gemm_q4_read_off(uint32_t slab, uint32_t wave, uint32_t li, uint32_t lh);
 /* Test instrumentation.  The context owns one fp32 (f16 plans) or int8 (block-int4 plans) image of ONE layer's matrices and one of the output matrix per plan
  * size; every route that reads an image fills the slots it reads in front of its own launches.  lh_ctx_poison_weight_images fills every such image with 0xFF
  * bytes (NaN as fp32, quant -1 as int8), enqueued on the context's stream, and stores the bytes filled (0: the context has no f16 or block-int4 plan).  A

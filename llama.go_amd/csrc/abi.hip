@@ -4,6 +4,7 @@
 #include "kernels_q8_pack.h"
 #include "stream_f16_layout.h"
 #include "stream_q4_layout.h"
+#include "gemm_q4_layout.h"
 #include "gemm_f16_layout.h"
 #include <stdarg.h>
 #include <math.h>
@@ -281,6 +282,8 @@ int lh_ctx_create(int device, void* stream, lh_ctx** out) {
     c->f16_tiles = ht && ht[0] == '1' ? 1 : 0;
     const char* qs = getenv("LLAMAHIP_Q4_STREAM");
     c->q4_stream = qs && qs[0] == '1' ? 1 : 0;
+    const char* qt = getenv("LLAMAHIP_Q4_TILES");
+    c->q4_tiles = qt && qt[0] == '1' ? 1 : 0;
     *out = c;
     return LH_OK;
 }
@@ -305,6 +308,25 @@ int lh_ctx_set_q4_stream(lh_ctx* ctx, int on) {
     return LH_OK;
 }
 int lh_ctx_q4_stream(lh_ctx* ctx) { return ctx ? ctx->q4_stream : 0; }
+int lh_ctx_set_q4_tiles(lh_ctx* ctx, int on) {
+    if (!ctx) return LH_EINVAL;
+    ctx->q4_tiles = on ? 1 : 0;
+    return LH_OK;
+}
+int lh_ctx_q4_tiles(lh_ctx* ctx) { return ctx ? ctx->q4_tiles : 0; }
+int64_t lh_gemm_q4_w_off(uint32_t slab, uint32_t row, uint32_t byte) {
+    if (row >= lh::GEMM_Q4_BM || byte >= 16) return -1;
+    return (int64_t)lh::gemm_q4_w_off(slab, row, byte);
+}
+int lh_gemm_q4_dma_lane(uint32_t wave, uint32_t lane, uint32_t out[2]) {
+    if (wave >= 8 || lane >= 64 || !out) return -1;
+    out[0] = lh::gemm_q4_dma_row(wave, lane); out[1] = lh::gemm_q4_dma_granule(lane);
+    return 0;
+}
+int64_t lh_gemm_q4_read_off(uint32_t slab, uint32_t wave, uint32_t li, uint32_t lh_) {
+    if (wave >= 8 || li >= 32 || lh_ >= 2) return -1;
+    return (int64_t)lh::gemm_q4_read_off(slab, wave, li, lh_);
+}
 // Test instrumentation: every image of lh_ctx::wide filled with 0xFF bytes (NaN in an fp32 image, quant -1 in an int8 one), enqueued on the stream behind
 // whatever read the images last.  The byte count of an image is in its key (wide_image, plan.hip): elements << 4 | element bytes << 1 | kind.
 int lh_ctx_poison_weight_images(lh_ctx* ctx, uint64_t* bytes) {

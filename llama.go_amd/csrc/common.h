@@ -164,6 +164,9 @@ struct lh_ctx {
     // kernels_stream_q4b.h).  A switch that chooses a kernel, like f16_stream: q4_stream_gen counts the changes for the same captured graphs' keys
     int q4_stream = 0;
     uint64_t q4_stream_gen = 0;
+    // lh_ctx_set_q4_tiles: block-int4 plans hand the k_gemm_q8b3 launches of their prefill route the model's nibbles (k_gemm_q4b3, kernels_gemm_q4.h).  No
+    // key of a captured graph holds it (the case of f16_tiles): the launch takes more than 64 rows (gemm_q8b3_ok) and no capture contains a prefill launch.
+    int q4_tiles = 0;
     // the activation rows of a long-prompt GEMM as three bf16 planes (k_gemm_b9); grows, never shrinks
     uint16_t* xs3 = nullptr;
     uint64_t xs3_elems = 0;

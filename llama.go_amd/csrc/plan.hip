@@ -13,6 +13,7 @@
 #include "kernels_stream_q4b.h"
 #include "kernels_stream_b9.h"
 #include "kernels_gemm_b9.h"
+#include "kernels_gemm_q4.h"
 #include "kernels_rows.h"
 #include "kernels_f16.h"
 #include "kernels_stream_f16.h"
@@ -696,10 +697,10 @@ static double gemm_q8b3_cost(const GemmArgs& a, uint32_t ncu, uint32_t* splits_o
     *splits_out = sp;
     return best;
 }
-static int launch_gemm_q8b3(lh_ctx* ctx, GemmArgs a, const char* name, uint32_t splits) {
-    auto kern = k_gemm_q8b3<4>;
-    const size_t lds = gemm_q8b3_lds_bytes(4);
-    static bool flags[16] = {};
+// k_gemm_q8b3 / k_gemm_q4b3: the launch is one (planes of X, split-K buffer, k_split3_rows in front, k_splitk_reduce behind); what differs is the kernel, its
+// LDS request and what a.w[] points at
+template <typename KernT>
+static int launch_gemm_b3(lh_ctx* ctx, GemmArgs a, const char* name, uint32_t splits, KernT kern, size_t lds, bool* flags, const char* family, int nst) {
     int rc = set_lds_once(ctx, kern, lds, flags);
     if (rc) return rc;
     // (allocations BEFORE the prepare-only return, as the stream kernels do: a capture pass must find xs3 and the split-K buffer sized - ADVICE r5)
@@ -720,8 +721,8 @@ static int launch_gemm_q8b3(lh_ctx* ctx, GemmArgs a, const char* name, uint32_t 
     }
     const uint64_t items = (uint64_t)((a.N + 127) / 128) * ((a.M + 255) / 256) * a.groups * (splits > 1 ? splits : 1);
     ProfScope ps(ctx->stream, name, (uint64_t)a.M * a.K / 32 * 36 * a.groups);
-    LH_TRACE("k_gemm_q8b3<4>/s%u", splits > 1 ? splits : 1u);
-    LH_LAUNCH_AS("k_gemm_q8b3", kern, dim3((uint32_t)std::min<uint64_t>(items, (uint64_t)ctx->ds->num_cu)), dim3(512), lds, ctx->stream, a);
+    LH_TRACE("%s<%d>/s%u", family, nst, splits > 1 ? splits : 1u);
+    LH_LAUNCH_AS(family, kern, dim3((uint32_t)std::min<uint64_t>(items, (uint64_t)ctx->ds->num_cu)), dim3(512), lds, ctx->stream, a);
     if (splits > 1) {
         const uint64_t quads = (uint64_t)a.groups * a.N * (a.M / 4);
         LH_TRACE("k_splitk_reduce");
@@ -730,10 +731,30 @@ static int launch_gemm_q8b3(lh_ctx* ctx, GemmArgs a, const char* name, uint32_t 
     LH_HIP(ctx, hipGetLastError());
     return 0;
 }
+static int launch_gemm_q8b3(lh_ctx* ctx, GemmArgs a, const char* name, uint32_t splits) {
+    static bool flags[16] = {};
+    return launch_gemm_b3(ctx, a, name, splits, k_gemm_q8b3<4>, gemm_q8b3_lds_bytes(4), flags, "k_gemm_q8b3", 4);
+}
+// the same launch on the nibble planes of a block-int4 model (k_gemm_q4b3, kernels_gemm_q4.h): a.w[] = the nibble planes, everything else - the scale
+// planes, the split count, the work items - as decided for the int8 image
+static int launch_gemm_q4b3(lh_ctx* ctx, GemmArgs a, const char* name, uint32_t splits) {
+    static bool flags[16] = {};
+    return launch_gemm_b3(ctx, a, name, splits, k_gemm_q4b3<Q4B3_NST>, gemm_q4b3_lds_bytes(Q4B3_NST), flags, "k_gemm_q4b3", Q4B3_NST);
+}
 
+// The nibbles behind int8 image slots (a block-int4 plan with lh_ctx_set_q4_stream or lh_ctx_set_q4_tiles on: eval_planes, eval_prefill): w[g] of a launch
+// names the image slot of a matrix whose n quants lie 4-bit at nib[g] and which is NOT expanded yet (HalfSrc's pattern).  expand: k_expand_q4 per matrix into
+// its slot, directly in front of a launch that reads int8.
+struct Q4Src {
+    const float* nib[3];
+    uint64_t n;
+    void expand(lh_ctx* ctx, const float* const* w, uint32_t groups) const {
+        for (uint32_t g = 0; g < groups; ++g) expand_q4_launch(ctx, nib[g], (void*)w[g], n);   // (a launch error surfaces at the layer's hipGetLastError)
+    }
+};
 // block-int8 weights, prompts beyond the 64 rows of k_stream_q8b (and shapes it is not built for): dequantising MFMA GEMM (k_gemm_q8), persistent one workgroup per CU
 static int gemm_q8_group(lh_ctx* ctx, const float* x, uint32_t ldx, uint32_t groups, const float* const* wq, const float* const* wsc, float* const* y,
-                         const float* const* r, uint32_t M, uint32_t K, uint32_t n, uint32_t ldy, const char* name) {
+                         const float* const* r, uint32_t M, uint32_t K, uint32_t n, uint32_t ldy, const char* name, const Q4Src* q4 = nullptr) {
     if (K % GBK || ldx % 4 || ((uintptr_t)x & 15)) LH_FAIL(ctx, LH_ESHAPE, "gemm_q8 %s: K=%u / ldx=%u / X alignment not supported", name, K, ldx);
     GemmArgs a = {};
     a.x = x; a.groups = groups; a.N = n; a.M = M; a.K = K; a.ldx = ldx; a.ldy = ldy;
@@ -763,8 +784,20 @@ static int gemm_q8_group(lh_ctx* ctx, const float* x, uint32_t ldx, uint32_t gro
         const uint32_t nkf = K / GBK, sp = a.splits ? a.splits : 1;
         uint32_t sp3 = 1;
         const double c8 = (double)((items + ncu - 1) / ncu) * (nkf / sp + 8) * bm, c3 = gemm_q8b3_cost(a, ncu, &sp3);
-        if (c3 < c8) return launch_gemm_q8b3(ctx, a, name, sp3);
+        if (c3 < c8) {
+            // q4 (lh_ctx_set_q4_tiles): the slots a.w[] are not filled yet and the quants lie 4-bit at q4->nib[].  Everything above was decided from the
+            // int8 sizes and the slots' addresses - the twin's launch; k_gemm_q4b3 reads the nibbles where their planes are 16-byte aligned
+            bool nib = q4 != nullptr;
+            for (uint32_t g = 0; nib && g < groups; ++g) nib = ((uintptr_t)q4->nib[g] & 15u) == 0;   // (the scale planes: gemm_q8b3_ok)
+            if (nib) {
+                for (uint32_t g = 0; g < groups; ++g) a.w[g] = q4->nib[g];
+                return launch_gemm_q4b3(ctx, a, name, sp3);
+            }
+            if (q4) q4->expand(ctx, wq, groups);
+            return launch_gemm_q8b3(ctx, a, name, sp3);
+        }
     }
+    if (q4) q4->expand(ctx, wq, groups);   // k_gemm_q8 reads int8
     ProfScope ps(ctx->stream, name, (uint64_t)M * K / 32 * 36 * groups);
     int rc;
     static bool flags[3][16] = {};
@@ -799,8 +832,8 @@ static int gemm_q8_group(lh_ctx* ctx, const float* x, uint32_t ldx, uint32_t gro
     return 0;
 }
 static int gemm_q8(lh_ctx* ctx, const float* wq, const float* wsc, const float* x, float* y, const float* resid, uint32_t M, uint32_t K, uint32_t n, uint32_t ldx,
-                   uint32_t ldy, const char* name) {
-    return gemm_q8_group(ctx, x, ldx, 1, &wq, &wsc, &y, resid ? &resid : nullptr, M, K, n, ldy, name);
+                   uint32_t ldy, const char* name, const Q4Src* q4 = nullptr) {
+    return gemm_q8_group(ctx, x, ldx, 1, &wq, &wsc, &y, resid ? &resid : nullptr, M, K, n, ldy, name, q4);
 }
 
 // Large-N prefill attention as batched MFMA GEMMs over heads, mirroring the reference's own structure (llama.go:300-333):
@@ -2152,16 +2185,6 @@ static const float* route_output(Plan* p, const ModelDesc& m) {
     }
     return m.output;
 }
-// The nibbles behind int8 image slots (a block-int4 plan with lh_ctx_set_q4_stream on: eval_planes, eval_prefill): w[g] of a launch names the image slot
-// of a matrix whose n quants lie 4-bit at nib[g] and which is NOT expanded yet (HalfSrc's pattern).  expand: k_expand_q4 per matrix into its slot,
-// directly in front of a launch that reads int8.
-struct Q4Src {
-    const float* nib[3];
-    uint64_t n;
-    void expand(lh_ctx* ctx, const float* const* w, uint32_t groups) const {
-        for (uint32_t g = 0; g < groups; ++g) expand_q4_launch(ctx, nib[g], (void*)w[g], n);   // (a launch error surfaces at the layer's hipGetLastError)
-    }
-};
 // One k_stream_q8b launch site over matrices that may still be nibbles: launch(w, wdt) is the site's gemm_q8b_group / gemm_q8b_split call.  The nibbles as
 // they are where the 4-bit chain has the launch (every ST_NA of it is the int8 chain's, except the alignment of the nibble planes themselves); otherwise
 // the int8 launch over the image, which is expanded only if that launch exists - asked with a prepare-only pass, which enqueues nothing - so that an
@@ -2516,15 +2539,19 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
     // makes the matrices lazy; which launches read halves is each switch's own (HalfSrc::stream / ::tiles).
     const bool f16p = &m == &p->md_wide && p->md.wtype == 1;
     const bool hstream = f16p && ctx->f16_stream, htiles = f16p && ctx->f16_tiles, lazy = hstream || htiles;
-    // block-int4 plan with lh_ctx_set_q4_stream on: no launch of this route reads nibbles (k_gemm_q8b3 and the dequantising GEMM read int8), so every matrix
+    // block-int4 plan with lh_ctx_set_q4_stream on (alone): no launch of this route reads nibbles (k_gemm_q8b3 and the dequantising GEMM read int8), so every matrix
     // is expanded - directly in front of the launch that reads it (q4x below) instead of in front of the layer, the one place an expansion stands under
     // the switch (eval_planes, Q4Src).  A plan whose shapes have no k_stream_q8b schedule never launches k_stream_q4b: the switch leaves it alone entirely.
-    const bool q4s = &m == &p->md_wide && p->md.wtype == 2 && ctx->q4_stream && q8b_shape_ok(ctx, m);
+    // lh_ctx_set_q4_tiles: a k_gemm_q8b3 launch reads the nibbles itself (k_gemm_q4b3, kernels_gemm_q4.h) - the launch sites hand their Q4Src down and
+    // gemm_q8_group expands only for a launch that still reads int8.  Either switch makes the matrices lazy (as f16_stream / f16_tiles do above).
+    const bool q4p = &m == &p->md_wide && p->md.wtype == 2, q4t = q4p && ctx->q4_tiles;
+    const bool q4s = q4t || (q4p && ctx->q4_stream && q8b_shape_ok(ctx, m));
     for (uint32_t il = m.layer0; il < m.layer1; ++il) {
         const LayerW& L = (lazy || q4s) ? m.layers[il] : route_layer(p, m, il);   // (lazy, q4s: the image slots, nothing in them yet)
         const LayerW& LS = (lazy || q4s) ? p->md.layers[il] : L;                  // the model's own matrices
         const Q4Src qqkv = {{LS.wq, LS.wk, LS.wv}, (uint64_t)d * d}, qo = {{LS.wo}, (uint64_t)d * d}, q13 = {{LS.w1, LS.w3}, (uint64_t)d * F}, q2 = {{LS.w2}, (uint64_t)d * F};
-        auto q4x = [&](const Q4Src& q, const float* const* w, uint32_t groups) { if (q4s) q.expand(ctx, w, groups); };
+        auto q4x = [&](const Q4Src& q, const float* const* w, uint32_t groups) { if (q4s && !q4t) q.expand(ctx, w, groups); };
+        auto q4n = [&](const Q4Src& q) -> const Q4Src* { return q4t ? &q : nullptr; };
         bool wide[7] = {};                                                  // wq wk wv wo w1 w3 w2: the slot holds the matrix
         const uint64_t dd_ = (uint64_t)d * d, dF_ = (uint64_t)d * F;
         const HalfSrc hqkv = {{LS.wq, LS.wk, LS.wv}, dd_, {&wide[0], &wide[1], &wide[2]}, hstream, htiles}, hq = {{LS.wq}, dd_, {&wide[0]}, hstream, htiles},
@@ -2561,7 +2588,7 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
         if (qkv_roped) {
         } else if (q8) {   // (prompts beyond k_stream_q8b's 64 rows)
             q4x(qqkv, wqkv, 3);
-            if ((rc = gemm_q8_group(ctx, p->h, d, 3, wqkv, sqkv, yqkv, nullptr, d, d, n, d, "gemm_q8_wqkv"))) return rc;
+            if ((rc = gemm_q8_group(ctx, p->h, d, 3, wqkv, sqkv, yqkv, nullptr, d, d, n, d, "gemm_q8_wqkv", q4n(qqkv)))) return rc;
         } else if (mfma) {
             int rs = ST_NA;
             for (uint32_t b0 = 0; b0 < n && sb <= stream_max_rows(); b0 += sb) {
@@ -2593,7 +2620,7 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
             hf_ready = wo_rs == 0;
         }
         if (wo_rs == 0) {
-        } else if (q8) { q4x(qo, &L.wo, 1); if ((rc = gemm_q8(ctx, L.wo, L.s_wo, p->attn, p->xb, x, d, d, n, d, d, "gemm_q8_wo"))) return rc; }
+        } else if (q8) { q4x(qo, &L.wo, 1); if ((rc = gemm_q8(ctx, L.wo, L.s_wo, p->attn, p->xb, x, d, d, n, d, d, "gemm_q8_wo", q4n(qo)))) return rc; }
         else if ((rc = gemm_small_n_src(ctx, L.wo, p->attn, p->xb, x, d, d, n, d, d, "gemm_wo", true, src(ho)))) return rc;
         const float* w13[2] = {L.w1, L.w3};
         const float* s13[2] = {L.s_w1, L.s_w3};
@@ -2611,7 +2638,7 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
         if (gated) {
         } else if (q8) {
             q4x(q13, w13, 2);
-            if ((rc = gemm_q8_group(ctx, p->h, d, 2, w13, s13, y13, nullptr, F, d, n, F, "gemm_q8_w1w3"))) return rc;
+            if ((rc = gemm_q8_group(ctx, p->h, d, 2, w13, s13, y13, nullptr, F, d, n, F, "gemm_q8_w1w3", q4n(q13)))) return rc;
         } else if (mfma) {
             StreamArgs fa = {};   // short prompts: silu(w1 h) * (w3 h) in the epilogue of (w1, w3) tile pairs
             fa.epi = ST_EPI_SILU_MUL;
@@ -2645,7 +2672,7 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
             h_ready = w2_rs == 0 && next_gamma != nullptr;
         }
         if (w2_rs == 0) {
-        } else if (q8) { q4x(q2, &L.w2, 1); if ((rc = gemm_q8(ctx, L.w2, L.s_w2, p->g, y, p->xb, d, F, n, F, d, "gemm_q8_w2"))) return rc; }
+        } else if (q8) { q4x(q2, &L.w2, 1); if ((rc = gemm_q8(ctx, L.w2, L.s_w2, p->g, y, p->xb, d, F, n, F, d, "gemm_q8_w2", q4n(q2)))) return rc; }
         else if ((rc = gemm_small_n_src(ctx, L.w2, p->g, y, p->xb, d, F, n, F, d, "gemm_w2", true, src(h2)))) return rc;
         x = p->xa;
         LH_HIP(ctx, hipGetLastError());
@@ -2657,7 +2684,8 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
         { TraceScope ts_(ctx->stream, "rmsnorm_rows_final"); LH_LAUNCH(k_rmsnorm_rows, dim3(nr), dim3(256), 0, ctx->stream, x + (size_t)r0 * d, m.norm, p->h + (size_t)r0 * d, d); }
         if (m.wtype == 7) {
             if (nr >= Q8_GEMM_MIN_ROWS) {
-                if ((rc = gemm_q8(ctx, route_output(p, m), m.s_output, p->h + (size_t)r0 * d, p->logits + (size_t)r0 * m.V, nullptr, m.V, d, nr, d, m.V, "gemm_q8_lmhead"))) return rc;
+                const Q4Src qout = {{p->md.output}, (uint64_t)m.V * d};   // (q4t: the output matrix lazily, as the layers' matrices)
+                if ((rc = gemm_q8(ctx, q4t ? m.output : route_output(p, m), m.s_output, p->h + (size_t)r0 * d, p->logits + (size_t)r0 * m.V, nullptr, m.V, d, nr, d, m.V, "gemm_q8_lmhead", q4t ? &qout : nullptr))) return rc;
             } else {   // a few rows (the last row of a long prompt): the int8 GEMV row by row (one row of a block-int4 model: on its nibbles)
                 const HeadRow hw = nr == 1 ? head_row(p, m) : HeadRow{route_output(p, m), 7};
                 for (uint32_t i = 0; i < nr; ++i) {

@@ -25,7 +25,7 @@
 #include <string.h>
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
-#define LH_STREAM_Q4_FN __host__ __device__ inline
+#define LH_STREAM_Q4_FN __host__ __device__ __forceinline__   // (forced: k_gemm_q4b3 carries a target attribute of its own, across which nothing else is inlined)
 #else
 #define LH_STREAM_Q4_FN inline
 #endif
@@ -68,7 +68,7 @@ LH_STREAM_Q4_FN uint32_t stream_q4_pack(uint32_t even, uint32_t odd) {
 // mask in an SGPR and the exponent word in a VGPR, the subtraction as a two-wide vector so that it becomes v_pk_add_f32 - it is 1 shift + 8 + 4 + 4 packs = 17.
 typedef float stream_q4_f2 __attribute__((ext_vector_type(2)));
 template <int S0, int S1>
-__device__ inline uint32_t stream_q4_pair(uint32_t v, uint32_t w) {
+__device__ __forceinline__ uint32_t stream_q4_pair(uint32_t v, uint32_t w) {
     uint32_t b0, b1;
     asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(b0) : "v"(v), "s"(15u << S0), "v"((uint32_t)(150 - S0) << 23));
     asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(b1) : "v"(w), "s"(15u << S1), "v"((uint32_t)(150 - S1) << 23));

@@ -432,6 +432,21 @@ class Context:
         L.llamago_Q4Stream.argtypes = [VP]
         return bool(L.llamago_Q4Stream(self.h))
 
+    def SetQ4Tiles(self, on=True):
+        """llamago_SetQ4Tiles: Evals of a block-int4 model from 89 rows run their k_gemm_q8b3 launches on the model's nibbles (k_gemm_q4b3), no expansion in front."""
+        L = self.ml.lib
+        L.llamago_SetQ4Tiles.restype = C.c_int
+        L.llamago_SetQ4Tiles.argtypes = [VP, C.c_int]
+        if L.llamago_SetQ4Tiles(self.h, 1 if on else 0):
+            raise MLError(f"llamago_SetQ4Tiles: {self.ml.last_error()}")
+
+    @property
+    def q4_tiles(self):
+        L = self.ml.lib
+        L.llamago_Q4Tiles.restype = C.c_int
+        L.llamago_Q4Tiles.argtypes = [VP]
+        return bool(L.llamago_Q4Tiles(self.h))
+
     def SetF16Tiles(self, on=True):
         """llamago_SetF16Tiles: Evals of an f16 model beyond 128 rows run their k_gemm_b9 launches on the model's halves (k_gemm_b9_h) instead of a widened image."""
         L = self.ml.lib
@@ -1099,6 +1114,21 @@ class Batch:
         L.llamago_BatchQ4Stream.restype = C.c_int
         L.llamago_BatchQ4Stream.argtypes = [VP]
         return bool(L.llamago_BatchQ4Stream(self.h))
+
+    def SetQ4Tiles(self, on=True):
+        """llamago_BatchSetQ4Tiles: Context.SetQ4Tiles for the Evals this batch makes."""
+        L = self.ml.lib
+        L.llamago_BatchSetQ4Tiles.restype = C.c_int
+        L.llamago_BatchSetQ4Tiles.argtypes = [VP, C.c_int]
+        if L.llamago_BatchSetQ4Tiles(self.h, 1 if on else 0):
+            raise MLError(f"llamago_BatchSetQ4Tiles: {self.ml.last_error()}")
+
+    @property
+    def q4_tiles(self):
+        L = self.ml.lib
+        L.llamago_BatchQ4Tiles.restype = C.c_int
+        L.llamago_BatchQ4Tiles.argtypes = [VP]
+        return bool(L.llamago_BatchQ4Tiles(self.h))
 
     def SetF16Stream(self, on=True):
         """llamago_BatchSetF16Stream: Context.SetF16Stream for the ticks, feeds and speculative passes of this batch."""
