@@ -104,6 +104,14 @@ int llamago_Q4Tiles(llama_context* c);
  * another weight type; independent of llamago_SetF16Stream.  The setter returns non-zero (ml_LastError) on a null argument; the getter 0 | 1. */
 int llamago_SetF16Tiles(llama_context* c, int on);
 int llamago_F16Tiles(llama_context* c);
+/* lh_ctx_set_f16_planes / lh_ctx_f16_planes (llamahip.h) on the lh_ctx the context / the batch evaluates in: with on != 0 the Evals of 49..64 rows of an f16
+ * model (prompts, ticks of 49..64 pods, speculative passes) run their k_stream_b9 launches on the model's halves (k_stream_b9_h: six bf16 products per weight
+ * instead of eight, no widening pass in front of a layer) - the same bytes ("Native planes kernel").  Off by default (LLAMAHIP_F16_PLANES=1 turns
+ * it on for contexts created afterwards); without effect on models of another weight type; independent of llamago_SetF16Stream / llamago_SetF16Tiles.  The
+ * setters return non-zero (ml_LastError) on a null argument; the getters 0 | 1.  llamago_BatchSetF16Planes / llamago_BatchF16Planes (declared with the batch
+ * below): the same for a batch's ticks, feeds and speculative passes. */
+int llamago_SetF16Planes(llama_context* c, int on);
+int llamago_F16Planes(llama_context* c);
 /* Block-int4 weight matrices (ML_TYPE_Q4_0 = dtype 2 of llamahip.h: 20 bytes per 32 weights; norm vectors and tok_embeddings stay f32).  A 4-bit quant
  * q in [-8, 7] with block scale d IS a block-int8 weight with the same q and d, so every Eval route of such a model produces the bytes its expansion
  * produces: one row and 2..4 rows on 4-bit forms of the decode stream kernels, every other row count on the int8 kernels behind an exact expansion
@@ -217,6 +225,8 @@ void llamago_FreeBatch(llama_batch* b);
 int llamago_BatchBatched(llama_batch* b);            /* lh_batch_batched */
 int llamago_BatchSetF16Stream(llama_batch* b, int on);   /* llamago_SetF16Stream on the lh_ctx the batch evaluates in */
 int llamago_BatchF16Stream(llama_batch* b);
+int llamago_BatchSetF16Planes(llama_batch* b, int on);   /* llamago_SetF16Planes on the lh_ctx the batch evaluates in */
+int llamago_BatchF16Planes(llama_batch* b);
 int llamago_BatchSetQ4Stream(llama_batch* b, int on);    /* llamago_SetQ4Stream on the lh_ctx the batch evaluates in */
 int llamago_BatchQ4Stream(llama_batch* b);
 int llamago_BatchSetQ4Tiles(llama_batch* b, int on);     /* llamago_SetQ4Tiles on the lh_ctx the batch evaluates in */

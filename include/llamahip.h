@@ -121,6 +121,24 @@ int lh_ctx_f16_tiles(lh_ctx* ctx);
 void lh_gemm_f16_split(uint16_t h, uint32_t* w, uint32_t* r1);
 int lh_gemm_f16_piece(uint32_t p, uint32_t lane, uint32_t out[3]);
 int64_t lh_gemm_f16_w_read_off(uint32_t wm, uint32_t li, uint32_t lh, uint32_t kk);
+/* f16 models on the bf16 stream kernel of 49..64 rows (csrc/kernels_stream_b9_h.h).  lh_ctx_set_f16_planes(ctx, on): with on != 0 every Eval of an f16 plan
+ * of this context that takes the route over activation planes hands every k_stream_b9 launch site the model's own halves (k_stream_b9_h: six exact bf16
+ * products per weight instead of eight) and enqueues no k_widen_f16 pass in front of a layer; the lm_head reads halves where the widened twin launches
+ * k_stream_b9 and is widened once, directly in front, otherwise.  Byte for byte the same results.  Off by default; the initial value is
+ * LLAMAHIP_F16_PLANES=1 of the environment, read once in lh_ctx_create.  Read at every Eval; accepted and without effect for fp32, block-int8 and block-int4
+ * plans; independent of lh_ctx_set_f16_stream and lh_ctx_set_f16_tiles.  A change makes every captured graph of an f16 plan on the context that may hold such
+ * a launch (ticks, speculative passes) run eagerly once and be captured anew.  lh_ctx_f16_planes: the current value (0 | 1; ctx NULL: 0). */
+int lh_ctx_set_f16_planes(lh_ctx* ctx, int on);
+int lh_ctx_f16_planes(lh_ctx* ctx);
+/* The ring image of k_stream_b9_h (csrc/stream_b9h_layout.h; pure host functions, for checks) for maxt (1..8) weight tiles and nct (1..4) column tiles.
+ * lh_stream_b9h_piece: DMA piece q (< 2 maxt + 6 nct), lane (< 64): out = {byte offset in the image, kind (0 weights, 1 + p plane p), row fetched (weights:
+ * image row, planes: activation row), source granule of the row's 128 chunk bytes}.  lh_stream_b9h_read_off: byte offset in the image of the 16 bytes (chunk
+ * columns 32 kb + 8 slot .. + 7) MFMA lane (r16 < 16, slot < 4) reads for k-block kb (< 2) - plane -1: of weight tile slot t (< maxt), plane 0..2: of column
+ * tile t (< nct) of that plane.  lh_stream_b9h_product: product i (< nprod) of the nprod (6 | 8) the kernel issues per weight: out = {activation plane,
+ * weight part} (0 hi, 1 mid, 2 lo).  An argument out of range: -1. */
+int lh_stream_b9h_piece(uint32_t maxt, uint32_t nct, uint32_t q, uint32_t lane, uint32_t out[4]);
+int64_t lh_stream_b9h_read_off(uint32_t maxt, uint32_t nct, int plane, uint32_t t, uint32_t r16, uint32_t kb, uint32_t slot);
+int lh_stream_b9h_product(int nprod, int i, int out[2]);
 /* Block-int4 models on the bf16 stream kernel of 5..64 rows of a tick / 5..88 of a prompt (csrc/kernels_stream_q4b.h).  lh_ctx_set_q4_stream(ctx, on): with
  * on != 0 every Eval of a block-int4 plan of this context that takes the route over activation planes hands the k_stream_q8b launch sites the model's own
  * nibble planes and scale planes (k_stream_q4b) and enqueues no k_expand_q4 pass for a matrix that only such launches read; a launch that still reads int8

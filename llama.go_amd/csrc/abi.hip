@@ -3,6 +3,7 @@
 #include "common.h"
 #include "kernels_q8_pack.h"
 #include "stream_f16_layout.h"
+#include "stream_b9h_layout.h"
 #include "stream_q4_layout.h"
 #include "gemm_q4_layout.h"
 #include "gemm_f16_layout.h"
@@ -280,6 +281,8 @@ int lh_ctx_create(int device, void* stream, lh_ctx** out) {
     c->f16_stream = hs && hs[0] == '1' ? 1 : 0;
     const char* ht = getenv("LLAMAHIP_F16_TILES");
     c->f16_tiles = ht && ht[0] == '1' ? 1 : 0;
+    const char* hp = getenv("LLAMAHIP_F16_PLANES");
+    c->f16_planes = hp && hp[0] == '1' ? 1 : 0;
     const char* qs = getenv("LLAMAHIP_Q4_STREAM");
     c->q4_stream = qs && qs[0] == '1' ? 1 : 0;
     const char* qt = getenv("LLAMAHIP_Q4_TILES");
@@ -301,6 +304,13 @@ int lh_ctx_set_f16_tiles(lh_ctx* ctx, int on) {
     return LH_OK;
 }
 int lh_ctx_f16_tiles(lh_ctx* ctx) { return ctx ? ctx->f16_tiles : 0; }
+int lh_ctx_set_f16_planes(lh_ctx* ctx, int on) {
+    if (!ctx) return LH_EINVAL;
+    const int v = on ? 1 : 0;
+    if (v != ctx->f16_planes) { ctx->f16_planes = v; ++ctx->f16_stream_gen; }   // (one counter for both f16 switches of the captured graphs' key)
+    return LH_OK;
+}
+int lh_ctx_f16_planes(lh_ctx* ctx) { return ctx ? ctx->f16_planes : 0; }
 int lh_ctx_set_q4_stream(lh_ctx* ctx, int on) {
     if (!ctx) return LH_EINVAL;
     const int v = on ? 1 : 0;
@@ -364,6 +374,22 @@ int lh_gemm_f16_piece(uint32_t p, uint32_t lane, uint32_t out[3]) {
 int64_t lh_gemm_f16_w_read_off(uint32_t wm, uint32_t li, uint32_t lh_, uint32_t kk) {
     if (wm >= 8 || li >= 32 || lh_ >= 2 || kk >= 2) return -1;
     return (int64_t)lh::gemm_h_w_read_off(wm, li, lh_, kk);
+}
+static bool b9h_shape(uint32_t maxt, uint32_t nct) { return maxt >= 1 && maxt <= 8 && nct >= 1 && nct <= 4; }
+int lh_stream_b9h_piece(uint32_t maxt, uint32_t nct, uint32_t q, uint32_t lane, uint32_t out[4]) {
+    if (!b9h_shape(maxt, nct) || q >= lh::b9h_pieces(maxt, nct) || lane >= 64 || !out) return -1;
+    const lh::B9hPiece pc = lh::b9h_piece(maxt, nct, q, lane);
+    out[0] = pc.dst; out[1] = pc.kind; out[2] = pc.row; out[3] = pc.gran;
+    return 0;
+}
+int64_t lh_stream_b9h_read_off(uint32_t maxt, uint32_t nct, int plane, uint32_t t, uint32_t r16, uint32_t kb, uint32_t slot) {
+    if (!b9h_shape(maxt, nct) || plane < -1 || plane > 2 || t >= (plane < 0 ? maxt : nct) || r16 >= 16 || kb >= 2 || slot >= 4) return -1;
+    return plane < 0 ? (int64_t)lh::b9h_w_read_off(t, r16, kb, slot) : (int64_t)lh::b9h_x_read_off(maxt, nct, (uint32_t)plane, t, r16, kb, slot);
+}
+int lh_stream_b9h_product(int nprod, int i, int out[2]) {
+    if ((nprod != 6 && nprod != 8) || i < 0 || i >= nprod || !out) return -1;
+    out[0] = lh::b9h_product_x(nprod, i); out[1] = lh::b9h_product_w(nprod, i);
+    return 0;
 }
 int64_t lh_stream_f16_image_off(uint32_t kc, uint32_t r, uint32_t g) {
     if ((kc != 64 && kc != 128) || r >= 128 || g >= kc / 8) return -1;

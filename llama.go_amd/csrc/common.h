@@ -160,6 +160,10 @@ struct lh_ctx {
     // holds it: k_gemm_b9 takes more than 128 rows (gemm_b9_ok), and every captured graph - ticks of at most 64 pods, speculative passes of a few rows,
     // the decode step - enqueues fewer, so the launch the switch chooses is always an eager one.
     int f16_tiles = 0;
+    // lh_ctx_set_f16_planes: f16 plans hand the k_stream_b9 launch sites of their Planes route (49..64 rows) the model's halves (k_stream_b9_h,
+    // kernels_stream_b9_h.h).  A switch that chooses a kernel inside captured graphs (ticks of 49..64 pods, speculative passes): its changes are counted in
+    // f16_stream_gen and its value is folded into the same key field as f16_stream (f16_stream_key, plan.hip).
+    int f16_planes = 0;
     // lh_ctx_set_q4_stream: block-int4 plans hand the k_stream_q8b launch sites of their Planes route the model's nibbles (k_stream_q4b,
     // kernels_stream_q4b.h).  A switch that chooses a kernel, like f16_stream: q4_stream_gen counts the changes for the same captured graphs' keys
     int q4_stream = 0;

@@ -12,6 +12,7 @@
 #include "kernels_stream_q8b.h"
 #include "kernels_stream_q4b.h"
 #include "kernels_stream_b9.h"
+#include "kernels_stream_b9_h.h"
 #include "kernels_gemm_b9.h"
 #include "kernels_gemm_q4.h"
 #include "kernels_rows.h"
@@ -748,6 +749,7 @@ static int launch_gemm_q4b3(lh_ctx* ctx, GemmArgs a, const char* name, uint32_t 
 struct Q4Src {
     const float* nib[3];
     uint64_t n;
+    bool half = false;   // nib[] are the halves of an f16 model instead (eval_planes under lh_ctx_set_f16_planes): handed to the launch as they are, never expanded
     void expand(lh_ctx* ctx, const float* const* w, uint32_t groups) const {
         for (uint32_t g = 0; g < groups; ++g) expand_q4_launch(ctx, nib[g], (void*)w[g], n);   // (a launch error surfaces at the layer's hipGetLastError)
     }
@@ -1247,11 +1249,32 @@ static int launch_stream_q8b_maxt(lh_ctx* ctx, const StreamArgs& a, const char* 
 // with eight), and the kernel is power-bound (the chip holds 1.6-1.9 GHz under it), so an MFMA saved is time saved: 92.2 -> 88.0 us.  Six products
 // (also xm * wl and xl * wm, 2^-24 each) measured 79.8 us at rms 6.311e-07 - not taken: those terms are the size of an fp32 product's own rounding.
 static constexpr int B9S_PRODUCTS = 8;
+// wdt = 1: a.w[] are the halves of an f16 model (k_stream_b9_h, kernels_stream_b9_h.h) - the same MAXT, NCT, CSP, grid and K-split, and ST_NA exactly where
+// the fp32 chain answers it (the fp32 ring predicate decides although halves would fit more: an f16 model must not take a launch its widened twin does not);
+// the ring depth is the half kernel's own and no part of the sums.  -DB9SH_PRODUCTS=8 issues the two products of the weights' zero part as well (DESIGN 3k:
+// the fallback, had six not been byte-equal on the GPU).
+#ifndef B9SH_PRODUCTS
+#define B9SH_PRODUCTS 6
+#endif
 template <int MAXT, int NCT>
-static int launch_stream_b9(lh_ctx* ctx, const StreamArgs& a, const char* name) {
+static int launch_stream_b9(lh_ctx* ctx, const StreamArgs& a, const char* name, int wdt = 0) {
     constexpr int NIMG = stream_b9_nimg(MAXT, NCT, 4);
     if constexpr (NIMG < 2 || (MAXT >= 8 && NCT >= 4)) return ST_NA;
-    else {
+    else if (wdt == 1) {
+        constexpr int NIMGH = b9h_nimg(MAXT, NCT, B9SH_NIMG_CAP);
+        static bool flags_h[16] = {};
+        auto kern = k_stream_b9_h<MAXT, NCT, NIMGH, B9SH_PRODUCTS>;
+        const size_t lds = std::max<size_t>((size_t)NIMGH * b9h_image_bytes(MAXT, NCT), 82 * 1024);   // one workgroup per CU
+        int rc = set_lds_once(ctx, kern, lds, flags_h);
+        if (rc) return rc;
+        if (g_prepare_only) return 0;
+        const uint32_t grid = a.ksplit > 1 ? (uint32_t)ctx->ds->num_cu / a.ksplit * a.ksplit : (uint32_t)ctx->ds->num_cu;
+        ProfScope ps(ctx->stream, name, (uint64_t)a.groups * a.M * a.K * 2);
+        LH_TRACE("k_stream_b9_h<%d,%d,%d,%d>/s%u", MAXT, NCT, NIMGH, B9SH_PRODUCTS, a.ksplit > 1 ? a.ksplit : 1u);
+        LH_LAUNCH_AS("k_stream_b9_h", kern, dim3(grid), dim3(B9S_TH), lds, ctx->stream, a);
+        LH_HIP(ctx, hipGetLastError());
+        return 0;
+    } else {
         static bool flags[16] = {};
         auto kern = k_stream_b9<MAXT, NCT, NIMG, B9S_PRODUCTS>;
         const size_t lds = std::max<size_t>((size_t)NIMG * stream_b9_image_bytes(MAXT, NCT), 82 * 1024);   // one workgroup per CU
@@ -1267,21 +1290,21 @@ static int launch_stream_b9(lh_ctx* ctx, const StreamArgs& a, const char* name) 
     }
 }
 template <int MAXT>
-static int launch_stream_b9_n(lh_ctx* ctx, const StreamArgs& a, const char* name) {
+static int launch_stream_b9_n(lh_ctx* ctx, const StreamArgs& a, const char* name, int wdt) {
     if (a.K % B9S_KC || a.K / B9S_KC < (a.ksplit > 1 ? a.ksplit : 1u)) return ST_NA;
-    if (a.n <= 16) return launch_stream_b9<MAXT, 1>(ctx, a, name);
-    if (a.n <= 32) return launch_stream_b9<MAXT, 2>(ctx, a, name);
-    if (a.n <= 48) return launch_stream_b9<MAXT, 3>(ctx, a, name);
-    if (a.n <= 64) return launch_stream_b9<MAXT, 4>(ctx, a, name);
+    if (a.n <= 16) return launch_stream_b9<MAXT, 1>(ctx, a, name, wdt);
+    if (a.n <= 32) return launch_stream_b9<MAXT, 2>(ctx, a, name, wdt);
+    if (a.n <= 48) return launch_stream_b9<MAXT, 3>(ctx, a, name, wdt);
+    if (a.n <= 64) return launch_stream_b9<MAXT, 4>(ctx, a, name, wdt);
     return ST_NA;
 }
-static int launch_stream_b9_maxt(lh_ctx* ctx, const StreamArgs& a, const char* name, uint32_t maxt) {
-    return with_stream_maxt(maxt, [&](auto mt) { return launch_stream_b9_n<decltype(mt)::value>(ctx, a, name); });
+static int launch_stream_b9_maxt(lh_ctx* ctx, const StreamArgs& a, const char* name, uint32_t maxt, int wdt = 0) {
+    return with_stream_maxt(maxt, [&](auto mt) { return launch_stream_b9_n<decltype(mt)::value>(ctx, a, name, wdt); });
 }
 static bool stream_b9_built(uint32_t maxt, uint32_t n) { return maxt >= 1 && maxt <= 8 && n >= 1 && n <= 64 && !(maxt > 6 && n > 48); }
 // groups (<= 3) matrices of equal shape - block-int8 (wsc: their scale planes) or fp32 (wsc[g] == nullptr: k_stream_b9) - times the same activation
 // planes in ONE launch; fused: the epilogue (RoPE + cache append | silu * mul).  wdt = 2: wq[] are the nibble planes of a block-int4 model (the alignment
-// checks below then hold for the nibble planes' addresses).
+// checks below then hold for the nibble planes' addresses).  wdt = 1 without scale planes: wq[] are the halves of an f16 model (k_stream_b9_h).
 static int gemm_q8b_group(lh_ctx* ctx, const uint16_t* xs, uint64_t xs_plane, uint32_t ldxs, uint32_t groups, const float* const* wq, const float* const* wsc, float* const* y,
                           const float* const* r, uint32_t M, uint32_t K, uint32_t n, uint32_t ldy, const char* name, const StreamArgs* fused = nullptr, int wdt = 7) {
     if (n == 0 || n > STREAM_ROWS_Q8 || groups > 3 || M % 16 || K % 128 || ldxs % 8 || ldy % 4 || ((uintptr_t)xs & 15) || (xs_plane * 2) % 16) return ST_NA;
@@ -1296,7 +1319,7 @@ static int gemm_q8b_group(lh_ctx* ctx, const uint16_t* xs, uint64_t xs_plane, ui
         a.w[g] = wq[g]; a.ws[g] = wsc[g]; a.y[g] = y ? y[g] : nullptr; a.r[g] = r ? r[g] : nullptr;
         if (((uintptr_t)wq[g] & 15) || ((uintptr_t)a.y[g] & 15) || (a.r[g] && ((uintptr_t)a.r[g] & 15)) || ((uintptr_t)a.ws[g] & 15)) return ST_NA;
     }
-    return a.ws[0] ? launch_stream_q8b_maxt(ctx, a, name, maxt, wdt) : launch_stream_b9_maxt(ctx, a, name, maxt);
+    return a.ws[0] ? launch_stream_q8b_maxt(ctx, a, name, maxt, wdt) : launch_stream_b9_maxt(ctx, a, name, maxt, wdt == 1 ? 1 : 0);
 }
 // One matrix as groups of S workgroups that split the contraction (a workgroup then holds S times the rows for a 1 / S of K: the single-tile
 // matrices wo and w2 read S times less of X out of L2 and run S times fewer, longer chunk loops), k_stream_reduce_norm adds the S partials +
@@ -1319,7 +1342,7 @@ static int gemm_q8b_split(lh_ctx* ctx, const float* wq, const float* wsc, const 
     StreamArgs a = {};
     a.xs = xs; a.xs_plane = xs_plane; a.ldxs = ldxs; a.groups = 1; a.M = M; a.K = K; a.n = n; a.ldy = M; a.w[0] = wq; a.ws[0] = wsc; a.y[0] = ctx->splitk;
     a.ksplit = S; a.ysplit = (uint64_t)n * M;
-    const int rs = wsc ? launch_stream_q8b_maxt(ctx, a, name, maxt, wdt) : launch_stream_b9_maxt(ctx, a, name, maxt);
+    const int rs = wsc ? launch_stream_q8b_maxt(ctx, a, name, maxt, wdt) : launch_stream_b9_maxt(ctx, a, name, maxt, wdt == 1 ? 1 : 0);
     if (rs) return rs;
     if (g_prepare_only) return 0;
     StreamReduceArgs r = {};
@@ -2154,7 +2177,7 @@ static const ModelDesc& sched_md(const Plan* p) { return p->md.wtype == 1 || p->
 // A block-int4 plan carries lh_ctx_set_q4_stream in the same field in the same way (its k_stream_q8b launch sites then launch k_stream_q4b): one key field, the
 // switch of the plan's own weight type - a plan has one weight type, so the two switches never meet in one key.
 static uint64_t f16_stream_key(const Plan* p) {
-    if (p->md.wtype == 1) return (p->ctx->f16_stream_gen << 1) | (uint64_t)p->ctx->f16_stream;
+    if (p->md.wtype == 1) return (p->ctx->f16_stream_gen << 2) | ((uint64_t)p->ctx->f16_planes << 1) | (uint64_t)p->ctx->f16_stream;   // (lh_ctx_set_f16_planes counts its changes in the same counter)
     if (p->md.wtype == 2) return (p->ctx->q4_stream_gen << 1) | (uint64_t)p->ctx->q4_stream;
     return 0;
 }
@@ -2192,6 +2215,7 @@ static const float* route_output(Plan* p, const ModelDesc& m) {
 template <typename F>
 static int q4_stream_src(lh_ctx* ctx, const Q4Src* qs, const float* const* w, uint32_t groups, F&& launch) {
     if (!qs) return launch(w, 7);
+    if (qs->half) return launch(qs->nib, 1);   // f16 halves: the half chain answers exactly what the fp32 chain answers for the shape
     int rs = launch(qs->nib, 2);
     if (rs != ST_NA) return rs;
     const bool was = g_prepare_only;
@@ -2429,12 +2453,23 @@ static int eval_planes(Plan* p, const EvalCall& c, const float* x) {
     // either way) and a matrix is expanded into its slot of the layer image only in front of a launch that reads int8 (Q4Src) - a layer whose launches
     // all stream enqueues no k_expand_q4.  m is the int8 shadow, so every decision here and down the chain is the expanded twin's.
     const bool q4s = &m == &p->md_wide && p->md.wtype == 2 && ctx->q4_stream;
+    // f16 plan with lh_ctx_set_f16_planes on: every launch site of the route reads the model's own halves (k_stream_b9_h, kernels_stream_b9_h.h) - the same
+    // hand-out, Q4Src naming the halves.  b9s_shape_ok above has held every layer launch to a k_stream_b9 instantiation, and the half chain answers ST_NA
+    // exactly where the fp32 chain does, so no k_widen_f16 stands in front of a layer and the image slots stay empty.  m is the fp32 shadow: every decision
+    // here and down the chain is the widened twin's.  (Halves that are not 16-byte aligned - no loader produces them - keep the widened route.)
+    bool hpl = &m == &p->md_wide && p->md.wtype == 1 && ctx->f16_planes;
+    for (uint32_t il = m.layer0; hpl && il < m.layer1; ++il) {
+        const LayerW& S = p->md.layers[il];
+        hpl = (((uintptr_t)S.wq | (uintptr_t)S.wk | (uintptr_t)S.wv | (uintptr_t)S.wo | (uintptr_t)S.w1 | (uintptr_t)S.w3 | (uintptr_t)S.w2) & 15) == 0;
+    }
+    if (hpl && m.last_stage() && ((uintptr_t)p->md.output & 15)) hpl = false;
+    const bool own = q4s || hpl;   // the launch sites are handed the model's own matrices
     for (uint32_t il = m.layer0; il < m.layer1; ++il) {
-        const LayerW& L = q4s ? m.layers[il] : route_layer(p, m, il);       // (q4s: the image slots, nothing in them yet)
-        const LayerW& LS = q4s ? p->md.layers[il] : L;                       // the model's own matrices
+        const LayerW& L = own ? m.layers[il] : route_layer(p, m, il);       // (own: the image slots, nothing in them yet)
+        const LayerW& LS = own ? p->md.layers[il] : L;                       // the model's own matrices
         const uint64_t dd_ = (uint64_t)d * d, dF_ = (uint64_t)d * F;
-        const Q4Src qqkv = {{LS.wq, LS.wk, LS.wv}, dd_}, qo = {{LS.wo}, dd_}, q13 = {{LS.w1, LS.w3}, dF_}, q2 = {{LS.w2}, dF_};
-        auto src = [&](const Q4Src& q) -> const Q4Src* { return q4s ? &q : nullptr; };
+        const Q4Src qqkv = {{LS.wq, LS.wk, LS.wv}, dd_, hpl}, qo = {{LS.wo}, dd_, hpl}, q13 = {{LS.w1, LS.w3}, dF_, hpl}, q2 = {{LS.w2}, dF_, hpl};
+        auto src = [&](const Q4Src& q) -> const Q4Src* { return own ? &q : nullptr; };
         const size_t slot = (size_t)(il - m.cache_layer0) * m.ctx * d;
         if (!h_ready) { TraceScope ts_(ctx->stream, "rmsnorm_rows_s3"); if (!g_prepare_only) LH_LAUNCH(k_rmsnorm_rows_s3, dim3(n), dim3(256), 0, ctx->stream, x, L.attn_norm, (float*)nullptr, hs, pd, d); }
         {   // wq|wk|wv -> RoPE(Q, new K rows) -> K, V appended   (llama.go:263-297)
@@ -2482,24 +2517,27 @@ static int eval_planes(Plan* p, const EvalCall& c, const float* x) {
     }
     if (m.last_stage()) {   // lm_head on the rows the caller reads (llama.go:374-384, 394-401); hs / p->h hold RMSNorm * norm of every row
         const auto [r0, nr] = logits_rows(c);
-        const float* wv = q4s ? m.output : route_output(p, m); const float* sv = m.s_output; float* yv = p->logits + (size_t)r0 * m.V;   // (m.output below: the same address)
-        const Q4Src qout = {{p->md.output}, (uint64_t)m.V * d};
+        const float* wv = own ? m.output : route_output(p, m); const float* sv = m.s_output; float* yv = p->logits + (size_t)r0 * m.V;   // (m.output below: the same address)
+        const Q4Src qout = {{p->md.output}, (uint64_t)m.V * d, hpl};
+        bool out_wide = !hpl;   // hpl: the output matrix is widened only in front of a launch that is not k_stream_b9's, once
         const uint32_t hrow0 = r0;   // (a structured binding is not captured by a lambda before C++20)
         for (uint32_t b0 = 0; b0 < nr; b0 += STREAM_ROWS_Q8) {
             float* yb = yv + (size_t)b0 * m.V;
             const uint32_t nb = std::min(STREAM_ROWS_Q8, nr - b0);
-            rc = q4_stream_src(ctx, q4s ? &qout : nullptr, &wv, 1, [&](const float* const* ws, int wdt) {
+            rc = q4_stream_src(ctx, own ? &qout : nullptr, &wv, 1, [&](const float* const* ws, int wdt) {
                 return gemm_q8b_group(ctx, hs + (size_t)(hrow0 + b0) * d, pd, d, 1, ws, &sv, &yb, nullptr, m.V, d, nb, m.V, m.wtype == 7 ? "q8b_lmhead" : "b9s_lmhead", nullptr, wdt); });
             if (rc == ST_NA && m.wtype == 0 && nb > 1 && m.V % 32 == 0) {
                 // fp32 output matrix with eight row tiles per workgroup next to four column tiles (7B at 49..64 rows): no k_stream_b9 launch of that shape - the two halves
                 // of the vocabulary have one each (four row tiles).  64 pods, 7B: 172 us on k_stream_dma -> see profiles/r06_lmhead_halves.txt
                 const uint32_t Vh = m.V / 2;
-                const float* wh[2] = {m.output, m.output + (size_t)Vh * d};
+                // (hpl: the second half starts Vh * d HALVES into the model's matrix)
+                const float* wh[2] = {hpl ? p->md.output : m.output, hpl ? (const float*)((const uint16_t*)p->md.output + (size_t)Vh * d) : m.output + (size_t)Vh * d};
                 float* yh[2] = {yb, yb + Vh};
                 for (int h2 = 0; h2 < 2; ++h2)
-                    if ((rc = gemm_q8b_group(ctx, hs + (size_t)(r0 + b0) * d, pd, d, 1, &wh[h2], &sv, &yh[h2], nullptr, Vh, d, nb, m.V, "b9s_lmhead"))) break;
+                    if ((rc = gemm_q8b_group(ctx, hs + (size_t)(r0 + b0) * d, pd, d, 1, &wh[h2], &sv, &yh[h2], nullptr, Vh, d, nb, m.V, "b9s_lmhead", nullptr, hpl ? 1 : 7))) break;
             }
             if (rc == ST_NA && m.wtype == 0) {   // fp32 output matrix without a k_stream_b9 launch (eight row tiles next to four column tiles): the fp32 rows
+                if (!out_wide) { widen_f16_launch(ctx, p->md.output, p->wide_out, (uint64_t)m.V * d); out_wide = true; }   // (hpl: one widening pass, directly in front)
                 if (nb == 1) {
                     GemvArgs ga = {};
                     ga.w[0] = m.output; ga.M = m.V; ga.K = d; ga.x = p->h + (size_t)(r0 + b0) * d; ga.y = yb;

@@ -526,6 +526,22 @@ func (ctx *Context) SetF16TilesHIP(on bool) {
 }
 func (ctx *Context) F16TilesHIP() bool { return C.lh_ctx_f16_tiles(ctx.hip.ctx) != 0 }
 
+// SetF16Planes / SetF16PlanesHIP: lh_ctx_set_f16_planes on the lh_ctx the batch / the context evaluates in - the Evals of 49..64 rows of an f16 model
+// (prompts, ticks of 49..64 pods, speculative passes) run their k_stream_b9 launches on the model's halves (k_stream_b9_h, six bf16 products instead of
+// eight) instead of an fp32 image widened in front of every layer (DESIGN 3k).  Same bytes; off by default; without effect on models of another weight
+// type; independent of SetF16StreamHIP and SetF16TilesHIP.
+func (bt *BatchHIP) SetF16Planes(on bool) { bt.ctx.SetF16PlanesHIP(on) }
+func (ctx *Context) SetF16PlanesHIP(on bool) {
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	if rc := C.lh_ctx_set_f16_planes(ctx.hip.ctx, v); rc != 0 {
+		hipHalt(ctx.hip.ctx)
+	}
+}
+func (ctx *Context) F16PlanesHIP() bool { return C.lh_ctx_f16_planes(ctx.hip.ctx) != 0 }
+
 // PoisonWeightImagesHIP / (*BatchHIP).PoisonWeightImages (test instrumentation): lh_ctx_poison_weight_images on the lh_ctx the context / the batch evaluates in - the fp32 / int8 images of f16 /
 // block-int4 matrices filled with 0xFF bytes behind the work already enqueued.  Returns the bytes filled (0: no such image exists).
 func (ctx *Context) PoisonWeightImagesHIP() uint64 {

@@ -462,6 +462,21 @@ class Context:
         L.llamago_F16Tiles.argtypes = [VP]
         return bool(L.llamago_F16Tiles(self.h))
 
+    def SetF16Planes(self, on=True):
+        """llamago_SetF16Planes: Evals of 49..64 rows of an f16 model run their k_stream_b9 launches on the model's halves (k_stream_b9_h), no widening pass per layer."""
+        L = self.ml.lib
+        L.llamago_SetF16Planes.restype = C.c_int
+        L.llamago_SetF16Planes.argtypes = [VP, C.c_int]
+        if L.llamago_SetF16Planes(self.h, 1 if on else 0):
+            raise MLError(f"llamago_SetF16Planes: {self.ml.last_error()}")
+
+    @property
+    def f16_planes(self):
+        L = self.ml.lib
+        L.llamago_F16Planes.restype = C.c_int
+        L.llamago_F16Planes.argtypes = [VP]
+        return bool(L.llamago_F16Planes(self.h))
+
     def TimeComputes(self, on=True):
         """lh_ctx_time_computes: HIP events around every lh_graph_compute of this context; zeroes the sums."""
         L = self.ml.lib
@@ -1144,6 +1159,21 @@ class Batch:
         L.llamago_BatchF16Stream.restype = C.c_int
         L.llamago_BatchF16Stream.argtypes = [VP]
         return bool(L.llamago_BatchF16Stream(self.h))
+
+    def SetF16Planes(self, on=True):
+        """llamago_BatchSetF16Planes: Context.SetF16Planes for the ticks, feeds and speculative passes of this batch."""
+        L = self.ml.lib
+        L.llamago_BatchSetF16Planes.restype = C.c_int
+        L.llamago_BatchSetF16Planes.argtypes = [VP, C.c_int]
+        if L.llamago_BatchSetF16Planes(self.h, 1 if on else 0):
+            raise MLError(f"llamago_BatchSetF16Planes: {self.ml.last_error()}")
+
+    @property
+    def f16_planes(self):
+        L = self.ml.lib
+        L.llamago_BatchF16Planes.restype = C.c_int
+        L.llamago_BatchF16Planes.argtypes = [VP]
+        return bool(L.llamago_BatchF16Planes(self.h))
 
     def GreedyDecode(self, prompts, n_predict, want_logits=False):
         """Every pod: its prompt as one Eval, then greedy steps; returns per pod the ids llama_GreedyDecode gives for its prompt alone."""
