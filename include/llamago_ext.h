@@ -112,6 +112,12 @@ int llamago_F16Tiles(llama_context* c);
  * below): the same for a batch's ticks, feeds and speculative passes. */
 int llamago_SetF16Planes(llama_context* c, int on);
 int llamago_F16Planes(llama_context* c);
+/* lh_ctx_set_wide_planes / lh_ctx_wide_planes (llamahip.h) on the lh_ctx the context evaluates in: with on != 0 a prompt Eval of 65..128 tokens of an f32
+ * model runs its layers on k_stream_b9w (exact bf16 products over activation planes, one weight pass) instead of k_stream_dma.  Off by
+ * default (LLAMAHIP_WIDE_PLANES=1 turns it on for contexts created afterwards); without effect on models of another weight type and on batches.  The
+ * setter returns non-zero (ml_LastError) on a null argument; the getter 0 | 1. */
+int llamago_SetWidePlanes(llama_context* c, int on);
+int llamago_WidePlanes(llama_context* c);
 /* Block-int4 weight matrices (ML_TYPE_Q4_0 = dtype 2 of llamahip.h: 20 bytes per 32 weights; norm vectors and tok_embeddings stay f32).  A 4-bit quant
  * q in [-8, 7] with block scale d IS a block-int8 weight with the same q and d, so every Eval route of such a model produces the bytes its expansion
  * produces: one row and 2..4 rows on 4-bit forms of the decode stream kernels, every other row count on the int8 kernels behind an exact expansion

@@ -130,6 +130,15 @@ int64_t lh_gemm_f16_w_read_off(uint32_t wm, uint32_t li, uint32_t lh, uint32_t k
  * a launch (ticks, speculative passes) run eagerly once and be captured anew.  lh_ctx_f16_planes: the current value (0 | 1; ctx NULL: 0). */
 int lh_ctx_set_f16_planes(lh_ctx* ctx, int on);
 int lh_ctx_f16_planes(lh_ctx* ctx);
+/* fp32 models at 65..128 rows of one weight pass on the bf16 matrix pipe (csrc/kernels_stream_b9w.h).  lh_ctx_set_wide_planes(ctx, on): with on != 0 a
+ * prompt Eval of 65..128 rows of an fp32 plan of this context runs its layers over activation planes on k_stream_b9w (eight exact bf16 products per
+ * weight, one pass over the weights) instead of k_stream_dma's fp32-input MFMAs, where every layer launch of the model's shape has an instantiation;
+ * otherwise, and for the lm_head, the launches are unchanged.  Results differ from the other route in summation order only (both inside the bound of
+ * tests/weight_probe_ref.py).  Off by default; the initial value is LLAMAHIP_WIDE_PLANES=1 of the environment, read once in lh_ctx_create.  Read at
+ * every Eval; accepted and without effect for f16, block-int8 and block-int4 plans, for the rows of a batch and for every other row count.  No captured
+ * graph holds a launch it chooses.  lh_ctx_wide_planes: the current value (0 | 1; ctx NULL: 0). */
+int lh_ctx_set_wide_planes(lh_ctx* ctx, int on);
+int lh_ctx_wide_planes(lh_ctx* ctx);
 /* The ring image of k_stream_b9_h (csrc/stream_b9h_layout.h; pure host functions, for checks) for maxt (1..8) weight tiles and nct (1..4) column tiles.
  * lh_stream_b9h_piece: DMA piece q (< 2 maxt + 6 nct), lane (< 64): out = {byte offset in the image, kind (0 weights, 1 + p plane p), row fetched (weights:
  * image row, planes: activation row), source granule of the row's 128 chunk bytes}.  lh_stream_b9h_read_off: byte offset in the image of the 16 bytes (chunk

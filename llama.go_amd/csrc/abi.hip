@@ -283,6 +283,8 @@ int lh_ctx_create(int device, void* stream, lh_ctx** out) {
     c->f16_tiles = ht && ht[0] == '1' ? 1 : 0;
     const char* hp = getenv("LLAMAHIP_F16_PLANES");
     c->f16_planes = hp && hp[0] == '1' ? 1 : 0;
+    const char* wp = getenv("LLAMAHIP_WIDE_PLANES");
+    c->wide_planes = wp && wp[0] == '1' ? 1 : 0;
     const char* qs = getenv("LLAMAHIP_Q4_STREAM");
     c->q4_stream = qs && qs[0] == '1' ? 1 : 0;
     const char* qt = getenv("LLAMAHIP_Q4_TILES");
@@ -311,6 +313,12 @@ int lh_ctx_set_f16_planes(lh_ctx* ctx, int on) {
     return LH_OK;
 }
 int lh_ctx_f16_planes(lh_ctx* ctx) { return ctx ? ctx->f16_planes : 0; }
+int lh_ctx_set_wide_planes(lh_ctx* ctx, int on) {
+    if (!ctx) return LH_EINVAL;
+    ctx->wide_planes = on ? 1 : 0;   // (no captured graph holds a launch it chooses: common.h)
+    return LH_OK;
+}
+int lh_ctx_wide_planes(lh_ctx* ctx) { return ctx ? ctx->wide_planes : 0; }
 int lh_ctx_set_q4_stream(lh_ctx* ctx, int on) {
     if (!ctx) return LH_EINVAL;
     const int v = on ? 1 : 0;

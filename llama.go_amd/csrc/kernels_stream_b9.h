@@ -35,6 +35,9 @@
 //     [3][NCT * 16 rows][64 bf16], 128-byte rows, granule g of row r at g ^ ((r >> 1) & 7) (two rows per bank line).
 // Products: EIGHT of the nine (B9S_PRODUCTS, plan.hip; xl * wl, <= 2^-32 of its product, is dropped).
 // Values: the contract of kernels_gemm_b9.h - exact products for finite inputs of magnitude >= 2^-100 (or 0), nothing promised beyond.
+// Above 64 rows: this kernel stops at four column tiles (an MFMA wave keeps two operand sets of ALL column tiles and the split fragments of half the tiles
+// in registers).  65..128 rows of one pass go to k_stream_b9w (kernels_stream_b9w.h: column halves per MFMA wave, fragments split tile by tile) under
+// lh_ctx_set_wide_planes, and to k_stream_dma otherwise.
 #pragma once
 #include "kernels_stream_q8b.h"
 

@@ -13,6 +13,8 @@
 #include "kernels_stream_q4b.h"
 #include "kernels_stream_b9.h"
 #include "kernels_stream_b9_h.h"
+#include "stream_b9w_layout.h"
+namespace lh_b9w_tu { const void* stream_b9w_kernel(int maxt, int nct, int* nimg); }   // csrc/stream_b9w.hip
 #include "kernels_gemm_b9.h"
 #include "kernels_gemm_q4.h"
 #include "kernels_rows.h"
@@ -1289,6 +1291,31 @@ static int launch_stream_b9(lh_ctx* ctx, const StreamArgs& a, const char* name, 
         return 0;
     }
 }
+// ---- k_stream_b9w (kernels_stream_b9w.h): the same planes and products at 65..128 rows of one pass, five to eight column tiles; only eval_planes under
+// lh_ctx_set_wide_planes hands a launch more than 64 rows.  b9w_built (stream_b9w_layout.h) names the instantiations; every other pair is ST_NA.
+// The instantiations live in csrc/stream_b9w.hip (a translation unit with its own code generation flags); this one only launches them.
+typedef void (*StreamB9wKernel)(const StreamArgs);
+static StreamB9wKernel stream_b9w_kernel(int maxt, int nct, int* nimg) { return (StreamB9wKernel)lh_b9w_tu::stream_b9w_kernel(maxt, nct, nimg); }
+template <int MAXT, int NCT>
+static int launch_stream_b9w(lh_ctx* ctx, const StreamArgs& a, const char* name) {
+    if constexpr (!b9w_built(MAXT, NCT)) return ST_NA;
+    else {
+        static bool flags[16] = {};
+        int nimg = 0;
+        const StreamB9wKernel kern = stream_b9w_kernel(MAXT, NCT, &nimg);
+        if (!kern || nimg != b9w_nimg(MAXT, NCT, 4)) LH_FAIL(ctx, LH_ESHAPE, "k_stream_b9w<%d,%d>: not in the library", MAXT, NCT);   // (a missing kernel is an error, never a fall-back)
+        const size_t lds = std::max<size_t>((size_t)nimg * b9w_image_bytes(MAXT, NCT), 82 * 1024);   // one workgroup per CU
+        int rc = set_lds_once(ctx, kern, lds, flags);
+        if (rc) return rc;
+        if (g_prepare_only) return 0;
+        const uint32_t grid = a.ksplit > 1 ? (uint32_t)ctx->ds->num_cu / a.ksplit * a.ksplit : (uint32_t)ctx->ds->num_cu;
+        ProfScope ps(ctx->stream, name, (uint64_t)a.groups * a.M * a.K * 4);
+        LH_TRACE("k_stream_b9w<%d,%d,%d,%d>/s%u", MAXT, NCT, nimg, B9S_PRODUCTS, a.ksplit > 1 ? a.ksplit : 1u);
+        LH_LAUNCH_AS("k_stream_b9w", kern, dim3(grid), dim3(B9S_TH), lds, ctx->stream, a);
+        LH_HIP(ctx, hipGetLastError());
+        return 0;
+    }
+}
 template <int MAXT>
 static int launch_stream_b9_n(lh_ctx* ctx, const StreamArgs& a, const char* name, int wdt) {
     if (a.K % B9S_KC || a.K / B9S_KC < (a.ksplit > 1 ? a.ksplit : 1u)) return ST_NA;
@@ -1296,6 +1323,11 @@ static int launch_stream_b9_n(lh_ctx* ctx, const StreamArgs& a, const char* name
     if (a.n <= 32) return launch_stream_b9<MAXT, 2>(ctx, a, name, wdt);
     if (a.n <= 48) return launch_stream_b9<MAXT, 3>(ctx, a, name, wdt);
     if (a.n <= 64) return launch_stream_b9<MAXT, 4>(ctx, a, name, wdt);
+    if (wdt != 0) return ST_NA;   // (f16 halves: k_stream_dma_h keeps 65..128 rows)
+    if (a.n <= 80) return launch_stream_b9w<MAXT, 5>(ctx, a, name);
+    if (a.n <= 96) return launch_stream_b9w<MAXT, 6>(ctx, a, name);
+    if (a.n <= 112) return launch_stream_b9w<MAXT, 7>(ctx, a, name);
+    if (a.n <= B9W_MAX_ROWS) return launch_stream_b9w<MAXT, 8>(ctx, a, name);
     return ST_NA;
 }
 static int launch_stream_b9_maxt(lh_ctx* ctx, const StreamArgs& a, const char* name, uint32_t maxt, int wdt = 0) {
@@ -1307,7 +1339,7 @@ static bool stream_b9_built(uint32_t maxt, uint32_t n) { return maxt >= 1 && max
 // checks below then hold for the nibble planes' addresses).  wdt = 1 without scale planes: wq[] are the halves of an f16 model (k_stream_b9_h).
 static int gemm_q8b_group(lh_ctx* ctx, const uint16_t* xs, uint64_t xs_plane, uint32_t ldxs, uint32_t groups, const float* const* wq, const float* const* wsc, float* const* y,
                           const float* const* r, uint32_t M, uint32_t K, uint32_t n, uint32_t ldy, const char* name, const StreamArgs* fused = nullptr, int wdt = 7) {
-    if (n == 0 || n > STREAM_ROWS_Q8 || groups > 3 || M % 16 || K % 128 || ldxs % 8 || ldy % 4 || ((uintptr_t)xs & 15) || (xs_plane * 2) % 16) return ST_NA;
+    if (n == 0 || n > (wsc[0] ? STREAM_ROWS_Q8 : B9W_MAX_ROWS) || groups > 3 || M % 16 || K % 128 || ldxs % 8 || ldy % 4 || ((uintptr_t)xs & 15) || (xs_plane * 2) % 16) return ST_NA;
     const uint32_t ncu = (uint32_t)ctx->ds->num_cu, T = M / 16 * groups;
     const uint32_t maxt = (fused && fused->epi == ST_EPI_SILU_MUL) ? 2 * ((M / 16 + ncu - 1) / ncu) : (T + ncu - 1) / ncu;
     if (maxt > 8) return ST_NA;
@@ -1333,7 +1365,7 @@ static uint32_t q8b_split_groups(uint32_t nchunks, uint32_t ncu) {   // S: fours
 }
 static int gemm_q8b_split(lh_ctx* ctx, const float* wq, const float* wsc, const uint16_t* xs, uint64_t xs_plane, uint32_t ldxs, uint32_t M, uint32_t K, uint32_t n,
                           const float* resid, float* y, const float* gamma, float* h, uint16_t* hs, uint64_t hs_plane, const char* name, int wdt = 7) {
-    if (n == 0 || n > STREAM_ROWS_Q8 || M % 16 || M > 8192 || M % 4 || K % 128 || ldxs % 8 || ((uintptr_t)xs & 15) || (xs_plane * 2) % 16) return ST_NA;
+    if (n == 0 || n > (wsc ? STREAM_ROWS_Q8 : B9W_MAX_ROWS) || M % 16 || M > 8192 || M % 4 || K % 128 || ldxs % 8 || ((uintptr_t)xs & 15) || (xs_plane * 2) % 16) return ST_NA;
     if ((((uintptr_t)wq | (uintptr_t)y | (uintptr_t)resid | (uintptr_t)gamma | (uintptr_t)h | (uintptr_t)hs | (uintptr_t)wsc) & 15)) return ST_NA;
     const uint32_t ncu = (uint32_t)ctx->ds->num_cu, nchunks = wsc ? K / (K % 256 == 0 ? 256u : 128u) : K / (uint32_t)B9S_KC;
     const uint32_t S = q8b_split_groups(nchunks, ncu), ngrp = ncu / S, maxt = (M / 16 + ngrp - 1) / ngrp;
@@ -1760,7 +1792,7 @@ int plan_ensure_rows(Plan* p, uint32_t n) {
     if (n > 1 && (m.wtype == 7 || m.wtype == 0 || m.wtype == 1 || m.wtype == 2)) {   // the activations as planes: every row of a block-int8 plan, up to k_stream_b9's 64 rows of an fp32 one (f16: the fp32 schedule; block-int4: the int8 one)
         if (p->s3) LH_HIP(ctx, hipFree(p->s3));
         p->s3 = nullptr;
-        p->s3_rows = m.wtype == 7 || m.wtype == 2 ? n : std::min<uint32_t>(n, B9S_MAX_ROWS);
+        p->s3_rows = m.wtype == 7 || m.wtype == 2 ? n : std::min<uint32_t>(n, m.wtype == 0 ? B9W_MAX_ROWS : B9S_MAX_ROWS);   // (fp32: k_stream_b9w's 128 rows)
         LH_HIP(ctx, hipMalloc((void**)&p->s3, (size_t)3 * p->s3_rows * (2 * (size_t)m.d + m.F) * 2));
     }
     if (p->tokens_dev) LH_HIP(ctx, hipFree(p->tokens_dev));
@@ -2110,6 +2142,11 @@ static bool b9s_shape_ok(lh_ctx* ctx, const ModelDesc& m, uint32_t n) {
     };
     return stream_b9_built((3 * d / 16 + ncu - 1) / ncu, n) && stream_b9_built(2 * ((F / 16 + ncu - 1) / ncu), n) && stream_b9_built(split_maxt(d), n) && stream_b9_built(split_maxt(F), n);
 }
+// fp32 weights at 65..128 rows of ONE pass on k_stream_b9w (lh_ctx_set_wide_planes): every layer launch has an instantiation (b9w_shape_ok,
+// stream_b9w_layout.h: the same tile counts gemm_q8b_group / gemm_q8b_split arrive at).  The lm_head keeps its launches.
+static bool b9w_shape_ok(lh_ctx* ctx, const ModelDesc& m, uint32_t n) {
+    return m.wtype == 0 && lh::b9w_shape_ok((uint32_t)ctx->ds->num_cu, m.d, m.F, m.hd, n);
+}
 static constexpr uint32_t Q8B_PROMPT_ROWS = 88;   // a prompt takes up to two 64-row passes; from 89 rows the tile GEMM k_gemm_q8b3 (one 128-row tile: 9.0-9.8 ms flat over
                                                   // 65..128 rows on 7B) is ahead of them (8.6 ms at 65 rows, 8.9 at 80, 9.75 at 96, 11.4 at 128: profiles/r05_gemm_q8b3_probe.txt)
 static bool q8_stream_ok(lh_ctx* ctx, const ModelDesc& m, uint32_t n, uint32_t n_min, bool batch_rows = true) {
@@ -2131,7 +2168,8 @@ static bool q8_stream_ok(lh_ctx* ctx, const ModelDesc& m, uint32_t n, uint32_t n
 // do Prefill's tile GEMM RoPE epilogue above 64 rows and its prompt attention kernels, which the at most BATCH_ROWS_MAX rows of a batch never take
 // (plan_batch_rows_ok; lh_batch evaluates what it refuses row by row on the rows' own plans).
 enum class EvalRoute { Step, Rows, Q8Steps, Skinny, Planes, Prefill };
-static EvalRoute eval_route(lh_ctx* ctx, const ModelDesc& m, uint32_t n, bool batched) {
+// wide: the plan's OWN weights are fp32 and lh_ctx_set_wide_planes is on (plan_eval; never for the rows of a batch, which are at most 64)
+static EvalRoute eval_route(lh_ctx* ctx, const ModelDesc& m, uint32_t n, bool batched, bool wide = false) {
     if (n == 1) return EvalRoute::Step;
     if (rows_path_ok(ctx, m, n)) return EvalRoute::Rows;
     // block-int8: 5..64 rows of a tick / 5..88 of a prompt on k_stream_q8b (two 64-row passes from 65); from 89 rows the tile GEMM k_gemm_q8b3 (Prefill)
@@ -2141,6 +2179,7 @@ static EvalRoute eval_route(lh_ctx* ctx, const ModelDesc& m, uint32_t n, bool ba
     if (q8_stream) return EvalRoute::Planes;   // block-int8, up to 64 rows: the bf16 matrix pipe (kernels_stream_q8b.h)
     static const int b9s_min = getenv("LLAMAHIP_B9S_MIN") ? atoi(getenv("LLAMAHIP_B9S_MIN")) : (int)B9S_MIN_ROWS;   // (A/B switch of round 6's measurements: 65 = off)
     if (m.wtype == 0 && (int)n >= b9s_min && n <= B9S_MAX_ROWS) return EvalRoute::Planes;   // fp32, 49..64 rows: the same schedule over planes on k_stream_b9
+    if (wide && !batched && b9w_shape_ok(ctx, m, n)) return EvalRoute::Planes;   // fp32, 65..128 rows of a prompt, switch on: one pass on k_stream_b9w
     return EvalRoute::Prefill;
 }
 // Prefill's grouped MFMA launches: from 9 rows (tile GEMM), fp32 weights from 2 rows on the streaming MFMA kernel
@@ -2439,8 +2478,11 @@ static int eval_planes(Plan* p, const EvalCall& c, const float* x) {
     const BatchRow* rows = c.bc ? c.bc->rows : nullptr;
     float* x_out_dev = c.x_out_dev;
     const uint32_t d = m.d, F = m.F;
-    if (!(m.wtype == 7 ? q8b_shape_ok(ctx, m) : b9s_shape_ok(ctx, m, n))) return ST_NA;
+    // fp32 above 64 rows: only plan_eval under lh_ctx_set_wide_planes sends them here - ONE pass of up to 128 rows per matrix (k_stream_b9w)
+    const bool wide = m.wtype == 0 && n > B9S_MAX_ROWS;
+    if (!(m.wtype == 7 ? q8b_shape_ok(ctx, m) : (wide ? p->md.wtype == 0 && !c.bc && b9w_shape_ok(ctx, m, n) : b9s_shape_ok(ctx, m, n)))) return ST_NA;
     if (!p->s3 || n > p->s3_rows) return ST_NA;
+    const uint32_t PASS = wide ? B9W_MAX_ROWS : STREAM_ROWS_Q8;   // rows of a weight pass
     const float scale = attn_scale(m);
     const uint64_t pd = (uint64_t)p->s3_rows * d, pf = (uint64_t)p->s3_rows * F;   // plane strides (elements)
     uint16_t* hs = p->s3;
@@ -2478,8 +2520,8 @@ static int eval_planes(Plan* p, const EvalCall& c, const float* x) {
             StreamArgs fq = {};
             fq.epi = ST_EPI_QKV_ROPE; fq.q_out = p->q; fq.k_cache = m.kc + slot; fq.v_cache = m.vc + slot; fq.rope = p->rope; fq.hd = m.hd; fq.past = past;
             fq.rows = rows; fq.kv_off = slot;
-            for (uint32_t b0 = 0; b0 < n; b0 += STREAM_ROWS_Q8) {   // (a prompt of 65..128 tokens: two passes over the weights, still 1.5x faster than the tile GEMM)
-                const uint32_t nb = std::min(STREAM_ROWS_Q8, n - b0);
+            for (uint32_t b0 = 0; b0 < n; b0 += PASS) {   // (a prompt of 65..128 tokens: two passes over the weights, still 1.5x faster than the tile GEMM)
+                const uint32_t nb = std::min(PASS, n - b0);
                 fq.q_out = p->q + (size_t)b0 * d; fq.past = past + b0;
                 PLANES_TRY(q4_stream_src(ctx, src(qqkv), wqkv, 3, [&](const float* const* ws, int wdt) {
                     return gemm_q8b_group(ctx, hs + (size_t)b0 * d, pd, d, 3, ws, sqkv, nullptr, nullptr, d, d, nb, d, m.wtype == 7 ? "q8b_wqkv_rope" : "b9s_wqkv_rope", &fq, wdt); }), "wq|wk|wv");
@@ -2487,28 +2529,28 @@ static int eval_planes(Plan* p, const EvalCall& c, const float* x) {
         }
         if ((rc = eval_attention(p, c, slot, scale, true, as, pd))) return rc;   // merged heads -> planes (mfma: this route's shapes all have the grouped MFMA launches)
         // wo + residual + RMSNorm * ffn_norm -> planes   (llama.go:336-351)
-        for (uint32_t b0 = 0; b0 < n; b0 += STREAM_ROWS_Q8)
+        for (uint32_t b0 = 0; b0 < n; b0 += PASS)
             PLANES_TRY(q4_stream_src(ctx, src(qo), &L.wo, 1, [&](const float* const* ws, int wdt) {
-                return gemm_q8b_split(ctx, ws[0], L.s_wo, as + (size_t)b0 * d, pd, d, d, d, std::min(STREAM_ROWS_Q8, n - b0), x + (size_t)b0 * d, p->xb + (size_t)b0 * d, L.ffn_norm, nullptr,
+                return gemm_q8b_split(ctx, ws[0], L.s_wo, as + (size_t)b0 * d, pd, d, d, d, std::min(PASS, n - b0), x + (size_t)b0 * d, p->xb + (size_t)b0 * d, L.ffn_norm, nullptr,
                                       hs + (size_t)b0 * d, pd, m.wtype == 7 ? "q8b_wo_ksplit" : "b9s_wo_ksplit", wdt); }), "wo");
         {   // w1|w3 -> silu(w1 h) * (w3 h) -> planes   (llama.go:354-361)
             const float* w13[2] = {L.w1, L.w3};
             const float* s13[2] = {L.s_w1, L.s_w3};
             StreamArgs fa = {};
             fa.epi = ST_EPI_SILU_MUL; fa.ys = gs; fa.ys_plane = pf; fa.ldys = F;
-            for (uint32_t b0 = 0; b0 < n; b0 += STREAM_ROWS_Q8) {
+            for (uint32_t b0 = 0; b0 < n; b0 += PASS) {
                 fa.ys = gs + (size_t)b0 * F;
                 PLANES_TRY(q4_stream_src(ctx, src(q13), w13, 2, [&](const float* const* ws, int wdt) {
-                    return gemm_q8b_group(ctx, hs + (size_t)b0 * d, pd, d, 2, ws, s13, nullptr, nullptr, F, d, std::min(STREAM_ROWS_Q8, n - b0), F, m.wtype == 7 ? "q8b_w1w3_silu" : "b9s_w1w3_silu", &fa, wdt); }), "w1|w3");
+                    return gemm_q8b_group(ctx, hs + (size_t)b0 * d, pd, d, 2, ws, s13, nullptr, nullptr, F, d, std::min(PASS, n - b0), F, m.wtype == 7 ? "q8b_w1w3_silu" : "b9s_w1w3_silu", &fa, wdt); }), "w1|w3");
             }
         }
         {   // w2 + residual (+ the next layer's first norm, or the final norm, on the reduce pass)   (llama.go:363-372)
             const bool last = il + 1 == m.layer1;
             float* y = (last && !m.last_stage()) ? x_out_dev : p->xa;
             const float* next_gamma = !last ? m.layers[il + 1].attn_norm : (m.last_stage() ? m.norm : nullptr);
-            for (uint32_t b0 = 0; b0 < n; b0 += STREAM_ROWS_Q8)
+            for (uint32_t b0 = 0; b0 < n; b0 += PASS)
                 PLANES_TRY(q4_stream_src(ctx, src(q2), &L.w2, 1, [&](const float* const* ws, int wdt) {
-                    return gemm_q8b_split(ctx, ws[0], L.s_w2, gs + (size_t)b0 * F, pf, F, d, F, std::min(STREAM_ROWS_Q8, n - b0), p->xb + (size_t)b0 * d, y + (size_t)b0 * d, next_gamma,
+                    return gemm_q8b_split(ctx, ws[0], L.s_w2, gs + (size_t)b0 * F, pf, F, d, F, std::min(PASS, n - b0), p->xb + (size_t)b0 * d, y + (size_t)b0 * d, next_gamma,
                                           (last && m.last_stage()) ? p->h + (size_t)b0 * d : nullptr, next_gamma ? hs + (size_t)b0 * d : nullptr, pd, m.wtype == 7 ? "q8b_w2_ksplit" : "b9s_w2_ksplit", wdt); }), "w2");
             h_ready = next_gamma != nullptr;
         }
@@ -2768,7 +2810,7 @@ int plan_eval(Plan* p, const uint32_t* tokens_host, const float* x_in_dev, float
     int rc;
     if (!bc && (rc = plan_ensure_rows(p, n))) return rc;
     const EvalCall c = {tokens_host, x_in_dev, x_out_dev, n, past, last_row_only, bc};
-    const EvalRoute route = eval_route(ctx, sched_md(p), n, bc != nullptr);
+    const EvalRoute route = eval_route(ctx, sched_md(p), n, bc != nullptr, p->md.wtype == 0 && ctx->wide_planes);
     const float* x = nullptr;   // the rows the first layer reads
     if (route != EvalRoute::Step && route != EvalRoute::Q8Steps && (rc = eval_input(p, c, route, &x))) return rc;   // (the single steps embed their own token)
     switch (route) {

@@ -542,6 +542,20 @@ func (ctx *Context) SetF16PlanesHIP(on bool) {
 }
 func (ctx *Context) F16PlanesHIP() bool { return C.lh_ctx_f16_planes(ctx.hip.ctx) != 0 }
 
+// SetWidePlanesHIP: lh_ctx_set_wide_planes on the lh_ctx the context evaluates in - a prompt Eval of 65..128 tokens of an f32 model runs its layers on
+// k_stream_b9w (exact bf16 products over activation planes, one weight pass) instead of k_stream_dma (DESIGN 3b).  Off by default; without effect on
+// models of another weight type and on batches.
+func (ctx *Context) SetWidePlanesHIP(on bool) {
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	if rc := C.lh_ctx_set_wide_planes(ctx.hip.ctx, v); rc != 0 {
+		hipHalt(ctx.hip.ctx)
+	}
+}
+func (ctx *Context) WidePlanesHIP() bool { return C.lh_ctx_wide_planes(ctx.hip.ctx) != 0 }
+
 // PoisonWeightImagesHIP / (*BatchHIP).PoisonWeightImages (test instrumentation): lh_ctx_poison_weight_images on the lh_ctx the context / the batch evaluates in - the fp32 / int8 images of f16 /
 // block-int4 matrices filled with 0xFF bytes behind the work already enqueued.  Returns the bytes filled (0: no such image exists).
 func (ctx *Context) PoisonWeightImagesHIP() uint64 {

@@ -1966,6 +1966,11 @@ int llamago_SetF16Planes(llama_context* c, int on) {
     return lh_ctx_set_f16_planes(c->mlctx->hip, on);
 }
 int llamago_F16Planes(llama_context* c) { return c && c->mlctx ? lh_ctx_f16_planes(c->mlctx->hip) : 0; }
+int llamago_SetWidePlanes(llama_context* c, int on) {
+    if (!c || !c->mlctx || !c->mlctx->hip) return halt_rc("llamago_SetWidePlanes: bad arguments");
+    return lh_ctx_set_wide_planes(c->mlctx->hip, on);
+}
+int llamago_WidePlanes(llama_context* c) { return c && c->mlctx ? lh_ctx_wide_planes(c->mlctx->hip) : 0; }
 int llamago_BatchSetF16Planes(llama_batch* b, int on) {
     if (!b || !b->mlctx || !b->mlctx->hip) return halt_rc("llamago_BatchSetF16Planes: bad arguments");
     return lh_ctx_set_f16_planes(b->mlctx->hip, on);

@@ -477,6 +477,21 @@ class Context:
         L.llamago_F16Planes.argtypes = [VP]
         return bool(L.llamago_F16Planes(self.h))
 
+    def SetWidePlanes(self, on=True):
+        """llamago_SetWidePlanes: prompt Evals of 65..128 tokens of an f32 model run their layers on k_stream_b9w (one pass over activation planes) instead of k_stream_dma."""
+        L = self.ml.lib
+        L.llamago_SetWidePlanes.restype = C.c_int
+        L.llamago_SetWidePlanes.argtypes = [VP, C.c_int]
+        if L.llamago_SetWidePlanes(self.h, 1 if on else 0):
+            raise MLError(f"llamago_SetWidePlanes: {self.ml.last_error()}")
+
+    @property
+    def wide_planes(self):
+        L = self.ml.lib
+        L.llamago_WidePlanes.restype = C.c_int
+        L.llamago_WidePlanes.argtypes = [VP]
+        return bool(L.llamago_WidePlanes(self.h))
+
     def TimeComputes(self, on=True):
         """lh_ctx_time_computes: HIP events around every lh_graph_compute of this context; zeroes the sums."""
         L = self.ml.lib
