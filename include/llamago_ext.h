@@ -107,14 +107,17 @@ int llamago_F16Tiles(llama_context* c);
 /* lh_ctx_set_f16_planes / lh_ctx_f16_planes (llamahip.h) on the lh_ctx the context / the batch evaluates in: with on != 0 the Evals of 49..64 rows of an f16
  * model (prompts, ticks of 49..64 pods, speculative passes) run their k_stream_b9 launches on the model's halves (k_stream_b9_h: six bf16 products per weight
  * instead of eight, no widening pass in front of a layer) - the same bytes ("Native planes kernel").  Off by default (LLAMAHIP_F16_PLANES=1 turns
- * it on for contexts created afterwards); without effect on models of another weight type; independent of llamago_SetF16Stream / llamago_SetF16Tiles.  The
+ * it on for contexts created afterwards); without effect on models of another weight type; independent of llamago_SetF16Stream / llamago_SetF16Tiles.
+ * Together with llamago_SetWidePlanes a prompt Eval of 65..128 tokens of an f16 model runs on k_stream_b9w_h over the halves ("Native wide planes kernel").  The
  * setters return non-zero (ml_LastError) on a null argument; the getters 0 | 1.  llamago_BatchSetF16Planes / llamago_BatchF16Planes (declared with the batch
  * below): the same for a batch's ticks, feeds and speculative passes. */
 int llamago_SetF16Planes(llama_context* c, int on);
 int llamago_F16Planes(llama_context* c);
 /* lh_ctx_set_wide_planes / lh_ctx_wide_planes (llamahip.h) on the lh_ctx the context evaluates in: with on != 0 a prompt Eval of 65..128 tokens of an f32
  * model runs its layers on k_stream_b9w (exact bf16 products over activation planes, one weight pass) instead of k_stream_dma.  Off by
- * default (LLAMAHIP_WIDE_PLANES=1 turns it on for contexts created afterwards); without effect on models of another weight type and on batches.  The
+ * default (LLAMAHIP_WIDE_PLANES=1 turns it on for contexts created afterwards); without effect on quantised models and on batches.  An f16 model follows
+ * it only while llamago_SetF16Planes is on as well: the same route on k_stream_b9w_h over the model's halves, byte for byte the widened model's results
+ * under this switch; with llamago_SetF16Planes off it is without effect on f16 models.  The
  * setter returns non-zero (ml_LastError) on a null argument; the getter 0 | 1. */
 int llamago_SetWidePlanes(llama_context* c, int on);
 int llamago_WidePlanes(llama_context* c);

@@ -127,7 +127,9 @@ int64_t lh_gemm_f16_w_read_off(uint32_t wm, uint32_t li, uint32_t lh, uint32_t k
  * k_stream_b9 and is widened once, directly in front, otherwise.  Byte for byte the same results.  Off by default; the initial value is
  * LLAMAHIP_F16_PLANES=1 of the environment, read once in lh_ctx_create.  Read at every Eval; accepted and without effect for fp32, block-int8 and block-int4
  * plans; independent of lh_ctx_set_f16_stream and lh_ctx_set_f16_tiles.  A change makes every captured graph of an f16 plan on the context that may hold such
- * a launch (ticks, speculative passes) run eagerly once and be captured anew.  lh_ctx_f16_planes: the current value (0 | 1; ctx NULL: 0). */
+ * a launch (ticks, speculative passes) run eagerly once and be captured anew.  Together with lh_ctx_set_wide_planes the same holds for a prompt Eval of
+ * 65..128 rows: its layers run on k_stream_b9w_h (csrc/kernels_stream_b9w_h.h) over the halves, byte for byte the fp32 twin's results under
+ * lh_ctx_set_wide_planes.  lh_ctx_f16_planes: the current value (0 | 1; ctx NULL: 0). */
 int lh_ctx_set_f16_planes(lh_ctx* ctx, int on);
 int lh_ctx_f16_planes(lh_ctx* ctx);
 /* fp32 models at 65..128 rows of one weight pass on the bf16 matrix pipe (csrc/kernels_stream_b9w.h).  lh_ctx_set_wide_planes(ctx, on): with on != 0 a
@@ -135,8 +137,10 @@ int lh_ctx_f16_planes(lh_ctx* ctx);
  * weight, one pass over the weights) instead of k_stream_dma's fp32-input MFMAs, where every layer launch of the model's shape has an instantiation;
  * otherwise, and for the lm_head, the launches are unchanged.  Results differ from the other route in summation order only (both inside the bound of
  * tests/weight_probe_ref.py).  Off by default; the initial value is LLAMAHIP_WIDE_PLANES=1 of the environment, read once in lh_ctx_create.  Read at
- * every Eval; accepted and without effect for f16, block-int8 and block-int4 plans, for the rows of a batch and for every other row count.  No captured
- * graph holds a launch it chooses.  lh_ctx_wide_planes: the current value (0 | 1; ctx NULL: 0). */
+ * every Eval; accepted and without effect for block-int8 and block-int4 plans, for the rows of a batch and for every other row count.  An f16 plan follows
+ * it only while lh_ctx_set_f16_planes is on as well: the same route with the model's halves handed to k_stream_b9w_h (six exact products per weight, no
+ * k_widen_f16 pass in front of a layer), byte for byte the results of the widened model under this switch; with lh_ctx_set_f16_planes off it is without
+ * effect for f16 plans.  No captured graph holds a launch it chooses.  lh_ctx_wide_planes: the current value (0 | 1; ctx NULL: 0). */
 int lh_ctx_set_wide_planes(lh_ctx* ctx, int on);
 int lh_ctx_wide_planes(lh_ctx* ctx);
 /* The ring image of k_stream_b9_h (csrc/stream_b9h_layout.h; pure host functions, for checks) for maxt (1..8) weight tiles and nct (1..4) column tiles.
@@ -148,6 +152,11 @@ int lh_ctx_wide_planes(lh_ctx* ctx);
 int lh_stream_b9h_piece(uint32_t maxt, uint32_t nct, uint32_t q, uint32_t lane, uint32_t out[4]);
 int64_t lh_stream_b9h_read_off(uint32_t maxt, uint32_t nct, int plane, uint32_t t, uint32_t r16, uint32_t kb, uint32_t slot);
 int lh_stream_b9h_product(int nprod, int i, int out[2]);
+/* The ring image of k_stream_b9w_h (csrc/stream_b9wh_layout.h; pure host functions, for checks) for maxt (1, 2, 3, 4, 6, 8) weight tiles and nct (5..8)
+ * column tiles: maxt * 2048 + nct * 6144 bytes in 2 maxt + 6 nct pieces.  Arguments and results as lh_stream_b9h_piece / lh_stream_b9h_read_off; the kernel's
+ * products are lh_stream_b9h_product's.  An argument out of range: -1. */
+int lh_stream_b9wh_piece(uint32_t maxt, uint32_t nct, uint32_t q, uint32_t lane, uint32_t out[4]);
+int64_t lh_stream_b9wh_read_off(uint32_t maxt, uint32_t nct, int plane, uint32_t t, uint32_t r16, uint32_t kb, uint32_t slot);
 /* Block-int4 models on the bf16 stream kernel of 5..64 rows of a tick / 5..88 of a prompt (csrc/kernels_stream_q4b.h).  lh_ctx_set_q4_stream(ctx, on): with
  * on != 0 every Eval of a block-int4 plan of this context that takes the route over activation planes hands the k_stream_q8b launch sites the model's own
  * nibble planes and scale planes (k_stream_q4b) and enqueues no k_expand_q4 pass for a matrix that only such launches read; a launch that still reads int8

@@ -4,6 +4,7 @@
 #include "kernels_q8_pack.h"
 #include "stream_f16_layout.h"
 #include "stream_b9h_layout.h"
+#include "stream_b9wh_layout.h"
 #include "stream_q4_layout.h"
 #include "gemm_q4_layout.h"
 #include "gemm_f16_layout.h"
@@ -398,6 +399,16 @@ int lh_stream_b9h_product(int nprod, int i, int out[2]) {
     if ((nprod != 6 && nprod != 8) || i < 0 || i >= nprod || !out) return -1;
     out[0] = lh::b9h_product_x(nprod, i); out[1] = lh::b9h_product_w(nprod, i);
     return 0;
+}
+int lh_stream_b9wh_piece(uint32_t maxt, uint32_t nct, uint32_t q, uint32_t lane, uint32_t out[4]) {
+    if (!lh::b9wh_built(maxt, nct) || q >= lh::b9wh_pieces(maxt, nct) || lane >= 64 || !out) return -1;
+    const lh::B9hPiece pc = lh::b9wh_piece(maxt, nct, q, lane);
+    out[0] = pc.dst; out[1] = pc.kind; out[2] = pc.row; out[3] = pc.gran;
+    return 0;
+}
+int64_t lh_stream_b9wh_read_off(uint32_t maxt, uint32_t nct, int plane, uint32_t t, uint32_t r16, uint32_t kb, uint32_t slot) {
+    if (!lh::b9wh_built(maxt, nct) || plane < -1 || plane > 2 || t >= (plane < 0 ? maxt : nct) || r16 >= 16 || kb >= 2 || slot >= 4) return -1;
+    return plane < 0 ? (int64_t)lh::b9wh_w_read_off(t, r16, kb, slot) : (int64_t)lh::b9wh_x_read_off(maxt, nct, (uint32_t)plane, t, r16, kb, slot);
 }
 int64_t lh_stream_f16_image_off(uint32_t kc, uint32_t r, uint32_t g) {
     if ((kc != 64 && kc != 128) || r >= 128 || g >= kc / 8) return -1;

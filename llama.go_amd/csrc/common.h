@@ -165,7 +165,7 @@ struct lh_ctx {
     // f16_stream_gen and its value is folded into the same key field as f16_stream (f16_stream_key, plan.hip).
     int f16_planes = 0;
     // lh_ctx_set_wide_planes: fp32 plans run a prompt Eval of 65..128 rows as ONE pass over activation planes on k_stream_b9w (kernels_stream_b9w.h)
-    // instead of k_stream_dma.  No key of a captured graph holds it: every captured graph - ticks of at most 64 pods, speculative passes, the decode
+    // instead of k_stream_dma; f16 plans with f16_planes on as well: the same route on k_stream_b9w_h over the halves.  No key of a captured graph holds it: every captured graph - ticks of at most 64 pods, speculative passes, the decode
     // step - enqueues at most 64 rows, and rows of a batch never take the route, so a launch the switch chooses is always an eager one.
     int wide_planes = 0;
     // lh_ctx_set_q4_stream: block-int4 plans hand the k_stream_q8b launch sites of their Planes route the model's nibbles (k_stream_q4b,

@@ -14,7 +14,8 @@
 #include "kernels_stream_b9.h"
 #include "kernels_stream_b9_h.h"
 #include "stream_b9w_layout.h"
-namespace lh_b9w_tu { const void* stream_b9w_kernel(int maxt, int nct, int* nimg); }   // csrc/stream_b9w.hip
+#include "stream_b9wh_layout.h"
+namespace lh_b9w_tu { const void* stream_b9w_kernel(int maxt, int nct, int wdt, int* nimg, int* nprod); }   // csrc/stream_b9w.hip
 #include "kernels_gemm_b9.h"
 #include "kernels_gemm_q4.h"
 #include "kernels_rows.h"
@@ -1294,15 +1295,33 @@ static int launch_stream_b9(lh_ctx* ctx, const StreamArgs& a, const char* name, 
 // ---- k_stream_b9w (kernels_stream_b9w.h): the same planes and products at 65..128 rows of one pass, five to eight column tiles; only eval_planes under
 // lh_ctx_set_wide_planes hands a launch more than 64 rows.  b9w_built (stream_b9w_layout.h) names the instantiations; every other pair is ST_NA.
 // The instantiations live in csrc/stream_b9w.hip (a translation unit with its own code generation flags); this one only launches them.
+// wdt = 1: a.w[] are the halves of an f16 model (k_stream_b9w_h, kernels_stream_b9w_h.h) - the same MAXT, NCT, grid and K-split, and ST_NA exactly where
+// the fp32 kernel answers it (b9wh_built is b9w_built); the ring depth is the half kernel's own and no part of the sums.
 typedef void (*StreamB9wKernel)(const StreamArgs);
-static StreamB9wKernel stream_b9w_kernel(int maxt, int nct, int* nimg) { return (StreamB9wKernel)lh_b9w_tu::stream_b9w_kernel(maxt, nct, nimg); }
+static StreamB9wKernel stream_b9w_kernel(int maxt, int nct, int wdt, int* nimg, int* nprod) { return (StreamB9wKernel)lh_b9w_tu::stream_b9w_kernel(maxt, nct, wdt, nimg, nprod); }
 template <int MAXT, int NCT>
-static int launch_stream_b9w(lh_ctx* ctx, const StreamArgs& a, const char* name) {
+static int launch_stream_b9w(lh_ctx* ctx, const StreamArgs& a, const char* name, int wdt = 0) {
     if constexpr (!b9w_built(MAXT, NCT)) return ST_NA;
-    else {
+    else if (wdt == 1) {
+        static_assert(b9wh_built(MAXT, NCT), "the half kernel is built wherever the fp32 kernel is");
+        static bool flags_h[16] = {};
+        int nimg = 0, nprod = 0;
+        const StreamB9wKernel kern = stream_b9w_kernel(MAXT, NCT, 1, &nimg, &nprod);
+        if (!kern || nimg != b9wh_nimg(MAXT, NCT, 4)) LH_FAIL(ctx, LH_ESHAPE, "k_stream_b9w_h<%d,%d>: not in the library", MAXT, NCT);   // (a missing kernel is an error, never a fall-back)
+        const size_t lds = std::max<size_t>((size_t)nimg * b9wh_image_bytes(MAXT, NCT), 82 * 1024);   // one workgroup per CU
+        int rc = set_lds_once(ctx, kern, lds, flags_h);
+        if (rc) return rc;
+        if (g_prepare_only) return 0;
+        const uint32_t grid = a.ksplit > 1 ? (uint32_t)ctx->ds->num_cu / a.ksplit * a.ksplit : (uint32_t)ctx->ds->num_cu;
+        ProfScope ps(ctx->stream, name, (uint64_t)a.groups * a.M * a.K * 2);
+        LH_TRACE("k_stream_b9w_h<%d,%d,%d,%d>/s%u", MAXT, NCT, nimg, nprod, a.ksplit > 1 ? a.ksplit : 1u);
+        LH_LAUNCH_AS("k_stream_b9w_h", kern, dim3(grid), dim3(B9S_TH), lds, ctx->stream, a);
+        LH_HIP(ctx, hipGetLastError());
+        return 0;
+    } else {
         static bool flags[16] = {};
-        int nimg = 0;
-        const StreamB9wKernel kern = stream_b9w_kernel(MAXT, NCT, &nimg);
+        int nimg = 0, nprod = 0;
+        const StreamB9wKernel kern = stream_b9w_kernel(MAXT, NCT, 0, &nimg, &nprod);
         if (!kern || nimg != b9w_nimg(MAXT, NCT, 4)) LH_FAIL(ctx, LH_ESHAPE, "k_stream_b9w<%d,%d>: not in the library", MAXT, NCT);   // (a missing kernel is an error, never a fall-back)
         const size_t lds = std::max<size_t>((size_t)nimg * b9w_image_bytes(MAXT, NCT), 82 * 1024);   // one workgroup per CU
         int rc = set_lds_once(ctx, kern, lds, flags);
@@ -1323,11 +1342,10 @@ static int launch_stream_b9_n(lh_ctx* ctx, const StreamArgs& a, const char* name
     if (a.n <= 32) return launch_stream_b9<MAXT, 2>(ctx, a, name, wdt);
     if (a.n <= 48) return launch_stream_b9<MAXT, 3>(ctx, a, name, wdt);
     if (a.n <= 64) return launch_stream_b9<MAXT, 4>(ctx, a, name, wdt);
-    if (wdt != 0) return ST_NA;   // (f16 halves: k_stream_dma_h keeps 65..128 rows)
-    if (a.n <= 80) return launch_stream_b9w<MAXT, 5>(ctx, a, name);
-    if (a.n <= 96) return launch_stream_b9w<MAXT, 6>(ctx, a, name);
-    if (a.n <= 112) return launch_stream_b9w<MAXT, 7>(ctx, a, name);
-    if (a.n <= B9W_MAX_ROWS) return launch_stream_b9w<MAXT, 8>(ctx, a, name);
+    if (a.n <= 80) return launch_stream_b9w<MAXT, 5>(ctx, a, name, wdt);
+    if (a.n <= 96) return launch_stream_b9w<MAXT, 6>(ctx, a, name, wdt);
+    if (a.n <= 112) return launch_stream_b9w<MAXT, 7>(ctx, a, name, wdt);
+    if (a.n <= B9W_MAX_ROWS) return launch_stream_b9w<MAXT, 8>(ctx, a, name, wdt);
     return ST_NA;
 }
 static int launch_stream_b9_maxt(lh_ctx* ctx, const StreamArgs& a, const char* name, uint32_t maxt, int wdt = 0) {
@@ -1792,7 +1810,7 @@ int plan_ensure_rows(Plan* p, uint32_t n) {
     if (n > 1 && (m.wtype == 7 || m.wtype == 0 || m.wtype == 1 || m.wtype == 2)) {   // the activations as planes: every row of a block-int8 plan, up to k_stream_b9's 64 rows of an fp32 one (f16: the fp32 schedule; block-int4: the int8 one)
         if (p->s3) LH_HIP(ctx, hipFree(p->s3));
         p->s3 = nullptr;
-        p->s3_rows = m.wtype == 7 || m.wtype == 2 ? n : std::min<uint32_t>(n, m.wtype == 0 ? B9W_MAX_ROWS : B9S_MAX_ROWS);   // (fp32: k_stream_b9w's 128 rows)
+        p->s3_rows = m.wtype == 7 || m.wtype == 2 ? n : std::min<uint32_t>(n, B9W_MAX_ROWS);   // (fp32 and f16: k_stream_b9w[_h]'s 128 rows)
         LH_HIP(ctx, hipMalloc((void**)&p->s3, (size_t)3 * p->s3_rows * (2 * (size_t)m.d + m.F) * 2));
     }
     if (p->tokens_dev) LH_HIP(ctx, hipFree(p->tokens_dev));
@@ -2215,6 +2233,8 @@ static const ModelDesc& sched_md(const Plan* p) { return p->md.wtype == 1 || p->
 // clears the warm bits - the kernels the new value chooses set their LDS attribute at their first launch (set_lds_once), which must be an eager one.
 // A block-int4 plan carries lh_ctx_set_q4_stream in the same field in the same way (its k_stream_q8b launch sites then launch k_stream_q4b): one key field, the
 // switch of the plan's own weight type - a plan has one weight type, so the two switches never meet in one key.
+// lh_ctx_set_wide_planes is in no key, for f16 plans either: with lh_ctx_set_f16_planes it moves Evals of 65..128 rows to k_stream_b9w_h, and no captured
+// graph can hold a launch of more than 64 rows.
 static uint64_t f16_stream_key(const Plan* p) {
     if (p->md.wtype == 1) return (p->ctx->f16_stream_gen << 2) | ((uint64_t)p->ctx->f16_planes << 1) | (uint64_t)p->ctx->f16_stream;   // (lh_ctx_set_f16_planes counts its changes in the same counter)
     if (p->md.wtype == 2) return (p->ctx->q4_stream_gen << 1) | (uint64_t)p->ctx->q4_stream;
@@ -2478,9 +2498,11 @@ static int eval_planes(Plan* p, const EvalCall& c, const float* x) {
     const BatchRow* rows = c.bc ? c.bc->rows : nullptr;
     float* x_out_dev = c.x_out_dev;
     const uint32_t d = m.d, F = m.F;
-    // fp32 above 64 rows: only plan_eval under lh_ctx_set_wide_planes sends them here - ONE pass of up to 128 rows per matrix (k_stream_b9w)
+    // fp32 above 64 rows: only plan_eval under lh_ctx_set_wide_planes sends them here - ONE pass of up to 128 rows per matrix (k_stream_b9w; an f16 plan
+    // with lh_ctx_set_f16_planes on as well: k_stream_b9w_h over its halves, the hpl hand-out below)
     const bool wide = m.wtype == 0 && n > B9S_MAX_ROWS;
-    if (!(m.wtype == 7 ? q8b_shape_ok(ctx, m) : (wide ? p->md.wtype == 0 && !c.bc && b9w_shape_ok(ctx, m, n) : b9s_shape_ok(ctx, m, n)))) return ST_NA;
+    const bool wide_plan = p->md.wtype == 0 || (p->md.wtype == 1 && ctx->f16_planes);
+    if (!(m.wtype == 7 ? q8b_shape_ok(ctx, m) : (wide ? wide_plan && !c.bc && b9w_shape_ok(ctx, m, n) : b9s_shape_ok(ctx, m, n)))) return ST_NA;
     if (!p->s3 || n > p->s3_rows) return ST_NA;
     const uint32_t PASS = wide ? B9W_MAX_ROWS : STREAM_ROWS_Q8;   // rows of a weight pass
     const float scale = attn_scale(m);
@@ -2499,6 +2521,7 @@ static int eval_planes(Plan* p, const EvalCall& c, const float* x) {
     // hand-out, Q4Src naming the halves.  b9s_shape_ok above has held every layer launch to a k_stream_b9 instantiation, and the half chain answers ST_NA
     // exactly where the fp32 chain does, so no k_widen_f16 stands in front of a layer and the image slots stay empty.  m is the fp32 shadow: every decision
     // here and down the chain is the widened twin's.  (Halves that are not 16-byte aligned - no loader produces them - keep the widened route.)
+    // Above 64 rows (wide) the same hand-out reaches k_stream_b9w_h through launch_stream_b9w; the lm_head keeps its passes of at most 64 rows.
     bool hpl = &m == &p->md_wide && p->md.wtype == 1 && ctx->f16_planes;
     for (uint32_t il = m.layer0; hpl && il < m.layer1; ++il) {
         const LayerW& S = p->md.layers[il];
@@ -2810,7 +2833,8 @@ int plan_eval(Plan* p, const uint32_t* tokens_host, const float* x_in_dev, float
     int rc;
     if (!bc && (rc = plan_ensure_rows(p, n))) return rc;
     const EvalCall c = {tokens_host, x_in_dev, x_out_dev, n, past, last_row_only, bc};
-    const EvalRoute route = eval_route(ctx, sched_md(p), n, bc != nullptr, p->md.wtype == 0 && ctx->wide_planes);
+    // (an f16 plan takes the wide route only with BOTH switches on: its launches then read the model's halves on k_stream_b9w_h)
+    const EvalRoute route = eval_route(ctx, sched_md(p), n, bc != nullptr, (p->md.wtype == 0 || (p->md.wtype == 1 && ctx->f16_planes)) && ctx->wide_planes);
     const float* x = nullptr;   // the rows the first layer reads
     if (route != EvalRoute::Step && route != EvalRoute::Q8Steps && (rc = eval_input(p, c, route, &x))) return rc;   // (the single steps embed their own token)
     switch (route) {

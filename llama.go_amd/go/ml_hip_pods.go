@@ -544,7 +544,8 @@ func (ctx *Context) F16PlanesHIP() bool { return C.lh_ctx_f16_planes(ctx.hip.ctx
 
 // SetWidePlanesHIP: lh_ctx_set_wide_planes on the lh_ctx the context evaluates in - a prompt Eval of 65..128 tokens of an f32 model runs its layers on
 // k_stream_b9w (exact bf16 products over activation planes, one weight pass) instead of k_stream_dma (DESIGN 3b).  Off by default; without effect on
-// models of another weight type and on batches.
+// quantised models and on batches.  An f16 model follows it only while SetF16PlanesHIP is on as well: the same route on k_stream_b9w_h over the halves,
+// byte for byte the widened model's results under this switch (DESIGN 3k).
 func (ctx *Context) SetWidePlanesHIP(on bool) {
 	v := C.int(0)
 	if on {

@@ -478,7 +478,8 @@ class Context:
         return bool(L.llamago_F16Planes(self.h))
 
     def SetWidePlanes(self, on=True):
-        """llamago_SetWidePlanes: prompt Evals of 65..128 tokens of an f32 model run their layers on k_stream_b9w (one pass over activation planes) instead of k_stream_dma."""
+        """llamago_SetWidePlanes: prompt Evals of 65..128 tokens of an f32 model run their layers on k_stream_b9w (one pass over activation planes) instead of k_stream_dma;
+        of an f16 model, while SetF16Planes is on as well, on k_stream_b9w_h over the halves."""
         L = self.ml.lib
         L.llamago_SetWidePlanes.restype = C.c_int
         L.llamago_SetWidePlanes.argtypes = [VP, C.c_int]
