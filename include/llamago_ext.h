@@ -70,7 +70,7 @@ int64_t llamago_PoisonWeightImages(llama_context* c);
  * llamago_NarrowModelF16 / llamago_WidenModelF16 (llamago_QuantizeModelQ8's shape; for synthetic models and the tests' f32 twin): the matrices through
  *   lh_buf_narrow_f16 (round to nearest even; *n_changed, optional, = elements whose value changed) / back through lh_buf_widen_f16 (exact), the old
  *   copies released.  Refused (non-zero, ml_LastError) while contexts, batches or pipelines of the model are alive, and on a block-int8 model.
- * llamago_ModelWeightType: 0 (f32) / 1 (f16) / 2 (block-int4) / 7 (block-int8).
+ * llamago_ModelWeightType: 0 (f32) / 1 (f16) / 2 (block-int4) / 3 (Q4_1) / 7 (block-int8).
  * On an f16 model llamago_SetModelTensor (of a matrix), llamago_QuantizeModelQ8 and llama_SaveModel refuse with a message that says so. */
 llama_model* llamago_LoadModelKeepF16(const char* fileName, uint32_t ctxSize);
 int llamago_NarrowModelF16(llama_model* m, uint64_t* n_changed);
@@ -138,6 +138,25 @@ int llamago_QuantizeModelQ4(llama_model* m);
 int llamago_ExpandModelQ4(llama_model* m);
 int llamago_SaveModelQ4(const llama_model* m, const char* fileName);
 llama_model* llamago_LoadModelKeepQ4(const char* fileName, uint32_t ctxSize);
+/* Q4_1 weight matrices (ML_TYPE_Q4_1 = dtype 3 of llamahip.h: 24 bytes per 32 weights {float d; float m; uint8 qs[16]}; norm vectors and tok_embeddings
+ * stay f32).  The value of a weight is w' = fl32(fma(d, n, m)), one rounding; a Q4_1 model and the f32 model of its w' hold identical values.  One row
+ * and 2..4 rows run on the nibbles (k_gemv_q41s / k_gemv_q41_rows; a row of a 2..4-row pass is the one-row step bit for bit); every other row count runs
+ * the fp32 schedule over an exact fp32 image and produces the bytes the expanded model produces.
+ * llamago_QuantizeModelQ41 (llamago_QuantizeModelQ8's shape): every weight matrix of an f32 model through lh_buf_quantize_q41, the f32 copies released.
+ * llamago_ExpandModelQ41: the matrices through lh_buf_expand_q41 - an f32 model of the w'.
+ * Both are refused (non-zero, ml_LastError) while contexts, batches or pipelines of the model are alive, and on a model of another weight type.
+ * llamago_ModelWeightType then returns 3 / 0.  On a Q4_1 model llamago_SetModelTensor (of a matrix), llamago_QuantizeModelQ8 / Q4,
+ * llamago_NarrowModelF16 and llama_SaveModel refuse with a message that says so.
+ * llamago_SaveModelQ41: a Q4_1 model as a ggjt file of ftype 3 - the matrices as their 24-byte blocks, norm vectors and tok_embeddings f32.
+ *   llama_LoadModel refuses such a file as the reference does (llama.go:956-959).
+ * llamago_LoadModelKeepQ41: llama_LoadModel, except that a file whose weight matrices (seven per layer + output) are ALL Q4_1 has their blocks registered
+ *   as they are (lh_tensor_register dtype 3: every bit kept); any other file loads exactly as llama_LoadModel loads it. */
+int llamago_QuantizeModelQ41(llama_model* m);
+int llamago_ExpandModelQ41(llama_model* m);
+int llamago_SaveModelQ41(const llama_model* m, const char* fileName);
+llama_model* llamago_LoadModelKeepQ41(const char* fileName, uint32_t ctxSize);
+/* the nelements / 32 blocks of 24 bytes of one weight matrix of a Q4_1 model, bit for bit what was registered (nblocks must be that count) */
+int llamago_ReadTensorQ41(llama_model* m, const char* name, void* dst_blocks, uint64_t nblocks);
 
 /* ---- [product] harness helper of the kept decode graph (no GPU needed) -------------------------------------------------- */
 /* The array llama_Eval hands to lh_graph_compute for N tokens (ids 1..N) at pastQuery, as numbers: per tensor 16 int64 = op, dtype, flags, ne[4],

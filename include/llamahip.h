@@ -62,11 +62,14 @@ void* lh_ctx_stream(lh_ctx* ctx);
  *      anonymous.  dtype is ml.DType (ml.go:85-94): 0 = f32; 1 = f16 (ml.TYPE_F16, weight matrices only:
  *      host = ne0 * ne1 uint16 halves, row-major [ne1][ne0], kept as halves in device memory); 2 = block-int4
  *      (ml.TYPE_Q4_0, weight matrices only: host = ne0 * ne1 / 32 blocks of 20 bytes {float d; uint8 qs[16]}, w = d * (n - 8),
- *      element 2j in the low nibble of qs[j]; ne0 = cols, a multiple of 32, ne1 = rows; every nibble is kept); 7 = block-int8
+ *      element 2j in the low nibble of qs[j]; ne0 = cols, a multiple of 32, ne1 = rows; every nibble is kept); 3 = Q4_1
+ *      (ml.TYPE_Q4_1, weight matrices only: host = ne0 * ne1 / 32 blocks of 24 bytes {float d; float m; uint8 qs[16]}, the value of a
+ *      weight is w' = fl32(fma(d, n, m)), n in [0, 15], dtype 2's nibble order and shape rule; every bit is kept); 7 = block-int8
  *      (ours).  host may be NULL (buffer zero-filled, as Go's make([]float32) is).  lh_buf_nfloats of a
  *      dtype-1, dtype-2 or dtype-7 buffer is its logical element count; lh_buf_upload, lh_buf_read and
  *      lh_buf_fill_synth refuse a dtype-1 buffer (LH_EINVAL); lh_buf_upload and lh_buf_fill_synth refuse a
- *      dtype-2 buffer (LH_EINVAL), lh_buf_read returns its fl32(d * q) as for dtype 7. ------------- */
+ *      dtype-2 or dtype-3 buffer (LH_EINVAL), lh_buf_read returns fl32(d * q) of a dtype-2 buffer as for dtype 7
+ *      and the values w' of a dtype-3 buffer. ------------------------------------------------------ */
 int lh_tensor_register(lh_ctx* ctx, uint64_t key, int dtype, const uint32_t ne[4], int persistent,
                        const void* host_or_null, lh_buf* out);
 int lh_buf_upload(lh_ctx* ctx, lh_buf buf, uint64_t off_floats, const float* host, uint64_t n);
@@ -87,6 +90,15 @@ int lh_buf_quantize_q4(lh_ctx* ctx, lh_buf src_f32, uint32_t rows, uint32_t cols
 int lh_buf_expand_q4(lh_ctx* ctx, lh_buf src_q4, lh_buf* out_q8);
 /* The 20-byte interchange blocks [block0, block0 + nblocks) of a dtype-2 buffer, exactly as lh_tensor_register takes them (for saving a model). */
 int lh_buf_read_q4(lh_ctx* ctx, lh_buf buf, uint64_t block0, void* dst_blocks, uint64_t nblocks);
+/* Q4_1 (dtype 3).  lh_buf_quantize_q41: a registered fp32 matrix [rows][cols], cols % 32 == 0, quantised on the device (k_quantize_q41) into a new
+ * dtype-3 buffer: per 32 columns m = min w, d = fl32(fl32(max w - m) / 15), n = clamp(rint(fl32(fl32(w - m) / d)), 0, 15) (d = 0 -> n = 0, so w' = m;
+ * a block with a NaN or an infinity, or whose max w - min w overflows: d = m = NaN, n = 0).  A source of another dtype: LH_EUNSUPPORTED, the message names it.
+ * lh_buf_expand_q41: a dtype-3 buffer as a new fp32 buffer of its values w' = fl32(fma(d, n, m)) (k_expand_q41) - the numbers every Q4_1 kernel
+ * multiplies by.  A source of another dtype: LH_EINVAL.  Both synchronise.
+ * lh_buf_read_q41: the 24-byte interchange blocks [block0, block0 + nblocks) of a dtype-3 buffer, exactly as lh_tensor_register takes them. */
+int lh_buf_quantize_q41(lh_ctx* ctx, lh_buf src_f32, uint32_t rows, uint32_t cols, lh_buf* out);
+int lh_buf_expand_q41(lh_ctx* ctx, lh_buf src_q41, lh_buf* out_f32);
+int lh_buf_read_q41(lh_ctx* ctx, lh_buf buf, uint64_t block0, void* dst_blocks, uint64_t nblocks);
 /* f16 (dtype 1).  lh_buf_narrow_f16: a registered fp32 matrix [rows][cols] converted on the device (k_narrow_f16) into a new dtype-1 buffer: round to
  * nearest even, overflow to +-inf, -0 kept; *n_changed (optional) = the elements whose value changed (0 for anything that came from an f16 file).
  * lh_buf_widen_f16: a dtype-1 buffer widened into a new fp32 buffer (k_widen_f16, the pass the prompt routes of an f16 model run in front of their
@@ -306,10 +318,11 @@ typedef struct lh_llama_desc {
     lh_buf tok_embeddings, norm, output;          /* needed on the first / last stage only (0 elsewhere) */
     const lh_llama_layer* layer;                  /* `layers` entries, only [layer0, layer1) are read */
     lh_buf k_cache, v_cache;                      /* embd * (layer1-layer0) * ctx floats each; layer il at slot (il-layer0) */
-    int weight_dtype;                             /* 0 = f32, 1 = f16, 2 = block-int4, 7 = block-int8 matrices; every matrix buffer must be of that dtype (f16: else LH_EINVAL).
+    int weight_dtype;                             /* 0 = f32, 1 = f16, 2 = block-int4, 3 = Q4_1, 7 = block-int8 matrices; every matrix buffer must be of that dtype (f16: else LH_EINVAL).
                                                    * f16: one row and 2..8 rows stream the halves (k_gemv_sa_h / k_gemv_rows_h); every other row count runs the
                                                    * fp32 schedule over an fp32 image widened layer by layer - in all cases the bytes an fp32 model holding the
-                                                   * same values produces */
+                                                   * same values produces.  Q4_1: one row and 2..4 rows stream the nibbles (k_gemv_q41s / k_gemv_q41_rows); every
+                                                   * other row count runs the fp32 schedule over an fp32 image of the values w' (k_expand_q41), layer by layer */
 } lh_llama_desc;
 typedef struct lh_llama lh_llama;
 

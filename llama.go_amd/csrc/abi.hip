@@ -431,25 +431,27 @@ void* lh_ctx_stream(lh_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 int lh_tensor_register(lh_ctx* ctx, uint64_t key, int dtype, const uint32_t ne[4], int persistent, const void* host, lh_buf* out) {
     if (!ctx || !ne || !out) LH_FAIL(ctx, LH_EINVAL, "lh_tensor_register: NULL argument");
     (void)persistent;
-    if (dtype != 0 && dtype != 1 && dtype != 2 && dtype != 7) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_tensor_register: dtype %d not supported (f32, f16, block-int4 and block-int8 only; the reference loader accepts f32/f16, llama.go:956-959)", dtype);
+    if (dtype != 0 && dtype != 1 && dtype != 2 && dtype != 3 && dtype != 7) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_tensor_register: dtype %d not supported (f32, f16, block-int4, Q4_1 and block-int8 only; the reference loader accepts f32/f16, llama.go:956-959)", dtype);
     LH_HIP(ctx, hipSetDevice(ctx->device));
-    if (dtype == 2) {   // block-int4 weight matrix from 20-byte blocks { float d; uint8 qs[16] }: every nibble kept as it is
-        if (ne[0] % 32 || ne[2] != 1 || ne[3] != 1 || !ne[0] || !ne[1] || !host) LH_FAIL(ctx, LH_ESHAPE, "lh_tensor_register: block-int4 needs a 2-D matrix with columns %% 32 == 0 and host blocks");
+    if (dtype == 2 || dtype == 3) {   // block-int4 weight matrix from 20-byte blocks { float d; uint8 qs[16] }: every nibble kept as it is; Q4_1 from 24-byte blocks { float d; float m; uint8 qs[16] }: every bit kept
+        const char* const tn = dtype == 2 ? "block-int4" : "Q4_1";
+        const uint64_t bb = dtype == 2 ? 20 : 24;   // bytes of an interchange block; bb - 16 of them go to the fp32 plane
+        if (ne[0] % 32 || ne[2] != 1 || ne[3] != 1 || !ne[0] || !ne[1] || !host) LH_FAIL(ctx, LH_ESHAPE, "lh_tensor_register: %s needs a 2-D matrix with columns %% 32 == 0 and host blocks", tn);
         const uint64_t nblocks = (uint64_t)ne[0] * ne[1] / 32;
         auto b = std::make_unique<Buffer>();
-        b->nfloats = (uint64_t)ne[0] * ne[1]; b->dtype = 2; b->rows = ne[1]; b->cols = ne[0]; b->key = key; b->device = ctx->device;
+        b->nfloats = (uint64_t)ne[0] * ne[1]; b->dtype = dtype; b->rows = ne[1]; b->cols = ne[0]; b->key = key; b->device = ctx->device;
         b->unchecked = true;
         const uint64_t qbytes = (b->nfloats / 2 + 255) & ~(uint64_t)255;
-        b->bytes = qbytes + nblocks * 4;
+        b->bytes = qbytes + nblocks * (bb - 16);
         void* raw = nullptr;
         LH_HIP(ctx, hipMalloc((void**)&b->dev, b->bytes));
         b->scales = (float*)((char*)b->dev + qbytes);
-        hipError_t e = hipMalloc(&raw, nblocks * 20);
-        if (e == hipSuccess) e = hipMemcpy(raw, host, nblocks * 20, hipMemcpyHostToDevice);
-        int rc = e == hipSuccess ? q4_deinterleave_launch(ctx, raw, b->dev, b->scales, nblocks) : 0;
+        hipError_t e = hipMalloc(&raw, nblocks * bb);
+        if (e == hipSuccess) e = hipMemcpy(raw, host, nblocks * bb, hipMemcpyHostToDevice);
+        int rc = e != hipSuccess ? 0 : dtype == 2 ? q4_deinterleave_launch(ctx, raw, b->dev, b->scales, nblocks) : q41_deinterleave_launch(ctx, raw, b->dev, b->scales, nblocks);
         if (e == hipSuccess && !rc) e = hipStreamSynchronize(ctx->stream);
         if (raw) hipFree(raw);
-        if (e != hipSuccess || rc) { hipFree(b->dev); if (rc) return rc; LH_FAIL(ctx, LH_EHIP, "lh_tensor_register: block-int4 upload: %s", hipGetErrorString(e)); }
+        if (e != hipSuccess || rc) { hipFree(b->dev); if (rc) return rc; LH_FAIL(ctx, LH_EHIP, "lh_tensor_register: %s upload: %s", tn, hipGetErrorString(e)); }
         std::lock_guard<std::mutex> lk(ctx->ds->mu);
         lh_buf id = ctx->ds->next_id++;
         if (key) ctx->ds->by_key[key] = id;
@@ -548,6 +550,7 @@ int lh_buf_upload(lh_ctx* ctx, lh_buf buf, uint64_t off, const float* host, uint
     if (rc) return rc;
     if (!host) LH_FAIL(ctx, LH_EINVAL, "lh_buf_upload: host is NULL");
     if (b->dtype == 2) LH_FAIL(ctx, LH_EINVAL, "lh_buf_upload: not an f32 buffer (block-int4: lh_buf_quantize_q4 of an f32 buffer, or lh_tensor_register of blocks)");
+    if (b->dtype == 3) LH_FAIL(ctx, LH_EINVAL, "lh_buf_upload: not an f32 buffer (Q4_1: lh_buf_quantize_q41 of an f32 buffer, or lh_tensor_register of blocks)");
     if (b->dtype != 0) LH_FAIL(ctx, LH_EINVAL, "lh_buf_upload: not an f32 buffer");
     LH_HIP(ctx, hipSetDevice(ctx->device));
     LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -579,6 +582,22 @@ int lh_buf_read(lh_ctx* ctx, lh_buf buf, uint64_t off, float* dst, uint64_t n) {
         }
         return LH_OK;
     }
+    if (b->dtype == 3) {   // the values w' = fl32(fma(d, n, m)): one rounding, as every kernel forms them
+        LH_HIP(ctx, hipSetDevice(ctx->device));
+        LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        const uint64_t b0 = off / 32, b1 = (off + n + 31) / 32;
+        std::vector<unsigned char> q((b1 - b0) * 16);
+        std::vector<float> dm((b1 - b0) * 2);
+        if (b1 > b0) {
+            LH_HIP(ctx, hipMemcpy(q.data(), (unsigned char*)b->dev + b0 * 16, (b1 - b0) * 16, hipMemcpyDeviceToHost));
+            LH_HIP(ctx, hipMemcpy(dm.data(), b->scales + b0 * 2, (b1 - b0) * 8, hipMemcpyDeviceToHost));
+        }
+        for (uint64_t i = 0; i < n; ++i) {
+            const uint64_t e = off + i - b0 * 32;
+            dst[i] = fmaf(dm[e / 32 * 2], (float)((q[e / 2] >> (4 * (e & 1))) & 15), dm[e / 32 * 2 + 1]);
+        }
+        return LH_OK;
+    }
     if (b->dtype != 0) LH_FAIL(ctx, LH_EINVAL, "lh_buf_read: an f16 buffer holds no floats (lh_buf_widen_f16 makes an fp32 copy)");
     LH_HIP(ctx, hipSetDevice(ctx->device));
     LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -593,6 +612,7 @@ int lh_buf_fill_synth(lh_ctx* ctx, lh_buf buf, uint64_t off, uint64_t n, uint64_
     if (rc) return rc;
     if (b->dtype == 1) LH_FAIL(ctx, LH_EINVAL, "lh_buf_fill_synth: not an f32 buffer (f16: fill an f32 buffer, then lh_buf_narrow_f16)");
     if (b->dtype == 2) LH_FAIL(ctx, LH_EINVAL, "lh_buf_fill_synth: not an f32 buffer (block-int4: fill an f32 buffer, then lh_buf_quantize_q4)");
+    if (b->dtype == 3) LH_FAIL(ctx, LH_EINVAL, "lh_buf_fill_synth: not an f32 buffer (Q4_1: fill an f32 buffer, then lh_buf_quantize_q41)");
     LH_HIP(ctx, hipSetDevice(ctx->device));
     const uint64_t key = mix64(seed ^ ((uint64_t)tensor_id * 0xD6E8FEB86659FD93ull));
     uint64_t blocks = (n + 255) / 256;
@@ -610,6 +630,7 @@ int lh_buf_quantize_q8(lh_ctx* ctx, lh_buf src, uint32_t rows, uint32_t cols, lh
     if (rc) return rc;
     if (sb->dtype == 1) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_buf_quantize_q8: the source is f16 (quantise before narrowing)");
     if (sb->dtype == 2) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_buf_quantize_q8: the source is block-int4 (lh_buf_expand_q4 makes the block-int8 buffer of the same values)");
+    if (sb->dtype == 3) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_buf_quantize_q8: the source is Q4_1 (w = d n + m is no block-int8 weight; lh_buf_expand_q41 makes the f32 buffer of its values)");
     if (sb->dtype != 0 || cols % 32) LH_FAIL(ctx, LH_ESHAPE, "lh_buf_quantize_q8: needs an f32 matrix with columns %% 32 == 0");
     LH_HIP(ctx, hipSetDevice(ctx->device));
     const uint64_t n = (uint64_t)rows * cols, nblocks = n / 32;
@@ -686,7 +707,7 @@ int lh_buf_quantize_q4(lh_ctx* ctx, lh_buf src, uint32_t rows, uint32_t cols, lh
     if (!out || !rows || !cols) return LH_EINVAL;
     int rc = get_buf(ctx, src, 0, (uint64_t)rows * cols, &sb, "lh_buf_quantize_q4");
     if (rc) return rc;
-    if (sb->dtype != 0) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_buf_quantize_q4: the source is %s (only an f32 matrix is quantised to block-int4)", sb->dtype == 1 ? "f16" : sb->dtype == 7 ? "block-int8" : "block-int4");
+    if (sb->dtype != 0) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_buf_quantize_q4: the source is %s (only an f32 matrix is quantised to block-int4)", sb->dtype == 1 ? "f16" : sb->dtype == 7 ? "block-int8" : sb->dtype == 3 ? "Q4_1" : "block-int4");
     if (cols % 32) LH_FAIL(ctx, LH_ESHAPE, "lh_buf_quantize_q4: needs an f32 matrix with columns %% 32 == 0");
     LH_HIP(ctx, hipSetDevice(ctx->device));
     const uint64_t n = (uint64_t)rows * cols, nblocks = n / 32;
@@ -740,6 +761,64 @@ int lh_buf_read_q4(lh_ctx* ctx, lh_buf buf, uint64_t block0, void* dst_blocks, u
     }
     unsigned char* o = (unsigned char*)dst_blocks;
     for (uint64_t i = 0; i < nblocks; ++i) { memcpy(o + i * 20, &sc[i], 4); memcpy(o + i * 20 + 4, &q[i * 16], 16); }
+    return LH_OK;
+}
+
+// ---- Q4_1 (dtype 3; kernels_q41.h): a nibble plane and a plane of (d, m) pairs behind Buffer::scales ----
+int lh_buf_quantize_q41(lh_ctx* ctx, lh_buf src, uint32_t rows, uint32_t cols, lh_buf* out) {
+    Buffer* sb;
+    if (!out || !rows || !cols) return LH_EINVAL;
+    int rc = get_buf(ctx, src, 0, (uint64_t)rows * cols, &sb, "lh_buf_quantize_q41");
+    if (rc) return rc;
+    if (sb->dtype != 0) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_buf_quantize_q41: the source is %s (only an f32 matrix is quantised to Q4_1)", sb->dtype == 1 ? "f16" : sb->dtype == 7 ? "block-int8" : sb->dtype == 2 ? "block-int4" : "Q4_1");
+    if (cols % 32) LH_FAIL(ctx, LH_ESHAPE, "lh_buf_quantize_q41: needs an f32 matrix with columns %% 32 == 0");
+    LH_HIP(ctx, hipSetDevice(ctx->device));
+    const uint64_t n = (uint64_t)rows * cols, nblocks = n / 32;
+    auto b = std::make_unique<Buffer>();
+    b->nfloats = n; b->dtype = 3; b->rows = rows; b->cols = cols; b->device = ctx->device;
+    b->unchecked = true;
+    const uint64_t qbytes = (n / 2 + 255) & ~(uint64_t)255;
+    b->bytes = qbytes + nblocks * 8;
+    LH_HIP(ctx, hipMalloc((void**)&b->dev, b->bytes));
+    b->scales = (float*)((char*)b->dev + qbytes);
+    rc = quantize_q41_launch(ctx, sb->dev, b->dev, b->scales, nblocks);
+    hipError_t e = rc ? hipErrorUnknown : hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { hipFree(b->dev); if (rc) return rc; LH_FAIL(ctx, LH_EHIP, "lh_buf_quantize_q41: %s", hipGetErrorString(e)); }
+    return add_buffer(ctx, std::move(b), out);
+}
+
+int lh_buf_expand_q41(lh_ctx* ctx, lh_buf src, lh_buf* out) {
+    if (!ctx || !out) return LH_EINVAL;
+    Buffer* sb = find_buffer(ctx->ds, src);
+    if (!sb) LH_FAIL(ctx, LH_EINVAL, "lh_buf_expand_q41: unknown buffer %llu", (unsigned long long)src);
+    if (sb->dtype != 3) LH_FAIL(ctx, LH_EINVAL, "lh_buf_expand_q41: the source must be a Q4_1 buffer");
+    LH_HIP(ctx, hipSetDevice(ctx->device));
+    auto b = std::make_unique<Buffer>();
+    b->nfloats = sb->nfloats; b->dtype = 0; b->device = ctx->device; b->bytes = sb->nfloats * 4;
+    b->unchecked = true;   // (values the host never saw: as after lh_buf_widen_f16)
+    LH_HIP(ctx, hipMalloc((void**)&b->dev, b->bytes));
+    const int rc = expand_q41_launch(ctx, sb->dev, sb->scales, b->dev, sb->nfloats);
+    hipError_t e = rc ? hipErrorUnknown : hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { hipFree(b->dev); if (rc) return rc; LH_FAIL(ctx, LH_EHIP, "lh_buf_expand_q41: %s", hipGetErrorString(e)); }
+    return add_buffer(ctx, std::move(b), out);
+}
+
+int lh_buf_read_q41(lh_ctx* ctx, lh_buf buf, uint64_t block0, void* dst_blocks, uint64_t nblocks) {
+    if (!ctx) return LH_EINVAL;
+    Buffer* b = find_buffer(ctx->ds, buf);
+    if (!b) LH_FAIL(ctx, LH_EINVAL, "lh_buf_read_q41: unknown buffer %llu", (unsigned long long)buf);
+    if (b->dtype != 3 || !dst_blocks) LH_FAIL(ctx, LH_EINVAL, "lh_buf_read_q41: not a Q4_1 buffer");
+    const uint64_t total = b->nfloats / 32;
+    if (block0 > total || nblocks > total - block0) LH_FAIL(ctx, LH_EINVAL, "lh_buf_read_q41: blocks [%llu,+%llu) outside the buffer's %llu", (unsigned long long)block0, (unsigned long long)nblocks, (unsigned long long)total);
+    LH_HIP(ctx, hipSetDevice(ctx->device));
+    LH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<unsigned char> q(nblocks * 16), dm(nblocks * 8);
+    if (nblocks) {
+        LH_HIP(ctx, hipMemcpy(q.data(), (unsigned char*)b->dev + block0 * 16, nblocks * 16, hipMemcpyDeviceToHost));
+        LH_HIP(ctx, hipMemcpy(dm.data(), (unsigned char*)b->scales + block0 * 8, nblocks * 8, hipMemcpyDeviceToHost));
+    }
+    unsigned char* o = (unsigned char*)dst_blocks;   // k_q41_deinterleave's inverse: (d, m) then the 16 nibble bytes
+    for (uint64_t i = 0; i < nblocks; ++i) { memcpy(o + i * 24, &dm[i * 8], 8); memcpy(o + i * 24 + 8, &q[i * 16], 16); }
     return LH_OK;
 }
 

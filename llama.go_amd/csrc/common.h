@@ -202,4 +202,9 @@ int narrow_f16_launch(lh_ctx* ctx, const float* src, void* dst_f16, uint64_t n, 
 int expand_q4_launch(lh_ctx* ctx, const void* src_q4, void* dst_q8, uint64_t n);
 int quantize_q4_launch(lh_ctx* ctx, const float* src, void* q, float* scales, uint64_t nblocks);
 int q4_deinterleave_launch(lh_ctx* ctx, const void* blocks, void* q, float* scales, uint64_t nblocks);
+// plan.hip (kernels_q41.h), enqueued on the context's stream: the nibble and (d, m) pair planes of n Q4_1 weights -> the fp32 matrix of their values
+// (k_expand_q41); nblocks blocks of 32 floats -> planes (k_quantize_q41); nblocks 24-byte interchange blocks -> planes (k_q41_deinterleave)
+int expand_q41_launch(lh_ctx* ctx, const void* nib, const float* pairs, float* dst, uint64_t n);
+int quantize_q41_launch(lh_ctx* ctx, const float* src, void* q, float* pairs, uint64_t nblocks);
+int q41_deinterleave_launch(lh_ctx* ctx, const void* blocks, void* q, float* pairs, uint64_t nblocks);
 }  // namespace lh

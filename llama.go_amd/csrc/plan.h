@@ -28,7 +28,7 @@ struct ModelDesc {
     uint32_t cache_layer0 = 0;        // layer stored in slot 0 of the caches
     const float *tok_emb = nullptr, *norm = nullptr, *output = nullptr;
     const float* s_output = nullptr;  // block-int8: scales of the output matrix
-    int wtype = 0;                    // dtype of the weight matrices: 0 = f32, 1 = f16 (halves at the pointers), 2 = block-int4 (nibble planes at the pointers, scales at s_*), 7 = block-int8 (norms and embeddings stay f32)
+    int wtype = 0;                    // dtype of the weight matrices: 0 = f32, 1 = f16 (halves at the pointers), 2 = block-int4 (nibble planes at the pointers, scales at s_*), 3 = Q4_1 (nibble planes at the pointers, (d, m) pair planes at s_*), 7 = block-int8 (norms and embeddings stay f32)
     std::vector<LayerW> layers;       // indexed by absolute layer id
     float *kc = nullptr, *vc = nullptr;
     std::shared_ptr<std::vector<uint32_t>> kv_hist;   // the K cache buffer's token history (Buffer::kv_hist); not part of same()
@@ -64,6 +64,8 @@ struct Plan {
     // and V d BYTES behind the float* type, filled by k_expand_q4 - and whose s_* pointers are the model's own scale planes.
     // (With lh_ctx_set_q4_stream on, Planes' launch sites read the nibble planes themselves - k_stream_q4b, kernels_stream_q4b.h - and a matrix is expanded
     // into its slot only directly in front of a launch that reads int8: eval_planes / eval_prefill, Q4Src.)
+    // Q4_1 plans (md.wtype == 3) take the f16 plan's shadow as it is: md_wide = md with wtype 0 over fp32 images of the values w' = fma(d, n, m), filled by
+    // k_expand_q41 where an f16 plan's are filled by k_widen_f16.  Step and Rows of 2..4 stream the nibbles (kernels_q41.h).
     ModelDesc md_wide;
     float *wide_layer = nullptr, *wide_out = nullptr;
     float* emb = nullptr;                    // LH_T_OUTPUT on llama.Eval's `embeddings`: the final norm rows [emb_cap][d]

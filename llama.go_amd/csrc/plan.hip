@@ -23,6 +23,7 @@ namespace lh_b9w_tu { const void* stream_b9w_kernel(int maxt, int nct, int wdt, 
 #include "kernels_stream_f16.h"
 #include "kernels_gemm_f16.h"
 #include "kernels_q4.h"
+#include "kernels_q41.h"
 #include "kernels_attn_seg.h"
 #include "kernels_attn_share.h"
 #include "kernels_spec.h"
@@ -161,7 +162,30 @@ int q4_deinterleave_launch(lh_ctx* ctx, const void* blocks, void* q, float* scal
     LH_HIP(ctx, hipGetLastError());
     return 0;
 }
-// an image of n elements of elem_bytes each (fp32 of f16 matrices, int8 of block-int4 ones) that lives as long as the context and never moves
+// ---- Q4_1 (kernels_q41.h) ----
+// the nibble plane and pair plane of n Q4_1 weights -> the fp32 matrix of their values w' = fma(d, n, m) (k_expand_q41)
+int expand_q41_launch(lh_ctx* ctx, const void* nib, const float* pairs, float* dst, uint64_t n) {
+    if (g_prepare_only || g_only) return 0;
+    TraceScope ts_(ctx->stream, "expand_q41");
+    LH_TRACE("k_expand_q41");
+    const uint64_t n8 = n / 16;   // 8-byte units of the nibble plane
+    LH_LAUNCH(k_expand_q41, dim3((unsigned)std::min<uint64_t>(std::max<uint64_t>((n8 + 255) / 256, 1), 16384)), dim3(256), 0, ctx->stream, (const u2*)nib, (const f2*)pairs, (f4*)dst, n8);
+    LH_HIP(ctx, hipGetLastError());
+    return 0;
+}
+int quantize_q41_launch(lh_ctx* ctx, const float* src, void* q, float* pairs, uint64_t nblocks) {
+    LH_TRACE("k_quantize_q41");
+    LH_LAUNCH(k_quantize_q41, dim3((unsigned)std::min<uint64_t>(std::max<uint64_t>((nblocks + 255) / 256, 1), 65535)), dim3(256), 0, ctx->stream, src, (unsigned char*)q, (f2*)pairs, nblocks);
+    LH_HIP(ctx, hipGetLastError());
+    return 0;
+}
+int q41_deinterleave_launch(lh_ctx* ctx, const void* blocks, void* q, float* pairs, uint64_t nblocks) {
+    LH_TRACE("k_q41_deinterleave");
+    LH_LAUNCH(k_q41_deinterleave, dim3((unsigned)std::min<uint64_t>(std::max<uint64_t>((nblocks + 255) / 256, 1), 65535)), dim3(256), 0, ctx->stream, (const unsigned int*)blocks, (unsigned char*)q, (u2*)pairs, nblocks);
+    LH_HIP(ctx, hipGetLastError());
+    return 0;
+}
+// an image of n elements of elem_bytes each (fp32 of f16 or Q4_1 matrices, int8 of block-int4 ones) that lives as long as the context and never moves
 // (lh_ctx::wide); kind 0 = a layer's matrices, 1 = the output matrix (a layer image and an output image of the same size stay two allocations: a
 // route reads both).  The element size is part of the key: an int8 image and an fp32 image of equal count do not alias.
 static int wide_image(lh_ctx* ctx, uint64_t n, uint64_t elem_bytes, int kind, float** out) {
@@ -286,9 +310,46 @@ static int gemv_q4(lh_ctx* ctx, const GemvArgs& a, const char* name) {
     LH_FAIL(ctx, LH_EUNSUPPORTED, "gemv_q4 %s: K=%u exceeds the supported 32768 columns", name, a.K);
 }
 
+template <int KI, int U, int TPR, int PRO, int EPI, int MAP, int THR = TH>
+static int launch_gemv_q41(lh_ctx* ctx, const GemvArgs& a, const char* name, uint64_t bytes) {
+    static bool flags[16] = {};
+    int rc = set_lds_once(ctx, k_gemv_q41s<KI, U, TPR, PRO, EPI, MAP, THR>, FAT_LDS, flags);
+    if (rc) return rc;
+    if (skip_launch(name)) return 0;
+    ProfScope ps(ctx->stream, name, bytes);
+    GemvArgs b = a;
+    b.wg_q = (a.M / 2) / (uint32_t)ctx->ds->num_cu; b.wg_r = (a.M / 2) % (uint32_t)ctx->ds->num_cu;   // wg_row_block
+    LH_TRACE("k_gemv_q41s<%d,%d,%d,%d>", KI, U, TPR, THR);
+    LH_LAUNCH((k_gemv_q41s<KI, U, TPR, PRO, EPI, MAP, THR>), dim3(ctx->ds->num_cu), dim3(THR), FAT_LDS, ctx->stream, b);
+    LH_HIP(ctx, hipGetLastError());
+    return 0;
+}
+// Q4_1 GEMV (kernels_q41.h): gemv_q4's launch forms - KI, TPR and the workgroup size per shape fix the lane -> column map and the cross-wave order,
+// hence the bits.  U (rows in flight, not part of the sums) starts at dtype 2's counts and is UNMEASURED for this format; the 1024-thread forms
+// carry half of them: a slot holds two more registers (d, m) than dtype 2's, and four waves per SIMD leave 128.
+template <int PRO, int EPI, int MAP>
+static int gemv_q41(lh_ctx* ctx, const GemvArgs& a, const char* name) {
+    if (a.K % 32 || ((EPI == EPI_QKV_ROPE || EPI == EPI_SILU_MUL) && a.M % 2))
+        LH_FAIL(ctx, LH_ESHAPE, "gemv_q41 %s: K=%u must be a multiple of 32%s", name, a.K, a.M % 2 ? " and the row count even" : "");
+    if ((uint64_t)a.M / ctx->ds->num_cu + 4 > (uint64_t)TH) LH_FAIL(ctx, LH_EUNSUPPORTED, "gemv_q41 %s: M=%u exceeds %d rows per workgroup", name, a.M, TH - 4);
+    const uint32_t K16 = a.K / 16;
+    const uint64_t bytes = (uint64_t)a.M * a.K / 32 * 24;
+    const uint32_t rows_wg = a.M / (uint32_t)ctx->ds->num_cu;
+    if (rows_wg + 4 <= 250) {
+        if (K16 <= 256) return launch_gemv_q41<1, 4, 256, PRO, EPI, MAP, 256>(ctx, a, name, bytes);
+        if (K16 > 512 && K16 <= 768) return launch_gemv_q41<3, 4, 256, PRO, EPI, MAP, 256>(ctx, a, name, bytes);
+    }
+    if (K16 <= 256) return launch_gemv_q41<1, 2, 256, PRO, EPI, MAP>(ctx, a, name, bytes);
+    if (K16 <= 512) return launch_gemv_q41<2, 2, 256, PRO, EPI, MAP>(ctx, a, name, bytes);
+    if (K16 <= 1024) return launch_gemv_q41<1, 2, 1024, PRO, EPI, MAP>(ctx, a, name, bytes);
+    if (K16 <= 2048) return launch_gemv_q41<2, 2, 1024, PRO, EPI, MAP>(ctx, a, name, bytes);
+    LH_FAIL(ctx, LH_EUNSUPPORTED, "gemv_q41 %s: K=%u exceeds the supported 32768 columns", name, a.K);
+}
+
 template <int PRO, int EPI, int MAP>
 static int gemv(lh_ctx* ctx, const GemvArgs& a, const char* name, int wtype = 0) {
     if (wtype == 1) return gemv_f16<PRO, EPI, MAP>(ctx, a, name);
+    if (wtype == 3) return gemv_q41<PRO, EPI, MAP>(ctx, a, name);
     if (wtype == 2) return gemv_q4<PRO, EPI, MAP>(ctx, a, name);
     return wtype == 7 ? gemv_q8<PRO, EPI, MAP>(ctx, a, name) : gemv_f32<PRO, EPI, MAP>(ctx, a, name);
 }
@@ -503,6 +564,29 @@ static int gemv_q4_rows_nc(lh_ctx* ctx, const GemvRowsArgs& a, const char* name)
     if (a.K / 16 <= 256) return launch_gemv_q4_rows<1, U, NC, PRO, EPI, MAP>(ctx, a, name, bytes);
     return launch_gemv_q4_rows<3, (NC <= 2 ? 4 : 2), NC, PRO, EPI, MAP>(ctx, a, name, bytes);
 }
+// Q4_1 (k_gemv_q41_rows): gemv_q8_rows_nc's shapes, limits and launch forms, dtype 2's weight rows in flight (unmeasured for this format)
+template <int KI, int U, int NC, int PRO, int EPI, int MAP>
+static int launch_gemv_q41_rows(lh_ctx* ctx, const GemvRowsArgs& a, const char* name, uint64_t bytes) {
+    static bool flags[16] = {};
+    int rc = set_lds_once(ctx, k_gemv_q41_rows<KI, U, 256, 256, NC, PRO, EPI, MAP>, FAT_LDS, flags);
+    if (rc) return rc;
+    if (g_prepare_only) return 0;
+    ProfScope ps(ctx->stream, name, bytes);
+    GemvRowsArgs b = a;
+    b.wg_q = (a.M / 2) / (uint32_t)ctx->ds->num_cu; b.wg_r = (a.M / 2) % (uint32_t)ctx->ds->num_cu;   // wg_row_block
+    LH_TRACE("k_gemv_q41_rows<%d,%d,%d>", KI, U, NC);
+    LH_LAUNCH((k_gemv_q41_rows<KI, U, 256, 256, NC, PRO, EPI, MAP>), dim3(ctx->ds->num_cu), dim3(256), FAT_LDS, ctx->stream, b);
+    LH_HIP(ctx, hipGetLastError());
+    return 0;
+}
+template <int NC, int PRO, int EPI, int MAP>
+static int gemv_q41_rows_nc(lh_ctx* ctx, const GemvRowsArgs& a, const char* name) {
+    if (!gemv_q8_rows_shape_ok(ctx, a.M, a.K)) LH_FAIL(ctx, LH_ESHAPE, "gemv_q41_rows %s: %u x %u has no instantiation", name, a.M, a.K);
+    const uint64_t bytes = (uint64_t)a.M * a.K / 32 * 24;
+    constexpr int U = NC <= 2 ? 8 : 4;
+    if (a.K / 16 <= 256) return launch_gemv_q41_rows<1, U, NC, PRO, EPI, MAP>(ctx, a, name, bytes);
+    return launch_gemv_q41_rows<3, (NC <= 2 ? 4 : 2), NC, PRO, EPI, MAP>(ctx, a, name, bytes);
+}
 // f16 twin (k_gemv_rows_h): gemv_rows_nc's shapes and limits (the activation registers are the same), twice its weight rows in flight
 template <int KI, int U, int THR, int NC, int PRO, int EPI, int MAP>
 static int launch_gemv_rows_h(lh_ctx* ctx, const GemvRowsArgs& a, const char* name, uint64_t bytes) {
@@ -553,20 +637,21 @@ static int gemv_rows(lh_ctx* ctx, const GemvRowsArgs& a, const char* name, int w
     }
     if (wtype == 7) return a.n <= 2 ? gemv_q8_rows_nc<2, PRO, EPI, MAP>(ctx, a, name) : gemv_q8_rows_nc<4, PRO, EPI, MAP>(ctx, a, name);
     if (wtype == 2) return a.n <= 2 ? gemv_q4_rows_nc<2, PRO, EPI, MAP>(ctx, a, name) : gemv_q4_rows_nc<4, PRO, EPI, MAP>(ctx, a, name);
+    if (wtype == 3) return a.n <= 2 ? gemv_q41_rows_nc<2, PRO, EPI, MAP>(ctx, a, name) : gemv_q41_rows_nc<4, PRO, EPI, MAP>(ctx, a, name);
     if (a.n > 4) return gemv_rows_nc<8, PRO, EPI, MAP>(ctx, a, name);
     return a.n <= 2 ? gemv_rows_nc<2, PRO, EPI, MAP>(ctx, a, name) : gemv_rows_nc<4, PRO, EPI, MAP>(ctx, a, name);
 }
 // rows the decode stream carries: fp32 and f16 up to 8 (round 4; 32 FMAs per 16-byte load = a sixth of a CU's vector rate at the stream's pace),
-// block-int8 and block-int4 up to 4 (their 16 converts + 16 NC FMAs per load saturate the vector ALU from there on)
+// block-int8, block-int4 and Q4_1 up to 4 (their 16 converts + 16 NC FMAs per load saturate the vector ALU from there on)
 static constexpr uint32_t GEMV_ROWS_MAX_F32 = 8, GEMV_ROWS_MAX_Q8 = 4;
-static uint32_t gemv_rows_max(int wtype) { return wtype == 7 || wtype == 2 ? GEMV_ROWS_MAX_Q8 : GEMV_ROWS_MAX_F32; }
+static uint32_t gemv_rows_max(int wtype) { return wtype == 7 || wtype == 2 || wtype == 3 ? GEMV_ROWS_MAX_Q8 : GEMV_ROWS_MAX_F32; }
 // every launch of a layer (and the lm_head on the last stage) has an n-row instantiation
 static bool rows_path_ok(lh_ctx* ctx, const ModelDesc& m, uint32_t n) {
     if (n > gemv_rows_max(m.wtype)) return false;
     const uint32_t nc = n <= 2 ? 2 : (n <= 4 ? 4 : 8);
     // (f16: the fp32 predicate - k_gemv_rows_h keeps k_gemv_rows' activation registers and takes no more for its weight slots)
-    // (block-int4: the int8 predicate - k_gemv_q4_rows takes k_gemv_q8_rows' launch forms)
-    auto ok = [&](uint32_t M, uint32_t K, bool norm) { return m.wtype == 7 || m.wtype == 2 ? gemv_q8_rows_shape_ok(ctx, M, K) : ((m.wtype == 0 || m.wtype == 1) && gemv_rows_shape_ok(ctx, M, K, nc, norm)); };
+    // (block-int4 and Q4_1: the int8 predicate - k_gemv_q4_rows and k_gemv_q41_rows take k_gemv_q8_rows' launch forms)
+    auto ok = [&](uint32_t M, uint32_t K, bool norm) { return m.wtype == 7 || m.wtype == 2 || m.wtype == 3 ? gemv_q8_rows_shape_ok(ctx, M, K) : ((m.wtype == 0 || m.wtype == 1) && gemv_rows_shape_ok(ctx, M, K, nc, norm)); };
     return m.hd % 2 == 0 && m.d % 4 == 0 && ok(3 * m.d, m.d, true) && ok(m.d, m.d, false) && ok(2 * m.F, m.d, true) && ok(m.d, m.F, false) && (!m.last_stage() || ok(m.V, m.d, true));
 }
 
@@ -1807,7 +1892,7 @@ int plan_ensure_rows(Plan* p, uint32_t n) {
     if (n > 1) { rc |= re(&p->qraw, nd); rc |= re(&p->kraw, nd); rc |= re(&p->vraw, nd); rc |= re(&p->a1, nf); rc |= re(&p->a3, nf); }
     if (m.last_stage()) rc |= re(&p->logits, (size_t)n * m.V);
     if (rc) return LH_EHIP;
-    if (n > 1 && (m.wtype == 7 || m.wtype == 0 || m.wtype == 1 || m.wtype == 2)) {   // the activations as planes: every row of a block-int8 plan, up to k_stream_b9's 64 rows of an fp32 one (f16: the fp32 schedule; block-int4: the int8 one)
+    if (n > 1 && (m.wtype == 7 || m.wtype == 0 || m.wtype == 1 || m.wtype == 2 || m.wtype == 3)) {   // the activations as planes: every row of a block-int8 plan, up to k_stream_b9's 64 rows of an fp32 one (f16: the fp32 schedule; block-int4: the int8 one)
         if (p->s3) LH_HIP(ctx, hipFree(p->s3));
         p->s3 = nullptr;
         p->s3_rows = m.wtype == 7 || m.wtype == 2 ? n : std::min<uint32_t>(n, B9W_MAX_ROWS);   // (fp32 and f16: k_stream_b9w[_h]'s 128 rows)
@@ -1837,15 +1922,17 @@ int plan_create(lh_ctx* ctx, const ModelDesc& md, Plan** out) {
     if (e != hipSuccess) { set_error(ctx, "plan_create: %s", hipGetErrorString(e)); plan_destroy(p); return LH_ENOMEM; }
     rc = plan_ensure_rows(p, 1);
     if (rc) { plan_destroy(p); return rc; }
-    if (md.wtype == 1) {   // the fp32 images of the widened routes (Plan::md_wide): sized here, once
+    if (md.wtype == 1 || md.wtype == 3) {   // the fp32 images of the widened (Q4_1: expanded) routes (Plan::md_wide): sized here, once
         const uint64_t d = md.d, F = md.F;
         if ((rc = wide_image(ctx, 4 * d * d + 3 * d * F, 4, 0, &p->wide_layer)) || (md.last_stage() && (rc = wide_image(ctx, (uint64_t)md.V * d, 4, 1, &p->wide_out)))) { plan_destroy(p); return rc; }
         p->md_wide = md;
         p->md_wide.wtype = 0;
         p->md_wide.output = p->wide_out;
+        p->md_wide.s_output = nullptr;   // (Q4_1: the shadow is a plain fp32 model - the launch sites take a scale plane for block-int8 weights)
         float* w = p->wide_layer;
         for (uint32_t il = md.layer0; il < md.layer1; ++il) {
             LayerW& L = p->md_wide.layers[il];
+            L.s_wq = L.s_wk = L.s_wv = L.s_wo = L.s_w1 = L.s_w3 = L.s_w2 = nullptr;
             L.wq = w; L.wk = w + d * d; L.wv = w + 2 * d * d; L.wo = w + 3 * d * d; L.w1 = w + 4 * d * d; L.w3 = w + 4 * d * d + d * F; L.w2 = w + 4 * d * d + 2 * d * F;
         }
     }
@@ -2203,9 +2290,11 @@ static EvalRoute eval_route(lh_ctx* ctx, const ModelDesc& m, uint32_t n, bool ba
 // Prefill's grouped MFMA launches: from 9 rows (tile GEMM), fp32 weights from 2 rows on the streaming MFMA kernel
 static bool prefill_mfma(const ModelDesc& m, uint32_t n) { return (n >= MFMA_MIN_ROWS || (n >= 2 && m.wtype == 0)) && m.d % GBK == 0 && m.F % GBK == 0; }
 static const ModelDesc& sched_md(const Plan* p);
+static bool q41_native_rows(const Plan* p, uint32_t n);
 bool plan_batch_rows_ok(const Plan* p, uint32_t n) {
     const ModelDesc& m = sched_md(p);
     if (n < 2 || n > BATCH_ROWS_MAX) return false;
+    if (q41_native_rows(p, n)) return true;
     const EvalRoute route = eval_route(p->ctx, m, n, true);
     if (route == EvalRoute::Rows) return true;   // two to eight (block-int8: four) rows ride the decode stream itself
     // block-int8 on the stream kernel: from 3 rows (one pass of the dequantising stream kernel costs 4.9 ms on 7B whatever the row count <= 16, a single-row
@@ -2227,7 +2316,11 @@ static float attn_scale(const ModelDesc& m) { return (float)(1.0 / sqrt((double)
 // what it picks for a wtype-0 model of the same shapes.  Step and Rows, which the same predicates admit for both, run on the model itself (sched_md is
 // not asked there); Skinny, Planes and Prefill open with it and see an fp32 model.
 // A block-int4 model (wtype 2) has a block-int8 shadow in the same way: Step, Rows and Q8Steps run on the nibbles, Planes and Prefill on the int8 image.
-static const ModelDesc& sched_md(const Plan* p) { return p->md.wtype == 1 || p->md.wtype == 2 ? p->md_wide : p->md; }
+// A Q4_1 model (wtype 3) has the f16 model's shadow, fp32 over an image of its w' (k_expand_q41) - but its own row kernels carry 2..4 rows only and under
+// the int8 shape rule, so the shadow's choice is overridden exactly there (q41_native_rows): Step and those Rows run on the nibbles, every other
+// row count on what eval_route picks for the wtype-0 shadow, Rows of 5..8 included (eval_rows then runs k_gemv_rows over the image).
+static const ModelDesc& sched_md(const Plan* p) { return p->md.wtype == 1 || p->md.wtype == 2 || p->md.wtype == 3 ? p->md_wide : p->md; }
+static bool q41_native_rows(const Plan* p, uint32_t n) { return p->md.wtype == 3 && n >= 2 && rows_path_ok(p->ctx, p->md, n); }
 // lh_ctx_set_f16_stream in the key of a captured graph whose launches may hold a stream launch (ticks, speculative passes): the switch and the count of its
 // changes for an f16 plan, 0 for every other plan (the switch does nothing there).  f16_stream_sync, in front of CapturedGraph::run: a changed value also
 // clears the warm bits - the kernels the new value chooses set their LDS attribute at their first launch (set_lds_once), which must be an eager one.
@@ -2253,8 +2346,10 @@ static const LayerW& route_layer(Plan* p, const ModelDesc& m, uint32_t il) {
     const uint64_t dd = (uint64_t)m.d * m.d, dF = (uint64_t)m.d * m.F;
     const float* src[7] = {S.wq, S.wk, S.wv, S.wo, S.w1, S.w3, S.w2};
     const float* dst[7] = {W.wq, W.wk, W.wv, W.wo, W.w1, W.w3, W.w2};
+    const float* pairs[7] = {S.s_wq, S.s_wk, S.s_wv, S.s_wo, S.s_w1, S.s_w3, S.s_w2};   // (Q4_1: the (d, m) planes)
     for (int k = 0; k < 7; ++k) {   // (a launch error surfaces at the layer's hipGetLastError)
         if (p->md.wtype == 2) expand_q4_launch(p->ctx, src[k], (void*)dst[k], k < 4 ? dd : dF);
+        else if (p->md.wtype == 3) expand_q41_launch(p->ctx, src[k], pairs[k], (float*)dst[k], k < 4 ? dd : dF);
         else widen_f16_launch(p->ctx, src[k], (float*)dst[k], k < 4 ? dd : dF);
     }
     return W;
@@ -2263,6 +2358,7 @@ static const LayerW& route_layer(Plan* p, const ModelDesc& m, uint32_t il) {
 static const float* route_output(Plan* p, const ModelDesc& m) {
     if (&m == &p->md_wide) {
         if (p->md.wtype == 2) expand_q4_launch(p->ctx, p->md.output, p->wide_out, (uint64_t)m.V * m.d);
+        else if (p->md.wtype == 3) expand_q41_launch(p->ctx, p->md.output, p->md.s_output, p->wide_out, (uint64_t)m.V * m.d);
         else widen_f16_launch(p->ctx, p->md.output, p->wide_out, (uint64_t)m.V * m.d);
     }
     return m.output;
@@ -2288,7 +2384,12 @@ static int q4_stream_src(lh_ctx* ctx, const Q4Src* qs, const float* const* w, ui
 // the output matrix for ONE logits row on the decode stream: an f16 model's halves / a block-int4 model's nibbles as they are (k_gemv_sa_h / k_gemv_q4s
 // compute the bits k_gemv_sa / k_gemv_q8s would over the image)
 struct HeadRow { const float* w; int wtype; };
-static HeadRow head_row(const Plan* p, const ModelDesc& m) { return &m == &p->md_wide ? HeadRow{p->md.output, p->md.wtype} : HeadRow{m.output, m.wtype}; }
+// A Q4_1 model's logits row behind an expanded route comes from the image: k_gemv_q41s sums in another order than k_gemv_sa, and the expanded routes
+// give the bytes of the fp32 model of the same values (k_gemv_q41s serves the row behind Step and behind 2..4 native rows).
+static HeadRow head_row(Plan* p, const ModelDesc& m) {
+    if (&m == &p->md_wide && p->md.wtype == 3) return HeadRow{route_output(p, m), 0};
+    return &m == &p->md_wide ? HeadRow{p->md.output, p->md.wtype} : HeadRow{m.output, m.wtype};
+}
 // The logits rows of the last stage, first row and count: all n as the reference evaluates them (llama.go:372-384), or the last one alone, which is all
 // llama.Eval reads (llama.go:394-401), for callers that say so (LH_GRAPH_LAST_ROW_LOGITS, the lh_llama_* entry points) - in its usual place.
 struct LogitsRows { uint32_t r0, nr; };
@@ -2356,7 +2457,7 @@ static int eval_step(Plan* p, const EvalCall& c) {
 // (kernels_rows.h): 5 launches per layer like the decode step, every row bit-identical to its solo step
 static int eval_rows(Plan* p, const EvalCall& c, const float* x) {
     lh_ctx* ctx = p->ctx;
-    const ModelDesc& m = p->md;
+    const ModelDesc& m = (p->md.wtype == 3 && !q41_native_rows(p, c.n)) ? p->md_wide : p->md;   // Q4_1 beyond its own row kernels: fp32 rows over the image
     const uint32_t n = c.n, past = c.past;
     const BatchRow* rows = c.bc ? c.bc->rows : nullptr;
     float* x_out_dev = c.x_out_dev;
@@ -2364,7 +2465,7 @@ static int eval_rows(Plan* p, const EvalCall& c, const float* x) {
     const float scale = attn_scale(m);
     const uint32_t d = m.d, F = m.F;
     for (uint32_t il = m.layer0; il < m.layer1; ++il) {
-        const LayerW& L = m.layers[il];
+        const LayerW& L = route_layer(p, m, il);
         const size_t slot = (size_t)(il - m.cache_layer0) * m.ctx * d;
         {   // RMSNorm*gamma -> wq|wk|wv -> RoPE(Q, new K rows) -> K, V appended   (llama.go:255-297)
             GemvRowsArgs a = {};
@@ -2397,11 +2498,11 @@ static int eval_rows(Plan* p, const EvalCall& c, const float* x) {
         const auto [r0, nr] = logits_rows(c);
         if (nr == 1) {
             GemvArgs a = {};
-            a.w[0] = m.output; a.ws[0] = m.s_output; a.M = m.V; a.K = d; a.x = x + (size_t)r0 * d; a.gamma = m.norm; a.y = p->logits + (size_t)r0 * m.V;
+            a.w[0] = route_output(p, m); a.ws[0] = m.s_output; a.M = m.V; a.K = d; a.x = x + (size_t)r0 * d; a.gamma = m.norm; a.y = p->logits + (size_t)r0 * m.V;
             if ((rc = gemv<PRO_RMSNORM, EPI_STORE, MAP_SINGLE>(ctx, a, "gemv_lmhead", m.wtype))) return rc;
         } else {
             GemvRowsArgs a = {};
-            a.w[0] = m.output; a.ws[0] = m.s_output; a.M = m.V; a.K = d; a.x = x + (size_t)r0 * d; a.ldx = d; a.n = nr; a.gamma = m.norm; a.y = p->logits + (size_t)r0 * m.V; a.ldy = m.V;
+            a.w[0] = route_output(p, m); a.ws[0] = m.s_output; a.M = m.V; a.K = d; a.x = x + (size_t)r0 * d; a.ldx = d; a.n = nr; a.gamma = m.norm; a.y = p->logits + (size_t)r0 * m.V; a.ldy = m.V;
             if ((rc = gemv_rows<PRO_RMSNORM, EPI_STORE, MAP_SINGLE>(ctx, a, "rows_lmhead", m.wtype))) return rc;
         }
     }
@@ -2834,7 +2935,8 @@ int plan_eval(Plan* p, const uint32_t* tokens_host, const float* x_in_dev, float
     if (!bc && (rc = plan_ensure_rows(p, n))) return rc;
     const EvalCall c = {tokens_host, x_in_dev, x_out_dev, n, past, last_row_only, bc};
     // (an f16 plan takes the wide route only with BOTH switches on: its launches then read the model's halves on k_stream_b9w_h)
-    const EvalRoute route = eval_route(ctx, sched_md(p), n, bc != nullptr, (p->md.wtype == 0 || (p->md.wtype == 1 && ctx->f16_planes)) && ctx->wide_planes);
+    const EvalRoute route = q41_native_rows(p, n) ? EvalRoute::Rows
+                                                  : eval_route(ctx, sched_md(p), n, bc != nullptr, (p->md.wtype == 0 || (p->md.wtype == 1 && ctx->f16_planes)) && ctx->wide_planes);
     const float* x = nullptr;   // the rows the first layer reads
     if (route != EvalRoute::Step && route != EvalRoute::Q8Steps && (rc = eval_input(p, c, route, &x))) return rc;   // (the single steps embed their own token)
     switch (route) {
@@ -3921,7 +4023,7 @@ int lh_llama_create(lh_ctx* ctx, const lh_llama_desc* desc, lh_llama** out) {
     if (!ctx || !desc || !out) LH_FAIL(ctx, LH_EINVAL, "lh_llama_create: NULL argument");
     *out = nullptr;
     LH_HIP(ctx, hipSetDevice(ctx->device));
-    if (desc->weight_dtype != 0 && desc->weight_dtype != 1 && desc->weight_dtype != 2 && desc->weight_dtype != 7) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_llama_create: weight dtype %d not supported", desc->weight_dtype);
+    if (desc->weight_dtype != 0 && desc->weight_dtype != 1 && desc->weight_dtype != 2 && desc->weight_dtype != 3 && desc->weight_dtype != 7) LH_FAIL(ctx, LH_EUNSUPPORTED, "lh_llama_create: weight dtype %d not supported", desc->weight_dtype);
     ModelDesc md;
     md.V = desc->vocab; md.d = desc->embd; md.H = desc->heads; md.L = desc->layers; md.F = desc->ff; md.ctx = desc->ctx;
     if (!md.H || !md.d || md.d % md.H) LH_FAIL(ctx, LH_ESHAPE, "lh_llama_create: bad embd/heads");
@@ -3944,7 +4046,7 @@ int lh_llama_create(lh_ctx* ctx, const lh_llama_desc* desc, lh_llama** out) {
         if (!bf) LH_FAIL(ctx, LH_EINVAL, "lh_llama_create: %s is not a registered buffer", what);
         if (md.wtype == 1 && bf->dtype != 1) LH_FAIL(ctx, LH_EINVAL, "lh_llama_create: weight_dtype 1 (f16) but %s is a dtype-%d buffer: every matrix of an f16 model must be f16", what, bf->dtype);
         if (bf->nfloats < rows * cols || bf->dtype != md.wtype) LH_FAIL(ctx, LH_ESHAPE, "lh_llama_create: %s has the wrong size or dtype", what);
-        if ((md.wtype == 7 || md.wtype == 2) && (bf->rows != rows || bf->cols != cols)) LH_FAIL(ctx, LH_ESHAPE, "lh_llama_create: %s %s shape mismatch", what, md.wtype == 7 ? "block-int8" : "block-int4");
+        if ((md.wtype == 7 || md.wtype == 2 || md.wtype == 3) && (bf->rows != rows || bf->cols != cols)) LH_FAIL(ctx, LH_ESHAPE, "lh_llama_create: %s %s shape mismatch", what, md.wtype == 7 ? "block-int8" : md.wtype == 2 ? "block-int4" : "Q4_1");
         *dst = bf->dev;
         *sc = bf->scales;
         return 0;

@@ -381,7 +381,7 @@ struct llama_layer { ml_tensor *attentionNorm, *wq, *wk, *wv, *wo, *ffn_norm, *w
 struct llama_model {  // llama.go:181-193
     llama_hparams hp;
     uint32_t ffSize;
-    int wtype = ML_TYPE_F32;  // dtype of the weight matrices (ML_TYPE_Q8_0 after llamago_QuantizeModelQ8; ML_TYPE_F16 after llamago_NarrowModelF16 / llamago_LoadModelKeepF16; ML_TYPE_Q4_0 after llamago_QuantizeModelQ4)
+    int wtype = ML_TYPE_F32;  // dtype of the weight matrices (ML_TYPE_Q8_0 after llamago_QuantizeModelQ8; ML_TYPE_F16 after llamago_NarrowModelF16 / llamago_LoadModelKeepF16; ML_TYPE_Q4_0 after llamago_QuantizeModelQ4; ML_TYPE_Q4_1 after llamago_QuantizeModelQ41 / llamago_LoadModelKeepQ41)
     ml_tensor *tokEmbeddings = nullptr, *norm = nullptr, *output = nullptr;
     std::vector<llama_layer> layers;
     uint32_t layer0, layer1;
@@ -587,13 +587,15 @@ static llama_model* load_model(const char* fileName, uint32_t ctxSize, int keep)
 llama_model* llama_LoadModel(const char* fileName, uint32_t ctxSize) { return load_model(fileName, ctxSize, 0); }
 llama_model* llamago_LoadModelKeepF16(const char* fileName, uint32_t ctxSize) { return load_model(fileName, ctxSize, ML_TYPE_F16); }
 llama_model* llamago_LoadModelKeepQ4(const char* fileName, uint32_t ctxSize) { return load_model(fileName, ctxSize, ML_TYPE_Q4_0); }
+llama_model* llamago_LoadModelKeepQ41(const char* fileName, uint32_t ctxSize) { return load_model(fileName, ctxSize, ML_TYPE_Q4_1); }
 int llamago_ModelWeightType(const llama_model* m) { return m ? m->wtype : -1; }
 // keep = ML_TYPE_F16: when EVERY weight matrix of the file is f16, the halves go to HBM as they are (dtype 1; norm vectors and tok_embeddings f32 as
-// ever); keep = ML_TYPE_Q4_0: the same for a file whose matrices are all Q4_0 - the 20-byte blocks are registered as they are (dtype 2).
+// ever); keep = ML_TYPE_Q4_0: the same for a file whose matrices are all Q4_0 - the 20-byte blocks are registered as they are (dtype 2); keep = ML_TYPE_Q4_1: likewise for Q4_1 and
+// its 24-byte blocks (dtype 3).
 // Any other file loads exactly as without the flag (a Q4_0 tensor then meets llama_LoadModel's own refusal).
-static size_t file_bytes(uint32_t dtype, uint64_t n) { return dtype == ML_TYPE_F16 ? n * 2 : dtype == ML_TYPE_Q4_0 ? n / 32 * 20 : n * 4; }
+static size_t file_bytes(uint32_t dtype, uint64_t n) { return dtype == ML_TYPE_F16 ? n * 2 : dtype == ML_TYPE_Q4_0 ? n / 32 * 20 : dtype == ML_TYPE_Q4_1 ? n / 32 * 24 : n * 4; }
 static llama_model* load_model(const char* fileName, uint32_t ctxSize, int keep) {
-    bool keep_native = keep != 0;   // the matrices stay in the file's own format (f16 or Q4_0, whichever `keep` names) - until the pre-scan says otherwise
+    bool keep_native = keep != 0;   // the matrices stay in the file's own format (f16, Q4_0 or Q4_1, whichever `keep` names) - until the pre-scan says otherwise
     FILE* f = fopen(fileName, "rb");
     if (!f) return (llama_model*)halt("[ERROR] cannot open model file");
     if (rd_u32(f) != LLAMA_FILE_MAGIC) { fclose(f); return (llama_model*)halt("[ERROR] Invalid model file! Wrong MAGIC in header"); }  // llama.go:722-732
@@ -618,7 +620,7 @@ static llama_model* load_model(const char* fileName, uint32_t ctxSize, int keep)
             char name[256];
             if (nameLen >= sizeof name || fread(name, 1, nameLen, f) != nameLen) { keep_native = false; break; }
             name[nameLen] = 0;
-            if (is_matrix_name(name)) { if (dtype != (uint32_t)keep || (keep == ML_TYPE_Q4_0 && (dims != 2 || n % 32))) { keep_native = false; break; } mats++; }
+            if (is_matrix_name(name)) { if (dtype != (uint32_t)keep || ((keep == ML_TYPE_Q4_0 || keep == ML_TYPE_Q4_1) && (dims != 2 || n % 32))) { keep_native = false; break; } mats++; }
             else if (dtype != ML_TYPE_F16 && dtype != ML_TYPE_F32) { keep_native = false; break; }
             if (n > (uint64_t)std::max(V, F) * d) { keep_native = false; break; }   // (the load below reports what is wrong)
             const long off = (ftell(f) + 31) & ~31L;
@@ -649,12 +651,12 @@ static llama_model* load_model(const char* fileName, uint32_t ctxSize, int keep)
         off = (off + 31) & ~31L;  // 32-byte alignment llama.go:926-933
         fseek(f, off, SEEK_SET);
         const uint64_t n = nelements(t);
-        if (keep_native && keep == ML_TYPE_Q4_0 && is_matrix_name(name)) {   // the 20-byte blocks as they are (every nibble kept)
-            blocks.resize(file_bytes(ML_TYPE_Q4_0, n));
-            if (t->buf || dtype != ML_TYPE_Q4_0 || fread(blocks.data(), 1, blocks.size(), f) != blocks.size()) { fclose(f); llama_FreeModel(m); return (llama_model*)halt("[ERROR] Failed to read Q4_0 tensor from model!"); }
+        if (keep_native && (keep == ML_TYPE_Q4_0 || keep == ML_TYPE_Q4_1) && is_matrix_name(name)) {   // the 20-byte (Q4_1: 24-byte) blocks as they are (every bit kept)
+            blocks.resize(file_bytes((uint32_t)keep, n));
+            if (t->buf || dtype != (uint32_t)keep || fread(blocks.data(), 1, blocks.size(), f) != blocks.size()) { fclose(f); llama_FreeModel(m); return (llama_model*)halt(keep == ML_TYPE_Q4_0 ? "[ERROR] Failed to read Q4_0 tensor from model!" : "[ERROR] Failed to read Q4_1 tensor from model!"); }
             const uint32_t ne4[4] = {t->ne[0], t->ne[1], 1, 1};
-            if (lh_tensor_register(h, 0, ML_TYPE_Q4_0, ne4, 1, blocks.data(), &t->buf)) { g_err = lh_last_error(h); fclose(f); llama_FreeModel(m); return nullptr; }
-            t->type = ML_TYPE_Q4_0;
+            if (lh_tensor_register(h, 0, keep, ne4, 1, blocks.data(), &t->buf)) { g_err = lh_last_error(h); fclose(f); llama_FreeModel(m); return nullptr; }
+            t->type = keep;
             continue;
         }
         if (keep_native && is_matrix_name(name)) {   // the halves as they are: no fp32 bounce, no fp32 copy in HBM
@@ -684,8 +686,8 @@ static void wr_u32(FILE* f, uint32_t v) { unsigned char b[4] = {(unsigned char)v
 static int wr_tensor(FILE* f, const char* name, ml_tensor* t, int ftype) {  // scripts/convert-pth-to-ggml.py:196-232
     const uint32_t dims = t->dims;
     const bool as16 = ftype == 1 && dims == 2;
-    const bool as_q4 = ftype == ML_TYPE_Q4_0 && t->type == ML_TYPE_Q4_0;   // the matrices of a block-int4 model: their blocks as they are; everything else f32
-    wr_u32(f, dims); wr_u32(f, (uint32_t)strlen(name)); wr_u32(f, as_q4 ? (uint32_t)ML_TYPE_Q4_0 : as16 ? 1u : 0u);
+    const bool as_q4 = (ftype == ML_TYPE_Q4_0 || ftype == ML_TYPE_Q4_1) && t->type == ftype;   // the matrices of a block-int4 / Q4_1 model: their blocks as they are; everything else f32
+    wr_u32(f, dims); wr_u32(f, (uint32_t)strlen(name)); wr_u32(f, as_q4 ? (uint32_t)ftype : as16 ? 1u : 0u);
     for (uint32_t i = 0; i < dims; i++) wr_u32(f, t->ne[i]);
     fwrite(name, 1, strlen(name), f);
     long off = ftell(f);
@@ -693,8 +695,8 @@ static int wr_tensor(FILE* f, const char* name, ml_tensor* t, int ftype) {  // s
     const uint64_t n = nelements(t);
     if (as_q4) {
         lh_ctx* h = model_ctx();
-        std::vector<unsigned char> blocks(n / 32 * 20);
-        if (!h || lh_buf_read_q4(h, t->buf, 0, blocks.data(), n / 32)) return halt_rc(h ? lh_last_error(h) : "no device context");
+        std::vector<unsigned char> blocks(file_bytes((uint32_t)ftype, n));
+        if (!h || (ftype == ML_TYPE_Q4_0 ? lh_buf_read_q4(h, t->buf, 0, blocks.data(), n / 32) : lh_buf_read_q41(h, t->buf, 0, blocks.data(), n / 32))) return halt_rc(h ? lh_last_error(h) : "no device context");
         return fwrite(blocks.data(), 1, blocks.size(), f) != blocks.size();
     }
     std::vector<float> host(n);
@@ -708,6 +710,8 @@ int llama_SaveModel(const llama_model* mc, const char* fileName, int ftype) {
     if (m->layer0 != 0 || m->layer1 != m->hp.layersCount) return halt_rc("llama_SaveModel: partial (layer-sharded) model");
     if (m->wtype == ML_TYPE_Q4_0 && ftype != ML_TYPE_Q4_0) return halt_rc("llama_SaveModel: the model's matrices are block-int4 in HBM (llamago_SaveModelQ4 writes them as they are)");
     if (ftype == ML_TYPE_Q4_0 && m->wtype != ML_TYPE_Q4_0) return halt_rc("llamago_SaveModelQ4: the model's matrices are not block-int4 (llamago_QuantizeModelQ4 first)");
+    if (m->wtype == ML_TYPE_Q4_1 && ftype != ML_TYPE_Q4_1) return halt_rc("llama_SaveModel: the model's matrices are Q4_1 in HBM (llamago_SaveModelQ41 writes them as they are)");
+    if (ftype == ML_TYPE_Q4_1 && m->wtype != ML_TYPE_Q4_1) return halt_rc("llamago_SaveModelQ41: the model's matrices are not Q4_1 (llamago_QuantizeModelQ41 first)");
     if (m->wtype == ML_TYPE_F16) return halt_rc("llama_SaveModel: the model's matrices are f16 in HBM; saving f16 models is not supported (llamago_WidenModelF16 first)");
     FILE* f = fopen(fileName, "wb");
     if (!f) return halt_rc("llama_SaveModel: cannot open file");
@@ -735,6 +739,13 @@ int llama_SaveModel(const llama_model* mc, const char* fileName, int ftype) {
 int llamago_SaveModelQ4(const llama_model* m, const char* fileName) {
     if (!m || !fileName) return halt_rc("llamago_SaveModelQ4: null argument");
     return llama_SaveModel(m, fileName, ML_TYPE_Q4_0);
+}
+
+// A Q4_1 model as a ggjt file of ftype 3: the matrices as 24-byte Q4_1 blocks, norm vectors and tok_embeddings f32.  llamago_LoadModelKeepQ41 reads it
+// back without touching a block; llama_LoadModel refuses it as the reference does (llama.go:956-959).
+int llamago_SaveModelQ41(const llama_model* m, const char* fileName) {
+    if (!m || !fileName) return halt_rc("llamago_SaveModelQ41: null argument");
+    return llama_SaveModel(m, fileName, ML_TYPE_Q4_1);
 }
 
 // ---- context + Eval -----------------------------------------------------------------------------------
@@ -1793,6 +1804,7 @@ int llamago_QuantizeModelQ8(llama_model* m) {
     if (m->wtype == ML_TYPE_Q8_0) return 0;
     if (m->wtype == ML_TYPE_F16) return halt_rc("llamago_QuantizeModelQ8: the model's matrices are f16 (quantise before narrowing)");
     if (m->wtype == ML_TYPE_Q4_0) return halt_rc("llamago_QuantizeModelQ8: the model's matrices are block-int4 (llamago_ExpandModelQ4 makes the block-int8 model of the same values)");
+    if (m->wtype == ML_TYPE_Q4_1) return halt_rc("llamago_QuantizeModelQ8: the model's matrices are Q4_1 (w = d n + m is no block-int8 weight; llamago_ExpandModelQ41 makes the f32 model of the same values)");
     { std::lock_guard<std::mutex> lk(m->mu);
       if (m->users > 0) return halt_rc("llamago_QuantizeModelQ8: contexts of this model are alive (their plans address the f32 weights); quantise before creating contexts"); }
     lh_ctx* h = model_ctx();
@@ -1821,7 +1833,7 @@ static int convert_matrices(llama_model* m, const char* who, int from, int to, u
     char msg[256];
     if (!m) { snprintf(msg, sizeof msg, "%s: null argument", who); return halt_rc(msg); }
     if (m->wtype == to) { if (n_changed) *n_changed = 0; return 0; }
-    auto tname = [](int t) { return t == ML_TYPE_F32 ? "f32" : t == ML_TYPE_F16 ? "f16" : t == ML_TYPE_Q4_0 ? "block-int4" : "block-int8"; };
+    auto tname = [](int t) { return t == ML_TYPE_F32 ? "f32" : t == ML_TYPE_F16 ? "f16" : t == ML_TYPE_Q4_0 ? "block-int4" : t == ML_TYPE_Q4_1 ? "Q4_1" : "block-int8"; };
     if (m->wtype != from) { snprintf(msg, sizeof msg, "%s: the model's matrices are %s (dtype %d), not %s", who, tname(m->wtype), m->wtype, tname(from)); return halt_rc(msg); }
     { std::lock_guard<std::mutex> lk(m->mu);
       if (m->users > 0) { snprintf(msg, sizeof msg, "%s: contexts of this model are alive (their plans address the weights); convert before creating contexts", who); return halt_rc(msg); } }
@@ -1833,7 +1845,8 @@ static int convert_matrices(llama_model* m, const char* who, int from, int to, u
         lh_buf nb = 0;
         uint64_t ch = 0;
         const int e = to == ML_TYPE_F16 ? lh_buf_narrow_f16(h, t->buf, t->ne[1], t->ne[0], &nb, &ch) : to == ML_TYPE_Q4_0 ? lh_buf_quantize_q4(h, t->buf, t->ne[1], t->ne[0], &nb)
-                    : to == ML_TYPE_Q8_0 ? lh_buf_expand_q4(h, t->buf, &nb) : lh_buf_widen_f16(h, t->buf, &nb);
+                    : to == ML_TYPE_Q8_0 ? lh_buf_expand_q4(h, t->buf, &nb) : to == ML_TYPE_Q4_1 ? lh_buf_quantize_q41(h, t->buf, t->ne[1], t->ne[0], &nb)
+                    : from == ML_TYPE_Q4_1 ? lh_buf_expand_q41(h, t->buf, &nb) : lh_buf_widen_f16(h, t->buf, &nb);
         if (e) return halt_rc(lh_last_error(h));
         lh_buf_free(h, t->buf);
         t->buf = nb;
@@ -1860,6 +1873,23 @@ int llamago_ExpandModelQ4(llama_model* m) {
     if (m && m->wtype != ML_TYPE_Q4_0) return halt_rc("llamago_ExpandModelQ4: the model's matrices are not block-int4");
     return convert_matrices(m, "llamago_ExpandModelQ4", ML_TYPE_Q4_0, ML_TYPE_Q8_0, nullptr);
 }
+// Q4_1 (ML_TYPE_Q4_1, dtype 3 of the C-ABI; format and the value of a weight in csrc/kernels_q41.h).  Quantise: every weight MATRIX of an f32 model through
+// lh_buf_quantize_q41, the f32 copies released.  Expand: the f32 model of the values w' = fl32(fma(d, n, m)) (lh_buf_expand_q41) - the tests' fp32 twin.
+int llamago_QuantizeModelQ41(llama_model* m) { return convert_matrices(m, "llamago_QuantizeModelQ41", ML_TYPE_F32, ML_TYPE_Q4_1, nullptr); }
+int llamago_ExpandModelQ41(llama_model* m) {
+    if (m && m->wtype != ML_TYPE_Q4_1) return halt_rc("llamago_ExpandModelQ41: the model's matrices are not Q4_1");
+    return convert_matrices(m, "llamago_ExpandModelQ41", ML_TYPE_Q4_1, ML_TYPE_F32, nullptr);
+}
+// the 24-byte blocks of one matrix of a Q4_1 model, as registered / as llamago_SaveModelQ41 writes them
+int llamago_ReadTensorQ41(llama_model* m, const char* name, void* dst_blocks, uint64_t nblocks) {
+    if (!m || !name || !dst_blocks) return halt_rc("llamago_ReadTensorQ41: null argument");
+    ml_tensor* t = llama_ModelTensor(m, name);
+    if (!t || t->type != ML_TYPE_Q4_1) return halt_rc("llamago_ReadTensorQ41: no Q4_1 tensor of that name");
+    lh_ctx* h = model_ctx();
+    if (!h) return 1;
+    if (nblocks != nelements(t) / 32) return halt_rc("llamago_ReadTensorQ41: the tensor has another number of blocks");
+    return lh_buf_read_q41(h, t->buf, 0, dst_blocks, nblocks) ? halt_rc(lh_last_error(h)) : 0;
+}
 // Test instrumentation (tests/test_gpu_attention_bound.py: the probe layer): one fp32 tensor of the model replaced by host values.
 int llamago_SetModelTensor(llama_model* m, const char* name, const float* data, uint64_t n) {
     if (!m || !name || !data) return halt_rc("llamago_SetModelTensor: null argument");
@@ -1870,6 +1900,7 @@ int llamago_SetModelTensor(llama_model* m, const char* name, const float* data, 
     if (!t) { snprintf(msg, sizeof msg, "llamago_SetModelTensor: the model has no tensor \"%s\"", name); return halt_rc(msg); }
     if (t->type == ML_TYPE_F16) { snprintf(msg, sizeof msg, "llamago_SetModelTensor: \"%s\" is f16 (set tensors before llamago_NarrowModelF16)", name); return halt_rc(msg); }
     if (t->type == ML_TYPE_Q4_0) { snprintf(msg, sizeof msg, "llamago_SetModelTensor: \"%s\" is block-int4 (set tensors before llamago_QuantizeModelQ4)", name); return halt_rc(msg); }
+    if (t->type == ML_TYPE_Q4_1) { snprintf(msg, sizeof msg, "llamago_SetModelTensor: \"%s\" is Q4_1 (set tensors before llamago_QuantizeModelQ41)", name); return halt_rc(msg); }
     if (t->type != ML_TYPE_F32) { snprintf(msg, sizeof msg, "llamago_SetModelTensor: \"%s\" is quantised (set tensors before llamago_QuantizeModelQ8)", name); return halt_rc(msg); }
     if (n != nelements(t)) { snprintf(msg, sizeof msg, "llamago_SetModelTensor: \"%s\" has %llu elements, %llu given", name, (unsigned long long)nelements(t), (unsigned long long)n); return halt_rc(msg); }
     lh_ctx* h = model_ctx();

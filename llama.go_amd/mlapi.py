@@ -235,6 +235,13 @@ class MLLib:
         f.restype, f.argtypes = VP, [C.c_char_p, C.c_uint32]
         return Model(self, self._chk(f(os.fsencode(path), ctxSize), "llamago_LoadModelKeepQ4"))
 
+    def LoadModelKeepQ41(self, path, ctxSize):
+        """llamago_LoadModelKeepQ41 (product only): LoadModel, except that a file whose weight matrices are all Q4_1 keeps their blocks as they are in
+        HBM (Model.weight_type == 3); any other file loads as LoadModel loads it."""
+        f = self.lib.llamago_LoadModelKeepQ41
+        f.restype, f.argtypes = VP, [C.c_char_p, C.c_uint32]
+        return Model(self, self._chk(f(os.fsencode(path), ctxSize), "llamago_LoadModelKeepQ41"))
+
 
 def make_hparams(vocab, embd, mult, heads, layers, ctx=128):
     hp = HParams()
@@ -321,9 +328,42 @@ class Model:
             raise MLError(f"llamago_ExpandModelQ4: {self.ml.last_error()}")
         return self
 
+    def QuantizeQ41(self):
+        """llamago_QuantizeModelQ41 (product only): every weight matrix quantised to Q4_1 in HBM (24 bytes per 32 weights: d, m, 16 nibble bytes;
+        the value of a weight is fl32(fma(d, n, m))), the f32 copies released.  Before any context of the model exists."""
+        f = self.ml.lib.llamago_QuantizeModelQ41
+        f.restype, f.argtypes = C.c_int, [VP]
+        if f(self.h):
+            raise MLError(f"llamago_QuantizeModelQ41: {self.ml.last_error()}")
+        return self
+
+    def ExpandQ41(self):
+        """llamago_ExpandModelQ41 (product only): a Q4_1 model as the f32 model of its weights' values (identical values)."""
+        f = self.ml.lib.llamago_ExpandModelQ41
+        f.restype, f.argtypes = C.c_int, [VP]
+        if f(self.h):
+            raise MLError(f"llamago_ExpandModelQ41: {self.ml.last_error()}")
+        return self
+
+    def SaveQ41(self, path):
+        """llamago_SaveModelQ41 (product only): a Q4_1 model as a ggjt file of ftype 3 (LoadModelKeepQ41 reads it back block for block)."""
+        f = self.ml.lib.llamago_SaveModelQ41
+        f.restype, f.argtypes = C.c_int, [VP, C.c_char_p]
+        if f(self.h, os.fsencode(path)):
+            raise MLError(f"llamago_SaveModelQ41: {self.ml.last_error()}")
+
+    def blocks_q41(self, name, nelements):
+        """llamago_ReadTensorQ41 (product only): the 24-byte blocks {d, m, qs[16]} of one matrix of a Q4_1 model as uint8 [nelements / 32][24]."""
+        f = self.ml.lib.llamago_ReadTensorQ41
+        f.restype, f.argtypes = C.c_int, [VP, C.c_char_p, VP, c_u64]
+        out = np.empty((nelements // 32, 24), np.uint8)
+        if f(self.h, name.encode(), out.ctypes.data_as(VP), nelements // 32):
+            raise MLError(f"llamago_ReadTensorQ41: {self.ml.last_error()}")
+        return out
+
     @property
     def weight_type(self):
-        """llamago_ModelWeightType (product only): 0 = f32, 1 = f16, 2 = block-int4, 7 = block-int8 weight matrices."""
+        """llamago_ModelWeightType (product only): 0 = f32, 1 = f16, 2 = block-int4, 3 = Q4_1, 7 = block-int8 weight matrices."""
         f = self.ml.lib.llamago_ModelWeightType
         f.restype, f.argtypes = C.c_int, [VP]
         return int(f(self.h))
