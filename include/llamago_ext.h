@@ -98,6 +98,13 @@ int llamago_Q4Stream(llama_context* c);
  * Evals a batch makes of its own (a pod's long feed). */
 int llamago_SetQ4Tiles(llama_context* c, int on);
 int llamago_Q4Tiles(llama_context* c);
+/* lh_ctx_set_q41_tiles / lh_ctx_q41_tiles (llamahip.h) on the lh_ctx the context / the batch evaluates in: with on != 0 the Evals of more than 128 rows of a
+ * Q4_1 model (and its multi-row lm_head: Score, all-rows Evals) run their k_gemm_b9 launches on the model's nibble and (d, m) planes (k_gemm_b9_q41) instead
+ * of an fp32 image expanded in front of them - the same bytes ("Native tile GEMM").  Off by default (LLAMAHIP_Q41_TILES=1 turns it on for every
+ * context created afterwards); without effect for every other weight type.  The setters return 0 | -1 (ml_LastError) on a null argument; the getters 0 | 1.
+ * llamago_BatchSetQ41Tiles / llamago_BatchQ41Tiles (declared with the batch below): the same for the lh_ctx of a batch. */
+int llamago_SetQ41Tiles(llama_context* c, int on);
+int llamago_Q41Tiles(llama_context* c);
 /* lh_ctx_set_f16_tiles / lh_ctx_f16_tiles (llamahip.h) on the lh_ctx the context evaluates in: with on != 0 the Evals of more than 128 rows of an f16 model
  * run their k_gemm_b9 launches on the model's halves (k_gemm_b9_h: six bf16 products per tile pair instead of eight, no widening pass in front) - the same
  * bytes ("Native tile GEMM").  Off by default (LLAMAHIP_F16_TILES=1 turns it on for contexts created afterwards); without effect on models of
@@ -259,6 +266,8 @@ int llamago_BatchSetQ4Stream(llama_batch* b, int on);    /* llamago_SetQ4Stream 
 int llamago_BatchQ4Stream(llama_batch* b);
 int llamago_BatchSetQ4Tiles(llama_batch* b, int on);     /* llamago_SetQ4Tiles on the lh_ctx the batch evaluates in */
 int llamago_BatchQ4Tiles(llama_batch* b);
+int llamago_BatchSetQ41Tiles(llama_batch* b, int on);    /* llamago_SetQ41Tiles on the lh_ctx the batch evaluates in */
+int llamago_BatchQ41Tiles(llama_batch* b);
 /* Test instrumentation: llamago_CacheRead / llamago_CacheWrite on the KV cache of pod `pod` (also fails on a pod outside the batch). */
 int llamago_BatchCacheRead(llama_batch* b, uint32_t pod, int which, uint64_t off_floats, float* dst, uint64_t n);
 int llamago_BatchCacheWrite(llama_batch* b, uint32_t pod, int which, uint64_t off_floats, const float* src, uint64_t n);

@@ -204,6 +204,20 @@ int lh_ctx_q4_tiles(lh_ctx* ctx);
 int64_t lh_gemm_q4_w_off(uint32_t slab, uint32_t row, uint32_t byte);
 int lh_gemm_q4_dma_lane(uint32_t wave, uint32_t lane, uint32_t out[2]);
 int64_t lh_gemm_q4_read_off(uint32_t slab, uint32_t wave, uint32_t li, uint32_t lh);
+/* Q4_1 models on the bf16 tile GEMM of prompts beyond 128 rows (csrc/kernels_gemm_q41.h).  lh_ctx_set_q41_tiles(ctx, on): with on != 0 every k_gemm_b9 launch
+ * of a Q4_1 plan of this context - the launches of a layer and the multi-row lm_head - reads the model's own nibble and (d, m) planes (k_gemm_b9_q41) and
+ * enqueues no k_expand_q41 pass for them; every other launch of the prefill route gets its matrices expanded directly in front of itself.  Byte for byte the
+ * same results: the launch choice, the split-K count and every sum are the expanded fp32 twin's.  Off by default; the initial value is LLAMAHIP_Q41_TILES=1
+ * of the environment, read once in lh_ctx_create.  Read at every Eval; accepted and without effect for every other weight type.  No captured graph holds a
+ * launch the switch chooses.  lh_ctx_q41_tiles: the current value (0 | 1; ctx NULL: 0). */
+int lh_ctx_set_q41_tiles(lh_ctx* ctx, int on);
+int lh_ctx_q41_tiles(lh_ctx* ctx);
+/* Where k_gemm_b9_q41 keeps its weight bytes (csrc/gemm_q41_layout.h; pure host functions, for checks).  lh_gemm_q41_piece: nibble / pair DMA piece q (< 4),
+ * lane (< 64): out = {tile row fetched, byte offset in the ring stage the row's 16 nibble bytes land at, byte offset in a pair slot its 16 (d, m) bytes land
+ * at}.  lh_gemm_q41_read_off: MFMA lane li (< 32) of wave `wave` (< 8): out = {offset in the stage of the 16 nibble bytes it reads per slab (k-step kk,
+ * lane half lh: dword 2 kk + lh), offset in a pair slot of its row's (d0, m0, d1, m1)}.  An argument out of range: -1. */
+int lh_gemm_q41_piece(uint32_t q, uint32_t lane, uint32_t out[3]);
+int lh_gemm_q41_read_off(uint32_t wave, uint32_t li, uint32_t out[2]);
 /* Test instrumentation.  The context owns one fp32 (f16 plans) or int8 (block-int4 plans) image of ONE layer's matrices and one of the output matrix per plan
  * size; every route that reads an image fills the slots it reads in front of its own launches.  lh_ctx_poison_weight_images fills every such image with 0xFF
  * bytes (NaN as fp32, quant -1 as int8), enqueued on the context's stream, and stores the bytes filled (0: the context has no f16 or block-int4 plan).  A

@@ -8,6 +8,7 @@
 #include "stream_q4_layout.h"
 #include "gemm_q4_layout.h"
 #include "gemm_f16_layout.h"
+#include "gemm_q41_layout.h"
 #include <stdarg.h>
 #include <math.h>
 #include <algorithm>
@@ -290,6 +291,8 @@ int lh_ctx_create(int device, void* stream, lh_ctx** out) {
     c->q4_stream = qs && qs[0] == '1' ? 1 : 0;
     const char* qt = getenv("LLAMAHIP_Q4_TILES");
     c->q4_tiles = qt && qt[0] == '1' ? 1 : 0;
+    const char* q1t = getenv("LLAMAHIP_Q41_TILES");
+    c->q41_tiles = q1t && q1t[0] == '1' ? 1 : 0;
     *out = c;
     return LH_OK;
 }
@@ -333,6 +336,22 @@ int lh_ctx_set_q4_tiles(lh_ctx* ctx, int on) {
     return LH_OK;
 }
 int lh_ctx_q4_tiles(lh_ctx* ctx) { return ctx ? ctx->q4_tiles : 0; }
+int lh_ctx_set_q41_tiles(lh_ctx* ctx, int on) {
+    if (!ctx) return LH_EINVAL;
+    ctx->q41_tiles = on ? 1 : 0;   // (no captured graph holds a launch it chooses: common.h)
+    return LH_OK;
+}
+int lh_ctx_q41_tiles(lh_ctx* ctx) { return ctx ? ctx->q41_tiles : 0; }
+int lh_gemm_q41_piece(uint32_t q, uint32_t lane, uint32_t out[3]) {
+    if (q >= 4 || lane >= 64 || !out) return -1;
+    out[0] = lh::gemm_q41_piece_row(q, lane); out[1] = lh::gemm_q41_nib_dst(q, lane); out[2] = lh::gemm_q41_pair_dst(q, lane);
+    return 0;
+}
+int lh_gemm_q41_read_off(uint32_t wave, uint32_t li, uint32_t out[2]) {
+    if (wave >= 8 || li >= 32 || !out) return -1;
+    out[0] = lh::gemm_q41_w_read_off(wave, li); out[1] = lh::gemm_q41_pair_read_off(wave, li);
+    return 0;
+}
 int64_t lh_gemm_q4_w_off(uint32_t slab, uint32_t row, uint32_t byte) {
     if (row >= lh::GEMM_Q4_BM || byte >= 16) return -1;
     return (int64_t)lh::gemm_q4_w_off(slab, row, byte);

@@ -175,6 +175,9 @@ struct lh_ctx {
     // lh_ctx_set_q4_tiles: block-int4 plans hand the k_gemm_q8b3 launches of their prefill route the model's nibbles (k_gemm_q4b3, kernels_gemm_q4.h).  No
     // key of a captured graph holds it (the case of f16_tiles): the launch takes more than 64 rows (gemm_q8b3_ok) and no capture contains a prefill launch.
     int q4_tiles = 0;
+    // lh_ctx_set_q41_tiles: Q4_1 plans hand the k_gemm_b9 launches of their prefill route the model's nibble and (d, m) planes (k_gemm_b9_q41,
+    // kernels_gemm_q41.h).  No key of a captured graph holds it (the case of f16_tiles): k_gemm_b9 takes more than 128 rows and no capture enqueues as many.
+    int q41_tiles = 0;
     // the activation rows of a long-prompt GEMM as three bf16 planes (k_gemm_b9); grows, never shrinks
     uint16_t* xs3 = nullptr;
     uint64_t xs3_elems = 0;

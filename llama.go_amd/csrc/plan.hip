@@ -22,6 +22,7 @@ namespace lh_b9w_tu { const void* stream_b9w_kernel(int maxt, int nct, int wdt, 
 #include "kernels_f16.h"
 #include "kernels_stream_f16.h"
 #include "kernels_gemm_f16.h"
+#include "kernels_gemm_q41.h"
 #include "kernels_q4.h"
 #include "kernels_q41.h"
 #include "kernels_attn_seg.h"
@@ -1505,12 +1506,15 @@ static bool gemm_b9_ok(const GemmArgs& a) {
 #ifndef B9H_PRODUCTS
 #define B9H_PRODUCTS 6
 #endif
+// wdt = 3: a.w[] / a.ws[] are the nibble and (d, m) planes of a Q4_1 model (k_gemm_b9_q41, kernels_gemm_q41.h) - again the same tiles, split count,
+// k_split3_rows and reduce pass, all eight products; a 28 KB stage, ring depth B9Q41_NST (no part of the sums; profiles/q41_tiles.txt).
 static int launch_gemm_b9(lh_ctx* ctx, GemmArgs a, const char* name, uint32_t splits, int wdt = 0) {
     auto kern = k_gemm_b9<1, 8, 4, 1, 2>;
     auto kern_h = k_gemm_b9_h<1, 8, 4, 1, B9H_NST, B9H_PRODUCTS>;
-    const size_t lds = wdt == 1 ? gemm_b9_h_lds_bytes(B9H_NST) : 2 * gemm_b9_stage_bytes(128, 256);
-    static bool flags[16] = {}, flags_h[16] = {};
-    int rc = wdt == 1 ? set_lds_once(ctx, kern_h, lds, flags_h) : set_lds_once(ctx, kern, lds, flags);
+    auto kern_q = k_gemm_b9_q41<1, 8, 4, 1, B9Q41_NST>;
+    const size_t lds = wdt == 1 ? gemm_b9_h_lds_bytes(B9H_NST) : wdt == 3 ? (size_t)gemm_q41_lds_bytes(B9Q41_NST) : 2 * gemm_b9_stage_bytes(128, 256);
+    static bool flags[16] = {}, flags_h[16] = {}, flags_q[16] = {};
+    int rc = wdt == 1 ? set_lds_once(ctx, kern_h, lds, flags_h) : wdt == 3 ? set_lds_once(ctx, kern_q, lds, flags_q) : set_lds_once(ctx, kern, lds, flags);
     if (rc) return rc;
     if (!ensure_xs3(ctx, (uint64_t)3 * a.N * a.K)) LH_FAIL(ctx, LH_ENOMEM, "%s: planes of %u x %u activations", name, a.N, a.K);
     a.xs = ctx->xs3; a.xs_plane = (uint64_t)a.N * a.K; a.ldxs = a.K;
@@ -1527,8 +1531,11 @@ static int launch_gemm_b9(lh_ctx* ctx, GemmArgs a, const char* name, uint32_t sp
         LH_LAUNCH(k_split3_rows, dim3(a.N), dim3(256), 0, ctx->stream, sa);
     }
     const uint64_t items = (uint64_t)((a.N + 127) / 128) * ((a.M + 255) / 256) * a.groups * (splits > 1 ? splits : 1);
-    ProfScope ps(ctx->stream, name, (uint64_t)a.M * a.K * (wdt == 1 ? 2 : 4) * a.groups);
-    if (wdt == 1) {
+    ProfScope ps(ctx->stream, name, wdt == 3 ? (uint64_t)a.M * a.K * 3 / 4 * a.groups : (uint64_t)a.M * a.K * (wdt == 1 ? 2 : 4) * a.groups);
+    if (wdt == 3) {
+        LH_TRACE("k_gemm_b9_q41<1,8,4,1,%d>/s%u", B9Q41_NST, splits > 1 ? splits : 1u);
+        LH_LAUNCH_AS("k_gemm_b9_q41", kern_q, dim3((uint32_t)std::min<uint64_t>(items, (uint64_t)ctx->ds->num_cu)), dim3(512), lds, ctx->stream, a);
+    } else if (wdt == 1) {
         LH_TRACE("k_gemm_b9_h<1,8,4,1,%d>/s%u", B9H_NST, splits > 1 ? splits : 1u);
         LH_LAUNCH_AS("k_gemm_b9_h", kern_h, dim3((uint32_t)std::min<uint64_t>(items, (uint64_t)ctx->ds->num_cu)), dim3(512), lds, ctx->stream, a);
     } else {
@@ -1551,14 +1558,28 @@ static int launch_gemm_b9(lh_ctx* ctx, GemmArgs a, const char* name, uint32_t sp
 // image slot of a matrix whose n halves are at half[g] and which is NOT widened yet.  A stream launch reads the halves (k_stream_*_h) if `stream` is set,
 // a k_gemm_b9 launch reads them (k_gemm_b9_h) if `tiles` is set; every other launch widens the matrix into its slot first, directly in front of itself
 // (HalfSrc::widen: k_widen_f16 per matrix), and reads the image as ever.
+// kind = 3: the same hand-out for a Q4_1 plan with lh_ctx_set_q41_tiles on - half[g] is the matrix's nibble plane, pairs[g] its (d, m) plane, a k_gemm_b9
+// launch reads them (k_gemm_b9_q41) if `tiles` is set, and widen is k_expand_q41 (no stream kernel reads Q4_1 blocks: `stream` stays off).
 struct HalfSrc {
     const float* half[3];
     uint64_t n;
     bool* wide[3];   // the caller's "slot holds the matrix" flags
     bool stream, tiles;
+    int kind = 1;                          // the dtype of the stored form: 1 | 3
+    const float* pairs[3] = {};
     void widen(lh_ctx* ctx, const float* const* w, uint32_t groups) const {
         for (uint32_t g = 0; g < groups; ++g)
-            if (!*wide[g]) { widen_f16_launch(ctx, half[g], (float*)w[g], n); *wide[g] = true; }   // (a launch error surfaces at the layer's hipGetLastError)
+            if (!*wide[g]) {   // (a launch error surfaces at the layer's hipGetLastError)
+                if (kind == 3) expand_q41_launch(ctx, half[g], pairs[g], (float*)w[g], n);
+                else widen_f16_launch(ctx, half[g], (float*)w[g], n);
+                *wide[g] = true;
+            }
+    }
+    // the stored form may stand in for the image in a k_gemm_b9 launch over K columns: planes the LDS-DMA can address (Q4_1: a row's pair granules too)
+    bool native(uint32_t groups, uint32_t K) const {
+        bool ok = kind != 3 || K % 64 == 0;
+        for (uint32_t g = 0; ok && g < groups; ++g) ok = ((uintptr_t)half[g] & 15) == 0 && (kind != 3 || (pairs[g] && ((uintptr_t)pairs[g] & 15) == 0));
+        return ok;
     }
 };
 // One launch site of the stream chain over matrices that may still be halves: launch(w, wdt) is the site's gemm_stream_group / gemm_stream_split call.
@@ -1621,11 +1642,9 @@ int gemm_mfma_group(lh_ctx* ctx, const float* x, uint32_t ldx, uint32_t groups, 
                 if (c < c9 * 0.95) { c9 = c; s9 = s2; }
             }
         if (c9 < 0.97 * std::min(c128, std::min(c160, c64))) {
-            bool halves = hs && hs->tiles && !a.ldw;
-            for (uint32_t g = 0; halves && g < groups; ++g) halves = ((uintptr_t)hs->half[g] & 15) == 0;
-            if (halves) {
-                for (uint32_t g = 0; g < groups; ++g) a.w[g] = hs->half[g];
-                return launch_gemm_b9(ctx, a, name, s9, 1);
+            if (hs && hs->tiles && !a.ldw && hs->native(groups, a.K)) {
+                for (uint32_t g = 0; g < groups; ++g) { a.w[g] = hs->half[g]; a.ws[g] = hs->pairs[g]; }
+                return launch_gemm_b9(ctx, a, name, s9, hs->kind);
             }
             wide();
             return launch_gemm_b9(ctx, a, name, s9);
@@ -2742,7 +2761,10 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
     // lh_ctx_set_f16_tiles: the same hand-out for the tile GEMM - a k_gemm_b9 launch reads the halves (k_gemm_b9_h, kernels_gemm_f16.h).  Either switch
     // makes the matrices lazy; which launches read halves is each switch's own (HalfSrc::stream / ::tiles).
     const bool f16p = &m == &p->md_wide && p->md.wtype == 1;
-    const bool hstream = f16p && ctx->f16_stream, htiles = f16p && ctx->f16_tiles, lazy = hstream || htiles;
+    // lh_ctx_set_q41_tiles: a Q4_1 plan's k_gemm_b9 launches read the nibble and (d, m) planes (k_gemm_b9_q41, kernels_gemm_q41.h) - the f16_tiles hand-out
+    // with HalfSrc::kind = 3; every other launch expands its matrices (k_expand_q41) directly in front of itself.
+    const bool q41t = &m == &p->md_wide && p->md.wtype == 3 && ctx->q41_tiles;
+    const bool hstream = f16p && ctx->f16_stream, htiles = (f16p && ctx->f16_tiles) || q41t, lazy = hstream || htiles;
     // block-int4 plan with lh_ctx_set_q4_stream on (alone): no launch of this route reads nibbles (k_gemm_q8b3 and the dequantising GEMM read int8), so every matrix
     // is expanded - directly in front of the launch that reads it (q4x below) instead of in front of the layer, the one place an expansion stands under
     // the switch (eval_planes, Q4Src).  A plan whose shapes have no k_stream_q8b schedule never launches k_stream_q4b: the switch leaves it alone entirely.
@@ -2758,10 +2780,14 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
         auto q4n = [&](const Q4Src& q) -> const Q4Src* { return q4t ? &q : nullptr; };
         bool wide[7] = {};                                                  // wq wk wv wo w1 w3 w2: the slot holds the matrix
         const uint64_t dd_ = (uint64_t)d * d, dF_ = (uint64_t)d * F;
-        const HalfSrc hqkv = {{LS.wq, LS.wk, LS.wv}, dd_, {&wide[0], &wide[1], &wide[2]}, hstream, htiles}, hq = {{LS.wq}, dd_, {&wide[0]}, hstream, htiles},
-                      hk = {{LS.wk}, dd_, {&wide[1]}, hstream, htiles}, hv = {{LS.wv}, dd_, {&wide[2]}, hstream, htiles}, ho = {{LS.wo}, dd_, {&wide[3]}, hstream, htiles},
-                      h13 = {{LS.w1, LS.w3}, dF_, {&wide[4], &wide[5]}, hstream, htiles}, h1 = {{LS.w1}, dF_, {&wide[4]}, hstream, htiles},
-                      h3 = {{LS.w3}, dF_, {&wide[5]}, hstream, htiles}, h2 = {{LS.w2}, dF_, {&wide[6]}, hstream, htiles};
+        const float* const stored[7] = {LS.wq, LS.wk, LS.wv, LS.wo, LS.w1, LS.w3, LS.w2};
+        const float* const spairs[7] = {LS.s_wq, LS.s_wk, LS.s_wv, LS.s_wo, LS.s_w1, LS.s_w3, LS.s_w2};   // (Q4_1: the (d, m) planes)
+        auto hsrc = [&](int k0, int cnt) {      // matrices k0 .. k0 + cnt - 1 of the list above
+            HalfSrc h = {{}, k0 < 4 ? dd_ : dF_, {}, hstream, htiles, q41t ? 3 : 1, {}};
+            for (int k = 0; k < cnt; ++k) { h.half[k] = stored[k0 + k]; h.wide[k] = &wide[k0 + k]; h.pairs[k] = q41t ? spairs[k0 + k] : nullptr; }
+            return h;
+        };
+        const HalfSrc hqkv = hsrc(0, 3), hq = hsrc(0, 1), hk = hsrc(1, 1), hv = hsrc(2, 1), ho = hsrc(3, 1), h13 = hsrc(4, 2), h1 = hsrc(4, 1), h3 = hsrc(5, 1), h2 = hsrc(6, 1);
         auto src = [&](const HalfSrc& h) -> const HalfSrc* { return lazy ? &h : nullptr; };
         const size_t slot = (size_t)(il - m.cache_layer0) * m.ctx * d;
         const bool mfma = prefill_mfma(m, n);
@@ -2905,7 +2931,7 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
             if ((rc = gemv<PRO_PLAIN, EPI_STORE, MAP_SINGLE>(ctx, ga, "gemv_lmhead_row", hw.wtype))) return rc;
         } else if (htiles) {   // the output matrix lazily: halves where the twin's launch is k_gemm_b9, one widening pass directly in front of any other launch
             bool wide_out = false;
-            const HalfSrc hout = {{p->md.output}, (uint64_t)m.V * d, {&wide_out}, false, true};
+            const HalfSrc hout = {{p->md.output}, (uint64_t)m.V * d, {&wide_out}, false, true, q41t ? 3 : 1, {q41t ? p->md.s_output : nullptr}};
             if ((rc = gemm_small_n_src(ctx, m.output, p->h + (size_t)r0 * d, p->logits + (size_t)r0 * m.V, nullptr, m.V, d, nr, d, m.V, "gemm_lmhead", true, &hout))) return rc;
         } else if ((rc = gemm_small_n(ctx, route_output(p, m), p->h + (size_t)r0 * d, p->logits + (size_t)r0 * m.V, nullptr, m.V, d, nr, d, m.V, "gemm_lmhead"))) return rc;
     }

@@ -1982,6 +1982,16 @@ int llamago_BatchSetQ4Tiles(llama_batch* b, int on) {
     return lh_ctx_set_q4_tiles(b->mlctx->hip, on);
 }
 int llamago_BatchQ4Tiles(llama_batch* b) { return b && b->mlctx ? lh_ctx_q4_tiles(b->mlctx->hip) : 0; }
+int llamago_SetQ41Tiles(llama_context* c, int on) {
+    if (!c || !c->mlctx || !c->mlctx->hip) return halt_rc("llamago_SetQ41Tiles: bad arguments");
+    return lh_ctx_set_q41_tiles(c->mlctx->hip, on);
+}
+int llamago_Q41Tiles(llama_context* c) { return c && c->mlctx ? lh_ctx_q41_tiles(c->mlctx->hip) : 0; }
+int llamago_BatchSetQ41Tiles(llama_batch* b, int on) {
+    if (!b || !b->mlctx || !b->mlctx->hip) return halt_rc("llamago_BatchSetQ41Tiles: bad arguments");
+    return lh_ctx_set_q41_tiles(b->mlctx->hip, on);
+}
+int llamago_BatchQ41Tiles(llama_batch* b) { return b && b->mlctx ? lh_ctx_q41_tiles(b->mlctx->hip) : 0; }
 int llamago_SetF16Tiles(llama_context* c, int on) {
     if (!c || !c->mlctx || !c->mlctx->hip) return halt_rc("llamago_SetF16Tiles: bad arguments");
     return lh_ctx_set_f16_tiles(c->mlctx->hip, on);

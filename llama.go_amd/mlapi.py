@@ -487,6 +487,21 @@ class Context:
         L.llamago_Q4Tiles.argtypes = [VP]
         return bool(L.llamago_Q4Tiles(self.h))
 
+    def SetQ41Tiles(self, on=True):
+        """llamago_SetQ41Tiles: Evals of a Q4_1 model beyond 128 rows run their k_gemm_b9 launches on the model's nibble and (d, m) planes (k_gemm_b9_q41), no expansion in front."""
+        L = self.ml.lib
+        L.llamago_SetQ41Tiles.restype = C.c_int
+        L.llamago_SetQ41Tiles.argtypes = [VP, C.c_int]
+        if L.llamago_SetQ41Tiles(self.h, 1 if on else 0):
+            raise MLError(f"llamago_SetQ41Tiles: {self.ml.last_error()}")
+
+    @property
+    def q41_tiles(self):
+        L = self.ml.lib
+        L.llamago_Q41Tiles.restype = C.c_int
+        L.llamago_Q41Tiles.argtypes = [VP]
+        return bool(L.llamago_Q41Tiles(self.h))
+
     def SetF16Tiles(self, on=True):
         """llamago_SetF16Tiles: Evals of an f16 model beyond 128 rows run their k_gemm_b9 launches on the model's halves (k_gemm_b9_h) instead of a widened image."""
         L = self.ml.lib
@@ -1200,6 +1215,21 @@ class Batch:
         L.llamago_BatchQ4Tiles.restype = C.c_int
         L.llamago_BatchQ4Tiles.argtypes = [VP]
         return bool(L.llamago_BatchQ4Tiles(self.h))
+
+    def SetQ41Tiles(self, on=True):
+        """llamago_BatchSetQ41Tiles: Context.SetQ41Tiles for the Evals this batch makes."""
+        L = self.ml.lib
+        L.llamago_BatchSetQ41Tiles.restype = C.c_int
+        L.llamago_BatchSetQ41Tiles.argtypes = [VP, C.c_int]
+        if L.llamago_BatchSetQ41Tiles(self.h, 1 if on else 0):
+            raise MLError(f"llamago_BatchSetQ41Tiles: {self.ml.last_error()}")
+
+    @property
+    def q41_tiles(self):
+        L = self.ml.lib
+        L.llamago_BatchQ41Tiles.restype = C.c_int
+        L.llamago_BatchQ41Tiles.argtypes = [VP]
+        return bool(L.llamago_BatchQ41Tiles(self.h))
 
     def SetF16Stream(self, on=True):
         """llamago_BatchSetF16Stream: Context.SetF16Stream for the ticks, feeds and speculative passes of this batch."""
