@@ -105,6 +105,14 @@ int llamago_Q4Tiles(llama_context* c);
  * llamago_BatchSetQ41Tiles / llamago_BatchQ41Tiles (declared with the batch below): the same for the lh_ctx of a batch. */
 int llamago_SetQ41Tiles(llama_context* c, int on);
 int llamago_Q41Tiles(llama_context* c);
+/* lh_ctx_set_q41_stream / lh_ctx_q41_stream (llamahip.h) on the lh_ctx the context / the batch evaluates in: with on != 0 the Evals of a Q4_1 model that take
+ * the stream kernels (9..48 rows of a prompt or a tick, prompts of 65..192 rows, the multi-row lm_head) read the model's nibble and (d, m) planes
+ * (k_stream_mm2_q41 / k_stream_dma_q41) instead of an fp32 image expanded in front of every layer - the same bytes ("Native stream kernels").  Off
+ * by default (LLAMAHIP_Q41_STREAM=1 turns it on for every context created afterwards); without effect for every other weight type; independent of
+ * llamago_SetQ41Tiles.  The setters return non-zero (ml_LastError) on a null argument; the getters 0 | 1.  llamago_BatchSetQ41Stream / llamago_BatchQ41Stream
+ * (declared with the batch below): the same for a batch's ticks and feeds. */
+int llamago_SetQ41Stream(llama_context* c, int on);
+int llamago_Q41Stream(llama_context* c);
 /* lh_ctx_set_f16_tiles / lh_ctx_f16_tiles (llamahip.h) on the lh_ctx the context evaluates in: with on != 0 the Evals of more than 128 rows of an f16 model
  * run their k_gemm_b9 launches on the model's halves (k_gemm_b9_h: six bf16 products per tile pair instead of eight, no widening pass in front) - the same
  * bytes ("Native tile GEMM").  Off by default (LLAMAHIP_F16_TILES=1 turns it on for contexts created afterwards); without effect on models of
@@ -268,6 +276,8 @@ int llamago_BatchSetQ4Tiles(llama_batch* b, int on);     /* llamago_SetQ4Tiles o
 int llamago_BatchQ4Tiles(llama_batch* b);
 int llamago_BatchSetQ41Tiles(llama_batch* b, int on);    /* llamago_SetQ41Tiles on the lh_ctx the batch evaluates in */
 int llamago_BatchQ41Tiles(llama_batch* b);
+int llamago_BatchSetQ41Stream(llama_batch* b, int on);   /* llamago_SetQ41Stream on the lh_ctx the batch evaluates in */
+int llamago_BatchQ41Stream(llama_batch* b);
 /* Test instrumentation: llamago_CacheRead / llamago_CacheWrite on the KV cache of pod `pod` (also fails on a pod outside the batch). */
 int llamago_BatchCacheRead(llama_batch* b, uint32_t pod, int which, uint64_t off_floats, float* dst, uint64_t n);
 int llamago_BatchCacheWrite(llama_batch* b, uint32_t pod, int which, uint64_t off_floats, const float* src, uint64_t n);

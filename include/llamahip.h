@@ -218,6 +218,30 @@ int lh_ctx_q41_tiles(lh_ctx* ctx);
  * lane half lh: dword 2 kk + lh), offset in a pair slot of its row's (d0, m0, d1, m1)}.  An argument out of range: -1. */
 int lh_gemm_q41_piece(uint32_t q, uint32_t lane, uint32_t out[3]);
 int lh_gemm_q41_read_off(uint32_t wave, uint32_t li, uint32_t out[2]);
+/* Q4_1 models on the weight-stream MFMA kernels (csrc/kernels_stream_q41.h).  lh_ctx_set_q41_stream(ctx, on): with on != 0 every Eval of a Q4_1 plan of this
+ * context that takes the fp32 stream schedule - prompts and ticks of 9..48 rows, prompts of 65..192 rows, 2..8 rows where the shape has no rows kernel, and
+ * the multi-row lm_head where its launch is a stream launch - hands its stream launches the model's own nibble and (d, m) planes (k_stream_mm2_q41 /
+ * k_stream_dma_q41) and expands a matrix (k_expand_q41) only directly in front of a launch that still reads fp32; a tick of 9..48 pods then expands nothing.
+ * Byte for byte the same results: every launch is the kernel of the expanded fp32 twin's template arguments and split count.  49..64 rows (k_stream_b9),
+ * 5..8 rows (k_gemv_rows) and the single logits row behind a prompt keep their expanded image.  Off by default; the initial value is LLAMAHIP_Q41_STREAM=1 of
+ * the environment, read once in lh_ctx_create.  Read at every Eval; accepted and without effect for every other weight type; independent of
+ * lh_ctx_set_q41_tiles.  A change makes every captured graph of a Q4_1 plan on the context that may hold a stream launch (ticks) run eagerly once and be
+ * captured anew; the change is counted where lh_ctx_set_q4_stream counts its own, so that call re-captures the ticks of Q4_1 plans once as well.
+ * lh_ctx_q41_stream: the current value (0 | 1; ctx NULL: 0). */
+int lh_ctx_set_q41_stream(lh_ctx* ctx, int on);
+int lh_ctx_q41_stream(lh_ctx* ctx);
+/* Where k_stream_dma_q41 keeps a chunk's weight bytes (csrc/stream_q41_layout.h; pure host functions, for checks), for kc-column chunks (64 | 128) and maxt
+ * (1..8) tile slots.  lh_stream_q41_weight_bytes: bytes of the weight part of a ring image (whole 1 KB LDS-DMA instructions).  lh_stream_q41_granule_src: the
+ * loader's side - what lands at 16-byte position pos of the weight part: out = {plane (0 nibbles | 1 (d, m) pairs), image row, source granule of that row's
+ * chunk (plane 0: quant block g; plane 1: the pairs of blocks 2 g, 2 g + 1)}.  lh_stream_q41_granule_off: byte offset of granule g of image row r of a
+ * plane.  The reader's side, MFMA lane (r16, slot) of tile slot t, k-block kb (< kc / 16): lh_stream_q41_read_off = offset of the two bytes that hold columns
+ * 16 kb + 4 slot .. + 3 (the lane reads the aligned dword around them), lh_stream_q41_pair_off = offset of the 8 bytes (d, m) of block kb >> 1.  An argument
+ * out of range: -1. */
+int64_t lh_stream_q41_weight_bytes(uint32_t kc, uint32_t maxt);
+int lh_stream_q41_granule_src(uint32_t kc, uint32_t maxt, uint32_t pos, uint32_t out[3]);
+int64_t lh_stream_q41_granule_off(uint32_t kc, uint32_t maxt, uint32_t plane, uint32_t r, uint32_t g);
+int64_t lh_stream_q41_read_off(uint32_t kc, uint32_t maxt, uint32_t t, uint32_t r16, uint32_t kb, uint32_t slot);
+int64_t lh_stream_q41_pair_off(uint32_t kc, uint32_t maxt, uint32_t t, uint32_t r16, uint32_t kb);
 /* Test instrumentation.  The context owns one fp32 (f16 plans) or int8 (block-int4 plans) image of ONE layer's matrices and one of the output matrix per plan
  * size; every route that reads an image fills the slots it reads in front of its own launches.  lh_ctx_poison_weight_images fills every such image with 0xFF
  * bytes (NaN as fp32, quant -1 as int8), enqueued on the context's stream, and stores the bytes filled (0: the context has no f16 or block-int4 plan).  A

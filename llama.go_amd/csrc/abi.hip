@@ -9,6 +9,7 @@
 #include "gemm_q4_layout.h"
 #include "gemm_f16_layout.h"
 #include "gemm_q41_layout.h"
+#include "stream_q41_layout.h"
 #include <stdarg.h>
 #include <math.h>
 #include <algorithm>
@@ -293,6 +294,8 @@ int lh_ctx_create(int device, void* stream, lh_ctx** out) {
     c->q4_tiles = qt && qt[0] == '1' ? 1 : 0;
     const char* q1t = getenv("LLAMAHIP_Q41_TILES");
     c->q41_tiles = q1t && q1t[0] == '1' ? 1 : 0;
+    const char* q1s = getenv("LLAMAHIP_Q41_STREAM");
+    c->q41_stream = q1s && q1s[0] == '1' ? 1 : 0;
     *out = c;
     return LH_OK;
 }
@@ -342,6 +345,33 @@ int lh_ctx_set_q41_tiles(lh_ctx* ctx, int on) {
     return LH_OK;
 }
 int lh_ctx_q41_tiles(lh_ctx* ctx) { return ctx ? ctx->q41_tiles : 0; }
+int lh_ctx_set_q41_stream(lh_ctx* ctx, int on) {
+    if (!ctx) return LH_EINVAL;
+    const int v = on ? 1 : 0;
+    if (v != ctx->q41_stream) { ctx->q41_stream = v; ++ctx->q4_stream_gen; }   // (the 4-bit stream switches share one counter of the captured graphs' key: common.h)
+    return LH_OK;
+}
+int lh_ctx_q41_stream(lh_ctx* ctx) { return ctx ? ctx->q41_stream : 0; }
+static bool stream_q41_shape(uint32_t kc, uint32_t maxt) { return (kc == 64 || kc == 128) && maxt >= 1 && maxt <= 8; }
+int64_t lh_stream_q41_weight_bytes(uint32_t kc, uint32_t maxt) { return stream_q41_shape(kc, maxt) ? (int64_t)lh::stream_q41_weight_bytes(kc, maxt) : -1; }
+int lh_stream_q41_granule_src(uint32_t kc, uint32_t maxt, uint32_t pos, uint32_t out[3]) {
+    if (!stream_q41_shape(kc, maxt) || pos >= lh::stream_q41_granules(kc, maxt) || !out) return -1;
+    const lh::StreamQ41Granule g = lh::stream_q41_granule_src(kc, maxt, pos);
+    out[0] = g.plane; out[1] = g.row; out[2] = g.g;
+    return 0;
+}
+int64_t lh_stream_q41_granule_off(uint32_t kc, uint32_t maxt, uint32_t plane, uint32_t r, uint32_t g) {
+    if (!stream_q41_shape(kc, maxt) || plane > 1 || r >= maxt * 16 || g >= (plane ? kc / 64 : kc / 32)) return -1;
+    return (int64_t)lh::stream_q41_granule_off(kc, maxt, plane, r, g);
+}
+int64_t lh_stream_q41_read_off(uint32_t kc, uint32_t maxt, uint32_t t, uint32_t r16, uint32_t kb, uint32_t slot) {
+    if (!stream_q41_shape(kc, maxt) || t >= maxt || r16 >= 16 || kb >= kc / 16 || slot >= 4) return -1;
+    return (int64_t)lh::stream_q41_read_off(kc, maxt, t, r16, kb, slot);
+}
+int64_t lh_stream_q41_pair_off(uint32_t kc, uint32_t maxt, uint32_t t, uint32_t r16, uint32_t kb) {
+    if (!stream_q41_shape(kc, maxt) || t >= maxt || r16 >= 16 || kb >= kc / 16) return -1;
+    return (int64_t)lh::stream_q41_pair_off(kc, maxt, t, r16, kb);
+}
 int lh_gemm_q41_piece(uint32_t q, uint32_t lane, uint32_t out[3]) {
     if (q >= 4 || lane >= 64 || !out) return -1;
     out[0] = lh::gemm_q41_piece_row(q, lane); out[1] = lh::gemm_q41_nib_dst(q, lane); out[2] = lh::gemm_q41_pair_dst(q, lane);

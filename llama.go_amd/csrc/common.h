@@ -178,6 +178,10 @@ struct lh_ctx {
     // lh_ctx_set_q41_tiles: Q4_1 plans hand the k_gemm_b9 launches of their prefill route the model's nibble and (d, m) planes (k_gemm_b9_q41,
     // kernels_gemm_q41.h).  No key of a captured graph holds it (the case of f16_tiles): k_gemm_b9 takes more than 128 rows and no capture enqueues as many.
     int q41_tiles = 0;
+    // lh_ctx_set_q41_stream: Q4_1 plans hand the stream launch sites of their prefill route (9..48 and 65..192 rows, the multi-row lm_head) the model's nibble
+    // and (d, m) planes (k_stream_mm2_q41 / k_stream_dma_q41, kernels_stream_q41.h).  A switch that chooses a kernel inside captured graphs (ticks): its changes
+    // are counted in q4_stream_gen and its value is the low bit of the same key field (f16_stream_key, plan.hip) - a plan has one weight type.
+    int q41_stream = 0;
     // the activation rows of a long-prompt GEMM as three bf16 planes (k_gemm_b9); grows, never shrinks
     uint16_t* xs3 = nullptr;
     uint64_t xs3_elems = 0;

@@ -23,6 +23,7 @@ namespace lh_b9w_tu { const void* stream_b9w_kernel(int maxt, int nct, int wdt, 
 #include "kernels_stream_f16.h"
 #include "kernels_gemm_f16.h"
 #include "kernels_gemm_q41.h"
+#include "kernels_stream_q41.h"
 #include "kernels_q4.h"
 #include "kernels_q41.h"
 #include "kernels_attn_seg.h"
@@ -39,6 +40,7 @@ namespace lh_b9w_tu { const void* stream_b9w_kernel(int maxt, int nct, int wdt, 
 namespace lh {
 
 static thread_local bool g_prepare_only = false;  // set kernel attributes without launching (before graph capture)
+static thread_local const float* const* g_q41_pairs = nullptr;   // stream_src -> gemm_stream_group / gemm_stream_split: the (d, m) planes of a wdt = 3 launch (null outside stream_src)
 static thread_local const char* g_only = nullptr;   // lh_llama_profile_decode: launch only the kernels of this name (timing pass)
 static inline bool skip_launch(const char* name) { return g_prepare_only || (g_only && strcmp(g_only, name) != 0); }
 
@@ -1030,7 +1032,7 @@ static int launch_stream(lh_ctx* ctx, const StreamArgs& a, const char* name, int
     static bool flags[16] = {};
     // k_stream_mm2 (loader waves + MFMA waves, two LDS images); shapes whose two images do not fit have no launch here (round 1's kernel in which
     // every wave loaded and multiplied took them until round 6: no LLaMA shape reached it - tests/test_gpu_zz_routes.py; tools/kernels_stream_mm_r1.h)
-    if (a.ws[0]) return ST_NA;   // (block-int8: k_stream_q8b)
+    if (a.ws[0] && wdt != 3) return ST_NA;   // (block-int8: k_stream_q8b; wdt = 3: ws[] are the launch's (d, m) planes, host side only)
     constexpr int KC2 = KC <= 256 ? KC : 256;
     if (stream2_lds_bytes(MAXT, NCT, KC2) > 160 * 1024) return ST_NA;
     const uint32_t grid = a.ksplit > 1 ? (uint32_t)ctx->ds->num_cu / a.ksplit * a.ksplit : (uint32_t)ctx->ds->num_cu;
@@ -1048,6 +1050,24 @@ static int launch_stream(lh_ctx* ctx, const StreamArgs& a, const char* name, int
             LH_HIP(ctx, hipGetLastError());
             return 0;
         } else LH_FAIL(ctx, LH_EUNSUPPORTED, "%s: k_stream_mm2_h is not built for %d column tiles", name, NCT);
+    }
+    if (wdt == 3) {   // (as for halves: only the one-column-tile forms are built)
+        if constexpr (NCT == 1 && KC2 >= 128) {
+            for (uint32_t g = 0; g < a.groups; ++g)
+                if (!a.w[g] || !a.ws[g]) LH_FAIL(ctx, LH_EINVAL, "%s: k_stream_mm2_q41 without the planes of matrix %u", name, g);
+            static bool flags_q[16] = {};
+            auto kern = k_stream_mm2_q41<MAXT, NCT, KC2>;
+            if (const int rq = set_lds_once(ctx, kern, lds, flags_q)) return rq;
+            if (g_prepare_only) return 0;
+            StreamArgs b = a;
+            const StreamQ41Pairs pp = {{a.ws[0], a.ws[1], a.ws[2]}};
+            b.ws[0] = b.ws[1] = b.ws[2] = nullptr;
+            ProfScope ps(ctx->stream, name, (uint64_t)a.groups * a.M * a.K * 3 / 4);
+            LH_TRACE("k_stream_mm2_q41<%d,%d,%d>/s%u", MAXT, NCT, KC2, a.ksplit > 1 ? a.ksplit : 1u);
+            LH_LAUNCH_AS("k_stream_mm2_q41", kern, dim3(grid), dim3(2 * ST_TH), lds, ctx->stream, b, pp);
+            LH_HIP(ctx, hipGetLastError());
+            return 0;
+        } else LH_FAIL(ctx, LH_EUNSUPPORTED, "%s: k_stream_mm2_q41 is not built for %d column tiles", name, NCT);
     }
     int rc = set_lds_once(ctx, k_stream_mm2<MAXT, NCT, KC2>, lds, flags);
     if (rc) return rc;
@@ -1114,6 +1134,39 @@ static int launch_stream_dma_h(lh_ctx* ctx, const StreamArgs& a, const char* nam
     LH_HIP(ctx, hipGetLastError());
     return 0;
 }
+// k_stream_dma_q41 (kernels_stream_q41.h): the same shape on Q4_1 planes.  Ring depth: the weight part of an image is 5.3 times smaller (768 B per tile and
+// 64 columns), so more images fit; shipped: as many as fit up to four with 64-column chunks and up to three with 128-column chunks - k_stream_dma_h's caps;
+// other depths are not measured (-DSTREAM_Q41_NIMG64=n / -DSTREAM_Q41_NIMG128=n, 2..5, are the probe builds); the sums do not depend on the depth.
+#ifndef STREAM_Q41_NIMG64
+#define STREAM_Q41_NIMG64 4
+#endif
+#ifndef STREAM_Q41_NIMG128
+#define STREAM_Q41_NIMG128 3
+#endif
+constexpr int dma_q41_nimg_fit(int maxt, int nct, int kc, int cap) {
+    int n = (int)(160 * 1024 / stream_dma_q41_image_bytes(maxt, nct, kc));
+    return n < cap ? n : cap;
+}
+template <int MAXT, int NCT, int KC, int CS = 1>
+static int launch_stream_dma_q41(lh_ctx* ctx, const StreamArgs& a, const char* name) {
+    constexpr int NIMG = dma_q41_nimg_fit(MAXT, NCT, KC, KC == 64 ? STREAM_Q41_NIMG64 : STREAM_Q41_NIMG128);
+    static_assert(NIMG >= 2, "ring");
+    static bool flags[16] = {};
+    auto kern = k_stream_dma_q41<MAXT, NCT, KC, NIMG, false, CS>;
+    const size_t lds = std::max<size_t>((size_t)NIMG * stream_dma_q41_image_bytes(MAXT, NCT, KC), 82 * 1024);   // one workgroup per CU
+    int rc = set_lds_once(ctx, kern, lds, flags);
+    if (rc) return rc;
+    if (g_prepare_only) return 0;
+    const uint32_t grid = a.ksplit > 1 ? (uint32_t)ctx->ds->num_cu / a.ksplit * a.ksplit : (uint32_t)ctx->ds->num_cu;
+    StreamArgs b = a;
+    const StreamQ41Pairs pp = {{a.ws[0], a.ws[1], a.ws[2]}};   // (host side the planes ride in ws[]; the kernel's StreamArgs is the fp32 kernels')
+    b.ws[0] = b.ws[1] = b.ws[2] = nullptr;
+    ProfScope ps(ctx->stream, name, (uint64_t)a.groups * a.M * a.K * 3 / 4);
+    LH_TRACE("k_stream_dma_q41<%d,%d,%d,%d,%d,%d>/s%u", MAXT, NCT, KC, NIMG, 0, CS, a.ksplit > 1 ? a.ksplit : 1u);
+    LH_LAUNCH_AS("k_stream_dma_q41", kern, dim3(grid), dim3(2 * ST_TH), lds, ctx->stream, b, pp);
+    LH_HIP(ctx, hipGetLastError());
+    return 0;
+}
 // variants: 0 = 64-column chunks, as many images as fit (<= 4); 2 = 128-column chunks, two images; 1 / 3 = the same with pipelined operands
 // (measured round 4, profiles/r04_stream_dma_variants.txt: the operand pipeline buys nothing on two to six column tiles - the LDS
 // latency behind a barrier is not what idles the matrix pipe - so only the eight-column-tile launches are built with it)
@@ -1129,6 +1182,13 @@ static int launch_stream_dma_v(lh_ctx* ctx, const StreamArgs& a, const char* nam
             if constexpr (N128 >= 2) if (v == 2) return launch_stream_dma_h<MAXT, NCT, 128>(ctx, a, name);
             return launch_stream_dma_h<MAXT, NCT, 64>(ctx, a, name);
         }
+    }
+    if (wdt == 3) {   // the fp32 branch's chunk length and column split for the variant stream_dma_default_variant names - the only one a launch asks for
+        constexpr bool L128 = NCT == 2 && MAXT >= 5 && N128 >= 2;
+        if (v != (L128 ? 2 : 0)) LH_FAIL(ctx, LH_EUNSUPPORTED, "%s: k_stream_dma_q41 is built for the default variant only", name);
+        if constexpr (NCT == 8) return launch_stream_dma_q41<MAXT, NCT, 64, 2>(ctx, a, name);
+        else if constexpr (L128) return launch_stream_dma_q41<MAXT, NCT, 128>(ctx, a, name);
+        else return launch_stream_dma_q41<MAXT, NCT, 64>(ctx, a, name);
     }
     if constexpr (NCT == 8) {   // eight column tiles: MFMA waves as 2 K-groups x 2 column halves, 64-column chunks
         static_assert(dma_pipe_ok(MAXT, NCT / 2), "column split");
@@ -1165,7 +1225,7 @@ static int launch_stream_nct(lh_ctx* ctx, const StreamArgs& a, const char* name,
     if constexpr (NCT >= 2) {
         // (one column tile, 9..16 rows, stays on k_stream_mm2 with the norm folded into the launch: on the LDS-DMA kernel with the norm's own launch
         // in front it measured 6.12-6.14 ms per Eval against 5.63-5.68, 16 pods 5.91 against 5.81 ms per tick - profiles/r04_stream_one_column_tile_probe.txt)
-        if (!a.ws[0] && !a.gamma && !a.tiled) return launch_stream_dma_v<MAXT, NCT>(ctx, a, name, stream_dma_default_variant(MAXT, NCT), wdt);
+        if ((!a.ws[0] || wdt == 3) && !a.gamma && !a.tiled) return launch_stream_dma_v<MAXT, NCT>(ctx, a, name, stream_dma_default_variant(MAXT, NCT), wdt);
     }
     if constexpr (NCT > 6) return ST_NA;   // (k_stream_mm2 holds MAXT x NCT accumulator tiles per wave: up to six column tiles)
     else return launch_stream_kc<MAXT, NCT>(ctx, a, name, wdt);
@@ -1221,6 +1281,10 @@ static int gemm_stream_group(lh_ctx* ctx, const float* x, uint32_t ldx, uint32_t
     for (uint32_t g = 0; g < groups; ++g) {
         a.w[g] = w[g]; a.y[g] = y ? y[g] : nullptr; a.r[g] = r ? r[g] : nullptr;
         if (((uintptr_t)w[g] & 15) || ((uintptr_t)a.y[g] & 15) || (a.r[g] && ((uintptr_t)a.r[g] & 15))) return ST_NA;
+        if (wdt == 3) {   // the (d, m) planes: 16-byte granules of two blocks
+            a.ws[g] = g_q41_pairs ? g_q41_pairs[g] : nullptr;
+            if (!a.ws[g] || ((uintptr_t)a.ws[g] & 15)) return ST_NA;
+        }
     }
     return launch_stream_maxt(ctx, a, name, maxt, wdt);
 }
@@ -1246,6 +1310,10 @@ static int gemm_stream_split(lh_ctx* ctx, const float* w, const float* x, uint32
     StreamArgs a = {};
     a.x = x; a.groups = 1; a.M = M; a.K = K; a.n = n; a.ldx = ldx; a.ldy = M; a.w[0] = w; a.y[0] = ctx->splitk;
     a.ksplit = S; a.ysplit = (uint64_t)n * M;
+    if (wdt == 3) {   // the (d, m) plane of the matrix
+        a.ws[0] = g_q41_pairs ? g_q41_pairs[0] : nullptr;
+        if (!a.ws[0] || ((uintptr_t)a.ws[0] & 15)) return ST_NA;
+    }
     const int rs = launch_stream_maxt(ctx, a, name, maxt, wdt);
     if (rs) return rs;
     if (g_prepare_only) return 0;
@@ -1559,7 +1627,8 @@ static int launch_gemm_b9(lh_ctx* ctx, GemmArgs a, const char* name, uint32_t sp
 // a k_gemm_b9 launch reads them (k_gemm_b9_h) if `tiles` is set; every other launch widens the matrix into its slot first, directly in front of itself
 // (HalfSrc::widen: k_widen_f16 per matrix), and reads the image as ever.
 // kind = 3: the same hand-out for a Q4_1 plan with lh_ctx_set_q41_tiles on - half[g] is the matrix's nibble plane, pairs[g] its (d, m) plane, a k_gemm_b9
-// launch reads them (k_gemm_b9_q41) if `tiles` is set, and widen is k_expand_q41 (no stream kernel reads Q4_1 blocks: `stream` stays off).
+// launch reads them (k_gemm_b9_q41) if `tiles` is set, a stream launch reads them (k_stream_mm2_q41 / k_stream_dma_q41, lh_ctx_set_q41_stream) if `stream`
+// is set, and widen is k_expand_q41.
 struct HalfSrc {
     const float* half[3];
     uint64_t n;
@@ -1588,7 +1657,12 @@ struct HalfSrc {
 template <typename F>
 static int stream_src(lh_ctx* ctx, const HalfSrc* hs, const float* const* w, uint32_t groups, F&& launch) {
     if (!hs) return launch(w, 0);
-    if (hs->stream) return launch(hs->half, 1);
+    if (hs->stream && hs->kind == 3) {   // the nibble planes stand in for the matrices, the (d, m) planes ride next to them
+        g_q41_pairs = hs->pairs;
+        const int rq = launch(hs->half, 3);
+        g_q41_pairs = nullptr;
+        if (rq != ST_NA) return rq;   // (ST_NA: no Q4_1 form of this launch - the image, as with the switch off)
+    } else if (hs->stream) return launch(hs->half, 1);
     const bool was = g_prepare_only;
     g_prepare_only = true;
     const int rs = launch(w, 0);
@@ -2350,6 +2424,9 @@ static bool q41_native_rows(const Plan* p, uint32_t n) { return p->md.wtype == 3
 static uint64_t f16_stream_key(const Plan* p) {
     if (p->md.wtype == 1) return (p->ctx->f16_stream_gen << 2) | ((uint64_t)p->ctx->f16_planes << 1) | (uint64_t)p->ctx->f16_stream;   // (lh_ctx_set_f16_planes counts its changes in the same counter)
     if (p->md.wtype == 2) return (p->ctx->q4_stream_gen << 1) | (uint64_t)p->ctx->q4_stream;
+    // Q4_1: lh_ctx_set_q41_stream counts its changes in q4_stream_gen too (abi.hip), so lh_ctx_set_q4_stream on a context of Q4_1 plans re-captures their
+    // ticks once - harmless: the launches are the same
+    if (p->md.wtype == 3) return (p->ctx->q4_stream_gen << 1) | (uint64_t)p->ctx->q41_stream;
     return 0;
 }
 template <typename G>
@@ -2763,8 +2840,10 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
     const bool f16p = &m == &p->md_wide && p->md.wtype == 1;
     // lh_ctx_set_q41_tiles: a Q4_1 plan's k_gemm_b9 launches read the nibble and (d, m) planes (k_gemm_b9_q41, kernels_gemm_q41.h) - the f16_tiles hand-out
     // with HalfSrc::kind = 3; every other launch expands its matrices (k_expand_q41) directly in front of itself.
-    const bool q41t = &m == &p->md_wide && p->md.wtype == 3 && ctx->q41_tiles;
-    const bool hstream = f16p && ctx->f16_stream, htiles = (f16p && ctx->f16_tiles) || q41t, lazy = hstream || htiles;
+    // lh_ctx_set_q41_stream: the same plan's stream launch sites read the planes (k_stream_mm2_q41 / k_stream_dma_q41, kernels_stream_q41.h) - the f16_stream
+    // hand-out with kind = 3, the multi-row lm_head included (hout below); the two switches are independent, either makes the matrices lazy.
+    const bool q41p = &m == &p->md_wide && p->md.wtype == 3, q41t = q41p && ctx->q41_tiles, q41s = q41p && ctx->q41_stream, q41l = q41t || q41s;
+    const bool hstream = (f16p && ctx->f16_stream) || q41s, htiles = (f16p && ctx->f16_tiles) || q41t, lazy = hstream || htiles;
     // block-int4 plan with lh_ctx_set_q4_stream on (alone): no launch of this route reads nibbles (k_gemm_q8b3 and the dequantising GEMM read int8), so every matrix
     // is expanded - directly in front of the launch that reads it (q4x below) instead of in front of the layer, the one place an expansion stands under
     // the switch (eval_planes, Q4Src).  A plan whose shapes have no k_stream_q8b schedule never launches k_stream_q4b: the switch leaves it alone entirely.
@@ -2783,8 +2862,8 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
         const float* const stored[7] = {LS.wq, LS.wk, LS.wv, LS.wo, LS.w1, LS.w3, LS.w2};
         const float* const spairs[7] = {LS.s_wq, LS.s_wk, LS.s_wv, LS.s_wo, LS.s_w1, LS.s_w3, LS.s_w2};   // (Q4_1: the (d, m) planes)
         auto hsrc = [&](int k0, int cnt) {      // matrices k0 .. k0 + cnt - 1 of the list above
-            HalfSrc h = {{}, k0 < 4 ? dd_ : dF_, {}, hstream, htiles, q41t ? 3 : 1, {}};
-            for (int k = 0; k < cnt; ++k) { h.half[k] = stored[k0 + k]; h.wide[k] = &wide[k0 + k]; h.pairs[k] = q41t ? spairs[k0 + k] : nullptr; }
+            HalfSrc h = {{}, k0 < 4 ? dd_ : dF_, {}, hstream, htiles, q41l ? 3 : 1, {}};
+            for (int k = 0; k < cnt; ++k) { h.half[k] = stored[k0 + k]; h.wide[k] = &wide[k0 + k]; h.pairs[k] = q41l ? spairs[k0 + k] : nullptr; }
             return h;
         };
         const HalfSrc hqkv = hsrc(0, 3), hq = hsrc(0, 1), hk = hsrc(1, 1), hv = hsrc(2, 1), ho = hsrc(3, 1), h13 = hsrc(4, 2), h1 = hsrc(4, 1), h3 = hsrc(5, 1), h2 = hsrc(6, 1);
@@ -2929,9 +3008,10 @@ static int eval_prefill(Plan* p, const EvalCall& c, const float* x) {
             const HeadRow hw = head_row(p, m);
             ga.w[0] = hw.w; ga.M = m.V; ga.K = d; ga.x = p->h + (size_t)r0 * d; ga.y = p->logits + (size_t)r0 * m.V;
             if ((rc = gemv<PRO_PLAIN, EPI_STORE, MAP_SINGLE>(ctx, ga, "gemv_lmhead_row", hw.wtype))) return rc;
-        } else if (htiles) {   // the output matrix lazily: halves where the twin's launch is k_gemm_b9, one widening pass directly in front of any other launch
+        } else if (htiles || q41s) {   // the output matrix lazily: halves where the twin's launch is k_gemm_b9, one widening pass directly in front of any other launch
+            // (q41s: the planes too where the twin's launch is a stream launch - a tick of 9..48 pods then expands nothing.  f16_stream leaves the lm_head alone.)
             bool wide_out = false;
-            const HalfSrc hout = {{p->md.output}, (uint64_t)m.V * d, {&wide_out}, false, true, q41t ? 3 : 1, {q41t ? p->md.s_output : nullptr}};
+            const HalfSrc hout = {{p->md.output}, (uint64_t)m.V * d, {&wide_out}, q41s, htiles, q41l ? 3 : 1, {q41l ? p->md.s_output : nullptr}};
             if ((rc = gemm_small_n_src(ctx, m.output, p->h + (size_t)r0 * d, p->logits + (size_t)r0 * m.V, nullptr, m.V, d, nr, d, m.V, "gemm_lmhead", true, &hout))) return rc;
         } else if ((rc = gemm_small_n(ctx, route_output(p, m), p->h + (size_t)r0 * d, p->logits + (size_t)r0 * m.V, nullptr, m.V, d, nr, d, m.V, "gemm_lmhead"))) return rc;
     }

@@ -527,6 +527,22 @@ func (ctx *Context) SetQ41TilesHIP(on bool) {
 }
 func (ctx *Context) Q41TilesHIP() bool { return C.lh_ctx_q41_tiles(ctx.hip.ctx) != 0 }
 
+// SetQ41Stream / SetQ41StreamHIP: lh_ctx_set_q41_stream on the lh_ctx the batch / the context evaluates in - the Evals of a Q4_1 model that take the stream
+// kernels (9..48 rows of a prompt or a tick, prompts of 65..192 rows, the multi-row lm_head) read the model's nibble and (d, m) planes (k_stream_mm2_q41 /
+// k_stream_dma_q41) instead of an fp32 image expanded in front of every layer (DESIGN 3m).  Same bytes; off by default; without effect on models of another
+// weight type.
+func (bt *BatchHIP) SetQ41Stream(on bool) { bt.ctx.SetQ41StreamHIP(on) }
+func (ctx *Context) SetQ41StreamHIP(on bool) {
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	if rc := C.lh_ctx_set_q41_stream(ctx.hip.ctx, v); rc != 0 {
+		hipHalt(ctx.hip.ctx)
+	}
+}
+func (ctx *Context) Q41StreamHIP() bool { return C.lh_ctx_q41_stream(ctx.hip.ctx) != 0 }
+
 // SetF16TilesHIP: lh_ctx_set_f16_tiles on the lh_ctx the context evaluates in - the Evals of more than 128 rows of an f16 model run their k_gemm_b9
 // launches on the model's halves (k_gemm_b9_h, six bf16 products instead of eight) instead of an fp32 image widened in front of every layer (DESIGN 3k).
 // Same bytes; off by default; without effect on models of another weight type; independent of SetF16StreamHIP.

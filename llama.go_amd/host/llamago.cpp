@@ -1992,6 +1992,16 @@ int llamago_BatchSetQ41Tiles(llama_batch* b, int on) {
     return lh_ctx_set_q41_tiles(b->mlctx->hip, on);
 }
 int llamago_BatchQ41Tiles(llama_batch* b) { return b && b->mlctx ? lh_ctx_q41_tiles(b->mlctx->hip) : 0; }
+int llamago_SetQ41Stream(llama_context* c, int on) {
+    if (!c || !c->mlctx || !c->mlctx->hip) return halt_rc("llamago_SetQ41Stream: bad arguments");
+    return lh_ctx_set_q41_stream(c->mlctx->hip, on);
+}
+int llamago_Q41Stream(llama_context* c) { return c && c->mlctx ? lh_ctx_q41_stream(c->mlctx->hip) : 0; }
+int llamago_BatchSetQ41Stream(llama_batch* b, int on) {
+    if (!b || !b->mlctx || !b->mlctx->hip) return halt_rc("llamago_BatchSetQ41Stream: bad arguments");
+    return lh_ctx_set_q41_stream(b->mlctx->hip, on);
+}
+int llamago_BatchQ41Stream(llama_batch* b) { return b && b->mlctx ? lh_ctx_q41_stream(b->mlctx->hip) : 0; }
 int llamago_SetF16Tiles(llama_context* c, int on) {
     if (!c || !c->mlctx || !c->mlctx->hip) return halt_rc("llamago_SetF16Tiles: bad arguments");
     return lh_ctx_set_f16_tiles(c->mlctx->hip, on);

@@ -502,6 +502,21 @@ class Context:
         L.llamago_Q41Tiles.argtypes = [VP]
         return bool(L.llamago_Q41Tiles(self.h))
 
+    def SetQ41Stream(self, on=True):
+        """llamago_SetQ41Stream: Evals of a Q4_1 model on the stream kernels (9..48 and 65..192 rows) read the model's nibble and (d, m) planes (k_stream_mm2_q41 / k_stream_dma_q41)."""
+        L = self.ml.lib
+        L.llamago_SetQ41Stream.restype = C.c_int
+        L.llamago_SetQ41Stream.argtypes = [VP, C.c_int]
+        if L.llamago_SetQ41Stream(self.h, 1 if on else 0):
+            raise MLError(f"llamago_SetQ41Stream: {self.ml.last_error()}")
+
+    @property
+    def q41_stream(self):
+        L = self.ml.lib
+        L.llamago_Q41Stream.restype = C.c_int
+        L.llamago_Q41Stream.argtypes = [VP]
+        return bool(L.llamago_Q41Stream(self.h))
+
     def SetF16Tiles(self, on=True):
         """llamago_SetF16Tiles: Evals of an f16 model beyond 128 rows run their k_gemm_b9 launches on the model's halves (k_gemm_b9_h) instead of a widened image."""
         L = self.ml.lib
@@ -1230,6 +1245,21 @@ class Batch:
         L.llamago_BatchQ41Tiles.restype = C.c_int
         L.llamago_BatchQ41Tiles.argtypes = [VP]
         return bool(L.llamago_BatchQ41Tiles(self.h))
+
+    def SetQ41Stream(self, on=True):
+        """llamago_BatchSetQ41Stream: Context.SetQ41Stream for the ticks and feeds of this batch."""
+        L = self.ml.lib
+        L.llamago_BatchSetQ41Stream.restype = C.c_int
+        L.llamago_BatchSetQ41Stream.argtypes = [VP, C.c_int]
+        if L.llamago_BatchSetQ41Stream(self.h, 1 if on else 0):
+            raise MLError(f"llamago_BatchSetQ41Stream: {self.ml.last_error()}")
+
+    @property
+    def q41_stream(self):
+        L = self.ml.lib
+        L.llamago_BatchQ41Stream.restype = C.c_int
+        L.llamago_BatchQ41Stream.argtypes = [VP]
+        return bool(L.llamago_BatchQ41Stream(self.h))
 
     def SetF16Stream(self, on=True):
         """llamago_BatchSetF16Stream: Context.SetF16Stream for the ticks, feeds and speculative passes of this batch."""
